@@ -13,9 +13,14 @@ the only exchange is the RCCL all-gather of the per-frame object counts at the e
 step.  torch is used for device memory, streams and torch.distributed only; all compute goes
 through the C ABI of libvideoanalysis_hip.so.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the chain, from HIP
-events recorded on the launch stream inside the timed region; `cpu_baseline` is the oracle's
-C restatement of the same chain timed on this box's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the
+headline (`value`, `ms_per_step`); everything else is measured only with `--full`: `roofline`
+for the dominant kernel of the chain, from HIP events recorded on the launch stream inside the
+timed region; `cpu_baseline`, the oracle's C restatement of the same chain timed on this box's
+host cores on a bounded sample; the oracle's check of one more step; copy ceilings and side legs.
+
+`--dump-outputs DIR` writes what the last timed step computed (the arrays a caller of the path
+receives) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -320,6 +325,25 @@ def cpu_baseline(sample, child_args, mode="--cpu-baseline-child", check=None):
                 os.unlink(q)
 
 
+DUMP_SAMPLE = 1 << 22            # elements kept of an output larger than this (float64: 32 MiB)
+
+
+def dump_outputs(torch, dirname, arrays):
+    """`--dump-outputs`: every array as DIR/<name>.npy, float32 as it is, anything else as float64
+    (exact for the int32 / uint8 outputs).  An array of more than DUMP_SAMPLE elements is cut to
+    the elements at a fixed set of flat indices drawn with a fixed seed from its size alone (the
+    same on every build and run); its file is then <name>_sample.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def roofline_of(stage, px_bytes_table, units, workload, peak=HBM_PEAK_GBS):
     """`roofline` object for the dominant stage by device time (HIP events on the launch stream
     inside the timed region).  `units` = pixels (or float elements) one launch processes."""
@@ -361,28 +385,32 @@ def bench_f32(args, torch, device, dev_index, rank, world):
     for _ in range(args.warmup):
         eng.run_device(frames.data_ptr(), batch, out.data_ptr(), None, None, None, None, stream.cuda_stream)
     torch.cuda.synchronize(device)
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         eng.run_device(frames.data_ptr(), batch, out.data_ptr(), None, None, None, None, stream.cuda_stream)
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
-    stage = eng.stage_times()
     fps = batch * args.steps / dt
-    alg = w * h * c * 4 * 2
     res = {"metric": "frames/sec (EMA bg + sigma=9 blur) 1080p float32x3", "value": round(fps, 2),
            "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "%s: %dx%dx%d float32, batch %d, EMA background (rate %g) + sigma=%g "
                                   "Gaussian; inputs resident in HBM" % (args.workload, w, h, c, batch, rate, sigma),
-                      "engine": eng.description, "batch": batch},
-           "roofline": roofline_of(stage, F32_STAGE_BYTES_PER_ELEM, w * h * c * batch, args.workload),
-           "chain": {"alg_bytes_per_frame": alg, "achieved_GBs": round(alg * fps / 1e9, 1),
-                     "frac_of_hbm_peak": round(alg * fps / 1e9 / HBM_PEAK_GBS, 5),
-                     "stage_avg_ms": {k: round(v[0] / max(v[1], 1), 3) for k, v in stage.items()}}}
+                      "engine": eng.description, "batch": batch}}
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"filtered": out})
     failed = False
-    if not args.no_cpu_baseline or not args.no_check:
+    if args.full:
+        stage = eng.stage_times()
+        alg = w * h * c * 4 * 2
+        res["roofline"] = roofline_of(stage, F32_STAGE_BYTES_PER_ELEM, w * h * c * batch, args.workload)
+        res["chain"] = {"alg_bytes_per_frame": alg, "achieved_GBs": round(alg * fps / 1e9, 1),
+                        "frac_of_hbm_peak": round(alg * fps / 1e9 / HBM_PEAK_GBS, 5),
+                        "stage_avg_ms": {k: round(v[0] / max(v[1], 1), 3) for k, v in stage.items()}}
+    if args.full and (not args.no_cpu_baseline or not args.no_check):
         # the oracle's verdict on the first frames of the workload, from a fresh pipeline (zero state):
         # outside the timed region, in the CPU child
         kf = max(1, min(args.cpu_frames_f32, batch))
@@ -451,12 +479,19 @@ def main():
     ap.add_argument("--workload", default="cfg3_1080p_full_chain",
                     choices=sorted(WORKLOADS) + sorted(F32_WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override frames per step per GPU")
-    ap.add_argument("--cpu-frames", type=int, default=160, help="frames in the CPU baseline sample")
-    ap.add_argument("--cpu-frames-f32", type=int, default=6, help="frames in the f32 CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle's check of one GPU step")
-    ap.add_argument("--check-frames", type=int, default=8, help="frames of one step the oracle recomputes")
-    ap.add_argument("--no-extra", action="store_true", help="skip the gauss_valu and e2e_pinned_h2d legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "a fixed seeded sample of an output larger than %d elements)" % DUMP_SAMPLE)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-stage HIP events and the "
+                         "roofline, the oracle's check of one more step, copy ceilings, the gauss_valu and "
+                         "e2e_pinned_h2d legs, the CPU baseline (the --no-* and --*-frames options below shape these)")
+    ap.add_argument("--cpu-frames", type=int, default=160, help="--full: frames in the CPU baseline sample")
+    ap.add_argument("--cpu-frames-f32", type=int, default=6, help="--full: frames in the f32 CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle's check of one GPU step")
+    ap.add_argument("--check-frames", type=int, default=8, help="--full: frames of one step the oracle recomputes")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the gauss_valu and e2e_pinned_h2d legs")
     ap.add_argument("--gauss", default="mfma", choices=["mfma", "valu"],
                     help="8-bit Gaussian of the chain: matrix cores (default) or the dot4/dot2 VALU kernel")
     ap.add_argument("--video", default="own", choices=["own", "shared"],
@@ -477,6 +512,8 @@ def main():
                     help="collective backend; gloo (CPU tensors) only to rehearse the multi-rank "
                          "control flow on a box with fewer GPUs than ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     under_torchrun = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not under_torchrun and (args.gpus > 1 or args.launcher):
@@ -617,10 +654,11 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
-    # per-stage HIP events inside the timed region, on every 4th step (an event per stage on every step costs
-    # about 2 % of the chain: tools/debug/profile_overhead.py); fewer than 8 steps: every step
+    # --full: per-stage HIP events inside the timed region, on every 4th step (an event per stage on every step
+    # costs about 2 % of the chain: tools/debug/profile_overhead.py); fewer than 8 steps: every step
     sample = 4 if args.steps >= 8 else 1
-    eng.profile(True, every=sample)
+    if args.full:
+        eng.profile(True, every=sample)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record(stream)
@@ -629,8 +667,9 @@ def main():
         marks[i + 1].record(stream)           # per-step device time on the launch stream (median below)
     fence()
     dt = time.perf_counter() - t0
-    stage = eng.stage_times()
-    eng.profile(False)
+    if args.full:
+        stage = eng.stage_times()
+        eng.profile(False)
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
     if distributed:
@@ -647,12 +686,12 @@ def main():
     fps = total_frames / dt
     if args.dump_counts and rank == 0:
         np.save(args.dump_counts, all_counts.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        # the last step's results (rank 0's labels, every rank's counts), before --full's extra step reuses the buffers
+        dump_outputs(torch, args.dump_outputs, {"labels": labels[(args.steps - 1) % len(labels)], "counts": all_counts}
+                     if ccl else {"mask": mask})
     failed = False
     if rank == 0:
-        px = w * h
-        # frame in + int32 labels out + count (10 368 004 B @1080p), or + u8 mask out
-        chain_bytes_per_frame = px * 1 + px * 4 + 4 if ccl else px * 2
-        stage_ms = {k: round(v[0] / max(v[1], 1), 4) for k, v in sorted(stage.items())}
         res = {
             "metric": ("frames/sec (bg-sub+blur+thresh+CCL) %s uint8" % ("1080p" if (w, h) == (1920, 1080) else "%dx%d" % (w, h)))
                       if ccl else "frames/sec (bg-sub+blur+thresh) %dx%d uint8" % (w, h),
@@ -683,15 +722,20 @@ def main():
                        "world_size": dist.get_world_size() if distributed else 1,
                        "backend": (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if distributed
                                   else "single process"},
-            "roofline": roofline_of(stage, STAGE_BYTES_PER_PX, px * batch, args.workload),
-            "chain": {"alg_bytes_per_frame": chain_bytes_per_frame,
-                      "achieved_GBs": round(chain_bytes_per_frame * fps / world / 1e9, 2),
-                      "frac_of_hbm_peak_per_gpu": round(chain_bytes_per_frame * fps / world / 1e9 / HBM_PEAK_GBS, 5),
-                      "stage_avg_ms": stage_ms,
-                      "stage_events": "HIP events on the launch stream, every %s step of the timed region (%d launches)"
-                                      % ("4th" if sample == 4 else "", max(v[1] for v in stage.values()) if stage else 0)},
         }
-        if world == 1:
+        if args.full:
+            px = w * h
+            # frame in + int32 labels out + count (10 368 004 B @1080p), or + u8 mask out
+            chain_bytes_per_frame = px * 1 + px * 4 + 4 if ccl else px * 2
+            res["roofline"] = roofline_of(stage, STAGE_BYTES_PER_PX, px * batch, args.workload)
+            res["chain"] = {
+                "alg_bytes_per_frame": chain_bytes_per_frame,
+                "achieved_GBs": round(chain_bytes_per_frame * fps / world / 1e9, 2),
+                "frac_of_hbm_peak_per_gpu": round(chain_bytes_per_frame * fps / world / 1e9 / HBM_PEAK_GBS, 5),
+                "stage_avg_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in sorted(stage.items())},
+                "stage_events": "HIP events on the launch stream, every %s step of the timed region (%d launches)"
+                                % ("4th" if sample == 4 else "", max(v[1] for v in stage.values()) if stage else 0)}
+        if world == 1 and args.full:
             # ---- everything below is outside the timed region ------------------------------------
             # (1) one more step of the same call, from a known background state, for the oracle
             check = None

@@ -1,5 +1,5 @@
 import os, sys, ctypes as C
-ROOT = "/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "video-analysis_amd"))
 from video import _hip
 _hip.LIB_PATH = os.path.join(ROOT, "video-analysis_amd/csrc/build/dbg/libva_dbg.so")

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VMEM_RD" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS"; do
   tag=$(echo $grp | cut -d' ' -f1)
-  rocprofv3 --pmc $grp --output-format csv -d $OUT -o $tag -- python3 $ROOT/bench.py --workload cfg3_1080p_full_chain --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/$tag.err || { tail -5 $OUT/$tag.err; }
+  rocprofv3 --pmc $grp --output-format csv -d $OUT -o $tag -- python3 $ROOT/bench.py --full --workload cfg3_1080p_full_chain --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/$tag.err || { tail -5 $OUT/$tag.err; }
 done
 python3 - <<PY
 import csv, glob, collections

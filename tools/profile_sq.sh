@@ -18,7 +18,7 @@ for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" \
            "SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_INSTS_GDS SQ_INSTS_BRANCH" \
            "GRBM_GUI_ACTIVE SQ_LEVEL_WAVES SQ_ACCUM_PREV_HIRES SQ_CYCLES"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --output-format csv -d $OUT -o p$i -- python3 $ROOT/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-check --no-extra > /dev/null 2> $OUT/p$i.err || { echo "pass $i ($grp) failed:"; tail -3 $OUT/p$i.err; }
+  rocprofv3 --pmc $grp --output-format csv -d $OUT -o p$i -- python3 $ROOT/bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-check --no-extra > /dev/null 2> $OUT/p$i.err || { echo "pass $i ($grp) failed:"; tail -3 $OUT/p$i.err; }
 done
 python3 - <<PY
 import csv, glob, collections, re
