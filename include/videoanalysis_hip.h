@@ -268,6 +268,52 @@ int va_largest_contour(const uint8_t *mask_dev, int n, int h, int w, int32_t *po
                        int32_t *ncomponents_dev, void *workspace_dev, size_t workspace_bytes,
                        void *stream);
 
+/* ------------------------------------------------------------------ A10 geodesic distance maps
+ * 8-neighbour geodesics inside masks: straight steps cost 1, diagonal steps sqrt2 (a diagonal step may
+ * pass between two wall pixels).  A distance d = a + b*sqrt2 is kept as the exact pair (a, b) and
+ * written as 2 + a + floor(b*sqrt2), the reference's int(2 + d); maps are relaxed to their fixpoint
+ * with one workgroup per frame.  Frames up to 8192 columns wide.  All three entry points work only
+ * in `workspace_dev` (va_geodesic_workspace_bytes) and on `stream`. */
+size_t va_geodesic_workspace_bytes(int n, int h, int w);
+/* replaces  make_distance_map(mask, start_points, end_points), video/analysis/regions.py:455-509
+ * fillable_dev: (n, h, w) u8, non-zero where the map may be filled (the reference's pixels equal to 1).
+ * starts_dev: (n, max_starts, 2) int32 (x, y), nstarts_dev[f] of them used; starts outside the frame
+ * or on a pixel that is not fillable are ignored.  ends_dev (nullable): (n, max_ends, 2) int32 (x, y),
+ * nends_dev[f] of them used: the fill stops at the nearest reachable end point -- pixels closer than
+ * it are filled, and it itself (the first listed among equally near ones); other pixels at exactly its
+ * distance stay unfilled, where the reference's choice depends on its float keys and set order.
+ * map_out_dev: (n, h, w) int32, 0 = not fillable, 1 = fillable but not reached, >= 2 = filled. */
+int va_distance_map_i32(const uint8_t *fillable_dev, int n, int h, int w, const int32_t *starts_dev,
+                        const int32_t *nstarts_dev, int max_starts, const int32_t *ends_dev,
+                        const int32_t *nends_dev, int max_ends, int32_t *map_out_dev, void *workspace_dev,
+                        size_t workspace_bytes, void *stream);
+/* replaces  shortest_path_in_distance_map(distance_map, end_point), video/analysis/regions.py:513-565
+ * The reference's walk, literally: values <= 1 and the one-pixel frame around the map read as INT64_MAX,
+ * each step moves to the first minimum (row-major) of (D - d) * weight over the 3x3 window (int64
+ * differences, float64 weights 1 / (1/sqrt2 at the corners)), continuing while the value falls or stays
+ * on an unvisited pixel.  map_dev: (n, h, w) int32; end_points_dev: (n, 2) int32 (x, y).
+ * path_out_dev: (n, max_points, 2) int32 (x, y); npath_out_dev[f] = full path length (only the first
+ * max_points stored); 0 when the end point is outside the frame or its value is <= 1 (the reference
+ * walks through its sentinels there). */
+int va_distance_map_path(const int32_t *map_dev, int n, int h, int w, const int32_t *end_points_dev,
+                         int32_t *path_out_dev, int max_points, int32_t *npath_out_dev, void *workspace_dev,
+                         size_t workspace_bytes, void *stream);
+/* replaces  get_farthest_points(mask, p1, ret_path), video/analysis/regions.py:568-611
+ * mask_dev: (n, h, w) u8, foreground = non-zero.  p1_dev (nullable): (n, 2) int32 (x, y) start points;
+ * NULL: the first point of the longest (cv2.arcLength, closed) cv2.findContours RETR_EXTERNAL /
+ * CHAIN_APPROX_SIMPLE contour, ties to the contour OpenCV lists first (the component whose first
+ * pixel comes last in raster order); with p1_dev NULL, p1_out = (-1, -1) marks a frame without a
+ * component (nothing else is computed for it).  A given start outside the frame or off the mask is
+ * ignored by the first map, as in the reference, so p2 becomes the first foreground pixel.  The whole loop -- map from p1, first raster argmax p2, stop when its value
+ * does not grow, else p1 = p2 -- runs on the device.  p1_out_dev, p2_out_dev: (n, 2) int32;
+ * dist_out_dev: (n) int32, the map value at p2; rounds_out_dev: (n, 2) int32, maps built and sweeps
+ * over all of them.  path_out_dev (nullable): (n, max_points, 2) int32, the walk of
+ * va_distance_map_path from p2 through the last map, npath_out_dev[f] its full length. */
+int va_farthest_points(const uint8_t *mask_dev, int n, int h, int w, const int32_t *p1_dev,
+                       int32_t *p1_out_dev, int32_t *p2_out_dev, int32_t *dist_out_dev, int32_t *rounds_out_dev,
+                       int32_t *path_out_dev, int max_points, int32_t *npath_out_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

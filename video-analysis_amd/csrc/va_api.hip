@@ -945,6 +945,121 @@ int va_largest_contour(const uint8_t *mask, int n, int h, int w, int32_t *points
     return launch_largest_contour(bits, forest, n, h, w, keys, points, max_points, npoints, area, st);
 }
 
+// ------------------------------------------------------------------------------ geodesic
+// [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
+// start is chosen the pairs hold the 8-connected forest and the background labels, the visited
+// bitmap the bit mask (the distance maps come after, in stream order)
+namespace {
+struct GeoLayout {
+    size_t pairs, visited, inv, rows, edge, keys, counts, p1, total;
+};
+GeoLayout geo_layout(int n, int h, int w)
+{
+    GeoLayout g;
+    size_t o = 0;
+    auto take = [&](size_t b) {
+        const size_t at = o;
+        o += align_up(b);
+        return at;
+    };
+    g.pairs = take(geodesic_pairs_bytes(n, h, w));
+    g.visited = take(geodesic_visited_bytes(n, h, w));
+    g.inv = take(geodesic_visited_bytes(n, h, w));
+    g.rows = take(ccl_rows_workspace_bytes(n, h));
+    g.edge = take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
+    g.keys = take((size_t)2 * n * sizeof(unsigned long long));
+    g.counts = take((size_t)2 * n * sizeof(int32_t));
+    g.p1 = take((size_t)2 * n * sizeof(int32_t));
+    g.total = o;
+    return g;
+}
+}  // namespace
+
+size_t va_geodesic_workspace_bytes(int n, int h, int w)
+{
+    if (n <= 0 || h <= 0 || w <= 0)
+        return 256;
+    return geo_layout(n, h, w).total;
+}
+
+#define VA_GEO_REQUIRE_SHAPE(name)                                                                        \
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,                               \
+               name ": frames above 2^29 pixels are not supported");                                     \
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, name ": bad shape");                                             \
+    VA_REQUIRE(geodesic_width_ok(w), name ": frames wider than 8192 columns are not supported");          \
+    VA_REQUIRE(ws && ws_bytes >= va_geodesic_workspace_bytes(n, h, w),                                    \
+               name ": workspace of %zu bytes < required %zu", ws_bytes, va_geodesic_workspace_bytes(n, h, w))
+
+int va_distance_map_i32(const uint8_t *fillable, int n, int h, int w, const int32_t *starts, const int32_t *nstarts,
+                        int max_starts, const int32_t *ends, const int32_t *nends, int max_ends, int32_t *map_out,
+                        void *ws, size_t ws_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_distance_map_i32");
+    VA_REQUIRE(fillable && map_out && starts && nstarts && max_starts > 0, "va_distance_map_i32: NULL argument");
+    VA_REQUIRE(!ends || (nends && max_ends > 0), "va_distance_map_i32: end points without counts");
+    if (n == 0)
+        return VA_OK;
+    const GeoLayout g = geo_layout(n, h, w);
+    char *base = (char *)ws;
+    return launch_distance_map(fillable, n, h, w, starts, nstarts, max_starts, ends, nends, ends ? max_ends : 0,
+                               map_out, (unsigned long long *)(base + g.pairs), nullptr, as_stream(stream));
+}
+
+int va_distance_map_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path_out,
+                         int max_points, int32_t *npath_out, void *ws, size_t ws_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_distance_map_path");
+    VA_REQUIRE(map && end_points && path_out && npath_out && max_points > 0, "va_distance_map_path: NULL argument");
+    if (n == 0)
+        return VA_OK;
+    const GeoLayout g = geo_layout(n, h, w);
+    return launch_distance_path(map, n, h, w, end_points, path_out, max_points, npath_out,
+                                (uint32_t *)((char *)ws + g.visited), as_stream(stream));
+}
+
+int va_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1, int32_t *p1_out, int32_t *p2_out,
+                       int32_t *dist_out, int32_t *rounds_out, int32_t *path_out, int max_points, int32_t *npath_out,
+                       void *ws, size_t ws_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_farthest_points");
+    VA_REQUIRE(mask && p1_out && p2_out && dist_out && rounds_out, "va_farthest_points: NULL argument");
+    VA_REQUIRE(!path_out || (npath_out && max_points > 0), "va_farthest_points: path without npath / max_points");
+    if (n == 0)
+        return VA_OK;
+    hipStream_t st = as_stream(stream);
+    const GeoLayout g = geo_layout(n, h, w);
+    char *base = (char *)ws;
+    unsigned long long *pairs = (unsigned long long *)(base + g.pairs);
+    uint32_t *visited = (uint32_t *)(base + g.visited);
+    const bool default_start = p1 == nullptr;
+    if (default_start) {
+        uint32_t *bits = visited, *inv = (uint32_t *)(base + g.inv);
+        int32_t *forest = (int32_t *)pairs, *bg_labels = forest + (size_t)n * h * w;
+        int32_t *counts = (int32_t *)(base + g.counts);
+        int32_t *start = (int32_t *)(base + g.p1);
+        int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
+        if (!rc)
+            rc = launch_ccl(bits, forest, counts, n, h, w, 8, base + g.rows, ccl_rows_workspace_bytes(n, h), nullptr,
+                            0, st, nullptr, /*paint=*/false);
+        if (!rc)
+            rc = launch_invert_bits(bits, inv, n, h, w, st);
+        if (!rc)
+            rc = launch_ccl(inv, bg_labels, counts + n, n, h, w, 4, base + g.rows, ccl_rows_workspace_bytes(n, h),
+                            nullptr, 0, st, nullptr, /*paint=*/true);
+        if (!rc)
+            rc = launch_longest_external_start(bits, forest, bg_labels, (uint32_t *)(base + g.edge), n, h, w,
+                                               (unsigned long long *)(base + g.keys), start, st);
+        if (rc)
+            return rc;
+        p1 = start;
+    }
+    return launch_farthest_points(mask, n, h, w, p1, p1_out, p2_out, dist_out, rounds_out, path_out, max_points,
+                                  npath_out, pairs, visited, default_start, st);
+}
+
 int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
                  int interpolation, void *stream)
 {

@@ -1713,6 +1713,157 @@ __global__ void contour_points_kernel(const uint32_t *__restrict__ bits,
         area[f] = 0.5 * (double)e.a.twice_area();
 }
 
+// ---- the start point of get_farthest_points (video/analysis/regions.py:574-583) -----------------
+// max(contours, key=cv2.arcLength(c, closed=True)) over the RETR_EXTERNAL contours, first point.
+// arcLength adds float32 sqrt(dx*dx + dy*dy) of float32 differences into a double.  Every term is 0
+// or a float in [1, 2^16) (a multiple of 2^-23) and the sum stays below 2^30, so the double sum is
+// exact in any order: the closing segment may be added last instead of first.
+struct ArcEmit {
+    double len = 0.0;
+    int n = 0, fx = 0, fy = 0, lx = 0, ly = 0;
+    __device__ static double seg(int x0, int y0, int x1, int y1)
+    {
+        const float dx = (float)x1 - (float)x0, dy = (float)y1 - (float)y0;
+        return (double)__fsqrt_rn(dx * dx + dy * dy);
+    }
+    __device__ __forceinline__ void operator()(int x, int y)
+    {
+        if (n == 0) {
+            fx = x;
+            fy = y;
+        } else {
+            len += seg(lx, ly, x, y);
+        }
+        lx = x;
+        ly = y;
+        n++;
+    }
+    __device__ __forceinline__ double total() const { return n ? len + seg(lx, ly, fx, fy) : 0.0; }
+};
+
+// RETR_EXTERNAL keeps a component only if it lies in no hole of another: the 4-connected background
+// component directly left of its first raster pixel (always background) must reach the frame edge.
+// The perimeter ranking needs this test explicitly -- unlike the contour area, a longer outline can
+// sit inside a ring's hole.  bg_labels: 4-connected labels of the inverted mask; edge_bits: bit l set
+// when background label l touches the frame edge.
+__device__ __forceinline__ bool is_external(const int32_t *bgl, const uint32_t *edge_bits, int w, int x, int y)
+{
+    if (x == 0)
+        return true;
+    const int l = bgl[(size_t)y * w + x - 1];
+    return (edge_bits[l >> 5] >> (l & 31)) & 1u;
+}
+
+__global__ void __launch_bounds__(kBlock)
+invert_bits_kernel(const uint32_t *__restrict__ bits, uint32_t *__restrict__ inv, int w, int w32, size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total)
+        return;
+    const int wi = (int)(i % w32), nvalid = min(32, w - wi * 32);
+    inv[i] = ~bits[i] & (nvalid == 32 ? 0xffffffffu : (1u << nvalid) - 1u);
+}
+
+__global__ void __launch_bounds__(kBlock)
+edge_labels_kernel(const int32_t *__restrict__ bgl, uint32_t *__restrict__ edge_bits, int h, int w,
+                   int edge_words)
+{
+    const int f = blockIdx.y;
+    const int per = 2 * (w + h);
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= per)
+        return;
+    int x, y;
+    if (i < w) {
+        x = i;
+        y = 0;
+    } else if (i < 2 * w) {
+        x = i - w;
+        y = h - 1;
+    } else if (i < 2 * w + h) {
+        x = 0;
+        y = i - 2 * w;
+    } else {
+        x = w - 1;
+        y = i - 2 * w - h;
+    }
+    const int l = bgl[(size_t)f * h * w + (size_t)y * w + x];
+    if (l > 0)
+        atomicOr(edge_bits + (size_t)f * edge_words + (l >> 5), 1u << (l & 31));
+}
+
+// pass 0: the longest external outline per frame (atomicMax on the bits of a non-negative double);
+// pass 1: among the outlines of exactly that length, the largest first-pixel index (OpenCV lists
+// contours most-recent-first and Python's max keeps the first maximum)
+template <int PASS>
+__global__ void __launch_bounds__(kBlock)
+contour_perimeters_kernel(const uint32_t *__restrict__ bits, const int32_t *__restrict__ forest,
+                          const int32_t *__restrict__ bg_labels, const uint32_t *__restrict__ edge_bits,
+                          int edge_words, unsigned long long *__restrict__ best_len,
+                          unsigned long long *__restrict__ best_idx, int h, int w, int w32, size_t total_rows)
+{
+    const SpanCtx c = span_ctx(h, w32, total_rows);
+    if (!c.valid)
+        return;
+    const uint32_t *row = bits + c.row * w32;
+    const int32_t *L = forest + (size_t)c.f * h * w;
+    const int32_t *B = bg_labels + (size_t)c.f * h * w;
+    const uint32_t *E = edge_bits + (size_t)c.f * edge_words;
+    BitImage im{bits + (size_t)c.f * h * w32, h, w, w32};
+    uint32_t prev = c.w0 > 0 ? row[c.w0 - 1] >> 31 : 0u;
+    for (int wi = c.w0; wi < c.w1; wi++) {
+        const uint32_t m = row[wi];
+        uint32_t s = m & ~((m << 1) | prev);
+        prev = m >> 31;
+        while (s) {
+            const int b = __ffs(s) - 1;
+            s &= s - 1;
+            const int x = (wi << 5) + b, idx = c.y * w + x;
+            const int v = L[idx];
+            if (v >= 0 || (-v & kNonRootBit))
+                continue;   // not a component's first pixel
+            if (!is_external(B, E, w, x, c.y))
+                continue;
+            ArcEmit e;
+            trace_outer_border(im, x, c.y, e);
+            const unsigned long long len = (unsigned long long)__double_as_longlong(e.total());
+            if (PASS == 0)
+                atomicMax(best_len + c.f, len);
+            else if (len == best_len[c.f])
+                atomicMax(best_idx + c.f, (unsigned long long)(idx + 1));
+        }
+    }
+}
+
+struct FirstEmit {
+    int n = 0, x = -1, y = -1;
+    __device__ __forceinline__ void operator()(int px, int py)
+    {
+        if (n++ == 0) {
+            x = px;
+            y = py;
+        }
+    }
+};
+
+__global__ void longest_contour_start_kernel(const uint32_t *__restrict__ bits,
+                                             const unsigned long long *__restrict__ best_idx, int h, int w,
+                                             int w32, int32_t *__restrict__ p1)
+{
+    const int f = blockIdx.x;
+    if (threadIdx.x != 0)
+        return;
+    const unsigned long long key = best_idx[f];
+    FirstEmit e;
+    if (key != 0) {
+        const int idx = (int)key - 1;
+        BitImage im{bits + (size_t)f * h * w32, h, w, w32};
+        trace_outer_border(im, idx % w, idx / w, e);
+    }
+    p1[2 * f] = e.x;
+    p1[2 * f + 1] = e.y;
+}
+
 inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 }  // namespace
@@ -2013,6 +2164,46 @@ int launch_largest_contour(const uint32_t *bits, const int32_t *forest, int n, i
     contour_points_kernel<<<n, 64, 0, st>>>(bits, best_keys, h, w, w32, points, max_points, npoints,
                                           area);
     VA_LAUNCH_CHECK("contour_points_kernel");
+    return VA_OK;
+}
+}  // namespace va
+
+namespace va {
+int edge_label_words(int h, int w) { return (int)(((size_t)h * w + 2 + 31) / 32); }
+
+int launch_invert_bits(const uint32_t *bits, uint32_t *inv, int n, int h, int w, hipStream_t st)
+{
+    const int w32 = words_per_row(w);
+    const size_t total = (size_t)n * h * w32;
+    if (total == 0)
+        return VA_OK;
+    invert_bits_kernel<<<cdiv((long long)total, kBlock), kBlock, 0, st>>>(bits, inv, w, w32, total);
+    VA_LAUNCH_CHECK("invert_bits_kernel");
+    return VA_OK;
+}
+
+int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
+                                  uint32_t *edge_bits, int n, int h, int w, unsigned long long *keys,
+                                  int32_t *p1, hipStream_t st)
+{
+    VA_REQUIRE(bits && forest && bg_labels && edge_bits && keys && p1, "longest contour: NULL argument");
+    if (n == 0)
+        return VA_OK;
+    const int w32 = words_per_row(w), ew = edge_label_words(h, w);
+    const size_t total_rows = (size_t)n * h;
+    VA_HIP(hipMemsetAsync(keys, 0, 2 * sizeof(unsigned long long) * n, st));
+    VA_HIP(hipMemsetAsync(edge_bits, 0, sizeof(uint32_t) * ew * (size_t)n, st));
+    edge_labels_kernel<<<dim3(cdiv(2ll * (w + h), kBlock), n), kBlock, 0, st>>>(bg_labels, edge_bits, h, w, ew);
+    VA_LAUNCH_CHECK("edge_labels_kernel");
+    const int sgrid = cdiv((long long)total_rows, 32);
+    contour_perimeters_kernel<0><<<sgrid, 256, 0, st>>>(bits, forest, bg_labels, edge_bits, ew, keys, keys + n, h,
+                                                         w, w32, total_rows);
+    VA_LAUNCH_CHECK("contour_perimeters_kernel");
+    contour_perimeters_kernel<1><<<sgrid, 256, 0, st>>>(bits, forest, bg_labels, edge_bits, ew, keys, keys + n, h,
+                                                         w, w32, total_rows);
+    VA_LAUNCH_CHECK("contour_perimeters_kernel");
+    longest_contour_start_kernel<<<n, 64, 0, st>>>(bits, keys + n, h, w, w32, p1);
+    VA_LAUNCH_CHECK("longest_contour_start_kernel");
     return VA_OK;
 }
 }  // namespace va

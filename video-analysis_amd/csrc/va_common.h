@@ -238,6 +238,28 @@ int launch_ccl_paint(const CclPaintPlan &plan, hipStream_t st, StageProfiler *pr
 int launch_largest_contour(const uint32_t *bits, const int32_t *forest, int n, int h, int w,
                            unsigned long long *best_keys, int32_t *points, int max_points,
                            int32_t *npoints, double *area, hipStream_t st);
+// get_farthest_points' default start: the first point of the longest (cv2.arcLength) RETR_EXTERNAL
+// contour, per frame, (-1, -1) without one.  forest as for launch_largest_contour; bg_labels: the
+// painted 4-connected labels of the inverted mask (launch_invert_bits); edge_bits: edge_label_words
+// words per frame; keys: 2 n
+int edge_label_words(int h, int w);
+int launch_invert_bits(const uint32_t *bits, uint32_t *inv, int n, int h, int w, hipStream_t st);
+int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
+                                  uint32_t *edge_bits, int n, int h, int w, unsigned long long *keys,
+                                  int32_t *p1, hipStream_t st);
+// geodesic distance maps (va_geodesic.hip): pairs = geodesic_pairs_bytes, visited = geodesic_visited_bytes
+size_t geodesic_pairs_bytes(int n, int h, int w);
+size_t geodesic_visited_bytes(int n, int h, int w);
+bool geodesic_width_ok(int w);
+int launch_distance_map(const uint8_t *fillable, int n, int h, int w, const int32_t *starts,
+                        const int32_t *nstarts, int max_starts, const int32_t *ends, const int32_t *nends,
+                        int max_ends, int32_t *out, unsigned long long *pairs, int32_t *sweeps, hipStream_t st);
+int launch_distance_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path,
+                         int max_points, int32_t *npath, uint32_t *visited, hipStream_t st);
+int launch_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1_in, int32_t *p1_out,
+                           int32_t *p2_out, int32_t *dist_out, int32_t *rounds_out, int32_t *path, int max_points,
+                           int32_t *npath, unsigned long long *pairs, uint32_t *visited, bool default_start,
+                           hipStream_t st);
 // FilterNormalize for uint8 / float32 frames, any of the three target dtypes; seeded noise frames
 int launch_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
                      double fmax, double alpha, double tmin, hipStream_t st);

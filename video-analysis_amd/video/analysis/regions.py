@@ -2,7 +2,8 @@
 
 Reference: video/analysis/regions.py -- corners_to_rect :23-29, rect_to_corners :33-45,
 rect_to_slices :49-53, get_overlapping_slices :57-110, find_bounding_box :113-149,
-expand_rectangle :153-155, get_largest_region :159-174, triangle_area :430-451.
+expand_rectangle :153-155, get_largest_region :159-174, triangle_area :430-451,
+make_distance_map :455-509, shortest_path_in_distance_map :513-565, get_farthest_points :568-611.
 """
 import numpy as np
 
@@ -119,3 +120,61 @@ def get_contour_from_largest_region(mask, ret_area=False):
     if ret_area:
         return contour, area
     return contour
+
+
+def make_distance_map(mask, start_points, end_points=None):
+    """fills the pixels equal to 1 of the integer array `mask` (int32 or int64, changed in place)
+    with 2 + the 8-neighbour geodesic distance to the nearest start point (x, y), as int(2 + d);
+    reference: video/analysis/regions.py:455-509.  Other values are walls and stay as they are, as
+    do pixels equal to 1 that cannot be reached; start points outside the array or on a pixel that
+    is not 1 are ignored.  With end_points the fill stops at the nearest reachable one: the pixels
+    closer than it are filled, and it itself.  Deviation: other pixels at exactly its distance stay
+    unfilled (the reference's choice among them follows its float keys and set order).  Returns None."""
+    from .. import ops
+    if not isinstance(mask, np.ndarray) or mask.dtype not in (np.int32, np.int64):
+        raise TypeError("make_distance_map works in place on an int32 or int64 array")
+    if mask.ndim != 2:
+        raise ValueError("mask must be 2-d")
+    out = ops.distance_map(mask == 1, list(start_points),
+                           None if end_points is None else list(end_points))
+    filled = out >= 2
+    mask[filled] = out[filled]
+
+
+def shortest_path_in_distance_map(distance_map, end_point):
+    """(N, 2) int64 array of the (x, y) points walked from `end_point` down the distance map to a
+    minimum; reference: video/analysis/regions.py:513-565, step for step.  Deviation: an end point
+    whose value is <= 1 (or that lies outside the map) raises ValueError, where the reference walks
+    through its sentinels."""
+    from .. import ops
+    path = ops.distance_map_path(np.asarray(distance_map), end_point)
+    if len(path) == 0:
+        raise ValueError("end point %s is not a filled pixel of the distance map" % (tuple(end_point),))
+    return path
+
+
+def get_farthest_points(mask, p1=None, ret_path=False):
+    """the two points of the mask's foreground (non-zero) farthest apart along geodesics, found by
+    repeating distance maps from the farthest point of the last one; reference:
+    video/analysis/regions.py:568-611.  p1 defaults to the first point of the longest external
+    contour (cv2.arcLength).  Returns (p1, p2) as tuples of ints, or with ret_path the path from p2
+    as shortest_path_in_distance_map gives it.  A p1 outside the frame or off the mask is ignored by
+    the first map, as in the reference, so p2 moves to the first foreground pixel.  ValueError for an
+    empty mask without p1 (max() of no contours in the reference), and for ret_path when no pixel
+    was reached.  Deviation: every non-zero pixel is foreground.  The reference's np.clip(mask, 0, 1)
+    agrees for bool and unsigned masks, but in signed masks it makes negative values background."""
+    from .. import ops
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError("mask must be 2-d")
+    if ret_path:
+        path = ops.farthest_points(m, p1, ret_path=True)
+        if len(path) == 0:
+            raise ValueError("max() arg is an empty sequence" if p1 is None else "no pixel of the mask was reached")
+        return path
+    a, b, _, rounds = ops.farthest_points(m, p1, ret_stats=True)
+    if p1 is None and a[0] == -1 and a[1] == -1:
+        raise ValueError("max() arg is an empty sequence")
+    if p1 is not None and rounds[0] == 1:     # never replaced: the caller's own start, as given
+        return (int(p1[0]), int(p1[1])), (int(b[0]), int(b[1]))
+    return (int(a[0]), int(a[1])), (int(b[0]), int(b[1]))

@@ -484,6 +484,156 @@ def largest_contour(mask, max_points=None, moments=False):
             _give(b)
 
 
+# ------------------------------------------------------------------------ geodesic distance maps
+_I32_MAX = 2 ** 31 - 1
+
+
+def _point_table(per_frame, n):
+    """(n, m, 2) int32 table + (n,) counts from one list of (x, y) points per frame; coordinates
+    beyond int32 become -1 (outside every frame, as they are)"""
+    lists = [[] if p is None else [tuple(q) for q in p] for p in per_frame]
+    if len(lists) != n:
+        raise ValueError("need one point list per frame (%d frames, %d lists)" % (n, len(lists)))
+    m = max([1] + [len(l) for l in lists])
+    tab = np.full((n, m, 2), -1, np.int32)
+    cnt = np.zeros(n, np.int32)
+    for f, l in enumerate(lists):
+        for i, q in enumerate(l):
+            for k in (0, 1):
+                v = int(q[k])
+                tab[f, i, k] = v if -1 <= v <= _I32_MAX else -1
+        cnt[f] = len(l)
+    return tab, cnt
+
+
+def distance_map(fillable, start_points, end_points=None):
+    """geodesic distance maps (8-neighbours, straight 1, diagonal sqrt2) -- make_distance_map,
+    video/analysis/regions.py:455-509.  fillable: (h, w) or (N, h, w), non-zero where the map may be
+    filled; start_points: (x, y) points, one list per frame when batched; end_points likewise or
+    None.  Returns int32 maps: 0 not fillable, 1 not reached, 2 + floor(distance) filled."""
+    arr, n, fshape, single = _as_batch(np.asarray(fillable), 2)
+    arr = np.ascontiguousarray(arr != 0, np.uint8)
+    h, w = fshape
+    if single:
+        start_points = [start_points]
+        end_points = None if end_points is None else [end_points]
+    st, nst = _point_table(start_points, n)
+    L = _hip.lib()
+    ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
+    bufs = [_upload(arr), _upload(st), _upload(nst), _take(arr.size * 4), _take(ws_bytes)]
+    src, sb, nsb, out, ws = bufs
+    try:
+        eb = neb = None
+        me = 0
+        if end_points is not None:
+            et, net = _point_table(end_points, n)
+            eb, neb = _upload(et), _upload(net)
+            bufs += [eb, neb]
+            me = et.shape[1]
+        check(L.va_distance_map_i32(src.ptr, n, h, w, sb.ptr, nsb.ptr, st.shape[1], eb.ptr if eb else None,
+                                    neb.ptr if neb else None, me, out.ptr, ws.ptr, ws_bytes, None))
+        return out.download(arr.shape, np.int32)
+    finally:
+        _give(*bufs)
+
+
+def _download_paths(pts, npath, n, cap):
+    allp = pts.download((n, cap, 2), np.int32)
+    return [allp[f, :npath[f]].astype(np.int64) for f in range(n)]
+
+
+def distance_map_path(dmap, end_point, max_points=None):
+    """the reference's walk from `end_point` down a distance map to its minimum --
+    shortest_path_in_distance_map, video/analysis/regions.py:513-565.  dmap: (h, w) or (N, h, w)
+    integers below 2^31; end_point: (x, y), or (N, 2) when batched.  Returns the (K, 2) int64 path of
+    (x, y) points (a list of them when batched); K = 0 where the end point lies outside the map or
+    its value is <= 1."""
+    a = np.asarray(dmap)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError("distance maps are integer arrays")
+    if a.size and a.max() > _I32_MAX:
+        raise ValueError("distance map values must stay below 2^31")
+    arr, n, fshape, single = _as_batch(a, 2)
+    arr = np.ascontiguousarray(np.maximum(arr, 0), np.int32)
+    h, w = fshape
+    ends, _ = _point_table([[end_point]] if single else [[e] for e in end_point], n)
+    L = _hip.lib()
+    ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
+    cap = int(max_points) if max_points else 4096
+    src, eb, npb, ws = _upload(arr), _upload(ends[:, 0].copy()), _take(n * 4), _take(ws_bytes)
+    bufs = [src, eb, npb, ws]
+    try:
+        while True:
+            pts = _take(n * cap * 8)
+            bufs.append(pts)
+            check(L.va_distance_map_path(src.ptr, n, h, w, eb.ptr, pts.ptr, cap, npb.ptr, ws.ptr, ws_bytes, None))
+            npath = npb.download((n,), np.int32)
+            if npath.max(initial=0) <= cap or max_points:
+                break
+            cap = int(npath.max())           # rare: a path longer than the buffer, run again with room
+        paths = _download_paths(pts, np.minimum(npath, cap), n, cap)
+        return paths[0] if single else paths
+    finally:
+        _give(*bufs)
+
+
+def farthest_points(masks, p1=None, ret_path=False, max_points=None, ret_stats=False):
+    """get_farthest_points, video/analysis/regions.py:568-611, for one mask (h, w) or a batch
+    (N, h, w), foreground = non-zero.  p1: (x, y), or (N, 2) when batched; None: the first point of
+    the longest external contour.  The whole iteration runs on the GPU.  Returns (p1, p2) as (N, 2)
+    int64 arrays ((2,) for one mask), (-1, -1) for a frame without a component when p1 is None (a
+    given p1 is only a start: one outside the frame or off the mask is ignored by the first map, and
+    comes back as given when the loop ends there, an empty mask); with
+    ret_path the (K, 2) int64 paths from p2 instead (a list when batched).  ret_stats appends
+    (distance value at p2 (N,), [maps built, sweeps] (N, 2)) as int32 arrays."""
+    arr, n, fshape, single = _as_batch(np.asarray(masks), 2)
+    arr = np.ascontiguousarray(arr != 0, np.uint8)
+    h, w = fshape
+    L = _hip.lib()
+    ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
+    src, p1o, p2o, dist, rounds, npb, ws = (_upload(arr), _take(n * 8), _take(n * 8), _take(n * 4),
+                                            _take(n * 8), _take(n * 4), _take(ws_bytes))
+    bufs = [src, p1o, p2o, dist, rounds, npb, ws]
+    try:
+        p1b = None
+        if p1 is not None:
+            given = [p1] if single else list(p1)
+            tab, _ = _point_table([[q] for q in given], n)
+            p1b = _upload(tab[:, 0].copy())
+            bufs.append(p1b)
+        cap = int(max_points) if max_points else 4096
+        while True:
+            pts = _take(n * cap * 8) if ret_path else None
+            if pts is not None:
+                bufs.append(pts)
+            check(L.va_farthest_points(src.ptr, n, h, w, p1b.ptr if p1b else None, p1o.ptr, p2o.ptr, dist.ptr,
+                                       rounds.ptr, pts.ptr if pts is not None else None, cap, npb.ptr, ws.ptr, ws_bytes, None))
+            if not ret_path:
+                break
+            npath = npb.download((n,), np.int32)
+            if npath.max(initial=0) <= cap or max_points:
+                break
+            cap = int(npath.max())
+        if ret_path:
+            res = _download_paths(pts, np.minimum(npath, cap), n, cap)
+            res = (res[0] if single else res,)
+        else:
+            a, b = p1o.download((n, 2), np.int32).astype(np.int64), p2o.download((n, 2), np.int32).astype(np.int64)
+            if p1 is not None:        # a start never replaced is returned as given, not as the kernel read it
+                kept = rounds.download((n, 2), np.int32)[:, 0] == 1
+                for f in np.nonzero(kept)[0]:
+                    q = [int(v) for v in given[f]]
+                    if all(-2 ** 63 <= v < 2 ** 63 for v in q):
+                        a[f] = q
+            res = (a[0], b[0]) if single else (a, b)
+        if ret_stats:
+            d, r = dist.download((n,), np.int32), rounds.download((n, 2), np.int32)
+            res += (d[0], r[0]) if single else (d, r)
+        return res if len(res) > 1 else res[0]
+    finally:
+        _give(*bufs)
+
+
 def contour_moments(contour):
     """the ten spatial moments of cv2.moments(contour) as a float64 array (m00 m10 m01 m20 m11 m02
     m30 m21 m12 m03) -- regionprops(contour=...), video/analysis/image.py:355; Polygon.moments,
