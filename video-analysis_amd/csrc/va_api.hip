@@ -149,9 +149,8 @@ struct va_pipeline {
     int64_t n_seen;
     double *bg_recip;  // per-frame reciprocals of the running mean's divisor
     void *diff;        // background-subtracted frames (cfg.dtype)
-    void *blur;        // blurred frames when the caller does not ask for them (generic path)
-    void *gscratch;    // generic Gaussian scratch (u16 / f32) or the planes of the re-laid-out u8 blur
-    int planes_wp;     // > 0: u8 blur through reflected-padded single-channel planes of this width
+    void *blur;        // blurred frames when the caller does not ask for them (Gaussians with scratch)
+    void *gscratch;    // Gaussian scratch: gauss_scratch_bytes(gauss, max_batch)
     // Mask ping-pong and labelling workspace exist twice ("slots") once va_pipeline_overlap is on: the
     // paint pass of batch k reads slot k % 2 on the side stream while the stages of batch k + 1 fill the
     // other one.  slot 1 is allocated by va_pipeline_overlap.
@@ -170,12 +169,8 @@ struct va_pipeline {
     const char *pstat_lo[2], *pstat_hi[2];     // statistics written by that paint pass
     int32_t *labels_scratch;
     int32_t *counts_scratch;
-    TapsQ8 tq;
-    TapsF32 tf;
+    GaussPlan gauss;   // family None: no blur
     RowSpans se[VA_MAX_MORPH_OPS];
-    bool fused;   // single-launch blur(+threshold+bits): MFMA or LDS/VALU kernel
-    bool mfma;
-    bool f32_fused;   // float32: [EMA + row pass] and marching column pass (va_gauss_f32_fused.hip)
     char desc[160];
     StageProfiler *prof;
 };
@@ -450,32 +445,28 @@ int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacit
     return VA_OK;
 }
 
-// Frames the matrix-core Gaussian can take after a re-layout: colour frames (the channels are
-// filtered independently, as OpenCV does) and widths that are not a multiple of 16 go through
-// planes (frame, channel, h, wp).  A plane that is wider than the frame carries the reflected
-// continuation of every row over at least the kernel's radius, so the blur of the plane is the
-// blur of the frame on the first w columns.  Returns the plane width, or 0 when this path does
-// not apply.
-static int planes_width(int h, int w, int c, const TapsQ8 &t)
+// The stand-alone Gaussian calls: argument checks, a plan, a scratch lease and a launch.  The test hooks
+// (force != None) keep their terse messages; the dot4/dot2 hook takes one channel only.
+static int gaussian_call(const char *who, int dtype, const void *src, void *dst, int n, int h, int w, int c,
+                         double sigma, int tap_rule, GaussFamily force, void *stream)
 {
-    const int wp = (w % 16 == 0) ? w : ((w + 16 + 15) / 16) * 16;
-    if (c >= 1 && c <= 4 && wp - w < w && gauss_mfma_supported(wp, h, t))
-        return wp;
-    return 0;
-}
-static size_t planes_scratch_bytes(int n, int h, int wp, int c) { return 2 * (size_t)n * c * h * wp; }
-static int blur_u8_planes(const uint8_t *src, uint8_t *dst, int n, int h, int w, int wp, int c,
-                          const TapsQ8 &t, void *scratch, hipStream_t st)
-{
-    const size_t plane_bytes = (size_t)n * c * h * wp;                   // multiple of 16
-    uint8_t *pin = (uint8_t *)scratch, *pout = pin + plane_bytes;        // both 16-byte aligned
-    int rc = launch_channel_planes(src, pin, n, h, w, wp, c, true, st);
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "%s: frames above 2^29 pixels are not supported", who);
+    const bool hook = force != GaussFamily::None;
+    VA_REQUIRE(src && dst && src != dst, hook ? "%s: bad pointers" : "%s: src/dst must be distinct non-NULL", who);
+    VA_REQUIRE(!hook || (n >= 0 && h > 0 && w > 0 && c > 0 && (c == 1 || force != GaussFamily::U8Dot)),
+               "%s: bad shape", who);
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "%s: bad shape (%d,%d,%d,%d)", who, n, h, w, c);
+    const bool aligned = (uintptr_t)src % 16 == 0 && (dtype == VA_F32 || (uintptr_t)dst % 4 == 0);
+    GaussPlan g;
+    int rc = plan_gaussian(&g, dtype, h, w, c, sigma, tap_rule, aligned, false, force);
     if (rc)
         return rc;
-    rc = launch_gauss_mfma_u8(pin, pout, nullptr, -1, n * c, h, wp, t, st);
-    if (rc)
+    ScratchLease scratch;
+    if (!g.single_pass() && (rc = scratch.acquire(gauss_scratch_bytes(g, n), as_stream(stream))))
         return rc;
-    return launch_channel_planes(pout, dst, n, h, w, wp, c, false, st);
+    return launch_gaussian(g, src, dst, nullptr, -1, 0, scratch.ptr, n, as_stream(stream), nullptr);
 }
 
 int va_gaussian_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
@@ -487,70 +478,24 @@ int va_gaussian_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c,
 int va_gaussian_u8_rule(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
                         int tap_rule, void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_gaussian_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_gaussian_u8: src/dst must be distinct non-NULL");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "va_gaussian_u8: bad shape (%d,%d,%d,%d)", n, h,
-               w, c);
-    TapsQ8 t;
-    int rc = gauss_taps_q8(sigma, &t.ksize, t.t, kMaxTaps, tap_rule);
-    if (rc)
-        return rc;
-    if (c == 1 && reinterpret_cast<uintptr_t>(src) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(dst) % 4 == 0) {
-        if (gauss_mfma_supported(w, h, t))
-            return launch_gauss_mfma_u8(src, dst, nullptr, -1, n, h, w, t, as_stream(stream));
-        if (gauss_fused_supported(w, h, t))
-            return launch_gauss_fused_u8(src, dst, nullptr, -1, n, h, w, t, as_stream(stream));
-    }
-    ScratchLease scratch;
-    if (const int wp = planes_width(h, w, c, t)) {
-        rc = scratch.acquire(planes_scratch_bytes(n, h, wp, c), as_stream(stream));
-        if (rc)
-            return rc;
-        return blur_u8_planes(src, dst, n, h, w, wp, c, t, scratch.ptr, as_stream(stream));
-    }
-    rc = scratch.acquire(gauss_generic_u8_scratch_bytes((size_t)n * h * w * c, t), as_stream(stream));
-    if (rc)
-        return rc;
-    return launch_gauss_generic_u8(src, dst, scratch.ptr, n, h, w, c, t, as_stream(stream));
+    return gaussian_call("va_gaussian_u8", VA_U8, src, dst, n, h, w, c, sigma, tap_rule, GaussFamily::None,
+                         stream);
 }
 
 // test hook: force the generic two-pass implementation
 int va_gaussian_u8_generic(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c,
                            double sigma, void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_gaussian_u8_generic: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_gaussian_u8_generic: bad pointers");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "va_gaussian_u8_generic: bad shape");
-    TapsQ8 t;
-    int rc = gauss_taps_q8(sigma, &t.ksize, t.t, kMaxTaps);
-    if (rc)
-        return rc;
-    ScratchLease scratch;
-    rc = scratch.acquire(gauss_generic_u8_scratch_bytes((size_t)n * h * w * c, t), as_stream(stream));
-    if (rc)
-        return rc;
-    return launch_gauss_generic_u8(src, dst, scratch.ptr, n, h, w, c, t, as_stream(stream));
+    return gaussian_call("va_gaussian_u8_generic", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
+                         GaussFamily::U8Generic, stream);
 }
 
 // test hook: force the LDS/VALU (dot4/dot2) fused implementation
 int va_gaussian_u8_valu(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
                         void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_gaussian_u8_valu: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_gaussian_u8_valu: bad pointers");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c == 1, "va_gaussian_u8_valu: bad shape");
-    TapsQ8 t;
-    int rc = gauss_taps_q8(sigma, &t.ksize, t.t, kMaxTaps);
-    if (rc)
-        return rc;
-    return launch_gauss_fused_u8(src, dst, nullptr, -1, n, h, w, t, as_stream(stream));
+    return gaussian_call("va_gaussian_u8_valu", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
+                         GaussFamily::U8Dot, stream);
 }
 
 // test hook: pin the labelling code path of every later call in this process
@@ -579,26 +524,8 @@ int va_test_hook_gaussian_f32(int generic_columns)
 int va_gaussian_f32(const float *src, float *dst, int n, int h, int w, int c, double sigma,
                     void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_gaussian_f32: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_gaussian_f32: src/dst must be distinct non-NULL");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "va_gaussian_f32: bad shape (%d,%d,%d,%d)", n,
-               h, w, c);
-    TapsF32 t;
-    int rc = gauss_taps_f32(sigma, &t.ksize, t.t, kMaxTaps);
-    if (rc)
-        return rc;
-    ScratchLease scratch;
-    rc = scratch.acquire((size_t)n * h * w * c * sizeof(float), as_stream(stream));
-    if (rc)
-        return rc;
-    if (gauss_f32_fused_supported(h, w, c, t) && reinterpret_cast<uintptr_t>(src) % 16 == 0)
-        return launch_gauss_f32_fused(src, dst, (float *)scratch.ptr, nullptr, nullptr, 0, 0.0, n, h, w, c, t,
-                                      as_stream(stream));
-    if (gauss_f32_fast_supported(w, c, t))
-        return launch_gauss_f32_fast(src, dst, (float *)scratch.ptr, n, h, w, c, t, as_stream(stream));
-    return launch_gauss_generic_f32(src, dst, (float *)scratch.ptr, n, h, w, c, t, as_stream(stream));
+    return gaussian_call("va_gaussian_f32", VA_F32, src, dst, n, h, w, c, sigma, VA_TAPS_CV4, GaussFamily::None,
+                         stream);
 }
 
 // ------------------------------------------------------------------------------ background
@@ -1180,17 +1107,9 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
         }                                                                                \
     } while (0)
 
-    if (cfg->sigma > 0) {
-        if (cfg->dtype == VA_U8) {
-            PIPE_TRY(gauss_taps_q8(cfg->sigma, &p->tq.ksize, p->tq.t, kMaxTaps, cfg->tap_rule));
-            p->mfma = cfg->channels == 1 && !g_gauss_u8_valu && gauss_mfma_supported(cfg->width, cfg->height, p->tq);
-            p->fused = p->mfma ||
-                       (cfg->channels == 1 && gauss_fused_supported(cfg->width, cfg->height, p->tq));
-        } else {
-            PIPE_TRY(gauss_taps_f32(cfg->sigma, &p->tf.ksize, p->tf.t, kMaxTaps));
-            p->f32_fused = gauss_f32_fused_supported(cfg->height, cfg->width, cfg->channels, p->tf);
-        }
-    }
+    if (cfg->sigma > 0)
+        PIPE_TRY(plan_gaussian(&p->gauss, cfg->dtype, cfg->height, cfg->width, cfg->channels, cfg->sigma,
+                               cfg->tap_rule, true, g_gauss_u8_valu != 0));
     for (int i = 0; i < cfg->morph_count; i++) {
         if (cfg->morph_op[i] != VA_MORPH_ERODE && cfg->morph_op[i] != VA_MORPH_DILATE) {
             set_error("va_pipeline_create: bad morph_op[%d]=%d", i, cfg->morph_op[i]);
@@ -1202,7 +1121,7 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
     if (cfg->bg_mode != VA_BG_NONE) {
         p->bg_bytes = p->px * (cfg->bg_mode == VA_BG_EMA ? sizeof(float) : sizeof(double));
         PIPE_MALLOC(p->bg_state, p->bg_bytes);
-        if (p->f32_fused && cfg->bg_mode == VA_BG_EMA)
+        if (p->gauss.folds_ema() && cfg->bg_mode == VA_BG_EMA)
             PIPE_MALLOC(p->bg_state_alt, p->bg_bytes);
         p->bg_in_u8_range = true;                        // (zeros)
         hipError_t e = hipMemset(p->bg_state, 0, p->bg_bytes);
@@ -1211,19 +1130,13 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
             pipeline_free(p);
             return VA_ERR_HIP;
         }
-        if (!p->f32_fused)      // (the fused float path never materialises the difference image)
+        if (!p->gauss.folds_ema())      // (the fused float path never materialises the difference image)
             PIPE_MALLOC(p->diff, nb * p->px * esz);
         if (cfg->bg_mode == VA_BG_MEAN)
             PIPE_MALLOC(p->bg_recip, bg_scratch_bytes(cfg->max_batch));
     }
-    if (cfg->sigma > 0 && !p->fused) {
-        size_t gs = cfg->dtype == VA_U8 ? gauss_generic_u8_scratch_bytes(nb * p->px, p->tq) : nb * p->px * 4;
-        if (cfg->dtype == VA_U8) {
-            p->planes_wp = planes_width(cfg->height, cfg->width, cfg->channels, p->tq);
-            if (p->planes_wp)
-                gs = planes_scratch_bytes(cfg->max_batch, cfg->height, p->planes_wp, cfg->channels);
-        }
-        PIPE_MALLOC(p->gscratch, gs);
+    if (cfg->sigma > 0 && !p->gauss.single_pass()) {
+        PIPE_MALLOC(p->gscratch, gauss_scratch_bytes(p->gauss, nb));
         PIPE_MALLOC(p->blur, nb * p->px * esz);
     }
     if (masks) {
@@ -1241,18 +1154,8 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
             PIPE_MALLOC(p->labels_scratch, nb * p->frame_px * sizeof(int32_t));
         }
     }
-    snprintf(p->desc, sizeof(p->desc), "bg=%d gauss=%s(ksize=%d) thresh=%d morph=%d ccl=%d",
-             cfg->bg_mode,
-             cfg->sigma > 0 ? (p->fused ? (p->mfma ? "mfma-i8" : "fused-lds")
-                                        : (cfg->dtype == VA_F32 && p->f32_fused
-                                               ? "f32-ema-row+col-march"
-                                               : cfg->dtype == VA_F32 &&
-                                                   gauss_f32_fast_supported(cfg->width, cfg->channels, p->tf)
-                                               ? "f32-packed"
-                                               : (p->planes_wp ? "mfma-i8-planes" : "generic")))
-                            : "none",
-             cfg->sigma > 0 ? (cfg->dtype == VA_U8 ? p->tq.ksize : p->tf.ksize) : 0, cfg->thresh,
-             cfg->morph_count, cfg->connectivity);
+    snprintf(p->desc, sizeof(p->desc), "bg=%d gauss=%s(ksize=%d) thresh=%d morph=%d ccl=%d", cfg->bg_mode,
+             gauss_plan_name(p->gauss), p->gauss.ksize(), cfg->thresh, cfg->morph_count, cfg->connectivity);
 #undef PIPE_TRY
 #undef PIPE_MALLOC
     *out = p;
@@ -1417,17 +1320,16 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
 
     // float32 frames: background update, difference and row pass in one kernel, then the columns
     // (16-byte aligned frame pointers: a contract of float32 pipelines, see the header)
-    if (c.dtype == VA_F32 && p->f32_fused) {
+    if (p->gauss.folds_ema()) {
         VA_REQUIRE(reinterpret_cast<uintptr_t>(frames) % 16 == 0 &&
                        (!filtered_out || reinterpret_cast<uintptr_t>(filtered_out) % 16 == 0),
                    "va_pipeline_run: float32 pipelines need 16-byte aligned frames_dev / filtered_out_dev "
                    "(hipMalloc'ed buffers and whole-frame offsets into them are)");
         void *dst = filtered_out ? filtered_out : p->blur;
         const bool ema = c.bg_mode == VA_BG_EMA;
-        rc = launch_gauss_f32_fused((const float *)frames, (float *)dst, (float *)p->gscratch,
-                                    ema ? (const float *)p->bg_state : nullptr,
-                                    ema ? (float *)p->bg_state_alt : nullptr, p->n_seen, (double)c.bg_rate, n,
-                                    c.height, c.width, c.channels, p->tf, st, prof);
+        rc = launch_gaussian(p->gauss, frames, dst, nullptr, -1, 0, p->gscratch, n, st, prof,
+                             ema ? (const float *)p->bg_state : nullptr, ema ? (float *)p->bg_state_alt : nullptr,
+                             p->n_seen, (double)c.bg_rate);
         if (rc)
             return rc;
         if (ema && n > 0) {
@@ -1459,52 +1361,19 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
     // 2. Gaussian blur (+ threshold + bit packing when fused)
     bool have_bits = false;
     if (c.sigma > 0) {
-        if (c.dtype == VA_U8 && p->mfma && masks && mask_out && !filtered_out && c.morph_count == 0 && !want_ccl &&
+        if (p->gauss.byte_mask() && masks && mask_out && !filtered_out && c.morph_count == 0 && !want_ccl &&
             reinterpret_cast<uintptr_t>(mask_out) % 4 == 0) {
             // the chain ends at FilterThreshold's uint8 mask (BASELINE configs[1]): the Gaussian's
             // epilogue writes the 0 / maxval bytes itself -- no bit mask, no unpack pass
-            rc = launch_gauss_mfma_u8((const uint8_t *)cur, mask_out, nullptr, c.thresh, n, c.height, c.width, p->tq,
-                                      st, c.maxval);
-            if (rc)
-                return rc;
-            VA_MARK("gauss_mfma_mask8");
-            return VA_OK;
+            return launch_gaussian(p->gauss, cur, mask_out, nullptr, c.thresh, c.maxval, p->gscratch, n, st, prof);
         }
-        if (c.dtype == VA_U8 && p->fused) {
-            if (p->mfma)
-                rc = launch_gauss_mfma_u8((const uint8_t *)cur, (uint8_t *)filtered_out, masks ? bits[0] : nullptr,
-                                          c.thresh, n, c.height, c.width, p->tq, st);
-            else
-                rc = launch_gauss_fused_u8((const uint8_t *)cur, (uint8_t *)filtered_out, masks ? bits[0] : nullptr,
-                                           c.thresh, n, c.height, c.width, p->tq, st);
-            if (rc)
-                return rc;
-            have_bits = masks;
-            cur = filtered_out;  // may be NULL; not needed any more when have_bits
-            VA_MARK(p->mfma ? "gauss_mfma" : "gauss_fused");
-        } else {
-            void *dst = filtered_out ? filtered_out : p->blur;
-            if (c.dtype == VA_U8 && p->planes_wp)
-                rc = blur_u8_planes((const uint8_t *)cur, (uint8_t *)dst, n, c.height, c.width,
-                                    p->planes_wp, c.channels, p->tq, p->gscratch, st);
-            else if (c.dtype == VA_U8)
-                rc = launch_gauss_generic_u8((const uint8_t *)cur, (uint8_t *)dst,
-                                             p->gscratch, n, c.height, c.width,
-                                             c.channels, p->tq, st);
-            else if (gauss_f32_fast_supported(c.width, c.channels, p->tf))
-                rc = launch_gauss_f32_fast((const float *)cur, (float *)dst, (float *)p->gscratch, n,
-                                           c.height, c.width, c.channels, p->tf, st);
-            else
-                rc = launch_gauss_generic_f32((const float *)cur, (float *)dst,
-                                              (float *)p->gscratch, n, c.height, c.width,
-                                              c.channels, p->tf, st);
-            if (rc)
-                return rc;
-            cur = dst;
-            VA_MARK(c.dtype == VA_U8 ? (p->planes_wp ? "gauss_planes" : "gauss_generic")
-                                     : (gauss_f32_fast_supported(c.width, c.channels, p->tf) ? "gauss_f32"
-                                                                                             : "gauss_generic"));
-        }
+        uint32_t *gbits = masks && p->gauss.single_pass() ? bits[0] : nullptr;
+        void *dst = filtered_out ? filtered_out : p->blur;      // (a single pass has no blur buffer)
+        rc = launch_gaussian(p->gauss, cur, dst, gbits, c.thresh, 0, p->gscratch, n, st, prof);
+        if (rc)
+            return rc;
+        have_bits = gbits != nullptr;
+        cur = dst;  // may be NULL after a single pass; not needed any more when have_bits
     } else if (filtered_out) {
         VA_HIP(hipMemcpyAsync(filtered_out, cur, (size_t)n * p->px * esz, hipMemcpyDeviceToDevice,
                               st));

@@ -97,8 +97,7 @@ struct TapsF32 {
 };
 
 // generic (any radius / channel count) two-pass Gaussian through a u16 / f32 scratch in HBM
-// scratch: gauss_generic_u8_scratch_bytes(n*h*w*c, taps) bytes (16-bit row sums while the tap sum allows)
-size_t gauss_generic_u8_scratch_bytes(size_t count, const TapsQ8 &taps);
+// (16-bit row sums while the tap sum allows)
 int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h,
                             int w, int c, const TapsQ8 &taps, hipStream_t st);
 int launch_gauss_generic_f32(const float *src, float *dst, float *scratch, int n, int h, int w,
@@ -134,6 +133,37 @@ bool gauss_mfma_supported(int w, int h, const TapsQ8 &taps);
 // mask8_maxval > 0: dst receives the thresholded mask as bytes (maxval / 0) instead of the blur
 int launch_gauss_mfma_u8(const uint8_t *src, uint8_t *dst, uint32_t *bits, int thresh, int n,
                          int h, int w, const TapsQ8 &taps, hipStream_t st, int mask8_maxval = 0);
+
+// ---- the Gaussian plan (va_gauss.hip): the one place that chooses the kernel family, for the stand-alone
+// calls and the pipeline alike.  Order of preference -- u8: the single pass on the matrix cores, the dot4/dot2
+// single pass (both: one channel, `aligned`), the matrix-core kernel on reflected-padded planes, the generic
+// two passes; f32: [EMA + row pass] + marching column pass (`aligned`), the fast passes, the generic passes.
+enum class GaussFamily { None, U8Mfma, U8Dot, U8Planes, U8Generic, F32Fused, F32Fast, F32Generic };
+struct GaussPlan {
+    GaussFamily family;   // None: no blur (a pipeline with sigma <= 0)
+    int dtype, h, w, c;
+    int wp;               // U8Planes: the plane width
+    TapsQ8 tq;            // u8 families
+    TapsF32 tf;           // f32 families
+    int ksize() const { return family == GaussFamily::None ? 0 : dtype == VA_U8 ? tq.ksize : tf.ksize; }
+    // one kernel and no scratch; it can threshold and pack the bit mask in its epilogue
+    bool single_pass() const { return family == GaussFamily::U8Mfma || family == GaussFamily::U8Dot; }
+    bool byte_mask() const { return family == GaussFamily::U8Mfma; }     // ... or write it as 0 / maxval bytes
+    bool folds_ema() const { return family == GaussFamily::F32Fused; }   // the f32 EMA update in the row pass
+};
+// aligned: the pointers suit the single-pass kernels (u8: src % 16, dst % 4; f32: src % 16); pipelines pass
+// true, their launchers check every run.  valu_hook (va_test_hook_gaussian_u8): the dot4/dot2 single pass in
+// place of the matrix-core one (what it cannot take still goes to the planes).  force: U8Dot / U8Generic pin
+// that family (the stand-alone test hooks; the launcher checks the shape).
+int plan_gaussian(GaussPlan *g, int dtype, int h, int w, int c, double sigma, int tap_rule, bool aligned,
+                  bool valu_hook = false, GaussFamily force = GaussFamily::None);
+size_t gauss_scratch_bytes(const GaussPlan &g, size_t n);    // device scratch of n frames (0: none)
+const char *gauss_plan_name(const GaussPlan &g);             // the pipeline description's name of the family
+// Enqueues the planned kernels and marks their stage on prof (F32Fused marks its row and column passes itself).
+// bits: single pass only; mask8_maxval > 0: byte_mask only; bg: F32Fused's EMA, as in launch_gauss_f32_fused.
+int launch_gaussian(const GaussPlan &g, const void *src, void *dst, uint32_t *bits, int thresh, int mask8_maxval,
+                    void *scratch, int n, hipStream_t st, StageProfiler *prof, const float *bg = nullptr,
+                    float *bg_out = nullptr, int64_t n_seen = 0, double rate = 0.0);
 
 // recip_scratch: bg_scratch_bytes(n) bytes of device memory for the per-frame reciprocals of the
 // division-free running mean of batches above 256 frames (nullptr: the plain-division kernel is used);

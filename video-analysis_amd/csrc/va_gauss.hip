@@ -4,11 +4,9 @@
 //          FilterBlur._process_frame, video/filters.py:388-392           (8-bit fixed point)
 //      and cv2.GaussianBlur(float image, (0,0), sigma), video/analysis/active_contour.py:108
 //
-// Two implementations:
-//   * generic  : any radius <= 127, any channel count; row pass -> scratch in HBM -> column
-//                pass.  Fallback and cross-check.
-//   * fused    : va_gauss_fused.hip -- single channel u8, radius <= 31, LDS-staged, one read
-//                of the input and one write of the output (optionally thresholded + bit-packed).
+// Here: the taps, the generic kernels (any radius <= 127, any channel count; row pass -> scratch
+// in HBM -> column pass; fallback and cross-check) and the Gaussian plan, which picks one of the
+// kernel families (va_common.h, GaussFamily) for every stand-alone call and pipeline.
 #include <math.h>
 
 #include "va_common.h"
@@ -217,11 +215,6 @@ static int taps_sum(const TapsQ8 &taps)
     return sum;
 }
 
-size_t gauss_generic_u8_scratch_bytes(size_t count, const TapsQ8 &taps)
-{
-    return count * (taps_sum(taps) <= 257 ? sizeof(uint16_t) : sizeof(uint32_t));     // row sums <= 255 * sum
-}
-
 int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h,
                             int w, int c, const TapsQ8 &taps, hipStream_t st)
 {
@@ -254,6 +247,110 @@ int launch_gauss_generic_f32(const float *src, float *dst, float *scratch, int n
     gauss_col_f32_generic<<<grid, kBlock, 0, st>>>(scratch, dst, h, w, c, taps, total);
     VA_LAUNCH_CHECK("gauss_col_f32_generic");
     return VA_OK;
+}
+
+// ---------------------------------------------------------------------------- host: plan
+// Frames the matrix-core Gaussian can take after a re-layout: colour frames (the channels are filtered
+// independently, as OpenCV does) and widths that are not a multiple of 16 go through planes (frame, channel,
+// h, wp).  A plane wider than the frame carries the reflected continuation of every row over at least the
+// radius, so its blur is the frame's on the first w columns.  Returns the plane width, or 0 (not applicable).
+static int planes_width(int h, int w, int c, const TapsQ8 &t)
+{
+    const int wp = (w % 16 == 0) ? w : ((w + 16 + 15) / 16) * 16;
+    if (c >= 1 && c <= 4 && wp - w < w && gauss_mfma_supported(wp, h, t))
+        return wp;
+    return 0;
+}
+static int blur_u8_planes(const uint8_t *src, uint8_t *dst, int n, int h, int w, int wp, int c,
+                          const TapsQ8 &t, void *scratch, hipStream_t st)
+{
+    const size_t plane_bytes = (size_t)n * c * h * wp;                   // multiple of 16
+    uint8_t *pin = (uint8_t *)scratch, *pout = pin + plane_bytes;        // both 16-byte aligned
+    int rc = launch_channel_planes(src, pin, n, h, w, wp, c, true, st);
+    if (rc)
+        return rc;
+    rc = launch_gauss_mfma_u8(pin, pout, nullptr, -1, n * c, h, wp, t, st);
+    if (rc)
+        return rc;
+    return launch_channel_planes(pout, dst, n, h, w, wp, c, false, st);
+}
+
+int plan_gaussian(GaussPlan *g, int dtype, int h, int w, int c, double sigma, int tap_rule, bool aligned,
+                  bool valu_hook, GaussFamily force)
+{
+    *g = GaussPlan{GaussFamily::None, dtype, h, w, c};
+    const int rc = dtype == VA_U8 ? gauss_taps_q8(sigma, &g->tq.ksize, g->tq.t, kMaxTaps, tap_rule)
+                                  : gauss_taps_f32(sigma, &g->tf.ksize, g->tf.t, kMaxTaps);
+    if (rc)
+        return rc;
+    if (dtype != VA_U8)
+        g->family = aligned && gauss_f32_fused_supported(h, w, c, g->tf) ? GaussFamily::F32Fused
+                    : gauss_f32_fast_supported(w, c, g->tf)              ? GaussFamily::F32Fast
+                                                                         : GaussFamily::F32Generic;
+    else if (force != GaussFamily::None)
+        g->family = force;
+    else if (c == 1 && aligned && !valu_hook && gauss_mfma_supported(w, h, g->tq))
+        g->family = GaussFamily::U8Mfma;
+    else if (c == 1 && aligned && gauss_fused_supported(w, h, g->tq))
+        g->family = GaussFamily::U8Dot;
+    else if ((g->wp = planes_width(h, w, c, g->tq)))
+        g->family = GaussFamily::U8Planes;
+    else
+        g->family = GaussFamily::U8Generic;
+    return VA_OK;
+}
+
+size_t gauss_scratch_bytes(const GaussPlan &g, size_t n)
+{
+    const size_t count = n * g.h * g.w * g.c;
+    if (g.family == GaussFamily::U8Planes)
+        return 2 * n * g.c * g.h * g.wp;                                    // the planes in and out
+    if (g.family == GaussFamily::U8Generic)
+        return count * (taps_sum(g.tq) <= 257 ? sizeof(uint16_t) : sizeof(uint32_t));     // row sums <= 255 * sum
+    return g.dtype == VA_F32 && g.family != GaussFamily::None ? count * sizeof(float) : 0;   // (single pass: none)
+}
+
+const char *gauss_plan_name(const GaussPlan &g)
+{
+    static const char *const names[] = {"none", "mfma-i8", "fused-lds", "mfma-i8-planes", "generic",
+                                        "f32-ema-row+col-march", "f32-packed", "generic"};    // GaussFamily order
+    return names[(int)g.family];
+}
+
+int launch_gaussian(const GaussPlan &g, const void *src, void *dst, uint32_t *bits, int thresh, int mask8_maxval,
+                    void *scratch, int n, hipStream_t st, StageProfiler *prof, const float *bg, float *bg_out,
+                    int64_t n_seen, double rate)
+{
+    VA_REQUIRE((!bits || g.single_pass()) && (mask8_maxval <= 0 || g.byte_mask()) && (!bg || g.folds_ema()),
+               "gaussian: the planned kernel cannot write the requested output");
+    const uint8_t *s8 = (const uint8_t *)src;
+    const float *sf = (const float *)src;
+    uint8_t *d8 = (uint8_t *)dst;
+    float *df = (float *)dst, *scratch_f = (float *)scratch;
+    auto marked = [&](int rc, const char *stage) {
+        if (rc == VA_OK && prof)
+            prof->mark(stage, st);
+        return rc;
+    };
+    switch (g.family) {
+    case GaussFamily::U8Mfma:
+        return marked(launch_gauss_mfma_u8(s8, d8, bits, thresh, n, g.h, g.w, g.tq, st, mask8_maxval),
+                      mask8_maxval > 0 ? "gauss_mfma_mask8" : "gauss_mfma");
+    case GaussFamily::U8Dot:
+        return marked(launch_gauss_fused_u8(s8, d8, bits, thresh, n, g.h, g.w, g.tq, st), "gauss_fused");
+    case GaussFamily::U8Planes:
+        return marked(blur_u8_planes(s8, d8, n, g.h, g.w, g.wp, g.c, g.tq, scratch, st), "gauss_planes");
+    case GaussFamily::U8Generic:
+        return marked(launch_gauss_generic_u8(s8, d8, scratch, n, g.h, g.w, g.c, g.tq, st), "gauss_generic");
+    case GaussFamily::F32Fused:     // (marks ema_row_f32 or row_f32, then col_f32)
+        return launch_gauss_f32_fused(sf, df, scratch_f, bg, bg_out, n_seen, rate, n, g.h, g.w, g.c, g.tf, st, prof);
+    case GaussFamily::F32Fast:
+        return marked(launch_gauss_f32_fast(sf, df, scratch_f, n, g.h, g.w, g.c, g.tf, st), "gauss_f32");
+    case GaussFamily::F32Generic:
+        return marked(launch_gauss_generic_f32(sf, df, scratch_f, n, g.h, g.w, g.c, g.tf, st), "gauss_generic");
+    default:
+        VA_REQUIRE(false, "gaussian: no kernel planned");
+    }
 }
 
 }  // namespace va
