@@ -50,7 +50,7 @@ extern "C" {
 /* dtypes */
 #define VA_U8 0
 #define VA_F32 1
-#define VA_F64 2 /* targets of va_normalize / va_gaussian_noise only */
+#define VA_F64 2 /* targets of va_normalize / va_gaussian_noise; frames of va_mean_any / va_welford_any */
 #define VA_I16 3 /* int16 frames (FilterTimeDifference's output): va_mean_any / va_welford_any only */
 /* background modes (BUILD-DEFINED FilterBackground; arithmetic of video/analysis/video.py) */
 #define VA_BG_NONE 0
@@ -141,7 +141,8 @@ int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacit
 int va_bg_update(int mode, int dtype, const void *frames_dev, void *diff_out_dev,
                  void *state_dev, int64_t n_seen, double rate, int n, size_t px, void *stream);
 /* measure_mean / measure_mean_std over frames of any dtype the reference meets (video/analysis/video.py:26-55):
- * dtype VA_U8, VA_I16 (FilterTimeDifference's int16) or VA_F32.  NumPy's promotions are kept:
+ * dtype VA_U8, VA_I16 (FilterTimeDifference's int16), VA_F32 or VA_F64 (FilterNormalize's float64 target).
+ * NumPy's promotions are kept:
  * `frame/(n + 1)` is rounded to float32 first for float32 frames, float64 otherwise. */
 int va_mean_any(const void *frames_dev, int dtype, double *mean_dev, int64_t n_seen, int n, size_t px,
                 void *stream);

@@ -602,8 +602,8 @@ int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m
                           size_t px, hipStream_t st)
 {
     VA_REQUIRE(frames && mean, "temporal statistics: NULL argument");
-    VA_REQUIRE(dtype == VA_U8 || dtype == VA_I16 || dtype == VA_F32,
-               "temporal statistics: frames must be uint8, int16 or float32 (dtype code %d)", dtype);
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_I16 || dtype == VA_F32 || dtype == VA_F64,
+               "temporal statistics: frames must be uint8, int16, float32 or float64 (dtype code %d)", dtype);
     if (n <= 0 || px == 0)
         return VA_OK;
     const int grid = cdiv((long long)px, kBlock);
@@ -618,8 +618,10 @@ int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m
         VA_TS(uint8_t);
     else if (dtype == VA_I16)
         VA_TS(int16_t);
-    else
+    else if (dtype == VA_F32)
         VA_TS(float);
+    else
+        VA_TS(double);
 #undef VA_TS
     VA_LAUNCH_CHECK("temporal_stats_kernel");
     return VA_OK;

@@ -11,7 +11,9 @@ namespace {
 
 constexpr int kBlock = 256;
 
-// np.clip(frame, fmin, fmax); (frame - fmin) * alpha + tmin in float64; astype(target)
+// np.clip(frame, fmin, fmax); (frame - fmin) * alpha + tmin; astype(target).  NumPy's types: uint8
+// frames give a uint8 difference and a float64 product; float32 frames stay float32 throughout (the
+// bounds, alpha and tmin are float32 or weak scalars there), whatever the target.
 template <typename SRC, typename DST>
 __global__ void __launch_bounds__(kBlock)
 normalize_kernel(const SRC *__restrict__ src, DST *__restrict__ dst, size_t count, double fmin, double fmax,
@@ -20,6 +22,17 @@ normalize_kernel(const SRC *__restrict__ src, DST *__restrict__ dst, size_t coun
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count)
         return;
+    if (sizeof(SRC) == 4) {
+        const float lo = (float)fmin, hi = (float)fmax;
+        float f = (float)src[i];
+        f = f < lo ? lo : (f > hi ? hi : f);
+        const float v = (f - lo) * (float)alpha + (float)tmin;
+        if (sizeof(DST) == 1)
+            dst[i] = (DST)(int)v;      // astype(uint8): C truncation
+        else
+            dst[i] = (DST)v;
+        return;
+    }
     double f = (double)src[i];
     f = f < fmin ? fmin : (f > fmax ? fmax : f);
     const double v = (f - fmin) * alpha + tmin;

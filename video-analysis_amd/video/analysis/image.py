@@ -93,28 +93,32 @@ class regionprops(object):
         m = self.moments
         a, b, c = m["mu20"], m["mu11"], m["mu02"]
         if a - c == 0:
-            return -math.pi / 4 if b > 0 else math.pi / 4
-        return -math.atan2(2 * b, (a - c)) / 2
+            return -np.pi / 4 if b > 0 else np.pi / 4
+        return -np.arctan2(2 * b, (a - c)) / 2
 
+    # NumPy's sqrt, as in the reference: an eigenvalue that rounding made slightly negative (a
+    # degenerate region such as a slanted line of pixels) gives NaN, not an exception
     @property
     def inertia_tensor_eigvals(self):
         m = self.moments
         a, b, c = m["mu20"] / m["m00"], -m["mu11"] / m["m00"], m["mu02"] / m["m00"]
-        root = math.sqrt(4 * b ** 2 + (a - c) ** 2)
+        root = np.sqrt(4 * b ** 2 + (a - c) ** 2)
         return (a + c) + root, (a + c) - root
 
     @property
     def eccentricity(self):
         e1, e2 = self.inertia_tensor_eigvals
-        return 0 if e1 == 0 else math.sqrt(1 - e2 / e1)
+        return 0 if e1 == 0 else np.sqrt(1 - e2 / e1)
 
     @property
     def major_axis_length(self):
-        return 4 * math.sqrt(self.inertia_tensor_eigvals[0])
+        with np.errstate(invalid="ignore"):
+            return 4 * np.sqrt(self.inertia_tensor_eigvals[0])
 
     @property
     def minor_axis_length(self):
-        return 4 * math.sqrt(self.inertia_tensor_eigvals[1])
+        with np.errstate(invalid="ignore"):
+            return 4 * np.sqrt(self.inertia_tensor_eigvals[1])
 
 
 def detect_peaks(img, include_plateaus=True):

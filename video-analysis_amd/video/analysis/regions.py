@@ -85,15 +85,25 @@ def label(mask, connectivity=4):
 
 
 def find_bounding_box(mask):
-    """[left, top, width, height] of the white region of a mask.  Like the reference it is
-    meant for a single connected region; an empty mask raises IndexError."""
+    """(left, top, width, height) of the white region of a mask, the reference's result for every
+    mask: top / left are the first occupied row / column, and the box ends at the first EMPTY row /
+    column after them (or at the edge).  For a region whose occupied rows and columns are each
+    contiguous -- every connected region -- this is the bounding box; otherwise it stops at the
+    first gap.  The bounding box comes from the GPU's region statistics; the row and column
+    occupancy inside it is a host reduction.  An empty mask raises IndexError."""
     from .. import ops
-    m = (np.asarray(mask) != 0).astype(np.int32)
-    st = ops.region_stats(m, 1)[0]
+    m = np.asarray(mask) != 0
+    st = ops.region_stats(m.astype(np.int32), 1)[0]
     if st[0] == 0:
         raise IndexError("mask is empty")
     xmin, ymin, xmax, ymax = (int(v) for v in st[10:14])
-    return (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1)
+    box = m[ymin:ymax + 1, xmin:xmax + 1]
+
+    def run(occupied):
+        """length of the leading run of occupied rows / columns (the first one is occupied)"""
+        gaps = np.flatnonzero(~occupied)
+        return int(gaps[0]) if len(gaps) else len(occupied)
+    return (xmin, ymin, run(box.any(axis=0)), run(box.any(axis=1)))
 
 
 def get_largest_region(mask, ret_area=False, connectivity=4):

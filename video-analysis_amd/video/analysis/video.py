@@ -13,16 +13,17 @@ def reduce_video(video, function, initial_value=None):
     return result
 
 
-_FRAME_DTYPES = (np.uint8, np.int16, np.float32)
+_FRAME_DTYPES = (np.uint8, np.int16, np.float32, np.float64)
 
 
 def _batches(video, batch):
-    """stacks of `batch` frames; uint8, int16 (FilterTimeDifference) and float32 videos"""
+    """stacks of `batch` frames; uint8, int16 (FilterTimeDifference), float32 and float64
+    (FilterNormalize(dtype=np.float64)) videos"""
     buf = []
     for frame in video:
         frame = np.asarray(frame)
         if frame.dtype not in _FRAME_DTYPES:
-            raise TypeError("the GPU path takes uint8, int16 or float32 frames, got %s" % frame.dtype)
+            raise TypeError("the GPU path takes uint8, int16, float32 or float64 frames, got %s" % frame.dtype)
         buf.append(np.array(frame))
         if len(buf) == batch:
             yield np.stack(buf)
@@ -41,7 +42,7 @@ def measure_mean(video, batch=32):
             if model is None:
                 model = ops.BackgroundModel(video.shape[1:], "mean", dtype=np.uint8)
             model.process(frames, want_diff=False)
-        else:                                   # int16 / float32 frames: NumPy's promotions restated
+        else:                                   # int16 / float32 / float64 frames: NumPy's promotions restated
             mean = ops.running_mean(frames, mean, n)
         n += len(frames)
     if model is not None:

@@ -54,7 +54,8 @@ class FilterFunction(VideoFilterBase):
 class FilterNormalize(VideoFilterBase):
     """maps the colour interval [vmin, vmax] onto the full range of `dtype`
     (reference :76-135): clip, (f - fmin)*alpha + tmin, astype.  uint8 and float32 frames,
-    uint8 / float32 / float64 targets, on the GPU.  (The reference clips the SOURCE frame in
+    uint8 / float32 / float64 targets, on the GPU; float32 frames are computed in float32, uint8
+    frames in float64, as NumPy does.  (The reference clips the SOURCE frame in
     place, `np.clip(..., out=frame)`; the source's frames are left untouched here.)"""
 
     def __init__(self, source, vmin=None, vmax=None, dtype=None):
@@ -76,8 +77,10 @@ class FilterNormalize(VideoFilterBase):
         if self._fmax is None:
             self._fmax = frame.max()
         if self._tmin is None:
+            # the reference's scalar arithmetic: learnt bounds are scalars of the frame's dtype, so
+            # float32 frames get a float32 alpha (and a float32 difference of the bounds)
             self._tmin, tmax = get_color_range(self._dtype)
-            self._alpha = (tmax - self._tmin) / (float(self._fmax) - float(self._fmin))
+            self._alpha = (tmax - self._tmin) / (self._fmax - self._fmin)
         if frame.dtype == np.uint8 and self._dtype == np.uint8:
             out = ops.normalize(frame, self._fmin, self._fmax, self._alpha, self._tmin)
         else:
@@ -598,10 +601,11 @@ class FilterDiffBase(VideoFilterBase):
 
 
 class FilterTimeDifference(FilterDiffBase):
-    """this_frame.astype(int16) - prev_frame (reference :542-568)"""
+    """this_frame.astype(int16) - prev_frame (reference :542-568).  Only dtype=int16 (the default):
+    the reference's dtype=None (uint8 differences that wrap) and other dtypes raise TypeError."""
 
     def __init__(self, source, dtype=np.int16):
-        if dtype is not None and np.dtype(dtype) != np.int16:
+        if dtype is None or np.dtype(dtype) != np.int16:
             raise TypeError("FilterTimeDifference: the GPU path computes int16 differences")
         self._dtype = np.int16
         super(FilterTimeDifference, self).__init__(source)

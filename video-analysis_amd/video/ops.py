@@ -180,19 +180,20 @@ class BackgroundModel(object):
 
 
 TEMPORAL_DTYPES = {np.dtype(np.uint8): _hip.VA_U8, np.dtype(np.int16): _hip.VA_I16,
-                   np.dtype(np.float32): _hip.VA_F32}
+                   np.dtype(np.float32): _hip.VA_F32, np.dtype(np.float64): _hip.VA_F64}
 
 
 def _temporal_frames(frames):
     arr = np.ascontiguousarray(frames)
     if arr.dtype not in TEMPORAL_DTYPES:
-        raise TypeError("temporal statistics take uint8, int16 or float32 frames on the GPU path, got %s" % arr.dtype)
+        raise TypeError("temporal statistics take uint8, int16, float32 or float64 frames on the GPU path, got %s"
+                        % arr.dtype)
     return arr
 
 
 def welford(frames, mean=None, m2=None, n_seen=0):
     """Welford update of measure_mean_std (video/analysis/video.py:48-50); returns (mean, M2).
-    uint8, int16 (FilterTimeDifference) or float32 frames."""
+    uint8, int16 (FilterTimeDifference), float32 or float64 (FilterNormalize's float64 target) frames."""
     arr = _temporal_frames(frames)
     fshape = arr.shape[1:]
     px = int(np.prod(fshape))
@@ -214,7 +215,7 @@ def welford(frames, mean=None, m2=None, n_seen=0):
 
 def running_mean(frames, mean=None, n_seen=0):
     """measure_mean's update `mean*n/(n+1) + frame/(n+1)` (video/analysis/video.py:33) over a batch of
-    uint8 / int16 / float32 frames, NumPy's promotions included; returns the float64 mean"""
+    uint8 / int16 / float32 / float64 frames, NumPy's promotions included; returns the float64 mean"""
     arr = _temporal_frames(frames)
     fshape = arr.shape[1:]
     px = int(np.prod(fshape))
