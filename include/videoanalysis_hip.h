@@ -315,6 +315,28 @@ int va_farthest_points(const uint8_t *mask_dev, int n, int h, int w, const int32
                        int32_t *path_out_dev, int max_points, int32_t *npath_out_dev, void *workspace_dev,
                        size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ A11 dense optical flow
+ * replaces  cv2.calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n,
+ *           poly_sigma, flags) and the magnitude of cv2.cartToPolar, FilterOpticalFlow, video/filters.py:572-589
+ * OpenCV's algorithm with flags = 0, bit for bit as DESIGN.md "Optical flow" pins it (no fused multiply-add).
+ * va_farneback_poly_consts (host only, no GPU needed): FarnebackPrepareGaussian's float g, xg, xxg
+ * (2 poly_n + 1 each, offsets -poly_n..poly_n) and ig_out = ig11, ig03, ig33, ig55. */
+int va_farneback_poly_consts(int poly_n, double poly_sigma, float *g_out, float *xg_out, float *xxg_out,
+                             double *ig_out);
+/* device workspace of va_optical_flow_farneback (0 for arguments it refuses) */
+size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels, int winsize,
+                                    int iterations, int poly_n);
+/* frames_dev: n >= 2 consecutive (h, w) frames, dtype VA_U8 or VA_F32; pair k is (frame k, frame k + 1).
+ * flow_out_dev (nullable): (n - 1, h, w, 2) float32 (dx, dy); mag_out_dev (nullable): (n - 1, h, w) float32
+ * sqrt(dx^2 + dy^2); not both NULL.  pyr_scale in (0, 1), levels >= 0, winsize >= 1, iterations >= 1,
+ * poly_n 5 or 7, flags 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not supported), else
+ * VA_ERR_INVALID; a workspace smaller than va_farneback_workspace_bytes is VA_ERR_RANGE.  The call drains
+ * `stream` before it uploads its resize tables, then enqueues its kernels on it. */
+int va_optical_flow_farneback(const void *frames_dev, int dtype, int n, int h, int w, double pyr_scale,
+                              int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                              float *flow_out_dev, float *mag_out_dev, void *workspace_dev,
+                              size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -987,6 +987,35 @@ int va_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *
                                   npath_out, pairs, visited, default_start, st);
 }
 
+int va_farneback_poly_consts(int poly_n, double poly_sigma, float *g, float *xg, float *xxg, double *ig)
+{
+    VA_REQUIRE(g && xg && xxg && ig, "va_farneback_poly_consts: NULL argument");
+    return farneback_poly_consts(poly_n, poly_sigma, g, xg, xxg, ig);
+}
+
+size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels, int winsize, int iterations,
+                                    int poly_n)
+{
+    if (farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, 0))
+        return 0;
+    return farneback_workspace_bytes(n, h, w, pyr_scale, levels);
+}
+
+int va_optical_flow_farneback(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
+                              int winsize, int iterations, int poly_n, double poly_sigma, int flags, float *flow_out,
+                              float *mag_out, void *ws, size_t ws_bytes, void *stream)
+{
+    VA_ENTER();
+    int rc = farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, flags);
+    if (rc)
+        return rc;
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "optical flow: frames must be VA_U8 or VA_F32 (got dtype %d)", dtype);
+    VA_REQUIRE(frames, "optical flow: NULL frames");
+    VA_REQUIRE(flow_out || mag_out, "optical flow: flow_out and mag_out are both NULL");
+    return launch_optical_flow(frames, dtype, n, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
+                               flow_out, mag_out, ws, ws_bytes, as_stream(stream));
+}
+
 int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
                  int interpolation, void *stream)
 {

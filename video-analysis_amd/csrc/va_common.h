@@ -84,6 +84,8 @@ inline int words_per_row(int w) { return (w + 31) / 32; }
 int gauss_ksize(double sigma, bool is_u8);
 int gauss_taps_q8(double sigma, int *ksize, uint16_t *taps, int cap, int rule = VA_TAPS_CV4);
 int gauss_taps_f32(double sigma, int *ksize, float *taps, int cap);
+// the n double taps of getGaussianKernelBitExact(n, sigma > 0), before any rounding to float
+void gauss_taps_f64(double sigma, int n, double *out);
 
 // ---- launchers (each enqueues on `stream`, returns VA_OK or an error) -------------------
 constexpr int kMaxTaps = 255;  // by-value tap tables in the kernel arguments
@@ -302,8 +304,22 @@ int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, doubl
 size_t resize_scratch_bytes(int sh, int sw, int dh, int dw);
 int launch_resize_u8(const uint8_t *src, uint8_t *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
                      void *scratch, hipStream_t st);
+// stage (float32): Upload puts the tables into scratch with a blocking copy and enqueues nothing; Launch then
+// enqueues the kernel on them without copying -- a caller that runs several geometries on one stream uploads
+// every table first, into disjoint scratch, so that no copy can overtake a kernel still reading its tables
+enum class ResizeStage { Both, Upload, Launch };
 int launch_resize_f32(const float *src, float *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
-                      void *scratch, hipStream_t st);
+                      void *scratch, hipStream_t st, ResizeStage stage = ResizeStage::Both);
+// cv2.calcOpticalFlowFarneback (flags 0) over n frames = n - 1 pairs (va_optflow.hip); g, xg, xxg: 2 poly_n + 1
+// floats (offsets -poly_n..poly_n), ig: ig11, ig03, ig33, ig55.  farneback_check: the argument rules (VA_OK or
+// VA_ERR_INVALID with a message)
+int farneback_poly_consts(int poly_n, double poly_sigma, float *g, float *xg, float *xxg, double ig[4]);
+int farneback_check(int n, int h, int w, double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                    int flags);
+size_t farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels);
+int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
+                        int winsize, int iterations, int poly_n, double poly_sigma, float *flow_out,
+                        float *mag_out, void *ws, size_t ws_bytes, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

@@ -43,6 +43,8 @@ static int taps_f64(double sigma, int n, double *out)
     return 0;
 }
 
+void gauss_taps_f64(double sigma, int n, double *out) { taps_f64(sigma, n, out); }
+
 int gauss_taps_q8(double sigma, int *ksize, uint16_t *taps, int cap, int rule)
 {
     VA_REQUIRE(sigma > 0 && sigma == sigma, "gaussian: sigma must be > 0 (got %g)", sigma);

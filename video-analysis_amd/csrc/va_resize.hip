@@ -406,9 +406,11 @@ size_t resize_scratch_bytes(int sh, int sw, int dh, int dw)
     return ints * 4 + shorts * 2 + tabs * sizeof(DecAlpha) + 1024;
 }
 
+// stage: ResizeStage::Both uploads the tables and launches; Upload only uploads them (nothing is enqueued);
+// Launch only launches, on tables an Upload of the same geometry put into the same scratch before
 template <class T>
 static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
-                         void *scratch, hipStream_t st)
+                         void *scratch, hipStream_t st, ResizeStage stage = ResizeStage::Both)
 {
     constexpr bool F32 = sizeof(T) == 4;
     VA_REQUIRE(src && dst && scratch, "resize: NULL argument");
@@ -416,7 +418,7 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
     VA_REQUIRE(mode >= 0 && mode <= 4, "resize: interpolation must be 0 nearest, 1 linear, 2 cubic, 3 area or 4 lanczos4");
     VA_REQUIRE(dh <= 65535, "resize: target frames of more than 65535 rows are not supported");
     const size_t total = (size_t)n * dh * dw * c;
-    if (total == 0)
+    if (total == 0 && stage != ResizeStage::Upload)
         return VA_OK;
     const double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
     const double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
@@ -425,7 +427,7 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
         for (int a = 0; a < n; a += 65535) {
             const int k = n - a < 65535 ? n - a : 65535;
             int rc = launch_resize<T>(src + (size_t)a * sh * sw * c, dst + (size_t)a * dh * dw * c, k, sh, sw, c, dh, dw, mode,
-                                      scratch, st);
+                                      scratch, st, stage);
             if (rc)
                 return rc;
         }
@@ -444,7 +446,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
         *dev = base + used;
         // (pageable source that dies with this call: a blocking copy -- complete on return; the destination is this
         //  call's own scratch, nothing on the stream uses it yet)
-        VA_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        if (stage != ResizeStage::Launch)
+            VA_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
         used += bytes;
         return VA_OK;
     };
@@ -463,6 +466,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
         void *dx, *dy;
         if ((rc = push(xo.data(), xo.size() * 4, &dx)) || (rc = push(yo.data(), yo.size() * 4, &dy)))
             return rc;
+        if (stage == ResizeStage::Upload)
+            return VA_OK;
         if constexpr (!F32) {
             if (x4) {
                 resize_nn_x4_kernel<<<grid4, kBlock, 0, st>>>(src, dst, (const int *)dx, (const int *)dy, sh, sw, dh, dw);
@@ -481,6 +486,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
         mode = 3;
     if (mode == 3 && scale_x >= 1 && scale_y >= 1) {
         if (area_fast) {
+            if (stage == ResizeStage::Upload)        // (no tables)
+                return VA_OK;
             int wfull = (int)(sw / scale_x);
             wfull = wfull < dw ? wfull : dw;
             if constexpr (F32)
@@ -500,6 +507,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
         if ((rc = push(xt.data(), xt.size() * sizeof(DecAlpha), &dxt)) || (rc = push(xs.data(), xs.size() * 4, &dxs)) ||
             (rc = push(yt.data(), yt.size() * sizeof(DecAlpha), &dyt)) || (rc = push(ys.data(), ys.size() * 4, &dys)))
             return rc;
+        if (stage == ResizeStage::Upload)
+            return VA_OK;
         resize_area_kernel<T><<<grid, kBlock, 0, st>>>(src, dst, (const DecAlpha *)dxt, (const int *)dxs,
                                                       (const DecAlpha *)dyt, (const int *)dys, sh, sw, c, dh, dw, total);
         VA_LAUNCH_CHECK("resize_area_kernel");
@@ -519,6 +528,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
     if constexpr (F32) {
         if ((rc = push(fa.data(), fa.size() * 4, &dia)) || (rc = push(fb.data(), fb.size() * 4, &dib)))
             return rc;
+        if (stage == ResizeStage::Upload)
+            return VA_OK;
 #define VA_F32_TAPS(KS)                                                                                              \
     resize_taps_f32_kernel<KS><<<grid, kBlock, 0, st>>>(src, dst, (const int *)dxo, (const float *)dia, (const int *)dyo, \
                                                        (const float *)dib, xmax, sh, sw, c, dh, dw, total)
@@ -532,6 +543,8 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
     } else {
         if ((rc = push(ia.data(), ia.size() * 2, &dia)) || (rc = push(ib.data(), ib.size() * 2, &dib)))
             return rc;
+        if (stage == ResizeStage::Upload)
+            return VA_OK;
 #define VA_U8_TAPS(KS)                                                                                               \
     do {                                                                                                             \
         if (many_rows)                                                                                               \
@@ -562,9 +575,9 @@ int launch_resize_u8(const uint8_t *src, uint8_t *dst, int n, int sh, int sw, in
 }
 
 int launch_resize_f32(const float *src, float *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
-                      void *scratch, hipStream_t st)
+                      void *scratch, hipStream_t st, ResizeStage stage)
 {
-    return launch_resize<float>(src, dst, n, sh, sw, c, dh, dw, mode, scratch, st);
+    return launch_resize<float>(src, dst, n, sh, sw, c, dh, dw, mode, scratch, st, stage);
 }
 
 }  // namespace va

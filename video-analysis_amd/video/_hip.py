@@ -117,6 +117,9 @@ SIGNATURES = {
     "va_distance_map_i32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "va_distance_map_path": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "va_farthest_points": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "va_farneback_poly_consts": (_i, [_i, _d, _vp, _vp, _vp, _vp]),
+    "va_farneback_workspace_bytes": (_sz, [_i, _i, _i, _d, _i, _i, _i, _i]),
+    "va_optical_flow_farneback": (_i, [_vp, _i, _i, _i, _i, _d, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "va_pipeline_create": (_i, [C.POINTER(va_config), C.POINTER(_vp)]),
     "va_pipeline_destroy": (_i, [_vp]),
     "va_pipeline_run": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -267,3 +270,14 @@ def gauss_taps_f32(sigma):
     ks = C.c_int()
     check(load_library().va_gauss_taps_f32(float(sigma), C.byref(ks), buf.ctypes.data, 256))
     return buf[:ks.value].copy()
+
+
+def farneback_poly_consts(poly_n, poly_sigma):
+    """FarnebackPrepareGaussian (host only): g, xg, xxg (float32, offsets -poly_n..poly_n) and
+    (ig11, ig03, ig33, ig55)"""
+    k = 2 * int(poly_n) + 1 if int(poly_n) in (5, 7) else 15
+    g, xg, xxg = (np.zeros(k, np.float32) for _ in range(3))
+    ig = np.zeros(4, np.float64)
+    check(load_library().va_farneback_poly_consts(int(poly_n), float(poly_sigma), g.ctypes.data, xg.ctypes.data,
+                                                  xxg.ctypes.data, ig.ctypes.data))
+    return g, xg, xxg, tuple(float(v) for v in ig)

@@ -2,7 +2,7 @@
 
 API surface of the reference's video/filters.py (FilterFunction :56, FilterNormalize :76,
 FilterCrop :158, FilterResize :252, FilterMonochrome :348, FilterBlur :378, FilterDiffBase :492,
-FilterTimeDifference :542) plus the BUILD-DEFINED classes the north star names but the
+FilterTimeDifference :542, FilterOpticalFlow :572) plus the BUILD-DEFINED classes the north star names but the
 reference does not contain: FilterBackground, FilterThreshold, FilterMorphology,
 and FilterAnalysisChain, the batched fused form of the whole chain.
 
@@ -614,6 +614,70 @@ class FilterTimeDifference(FilterDiffBase):
         if this_frame.dtype != np.uint8 or prev_frame.dtype != np.uint8:
             raise TypeError("FilterTimeDifference expects uint8 frames")
         return ops.time_difference(this_frame, prev_frame)
+
+
+class FilterOpticalFlow(FilterDiffBase):
+    """frame k = the magnitude of cv2.calcOpticalFlowFarneback(source[k], source[k+1], None, 0.5, 3, 2, 3, 5,
+    1.2, 0), float32 (reference :572-589).  On a seekable source, reads compute `batch` pairs in one call
+    and serve the following frames from it; other sources go pair by pair.  Single-channel frames only
+    (cv2 asserts one channel): colour frames raise ValueError."""
+
+    batch = 32          # pairs per GPU call (seekable sources)
+    params = dict(pyr_scale=0.5, levels=3, winsize=2, iterations=3, poly_n=5, poly_sigma=1.2, flags=0)
+
+    def __init__(self, source):
+        self._cache_start, self._cache = 0, None
+        super(FilterOpticalFlow, self).__init__(source)
+
+    @staticmethod
+    def _mono(frame):
+        frame = np.asarray(frame)
+        if frame.ndim == 3 and frame.shape[2] == 1:
+            frame = frame[..., 0]
+        if frame.ndim != 2:
+            raise ValueError("FilterOpticalFlow: the flow takes single-channel frames, got shape %r"
+                             % (frame.shape,))
+        return frame
+
+    def _compare_frames(self, this_frame, prev_frame):
+        return ops.optical_flow_farneback(np.stack([self._mono(prev_frame), self._mono(this_frame)]),
+                                          **self.params)[0]
+
+    def _batched(self, index):
+        """frame `index` of the filter from the current batch, computing the batch that starts there if needed"""
+        if self._cache is None or not 0 <= index - self._cache_start < len(self._cache):
+            stop = min(self.frame_count, index + max(1, int(self.batch)))
+            frames = np.stack([self._mono(self._source.get_frame(k)) for k in range(index, stop + 1)])
+            self._cache, self._cache_start = None, index
+            self._cache = ops.optical_flow_farneback(frames, **self.params)
+        return self._cache[index - self._cache_start]
+
+    def set_frame_pos(self, index):
+        if not self._source.seekable:
+            return super(FilterOpticalFlow, self).set_frame_pos(index)
+        if index < 0:
+            index += self.frame_count
+        if not 0 <= index < self.frame_count:
+            raise IndexError("Seeking to frame %d was not possible." % index)
+        self._frame_pos = index
+
+    def get_frame(self, index):
+        if not self._source.seekable:
+            return super(FilterOpticalFlow, self).get_frame(index)
+        if index < 0:
+            index += self.frame_count
+        if not 0 <= index < self.frame_count:
+            raise IndexError("frame %d is out of range" % index)
+        return self._process_frame(self._batched(index))
+
+    def get_next_frame(self):
+        if not self._source.seekable:
+            return super(FilterOpticalFlow, self).get_next_frame()
+        if self._frame_pos >= self.frame_count:
+            raise StopIteration
+        out = self._batched(self._frame_pos)
+        self._frame_pos += 1
+        return self._process_frame(out)
 
 
 class _SequentialStateFilter(VideoFilterBase):

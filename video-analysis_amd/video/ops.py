@@ -713,3 +713,55 @@ def image_statistics(img, kernel="box", ksize=5, prior=0.0, exclude_center=False
         for b in (src, dm, dv):
             if b:
                 _give(b)
+
+
+# ------------------------------------------------------------------------ dense optical flow
+OPTFLOW_WORKSPACE_BUDGET = 2 << 30      # device workspace of one call; longer stacks go in overlapping chunks
+
+
+def optical_flow_farneback(frames, pyr_scale=0.5, levels=3, winsize=2, iterations=3, poly_n=5, poly_sigma=1.2,
+                           flags=0, ret_flow=False):
+    """cv2.calcOpticalFlowFarneback(frames[k], frames[k + 1], None, ...) for every consecutive pair of an
+    (n, h, w) stack (n >= 2), and the magnitude of cv2.cartToPolar -- FilterOpticalFlow,
+    video/filters.py:572-589.  uint8 and float32 frames go to the GPU as they are; other real dtypes are
+    converted with astype(float32), as convertTo does.  Returns the magnitudes, (n - 1, h, w) float32, or
+    (flow (n - 1, h, w, 2), magnitudes) with ret_flow=True.  Stacks whose workspace would exceed
+    OPTFLOW_WORKSPACE_BUDGET run in chunks that share one frame; the result does not depend on it."""
+    arr = np.asarray(frames)
+    if arr.ndim != 3:
+        raise ValueError("expected an (n, h, w) stack of single-channel frames, got shape %r" % (arr.shape,))
+    if arr.dtype == np.uint8:
+        dtype = _hip.VA_U8
+    elif arr.dtype == np.float32:
+        dtype = _hip.VA_F32
+    elif arr.dtype.kind in "biuf":
+        arr, dtype = arr.astype(np.float32), _hip.VA_F32
+    else:
+        raise TypeError("optical flow: frames of dtype %s are not supported" % arr.dtype)
+    arr = np.ascontiguousarray(arr)
+    n, h, w = arr.shape
+    args = (float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n))
+    L = _hip.lib()
+    ws_of = lambda k: L.va_farneback_workspace_bytes(k, h, w, *args)
+    if n < 2 or ws_of(2) == 0 or int(flags) != 0:       # let the library name the bad argument
+        check(L.va_optical_flow_farneback(None, dtype, n, h, w, *args, float(poly_sigma), int(flags), None, None,
+                                          None, 0, None))
+    per_pair = ws_of(3) - ws_of(2)
+    pairs = max(1, min(n - 1, (OPTFLOW_WORKSPACE_BUDGET - ws_of(2)) // per_pair + 1))
+    mag = np.empty((n - 1, h, w), np.float32)
+    flow = np.empty((n - 1, h, w, 2), np.float32) if ret_flow else None
+    for a in range(0, n - 1, pairs):
+        k = min(pairs, n - 1 - a)
+        ws_bytes = ws_of(k + 1)
+        bufs = [_upload(arr[a:a + k + 1]), _take(k * h * w * 4), _take(k * h * w * 8) if ret_flow else None,
+                _take(ws_bytes)]
+        src, mb, fb, ws = bufs
+        try:
+            check(L.va_optical_flow_farneback(src.ptr, dtype, k + 1, h, w, *args, float(poly_sigma), 0,
+                                              fb.ptr if fb else None, mb.ptr, ws.ptr, ws_bytes, None))
+            mag[a:a + k] = mb.download((k, h, w), np.float32)
+            if ret_flow:
+                flow[a:a + k] = fb.download((k, h, w, 2), np.float32)
+        finally:
+            _give(*bufs)
+    return (flow, mag) if ret_flow else mag
