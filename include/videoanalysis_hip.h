@@ -337,6 +337,33 @@ int va_optical_flow_farneback(const void *frames_dev, int dtype, int n, int h, i
                               float *flow_out_dev, float *mag_out_dev, void *workspace_dev,
                               size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ A12 active contours
+ * replaces  cv2.Sobel(p, cv2.CV_64F, 1, 0, ksize=5) and cv2.Sobel(p, cv2.CV_64F, 0, 1, ksize=5),
+ *           ActiveContour.set_potential, video/analysis/active_contour.py:109-110
+ * src_dev: (n, h, w) frames of dtype VA_U8 or VA_F32 (the blurred potential: va_gaussian_u8 / va_gaussian_f32
+ * before it).  fx_out_dev, fy_out_dev (nullable, not both): (n, h, w) float64, OpenCV's FilterEngine
+ * arithmetic with a CV_64F kernel and BORDER_REFLECT_101, -0.0 and +0.0 as it gives them. */
+int va_sobel5_f64(const void *src_dev, int dtype, double *fx_out_dev, double *fy_out_dev, int n, int h, int w,
+                  void *stream);
+/* replaces  the iteration of ActiveContour.find_contour, video/analysis/active_contour.py:160-191
+ * m contours on an (n, h, w) stack of float64 gradients (h, w >= 2), every iteration of every contour in one
+ * launch.  Per contour c: npts_dev[c] points (<= max_points <= 1024; <= 2 leaves the contour as it is with
+ * 0 iterations), frame_dev[c] its frame, mat_offset_dev[c] the element offset in mats_dev (mats_count
+ * doubles) of its inverse evolution matrix stored TRANSPOSED (element (j, i) = Pinv[i, j]).
+ * anchor_flags_dev (nullable): (m, max_points) u8, bit 0 = x fixed, bit 1 = y fixed, at the value in
+ * anchor_vals_dev (m, max_points, 2) float64.  pts_inout_dev: (m, max_points, 2) float64 (x, y), the
+ * equidistant curve in, the contour out.  An iteration stops the contour when its residual is below
+ * tol_gamma (residual_tolerance*gamma); iterations_out_dev[c] (int32) counts them (-1: an entry out of
+ * range, contour untouched), total_variation_out_dev[c] (float64) = sum |clipped start - end|.  The
+ * matrices of calls whose max_points <= 128 are staged in LDS, longer ones are read from global memory.
+ * Nothing is copied: the call enqueues one kernel on `stream`. */
+int va_active_contour(const double *fx_dev, const double *fy_dev, int n, int h, int w, int m, int max_points,
+                      const int32_t *npts_dev, const int32_t *frame_dev, const double *mats_dev,
+                      const int64_t *mat_offset_dev, int64_t mats_count, const uint8_t *anchor_flags_dev,
+                      const double *anchor_vals_dev, double gamma, double tol_gamma, int max_iterations,
+                      double *pts_inout_dev, int32_t *iterations_out_dev, double *total_variation_out_dev,
+                      void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -1016,6 +1016,43 @@ int va_optical_flow_farneback(const void *frames, int dtype, int n, int h, int w
                                flow_out, mag_out, ws, ws_bytes, as_stream(stream));
 }
 
+int va_sobel5_f64(const void *src, int dtype, double *fx_out, double *fy_out, int n, int h, int w, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "va_sobel5_f64: frames must be VA_U8 or VA_F32 (got dtype %d)",
+               dtype);
+    VA_REQUIRE(src && (fx_out || fy_out), "va_sobel5_f64: NULL frames, or fx_out and fy_out both NULL");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && (size_t)h * w < kMaxFramePixels, "va_sobel5_f64: bad shape (%d, %d, %d)",
+               n, h, w);
+    if (n == 0)
+        return VA_OK;
+    return launch_sobel5_f64(src, dtype, fx_out, fy_out, n, h, w, as_stream(stream));
+}
+
+int va_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
+                      const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_offset,
+                      int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
+                      double tol_gamma, int max_iterations, double *pts_inout, int32_t *iterations_out,
+                      double *total_variation_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n > 0 && h >= 2 && w >= 2 && (size_t)h * w < kMaxFramePixels,
+               "va_active_contour: bad gradient shape (%d, %d, %d): frames need h, w >= 2", n, h, w);
+    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
+               "va_active_contour: bad contour table (%d contours of up to %d points; at most %d points)", m,
+               max_points, kSnakeMaxN);
+    VA_REQUIRE(max_iterations >= 1, "va_active_contour: max_iterations must be >= 1 (got %d)", max_iterations);
+    VA_REQUIRE(mats_count >= 0, "va_active_contour: negative matrix table size");
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(fx && fy && npts && frame && mats && mat_offset && pts_inout && iterations_out && total_variation_out,
+               "va_active_contour: NULL argument");
+    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour: anchor flags without anchor values");
+    return launch_active_contour(fx, fy, n, h, w, m, max_points, npts, frame, mats, mat_offset, mats_count,
+                                 anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts_inout,
+                                 iterations_out, total_variation_out, as_stream(stream));
+}
+
 int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
                  int interpolation, void *stream)
 {

@@ -320,6 +320,17 @@ size_t farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int leve
 int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
                         int winsize, int iterations, int poly_n, double poly_sigma, float *flow_out,
                         float *mag_out, void *ws, size_t ws_bytes, hipStream_t st);
+// ActiveContour (va_snake.hip): both 5-tap Sobel planes in float64, and every iteration of m snakes in one
+// launch.  Contours of up to kSnakeLdsMaxN points keep their matrix in LDS, longer ones read it from global
+// memory; kSnakeMaxN is the longest contour a call takes
+constexpr int kSnakeLdsMaxN = 128;
+constexpr int kSnakeMaxN = 1024;
+int launch_sobel5_f64(const void *src, int dtype, double *fx, double *fy, int n, int h, int w, hipStream_t st);
+int launch_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
+                          const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_off,
+                          int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
+                          double tol_gamma, int max_iterations, double *pts, int32_t *iterations,
+                          double *total_variation, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

@@ -120,6 +120,9 @@ SIGNATURES = {
     "va_farneback_poly_consts": (_i, [_i, _d, _vp, _vp, _vp, _vp]),
     "va_farneback_workspace_bytes": (_sz, [_i, _i, _i, _d, _i, _i, _i, _i]),
     "va_optical_flow_farneback": (_i, [_vp, _i, _i, _i, _i, _d, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    "va_sobel5_f64": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "va_active_contour": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _d, _d, _i, _vp,
+                               _vp, _vp, _vp]),
     "va_pipeline_create": (_i, [C.POINTER(va_config), C.POINTER(_vp)]),
     "va_pipeline_destroy": (_i, [_vp]),
     "va_pipeline_run": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

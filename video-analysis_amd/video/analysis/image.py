@@ -1,6 +1,6 @@
 """Image operations: region properties from image moments, morphology, statistics.
 
-Reference: video/analysis/image.py -- set_image_border :205-210, regionprops :310-405.
+Reference: video/analysis/image.py -- subpixel(s) :23-57, set_image_border :205-210, regionprops :310-405.
 The ten spatial moments are accumulated on the GPU from run segments (exact integers); the
 central / normalised moments and the derived scalars are the reference's formulas evaluated in
 float64 on the host (a few dozen flops per region).
@@ -18,6 +18,43 @@ def set_image_border(img, size=1, color=0):
     img[-size:, :] = color
     img[:, :size] = color
     img[:, -size:] = color
+
+
+def subpixel(img, pt):
+    """gets image intensities at a single point with sub pixel accuracy (image.py:23-38)"""
+    x, y = pt
+    xi = int(x)
+    yi = int(y)
+    dx = x - xi
+    dy = y - int(y)
+
+    weight_tl = (1.0 - dx) * (1.0 - dy)
+    weight_tr = (dx) * (1.0 - dy)
+    weight_bl = (1.0 - dx) * (dy)
+    weight_br = (dx) * (dy)
+    return (weight_tl * img[yi, xi] +
+            weight_tr * img[yi, xi + 1] +
+            weight_bl * img[yi + 1, xi] +
+            weight_br * img[yi + 1, xi + 1])
+
+
+def subpixels(img, pts):
+    """gets image intensities of multiple points with sub pixel accuracy (image.py:42-57); the snake
+    kernel of ActiveContour gathers its forces with this arithmetic"""
+    x, y = pts[:, 0], pts[:, 1]
+    xi = x.astype(np.int64)
+    yi = y.astype(np.int64)
+    dx = x - xi
+    dy = y - yi
+
+    weight_tl = (1.0 - dx) * (1.0 - dy)
+    weight_tr = (dx) * (1.0 - dy)
+    weight_bl = (1.0 - dx) * (dy)
+    weight_br = (dx) * (dy)
+    return (weight_tl * img[yi, xi] +
+            weight_tr * img[yi, xi + 1] +
+            weight_bl * img[yi + 1, xi] +
+            weight_br * img[yi + 1, xi + 1])
 
 
 def moments_from_spatial(spatial):

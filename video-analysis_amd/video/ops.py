@@ -765,3 +765,96 @@ def optical_flow_farneback(frames, pyr_scale=0.5, levels=3, winsize=2, iteration
         finally:
             _give(*bufs)
     return (flow, mag) if ret_flow else mag
+
+
+# ------------------------------------------------------------------------------- active contours
+SNAKE_MAX_POINTS = 1024          # kSnakeMaxN: the longest contour va_active_contour takes
+
+
+def _potential_stack(frames):
+    """(contiguous (n, h, w) uint8 / float32 array, VA dtype) for the Sobel pass"""
+    arr = np.asarray(frames)
+    if arr.dtype not in (np.uint8, np.float32):
+        raise TypeError("active contour potentials must be uint8 or float32, got %s" % arr.dtype)
+    if arr.ndim == 2:
+        arr = arr[None]
+    if arr.ndim != 3:
+        raise ValueError("expected an (h, w) potential or an (n, h, w) stack, got shape %r" % (arr.shape,))
+    return np.ascontiguousarray(arr), (_hip.VA_U8 if arr.dtype == np.uint8 else _hip.VA_F32)
+
+
+def potential_gradients(frames, sigma=0.0, stream=None):
+    """ActiveContour.set_potential's dense part on the device (video/analysis/active_contour.py:104-110):
+    cv2.GaussianBlur(p, (0, 0), sigma) when sigma > 0 (va_gaussian_u8 / va_gaussian_f32, the taps FilterBlur
+    uses), then cv2.Sobel(p, CV_64F, 1, 0, ksize=5) and (0, 1).  frames: (h, w) or (n, h, w), uint8 or float32.
+    Returns (fx, fy, (n, h, w)) with fx and fy float64 DeviceBuffers that the caller owns."""
+    arr, dtype = _potential_stack(frames)
+    n, h, w = arr.shape
+    L = _hip.lib()
+    fx, fy = DeviceBuffer(arr.nbytes * (8 // arr.itemsize)), DeviceBuffer(arr.nbytes * (8 // arr.itemsize))
+    src = _upload(arr, stream)
+    blur = None
+    try:
+        if sigma > 0 and n:
+            blur = _take(arr.nbytes)
+            fn = L.va_gaussian_u8 if dtype == _hip.VA_U8 else L.va_gaussian_f32
+            check(fn(src.ptr, blur.ptr, n, h, w, 1, float(sigma), stream))
+        check(L.va_sobel5_f64((blur or src).ptr, dtype, fx.ptr, fy.ptr, n, h, w, stream))
+        check(L.va_stream_sync(stream))
+    except Exception:
+        fx.free()
+        fy.free()
+        raise
+    finally:
+        _give(src, blur)
+    return fx, fy, (n, h, w)
+
+
+def sobel5_f64(frames, dx=True, dy=True):
+    """cv2.Sobel(frame, cv2.CV_64F, 1, 0, ksize=5) and cv2.Sobel(frame, cv2.CV_64F, 0, 1, ksize=5) of uint8 or
+    float32 frames, (h, w) or (n, h, w); returns (fx, fy), float64 arrays of the input's shape (None for a
+    plane not asked for)"""
+    frames = np.asarray(frames)
+    arr, dtype = _potential_stack(frames)
+    n, h, w = arr.shape
+    L = _hip.lib()
+    src = _upload(arr)
+    bx = _take(arr.size * 8) if dx else None
+    by = _take(arr.size * 8) if dy else None
+    try:
+        check(L.va_sobel5_f64(src.ptr, dtype, bx.ptr if bx else None, by.ptr if by else None, n, h, w, None))
+        return tuple(b.download(arr.shape, np.float64).reshape(frames.shape) if b else None for b in (bx, by))
+    finally:
+        _give(src, bx, by)
+
+
+def active_contour(fx, fy, shape, points, npoints, frames, mats, mat_offsets, anchor_flags, anchor_vals, gamma,
+                   tol_gamma, max_iterations, stream=None):
+    """every iteration of m snakes in one launch (ActiveContour.find_contour's loop, active_contour.py:160-191).
+    fx, fy: float64 DeviceBuffers of `shape` = (n, h, w) (potential_gradients).  points: (m, max_points, 2)
+    float64 equidistant curves, npoints (m,) their lengths, frames (m,) their frames; mats: the flat float64
+    table of TRANSPOSED inverse evolution matrices, mat_offsets (m,) the element offset of each contour's;
+    anchor_flags (m, max_points) uint8 (bit 0: x fixed, bit 1: y fixed) or None, anchor_vals (m, max_points, 2).
+    Returns (points, iterations, total_variation).  Every upload waits for `stream`'s earlier work
+    (va_memcpy_h2d), so back-to-back calls on one stream cannot overwrite inputs still in use."""
+    n, h, w = shape
+    pts = np.ascontiguousarray(points, np.float64)
+    m, max_points = pts.shape[:2]
+    L = _hip.lib()
+    host = [pts, np.ascontiguousarray(npoints, np.int32), np.ascontiguousarray(frames, np.int32),
+            np.ascontiguousarray(mats, np.float64), np.ascontiguousarray(mat_offsets, np.int64)]
+    if anchor_flags is not None:
+        host += [np.ascontiguousarray(anchor_flags, np.uint8), np.ascontiguousarray(anchor_vals, np.float64)]
+    bufs = [_upload(a, stream) for a in host]
+    it_buf, tv_buf = _take(max(m, 1) * 4), _take(max(m, 1) * 8)
+    try:
+        pb, nb, fb, mb, ob = bufs[:5]
+        ab, vb = bufs[5:] if anchor_flags is not None else (None, None)
+        check(L.va_active_contour(fx.ptr, fy.ptr, n, h, w, m, max_points, nb.ptr, fb.ptr, mb.ptr, ob.ptr,
+                                  host[3].size, ab.ptr if ab else None, vb.ptr if vb else None, float(gamma),
+                                  float(tol_gamma), int(max_iterations), pb.ptr, it_buf.ptr, tv_buf.ptr, stream))
+        return (pb.download(pts.shape, np.float64, stream), it_buf.download((m,), np.int32, stream),
+                tv_buf.download((m,), np.float64, stream))
+    finally:
+        _give(*bufs)
+        _give(it_buf, tv_buf)
