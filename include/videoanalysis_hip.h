@@ -364,6 +364,41 @@ int va_active_contour(const double *fx_dev, const double *fy_dev, int n, int h, 
                       double *pts_inout_dev, int32_t *iterations_out_dev, double *total_variation_out_dev,
                       void *stream);
 
+/* ------------------------------------------------------------------ A13 polygons
+ * Limits of one polygon / mask of the two calls below (beyond them its status is VA_ERR_RANGE):
+ * fill: 1 .. VA_FILL_MAX_VERTS vertices, box sides 0 .. VA_FILL_MAX_SIDE, every vertex within
+ * +-VA_FILL_MAX_COORD of its box's origin (so that x << 16 and (y - y0)*dx stay far inside int64);
+ * distance transform: width 0 .. VA_DT_MAX_WIDTH, height 0 .. VA_DT_MAX_HEIGHT (its unsigned sums
+ * INIT_DIST0 + (rows + 1)*65536 + 143976 stay below 2^32). */
+#define VA_FILL_MAX_VERTS 1024
+#define VA_FILL_MAX_SIDE 16384
+#define VA_FILL_MAX_COORD (1 << 20)
+#define VA_DT_MAX_WIDTH 4096
+#define VA_DT_MAX_HEIGHT 16384
+/* replaces  cv2.fillPoly(mask, [contour], color=1, offset=(-x, -y)) with lineType LINE_8, shift 0,
+ *           Polygon.get_mask, video/analysis/shapes.py:577-597
+ * m polygons, each drawn into its own (h, w) box of a ragged packed buffer.  verts_dev: int32 (x, y)
+ * vertices of all polygons; polygon i owns vertices vert_off_dev[i] .. vert_off_dev[i + 1] - 1
+ * (int64, m + 1 entries, within 0 .. nverts).  boxes_dev: (m, 4) int32 (x, y, w, h): the box's origin
+ * in vertex coordinates and its size.  out_off_dev[i] (int64): element offset of box i in out_dev,
+ * which holds out_elems elements of elem_size bytes (1: uint8, 4: int32).  Every pixel of a box is
+ * written: 1 inside (OpenCV's scanline fill and the edges' 8-connected lines), 0 else.
+ * status_dev[i] (int32): VA_OK, or VA_ERR_RANGE for a polygon beyond the limits (its box is not
+ * written).  Nothing is copied: the call enqueues one kernel on `stream`. */
+int va_fill_poly(const int32_t *verts_dev, const int64_t *vert_off_dev, int64_t nverts, const int32_t *boxes_dev,
+                 const int64_t *out_off_dev, int64_t out_elems, int m, int elem_size, void *out_dev,
+                 int32_t *status_dev, void *stream);
+/* replaces  cv2.distanceTransform(mask, cv2.DIST_L2, 5) (float32 output),
+ *           Polygon.get_centerline_optimized, video/analysis/shapes.py:742
+ * m uint8 masks (non-zero = foreground) of a ragged packed buffer: mask i is (shapes_dev[2i],
+ * shapes_dev[2i + 1]) = (h, w) at element offset offsets_dev[i] (int64) of masks_dev, and its
+ * float32 distances go to the same offset of out_dev; both buffers hold `total` elements.  max_w:
+ * the widest mask of the call (<= VA_DT_MAX_WIDTH; it sizes the LDS).  OpenCV's
+ * distanceTransform_5x5, both passes in its order; a mask without background gives
+ * DIST_MAX / 65536 everywhere.  status_dev[i]: VA_OK or VA_ERR_RANGE (mask not written). */
+int va_distance_transform_l2_5(const uint8_t *masks_dev, const int32_t *shapes_dev, const int64_t *offsets_dev,
+                               int64_t total, int m, int max_w, float *out_dev, int32_t *status_dev, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -1053,6 +1053,38 @@ int va_active_contour(const double *fx, const double *fy, int n, int h, int w, i
                                  iterations_out, total_variation_out, as_stream(stream));
 }
 
+int va_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
+                 const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
+                 void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && nverts >= 0 && out_elems >= 0, "va_fill_poly: negative count (m %d, nverts %lld, out %lld)",
+               m, (long long)nverts, (long long)out_elems);
+    VA_REQUIRE(elem_size == 1 || elem_size == 4, "va_fill_poly: elem_size must be 1 (uint8) or 4 (int32), got %d",
+               elem_size);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(vert_off && boxes && out_off && status && (verts || nverts == 0) && (out || out_elems == 0),
+               "va_fill_poly: NULL argument");
+    return launch_fill_poly(verts, vert_off, nverts, boxes, out_off, out_elems, m, elem_size, out, status,
+                            as_stream(stream));
+}
+
+int va_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
+                               int m, int max_w, float *out, int32_t *status, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_distance_transform_l2_5: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_w >= 0 && max_w <= kDtMaxWidth, "va_distance_transform_l2_5: max_w %d outside 0 .. %d", max_w,
+               kDtMaxWidth);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(shapes && offsets && status && ((masks && out) || total == 0),
+               "va_distance_transform_l2_5: NULL argument");
+    return launch_distance_transform_l2_5(masks, shapes, offsets, total, m, max_w, out, status, as_stream(stream));
+}
+
 int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
                  int interpolation, void *stream)
 {

@@ -331,6 +331,17 @@ int launch_active_contour(const double *fx, const double *fy, int n, int h, int 
                           int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
                           double tol_gamma, int max_iterations, double *pts, int32_t *iterations,
                           double *total_variation, hipStream_t st);
+// Polygons (va_polygon.hip): batched cv2.fillPoly and cv2.distanceTransform(DIST_L2, 5), one workgroup per item
+constexpr int kFillMaxVerts = VA_FILL_MAX_VERTS;
+constexpr int kPolyMaxSide = VA_FILL_MAX_SIDE;
+constexpr int64_t kPolyMaxCoord = VA_FILL_MAX_COORD;
+constexpr int kDtMaxWidth = VA_DT_MAX_WIDTH;
+constexpr int kDtMaxHeight = VA_DT_MAX_HEIGHT;
+int launch_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
+                     const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
+                     hipStream_t st);
+int launch_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets,
+                                   int64_t total, int m, int max_w, float *out, int32_t *status, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

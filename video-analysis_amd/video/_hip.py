@@ -123,6 +123,8 @@ SIGNATURES = {
     "va_sobel5_f64": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "va_active_contour": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _d, _d, _i, _vp,
                                _vp, _vp, _vp]),
+    "va_fill_poly": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "va_distance_transform_l2_5": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "va_pipeline_create": (_i, [C.POINTER(va_config), C.POINTER(_vp)]),
     "va_pipeline_destroy": (_i, [_vp]),
     "va_pipeline_run": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

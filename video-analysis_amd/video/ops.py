@@ -858,3 +858,104 @@ def active_contour(fx, fy, shape, points, npoints, frames, mats, mat_offsets, an
     finally:
         _give(*bufs)
         _give(it_buf, tv_buf)
+
+
+# ------------------------------------------------------------------------------------------ polygons
+FILL_MAX_VERTS = 1024            # VA_FILL_MAX_VERTS .. VA_DT_MAX_HEIGHT, include/videoanalysis_hip.h
+FILL_MAX_SIDE = 16384
+FILL_MAX_COORD = 1 << 20
+DT_MAX_WIDTH = 4096
+DT_MAX_HEIGHT = 16384
+
+
+def _check_status(status, what):
+    bad = np.flatnonzero(status != 0)
+    if len(bad):
+        raise ValueError("%s: item %d is beyond the kernel's limits (status %d)" % (what, bad[0], status[bad[0]]))
+
+
+def fill_polys(contours, boxes, dtype=np.uint8, stream=None):
+    """cv2.fillPoly(np.zeros((h, w), dtype), [contour], color=1, offset=(-x, -y)) for every polygon of a list, in
+    one launch (Polygon.get_mask, video/analysis/shapes.py:586-592; lineType LINE_8, shift 0).  contours: (k, 2)
+    integer (x, y) vertices per polygon; boxes: one (x, y, w, h) per polygon, the box's origin in vertex
+    coordinates and its size; dtype uint8 or int32.  Returns the list of (h, w) masks (0 / 1)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.uint8, np.int32):
+        raise TypeError("fill_polys: masks are uint8 or int32, got %s" % dtype)
+    m = len(contours)
+    bx = np.asarray(boxes, np.int64).reshape(-1, 4) if m else np.zeros((0, 4), np.int64)
+    if len(bx) != m:
+        raise ValueError("fill_polys: need one box per contour (%d contours, %d boxes)" % (m, len(bx)))
+    if m == 0:
+        return []
+    polys = []
+    for k, c in enumerate(contours):
+        c = np.asarray(c)
+        if not np.issubdtype(c.dtype, np.integer):
+            raise TypeError("fill_polys: contour %d must hold integer vertices, got %s" % (k, c.dtype))
+        c = c.reshape(-1, 2).astype(np.int64)
+        if not 1 <= len(c) <= FILL_MAX_VERTS:
+            raise ValueError("fill_polys: contour %d has %d vertices (1 .. %d are supported)"
+                             % (k, len(c), FILL_MAX_VERTS))
+        if np.any(np.abs(c - bx[k, :2]) > FILL_MAX_COORD) or np.any(np.abs(c) >= 2 ** 31):
+            raise ValueError("fill_polys: contour %d has a vertex more than %d px from its box" % (k, FILL_MAX_COORD))
+        polys.append(c)
+    if np.any(bx[:, 2:] < 0):
+        raise ValueError("negative dimensions are not allowed")
+    if np.any(bx[:, 2:] > FILL_MAX_SIDE) or np.any(np.abs(bx[:, :2]) >= 2 ** 31):
+        raise ValueError("fill_polys: boxes are limited to %d x %d px with int32 origins" % (FILL_MAX_SIDE, FILL_MAX_SIDE))
+    verts = np.ascontiguousarray(np.concatenate(polys), np.int32)
+    vert_off = np.zeros(m + 1, np.int64)
+    vert_off[1:] = np.cumsum([len(c) for c in polys])
+    sizes = bx[:, 2] * bx[:, 3]
+    out_off = np.zeros(m, np.int64)
+    out_off[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    L = _hip.lib()
+    bufs = [_upload(verts, stream), _upload(vert_off, stream), _upload(bx.astype(np.int32), stream),
+            _upload(out_off, stream), _take(max(total, 1) * dtype.itemsize), _take(m * 4)]
+    vb, ob, bb, oob, out, st = bufs
+    try:
+        check(L.va_fill_poly(vb.ptr, ob.ptr, len(verts), bb.ptr, oob.ptr, total, m, dtype.itemsize, out.ptr, st.ptr,
+                             stream))
+        _check_status(st.download((m,), np.int32, stream), "fill_polys")
+        flat = out.download((total,), dtype, stream)
+    finally:
+        _give(*bufs)
+    return [flat[o:o + s].reshape(int(h), int(w)) for o, s, (h, w) in zip(out_off, sizes, bx[:, [3, 2]])]
+
+
+def distance_transform(masks, stream=None):
+    """cv2.distanceTransform(mask, cv2.DIST_L2, 5) (float32) of every mask of a list, in one launch
+    (Polygon.get_centerline_optimized, video/analysis/shapes.py:742).  masks: 2-d arrays, non-zero = foreground,
+    at most DT_MAX_WIDTH columns and DT_MAX_HEIGHT rows.  Returns the list of float32 distance maps."""
+    arrs = []
+    for k, a in enumerate(masks):
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError("distance_transform: mask %d is not 2-d (shape %r)" % (k, a.shape))
+        if a.shape[1] > DT_MAX_WIDTH or a.shape[0] > DT_MAX_HEIGHT:
+            raise ValueError("distance_transform: mask %d of shape %r exceeds %d rows x %d columns"
+                             % (k, a.shape, DT_MAX_HEIGHT, DT_MAX_WIDTH))
+        arrs.append(np.ascontiguousarray(a != 0, np.uint8))
+    m = len(arrs)
+    if m == 0:
+        return []
+    shapes = np.array([a.shape for a in arrs], np.int32).reshape(m, 2)
+    sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
+    offsets = np.zeros(m, np.int64)
+    offsets[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    flat = np.concatenate([a.reshape(-1) for a in arrs]) if total else np.zeros(1, np.uint8)
+    L = _hip.lib()
+    bufs = [_upload(flat, stream), _upload(shapes, stream), _upload(offsets, stream), _take(max(total, 1) * 4),
+            _take(m * 4)]
+    src, sb, ob, out, st = bufs
+    try:
+        check(L.va_distance_transform_l2_5(src.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()), out.ptr,
+                                           st.ptr, stream))
+        _check_status(st.download((m,), np.int32, stream), "distance_transform")
+        res = out.download((max(total, 1),), np.float32, stream)
+    finally:
+        _give(*bufs)
+    return [res[o:o + s].reshape(a.shape) for o, s, a in zip(offsets, sizes, arrs)]
