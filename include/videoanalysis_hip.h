@@ -399,6 +399,55 @@ int va_fill_poly(const int32_t *verts_dev, const int64_t *vert_off_dev, int64_t 
 int va_distance_transform_l2_5(const uint8_t *masks_dev, const int32_t *shapes_dev, const int64_t *offsets_dev,
                                int64_t total, int m, int max_w, float *out_dev, int32_t *status_dev, void *stream);
 
+/* ------------------------------------------------------------------ A14 Guo-Hall thinning
+ * replaces  thinning.guo_hall_thinning(img), the `guo-hall` method of mask_thinning,
+ *           video/analysis/image.py:236-241
+ * The definition ("Guo-Hall thinning"): foreground is img != 0; with p2 .. p9 the neighbours
+ * N, NE, E, SE, S, SW, W, NW of a pixel, a foreground pixel with 1 <= y <= h - 2 and 1 <= x <= w - 2 is
+ * deleted by a sub-iteration iff C == 1, 2 <= min(N1, N2) <= 3 and m == 0, where
+ *   C  = (!p2 & (p3|p4)) + (!p4 & (p5|p6)) + (!p6 & (p7|p8)) + (!p8 & (p9|p2)),
+ *   N1 = (p9|p2) + (p3|p4) + (p5|p6) + (p7|p8),   N2 = (p2|p3) + (p4|p5) + (p6|p7) + (p8|p9),
+ *   m  = (p6 | p7 | !p9) & p8 in sub-iteration 0,  (p2 | p3 | !p5) & p4 in sub-iteration 1,
+ * all of the state before the sub-iteration (parallel deletion).  An iteration is sub-iteration 0 then 1;
+ * iterations repeat until one deletes nothing, and the count includes that last one.  Pixels of the first
+ * and last row and column are never deleted (a mask with h < 3 or w < 3 comes back unchanged, 1 iteration).
+ * The output holds the input's own value where the pixel survives and 0 elsewhere; the input is not
+ * modified (the module thins in place).
+ * Limits: the resident call keeps a mask in LDS at one bit per pixel, rows padded to 32-bit words:
+ * h * ((w + 31) / 32) <= VA_THIN_RESIDENT_MAX_WORDS (60 KiB, so that two workgroups of the largest size
+ * still share a CU's 160 KiB); beyond it the item's status is VA_ERR_RANGE and its box is not written.
+ * The tiled call takes 1 .. 65535 frames of fewer than 2^29 pixels and at most VA_THIN_MAX_ROWS rows (its
+ * grid has one row of tiles per 32 .. 60 image rows), fewer than 2^31 packed words in all; beyond that it
+ * returns VA_ERR_INVALID (va_guo_hall_thinning_scratch_bytes returns 0). */
+#define VA_THIN_RESIDENT_MAX_WORDS 15360
+#define VA_THIN_MAX_SUB_ITERATIONS 16
+#define VA_THIN_MAX_POLL 64
+#define VA_THIN_MAX_ROWS (65535 * 32)
+/* m uint8 masks of a ragged packed buffer, laid out as for va_distance_transform_l2_5: mask i is
+ * (shapes_dev[2i], shapes_dev[2i + 1]) = (h, w) at element offset offsets_dev[i] (int64) of masks_dev,
+ * and its skeleton goes to the same offset of out_dev; both buffers hold `total` elements.  max_words:
+ * the largest h * ((w + 31) / 32) of the call (<= VA_THIN_RESIDENT_MAX_WORDS; it sizes the LDS).  One
+ * workgroup runs a mask to its fixed point; iterations_out_dev[i] (int32) is its iteration count,
+ * status_dev[i] VA_OK or VA_ERR_RANGE.  Nothing is copied: the call enqueues one kernel on `stream`. */
+int va_guo_hall_thinning_batch(const uint8_t *masks_dev, const int32_t *shapes_dev, const int64_t *offsets_dev,
+                               int64_t total, int m, int max_words, uint8_t *out_dev,
+                               int32_t *iterations_out_dev, int32_t *status_dev, void *stream);
+/* scratch of the call below: two bit planes of the stack and the iteration flags */
+size_t va_guo_hall_thinning_scratch_bytes(int n, int h, int w);
+/* the same definition (video/analysis/image.py:236-241) for an (n, h, w) stack of equal-sized uint8
+ * frames of any size: bit planes ping-pong in scratch_dev (va_guo_hall_thinning_scratch_bytes), every
+ * launch advances all tiles by sub_iterations (even, 2 .. VA_THIN_MAX_SUB_ITERATIONS; 0: the default 16)
+ * sub-iterations, and the host reads one changed flag per iteration and frame after every poll_period
+ * (1 .. VA_THIN_MAX_POLL; 0: the default 2) launches -- it synchronises `stream` that often, and stops
+ * after an iteration that deleted nothing in any frame.  dst_dev: (n, h, w) skeletons (enqueued; complete
+ * when `stream` is).  iterations_out (host, nullable): n int32 iteration counts as the definition gives
+ * them.  stats_out (host, nullable): 2 int32, the tile launches and the host reads of this call.
+ * Because it waits for `stream` and copies the flags to the host inside the call, it cannot be captured
+ * into a graph (va_guo_hall_thinning_batch can: it only enqueues). */
+int va_guo_hall_thinning_u8(const uint8_t *src_dev, void *scratch_dev, size_t scratch_bytes, uint8_t *dst_dev,
+                            int n, int h, int w, int sub_iterations, int poll_period, int32_t *iterations_out,
+                            int32_t *stats_out, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

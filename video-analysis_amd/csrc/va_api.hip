@@ -808,6 +808,60 @@ int va_mask_thinning_u8(uint8_t *img, uint8_t *scratch, uint8_t *skel, int h, in
     return VA_OK;
 }
 
+int va_guo_hall_thinning_batch(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
+                               int m, int max_words, uint8_t *out, int32_t *iterations_out, int32_t *status,
+                               void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_guo_hall_thinning_batch: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_words >= 0 && max_words <= kThinResidentMaxWords,
+               "va_guo_hall_thinning_batch: max_words %d outside 0 .. %d", max_words, kThinResidentMaxWords);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(masks && shapes && offsets && out && iterations_out && status,
+               "va_guo_hall_thinning_batch: NULL argument");
+    return launch_guo_hall_resident(masks, shapes, offsets, total, m, max_words, out, iterations_out, status,
+                                    as_stream(stream));
+}
+
+size_t va_guo_hall_thinning_scratch_bytes(int n, int h, int w)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || n > 65535 || h > VA_THIN_MAX_ROWS || (size_t)h * (size_t)w >= kMaxFramePixels ||
+        (size_t)n * h * words_per_row(w) >= ((size_t)1 << 31))
+        return 0;
+    return guo_hall_tiled_scratch_bytes(n, h, w);
+}
+
+int va_guo_hall_thinning_u8(const uint8_t *src, void *scratch, size_t scratch_bytes, uint8_t *dst, int n, int h,
+                            int w, int sub_iterations, int poll_period, int32_t *iterations_out,
+                            int32_t *stats_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && n <= 65535 && h > 0 && w > 0, "va_guo_hall_thinning_u8: bad shape (%d, %d, %d)", n, h, w);
+    VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels,
+               "va_guo_hall_thinning_u8: frames above 2^29 pixels are not supported");
+    // grid.y = ceil(h / (64 - 2 K)) <= 65535 for every K, and the pack / unpack grids count words in 32 bits
+    VA_REQUIRE(h <= VA_THIN_MAX_ROWS, "va_guo_hall_thinning_u8: %d rows, at most %d are supported", h,
+               VA_THIN_MAX_ROWS);
+    VA_REQUIRE((size_t)n * h * words_per_row(w) < ((size_t)1 << 31),
+               "va_guo_hall_thinning_u8: a stack of 2^31 or more packed words is not supported");
+    const int K = sub_iterations ? sub_iterations : 16, poll = poll_period ? poll_period : 2;
+    VA_REQUIRE(K >= 2 && K <= kThinMaxK && K % 2 == 0,
+               "va_guo_hall_thinning_u8: sub_iterations %d is not an even number in 2 .. %d", K, kThinMaxK);
+    VA_REQUIRE(poll >= 1 && poll <= kThinMaxPoll, "va_guo_hall_thinning_u8: poll_period %d outside 1 .. %d", poll,
+               kThinMaxPoll);
+    if (stats_out)
+        stats_out[0] = stats_out[1] = 0;
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(src && scratch && dst, "va_guo_hall_thinning_u8: NULL argument");
+    VA_REQUIRE(scratch_bytes >= guo_hall_tiled_scratch_bytes(n, h, w),
+               "va_guo_hall_thinning_u8: scratch of %zu bytes, %zu needed", scratch_bytes,
+               guo_hall_tiled_scratch_bytes(n, h, w));
+    return run_guo_hall_tiled(src, dst, scratch, n, h, w, K, poll, iterations_out, stats_out, as_stream(stream));
+}
+
 int va_image_statistics_u8(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
                            int w, int kernel, int ksize, double prior, int exclude_center,
                            void *stream)

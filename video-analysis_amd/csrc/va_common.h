@@ -342,6 +342,17 @@ int launch_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nver
                      hipStream_t st);
 int launch_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets,
                                    int64_t total, int m, int max_w, float *out, int32_t *status, hipStream_t st);
+// Guo-Hall thinning (va_thinning.hip): one workgroup per mask in LDS, or K sub-iterations per launch on tiles
+// of bit planes in HBM (scratch: guo_hall_tiled_scratch_bytes; iterations_out / stats_out are host pointers)
+constexpr int kThinResidentMaxWords = VA_THIN_RESIDENT_MAX_WORDS;
+constexpr int kThinMaxK = VA_THIN_MAX_SUB_ITERATIONS;
+constexpr int kThinMaxPoll = VA_THIN_MAX_POLL;
+int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const int64_t *offsets, int64_t total,
+                             int m, int max_words, uint8_t *dst, int32_t *iterations, int32_t *status,
+                             hipStream_t st);
+size_t guo_hall_tiled_scratch_bytes(int n, int h, int w);
+int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
+                       int32_t *iterations_out, int32_t *stats_out, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

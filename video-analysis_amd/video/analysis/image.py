@@ -166,15 +166,19 @@ def detect_peaks(img, include_plateaus=True):
 
 
 def mask_thinning(img, method="auto"):
-    """skeleton of a mask.  Only the reference's `python` method (iterated 3x3-cross
-    erosion/dilation, :243-258) exists on the GPU; 'guo-hall' needs the external `thinning`
-    module in the reference as well and is not provided."""
+    """skeleton (thinned image) of a mask (reference :214-263).
+
+    `method`: 'guo-hall' is thinning.guo_hall_thinning (reference :236-241) on the GPU: a connected, one pixel
+        wide curve that keeps the mask's topology (ops.guo_hall_thinning; DESIGN.md §9 pins the definition).
+        'python' is the reference's fallback of iterated 3x3-cross erosions (:243-258), a different skeleton of
+        disconnected ridge pixels.  'auto' is 'python' here, what the reference does without the `thinning` module;
+        where that module is installed the reference's 'auto' means 'guo-hall', so ask for it by name.
+    Deviation: 'guo-hall' returns a new array and leaves `img` alone (the module thins its argument in place)."""
+    from .. import ops
     if method == "guo-hall":
-        raise ImportError("Using the `guo-hall` method for thinning requires the `thinning` "
-                          "module, which is not part of the GPU path.")
+        return ops.guo_hall_thinning([img])[0]
     if method not in ("auto", "python"):
         raise ValueError("Unknown thinning method `%s`" % method)
-    from .. import ops
     return ops.mask_thinning(img)[0]
 
 

@@ -178,25 +178,26 @@ class Polygon(object):
         masks, offsets = get_masks([self], margin, dtype, ret_offset=True)
         return (masks[0], offsets[0]) if ret_offset else masks[0]
 
-    def get_skeleton(self, ret_offset=False):
+    def get_skeleton(self, ret_offset=False, method="auto"):
         """ gets the binary skeleton image of the polygon (mask_thinning on the GPU, reference :600-616)
 
         `ret_offset` determines whether the coordinates of the upper left point
             of the skeleton mask are returned
+        `method` is mask_thinning's: 'auto' / 'python' (cross erosions) or 'guo-hall'
         """
         from .image import mask_thinning
         if ret_offset:
             mask, offset = self.get_mask(margin=5, ret_offset=True)
         else:
             mask = self.get_mask(ret_offset=False)
-        skeleton = mask_thinning(mask)
+        skeleton = mask_thinning(mask, method)
         if ret_offset:
             return skeleton, offset
         return skeleton
 
-    def get_skeleton_points(self):
+    def get_skeleton_points(self, method="auto"):
         """ returns points along the skeleton of the shape """
-        skeleton, offset = self.get_skeleton(ret_offset=True)
+        skeleton, offset = self.get_skeleton(ret_offset=True, method=method)
         y, x = np.nonzero(skeleton)
         return np.c_[x, y] + offset
 
@@ -303,6 +304,22 @@ def get_masks(polygons, margin=0, dtype=np.uint8, ret_offset=False):
         masks = [m.astype(dtype) for m in masks]
     offsets = [(int(r[0]), int(r[1])) for r in rects]
     return (masks, offsets) if ret_offset else masks
+
+
+def get_skeletons(polygons, method="guo-hall", ret_offset=False):
+    """Polygon.get_skeleton(ret_offset, method) of every polygon of a list: one fill launch for the masks (margin 5
+    with offsets, 0 without, as the reference's get_skeleton, :606-609) and, for 'guo-hall', one thinning call for
+    all of them.  Returns the list of skeletons, and with ret_offset also the list of (x, y) offsets."""
+    from .. import ops
+    from .image import mask_thinning
+    if method not in ("auto", "python", "guo-hall"):
+        raise ValueError("Unknown thinning method `%s`" % method)
+    masks, offsets = get_masks(polygons, 5 if ret_offset else 0, ret_offset=True)
+    if method == "guo-hall":
+        skeletons = ops.guo_hall_thinning(masks)
+    else:
+        skeletons = [mask_thinning(m, method) for m in masks]
+    return (skeletons, offsets) if ret_offset else skeletons
 
 
 def _bucket(shape):

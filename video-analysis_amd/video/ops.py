@@ -959,3 +959,113 @@ def distance_transform(masks, stream=None):
     finally:
         _give(*bufs)
     return [res[o:o + s].reshape(a.shape) for o, s, a in zip(offsets, sizes, arrs)]
+
+
+# ------------------------------------------------------------------------------------ Guo-Hall thinning
+THIN_RESIDENT_MAX_WORDS = 15360  # VA_THIN_RESIDENT_MAX_WORDS: h * ceil(w / 32) of a mask the resident kernel takes
+THIN_RESIDENT_DEFAULT_WORDS = 4096  # larger masks take the tiled path by default: at 15360 words it measured 3.1x faster
+THIN_TILED_SUB_ITERATIONS = 0    # sub-iterations per launch of the tiled path (0: the library's default, 16)
+THIN_TILED_POLL = 0              # launches between two host reads of the changed flags (0: the default, 2)
+
+
+def _thin_words(shape):
+    return int(shape[0]) * ((int(shape[1]) + 31) // 32)
+
+
+def _thin_resident(arrs, stream):
+    """one va_guo_hall_thinning_batch call over 2-d uint8 arrays; (skeletons, int32 iterations)"""
+    m = len(arrs)
+    shapes = np.array([a.shape for a in arrs], np.int32).reshape(m, 2)
+    sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
+    offsets = np.zeros(m, np.int64)
+    offsets[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    flat = np.concatenate([a.reshape(-1) for a in arrs]) if total else np.zeros(1, np.uint8)
+    L = _hip.lib()
+    bufs = [_upload(flat, stream), _upload(shapes, stream), _upload(offsets, stream), _take(max(total, 1)),
+            _take(m * 4), _take(m * 4)]
+    src, sb, ob, out, it, st = bufs
+    try:
+        check(L.va_guo_hall_thinning_batch(src.ptr, sb.ptr, ob.ptr, total, m, max(_thin_words(a.shape) for a in arrs),
+                                           out.ptr, it.ptr, st.ptr, stream))
+        _check_status(st.download((m,), np.int32, stream), "guo_hall_thinning")
+        iters = it.download((m,), np.int32, stream)
+        res = out.download((max(total, 1),), np.uint8, stream)
+    finally:
+        _give(*bufs)
+    return [res[o:o + n].reshape(a.shape) for o, n, a in zip(offsets, sizes, arrs)], iters
+
+
+def _thin_tiled(stack, stream):
+    """va_guo_hall_thinning_u8 on an (n, h, w) uint8 stack with n, h, w >= 1; (skeletons, int32 iterations)"""
+    n, h, w = stack.shape
+    L = _hip.lib()
+    need = L.va_guo_hall_thinning_scratch_bytes(n, h, w)
+    if need == 0:
+        raise ValueError("guo_hall_thinning: a stack of shape %r is beyond the tiled path's limits" % (stack.shape,))
+    iters = np.zeros(n, np.int32)
+    bufs = [_upload(stack, stream), _take(need), _take(stack.size)]
+    src, scratch, dst = bufs
+    try:
+        check(L.va_guo_hall_thinning_u8(src.ptr, scratch.ptr, need, dst.ptr, n, h, w, int(THIN_TILED_SUB_ITERATIONS),
+                                        int(THIN_TILED_POLL), iters.ctypes.data, None, stream))
+        return dst.download(stack.shape, np.uint8, stream), iters
+    finally:
+        _give(*bufs)
+
+
+def guo_hall_thinning(masks, implementation=None, ret_iterations=False, stream=None):
+    """thinning.guo_hall_thinning(mask) -- the `guo-hall` method of mask_thinning, video/analysis/image.py:236-241 --
+    of every mask of a list of 2-d arrays (ragged) or of one (n, h, w) stack; uint8 or bool, non-zero = foreground.
+    The definition is pinned in DESIGN.md §9: parallel sub-iterations until an iteration deletes nothing, the first
+    and last row and column never tested.  Returns uint8 skeletons in the same form (the input's own values where a
+    pixel survives; the inputs are left alone), and with ret_iterations also the int32 iteration counts.
+    implementation: None (masks of up to THIN_RESIDENT_DEFAULT_WORDS packed words run to their fixed point in LDS, one
+    launch per size class of the kernel, at most three; larger ones go through bit planes in HBM, equal shapes stacked), 'resident' or 'tiled'."""
+    if implementation not in (None, "resident", "tiled"):
+        raise ValueError("guo_hall_thinning: unknown implementation %r" % (implementation,))
+    is_stack = isinstance(masks, np.ndarray)
+    if is_stack and masks.ndim != 3:
+        raise ValueError("guo_hall_thinning: expected a list of 2-d masks or an (n, h, w) stack, got shape %r"
+                         % (masks.shape,))
+    arrs = []
+    for k, a in enumerate(masks):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 and a.dtype != np.bool_:
+            raise TypeError("guo_hall_thinning: mask %d has dtype %s (uint8 or bool are supported)" % (k, a.dtype))
+        if a.ndim != 2:
+            raise ValueError("guo_hall_thinning: mask %d is not 2-d (shape %r)" % (k, a.shape))
+        if implementation == "resident" and _thin_words(a.shape) > THIN_RESIDENT_MAX_WORDS:
+            raise ValueError("guo_hall_thinning: mask %d of shape %r needs %d packed words, the resident kernel "
+                             "takes %d" % (k, a.shape, _thin_words(a.shape), THIN_RESIDENT_MAX_WORDS))
+        arrs.append(np.ascontiguousarray(a).view(np.uint8))
+    m = len(arrs)
+    out, iters = [None] * m, np.ones(m, np.int32)
+    resident, tiled = [], {}
+    for k, a in enumerate(arrs):
+        if a.size == 0:                                      # nothing to test: unchanged after one iteration
+            out[k] = a.copy()
+        elif implementation != "tiled" and _thin_words(a.shape) <= (
+                THIN_RESIDENT_MAX_WORDS if implementation == "resident" else THIN_RESIDENT_DEFAULT_WORDS):
+            resident.append(k)
+        else:
+            tiled.setdefault(a.shape, []).append(k)
+    # one launch per size class of the kernel (4 / 16 / 60 words per thread): the LDS and the registers of a launch
+    # are those of its largest mask, so one large mask must not cost the small ones their occupancy
+    classes = {}
+    for k in resident:
+        words = _thin_words(arrs[k].shape)
+        classes.setdefault(0 if words <= 1024 else 1 if words <= 4096 else 2, []).append(k)
+    for idx in classes.values():
+        res, it = _thin_resident([arrs[k] for k in idx], stream)
+        for k, r, i in zip(idx, res, it):
+            out[k], iters[k] = r, i
+    for shape, idx in tiled.items():
+        for a in range(0, len(idx), 65535):
+            part = idx[a:a + 65535]
+            res, it = _thin_tiled(np.stack([arrs[k] for k in part]), stream)
+            for k, r, i in zip(part, res, it):
+                out[k], iters[k] = r, i
+    if is_stack:
+        out = np.stack(out) if m else np.zeros(masks.shape, np.uint8)
+    return (out, iters) if ret_iterations else out
