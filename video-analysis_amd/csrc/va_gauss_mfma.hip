@@ -38,6 +38,22 @@
 //   row:  sum w x = X + 128 S,  X = 256 hi + lo' + 128  (hi = X >> 8 signed, lo' = (X & 255) - 128)
 //   col:  acc = sum w (X + 128 S) = 256 sum w hi + sum w lo' + (128 + 128 S) S
 // i.e. the same integer the oracle accumulates; nothing is rounded before (acc + 2^15) >> 16.
+//
+// Registers and workgroups per CU.  The launch is 8 cdiv(n, 8) cdiv(w, 128) workgroups, 3840 for 256 x 1080p
+// and for 128 x 4K alike: 480 per XCD.  At four workgroups per CU (128 registers) an XCD has 128 slots and
+// runs 3.75 rounds, a quarter of the slots idle in the last one; at five (96 registers) it has 160 and runs
+// exactly 3.  The kernel is bound by its vector issue (about 55 % of the SIMD cycles at four per CU, another
+// 26 % are the MFMAs), so the fifth workgroup only pays if it costs no instructions.  The bit-mask
+// instantiation gets to 96 registers without scratch by
+//   * reading the four Toeplitz fragments from a 4 KB LDS table in every step (four ds_read_b128 on the
+//     LDS port, which has room) instead of holding sixteen registers across the loop,
+//   * loading the halo chunks as one dword per thread (five prefetch registers instead of eight, and no
+//     branch around a load that only one wave issued),
+//   * addressing the loads as a uniform 64-bit base plus one 32-bit register per lane.
+// c_lo stays in sixteen registers as the C operand of the low-byte chain: starting that chain from zero and
+// adding c_lo per element frees them as well, but the sixteen extra vector instructions per step cost what
+// the fifth workgroup returns.  The instantiations with a byte output need 56..112 bytes of
+// scratch at five per CU and stay at four, with the fragments in registers.
 #include "va_common.h"
 
 namespace va {
@@ -58,6 +74,10 @@ constexpr int kTapTable = 128;     // zero-padded tap table, tap i at [48 + i]
 #ifndef GMF_DST_AUX
 #define GMF_DST_AUX 0              // cache policy bits of the u8 output stores (2 = non-temporal)
 #endif
+// workgroups per CU the register allocation aims at (__launch_bounds__): five -- 96 registers -- where the
+// instantiation gets there without scratch, see the header
+constexpr int kWgBits = 5;         // bit mask only (the labelling chains)
+constexpr int kWgBytes = 4;        // u8 blur or byte mask: 56..112 bytes of scratch at five
 constexpr int kFlushTiles = 8;     // mask words are written out every 8 output tiles
 constexpr int kFlushRows = 32 * kFlushTiles;
 static_assert(kFlushRows == kWaves * 64, "one thread per collected row at a flush");
@@ -75,14 +95,17 @@ __device__ __forceinline__ uint32_t bswap32(uint32_t v)
 
 // MASK8 (with HAS_DST): dst receives the thresholded mask as bytes, maxval where blur > thresh and 0
 // elsewhere (the chain that ends at FilterThreshold's uint8 mask: no bit mask, no unpack pass)
-template <bool HAS_DST, bool HAS_BITS, bool MASK8 = false>
-__global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
+template <bool HAS_DST, bool HAS_BITS, bool MASK8 = false, int MIN_WG = 4>
+__global__ __launch_bounds__(kWaves * 64, MIN_WG) void gauss_mfma_kernel(
     const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t *__restrict__ bits,
     int thresh, int h, int w, int w32, int nstrips, int blocks_per_frame, int nframes, MfmaTaps tp,
     int maxval = 255)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_stage[2][32 * kLdsStride];
     __shared__ int8_t s_taps[kTapTable];
+    // at five workgroups per CU the Toeplitz fragments live here and are re-read in every step (see the header)
+    constexpr bool kFragLds = MIN_WG > 4;
+    __shared__ __attribute__((aligned(16))) v4i s_frag[kFragLds ? 4 : 1][64];
     // outputs are collected in LDS and leave as 16-byte pieces: four-byte stores scattered over 32
     // rows per instruction cost this kernel 30 % (measured), although they add no HBM bytes
     __shared__ __attribute__((aligned(16))) uint32_t s_bits[2][kFlushRows][kWaves];        // HAS_BITS
@@ -141,6 +164,14 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
             bcol[ks][g] = (int)wc;
         }
 
+    if (kFragLds && wave == 0) {                         // (visible after the barrier in front of the loop)
+        s_frag[0][lane] = brow[0];
+        s_frag[kFragLds ? 1 : 0][lane] = brow[1];
+        s_frag[kFragLds ? 2 : 0][lane] = bcol[0];
+        s_frag[kFragLds ? 3 : 0][lane] = bcol[1];
+    }
+    int frag_tab = lane * 16;                            // this lane's 16 bytes in each of the four tables
+
     // acc = 256 Yhi + Ylo + k0; the column MFMAs run on the negated taps and start the low
     // chain at c_lo, so that t = (nYhi << 8) + nYlo = acc_min - 1 - acc.
     const int k0 = (128 + 128 * tp.sum) * tp.sum;
@@ -153,11 +184,12 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
 
     // ---- cooperative loads: 32 rows x 10 chunks of 16 B.  load A: thread -> (row tid/8, chunk
     //      tid%8): eight lanes per row read 128 contiguous bytes; load B: the last two chunks of
-    //      every row, issued by every wave alike (identical bytes land on identical LDS
-    //      addresses) so that all waves have the same number of loads in flight.
+    //      every row, one dword per thread (row tid/8, word tid%8 of the 32 bytes): every wave
+    //      has the same two loads in flight, no branch, and the prefetch holds five registers
+    //      (one wave loading the two chunks as 16 bytes per lane held eight in all four).
     const int tid = threadIdx.x;
     const int row_a = tid >> 3, ch_a = tid & 7;
-    const int row_b = lane >> 1, ch_b = 8 + (lane & 1);
+    const int row_b = tid >> 3, ch_b = 8 + ((tid >> 2) & 1), wd_b = tid & 3;
     auto chunk_src = [&](int ch, bool &mir) {            // source column of a chunk (w % 16 == 0)
         const int xc = xb - 16 + 16 * ch;
         mir = xc < 0 || xc >= w;
@@ -165,7 +197,10 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
         return min(max(xs, 0), w - 16);                  // far outside: never used, keep in range
     };
     bool mir_a, mir_b;
-    const int xs_a = chunk_src(ch_a, mir_a), xs_b = chunk_src(ch_b, mir_b);
+    // (load B: a mirrored chunk is its source chunk byte-reversed, i.e. word k is the byte-swapped source
+    //  word 3 - k)
+    const int xs_a = chunk_src(ch_a, mir_a), xs_b0 = chunk_src(ch_b, mir_b);
+    const int xs_b = xs_b0 + 4 * (mir_b ? 3 - wd_b : wd_b);
     const bool border_block = (xb == 0) || (xb + kTileCols + 16 > w);   // workgroup-uniform
 
     auto row_of = [&](int t, int r) {                     // BORDER_REFLECT_101, then clamp
@@ -174,39 +209,34 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
         y = y >= h ? 2 * (h - 1) - y : y;
         return min(max(y, 0), h - 1);
     };
-    auto fetch = [&](int t, u4 &ga, u4 &gb) {
-        const uint8_t *pa, *pb;
+    // (offsets inside a frame are 32-bit -- h * w fits an int, see dst_rsrc -- so that each address is a
+    //  uniform base plus ONE register per lane: as 64-bit pairs they cost three registers more, which
+    //  at 96 is a spill reloaded in every step)
+    const uint32_t off_a = (uint32_t)(row_a * w + xs_a), off_b = (uint32_t)(row_b * w + xs_b);
+    typedef uint32_t u1_unaligned __attribute__((aligned(1)));
+    auto fetch = [&](int t, u4 &ga, uint32_t &gb) {
+        const uint8_t *base = fsrc;
+        uint32_t oa = off_a, ob = off_b;
         if (t >= 1 && 32 * t + 16 <= h) {                // tile inside the frame: add-only
-            const uint8_t *base = fsrc + (size_t)(32 * t - 16) * w;
-            pa = base + (size_t)row_a * w + xs_a;
-            pb = base + (size_t)row_b * w + xs_b;
+            base = fsrc + (size_t)(32 * t - 16) * w;
         } else {
-            pa = fsrc + (size_t)row_of(t, row_a) * w + xs_a;
-            pb = fsrc + (size_t)row_of(t, row_b) * w + xs_b;
+            oa += (uint32_t)((row_of(t, row_a) - row_a) * w);
+            ob += (uint32_t)((row_of(t, row_b) - row_b) * w);
         }
+        const uint8_t *pa = base + oa, *pb = base + ob;
         // straight-line loads (aligned except for mirrored border chunks)
         ga = *reinterpret_cast<const u4_unaligned *>(pa);
-        if (wave == 0)
-            gb = *reinterpret_cast<const u4_unaligned *>(pb);
+        gb = *reinterpret_cast<const u1_unaligned *>(pb);
     };
-    auto stage_write = [&](uint8_t *buf, u4 ga, u4 gb) {
+    auto stage_write = [&](uint8_t *buf, u4 ga, uint32_t gb) {
         if (border_block) {                               // uniform; VALU only
             const u4 ra = {bswap32(ga.w), bswap32(ga.z), bswap32(ga.y), bswap32(ga.x)};
-            const u4 rb = {bswap32(gb.w), bswap32(gb.z), bswap32(gb.y), bswap32(gb.x)};
             ga = mir_a ? ra : ga;
-            gb = mir_b ? rb : gb;
+            gb = mir_b ? bswap32(gb) : gb;
         }
         *reinterpret_cast<u4 *>(buf + row_a * kLdsStride + 16 * ch_a) = ga ^ 0x80808080u;
-        if (wave == 0)
-            *reinterpret_cast<u4 *>(buf + row_b * kLdsStride + 16 * ch_b) = gb ^ 0x80808080u;
+        *reinterpret_cast<uint32_t *>(buf + row_b * kLdsStride + 16 * ch_b + 4 * wd_b) = gb ^ 0x80808080u;
     };
-
-    // sixteen registers that stay c_lo: the C operand of the low-byte chain
-    v16i c_init;
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        c_init[i] = c_lo;
-    asm volatile("" : "+v"(c_init));
 
     // Outputs go through buffer stores (a lane that must not store gets an out-of-range offset,
     // which the hardware drops: no branch, so the waits can count the stores in flight).
@@ -217,10 +247,22 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
         HAS_DST ? (void *)(dst + (size_t)frame * h * w) : nullptr, 0, h * w, 0x00027000);
     const int xbw = xb >> 5;                              // first mask word of the workgroup's strip
     const int valid = max(0, min(32, w - x0));
-    const uint32_t colmask = valid < 32 ? (1u << valid) - 1u : ~0u;
+    // (the same for the whole wave, so it is held as a scalar; zero for the waves right of the frame)
+    const uint32_t colmask = (uint32_t)__builtin_amdgcn_readfirstlane(
+        !active ? 0 : valid < 32 ? (int)((1u << valid) - 1u) : -1);
     const int frag_off = nn * kLdsStride + 32 * wave + 16 * hh;           // this lane's A bytes
 
-    u4 ga, gb = {};
+    // sixteen registers that stay c_lo: the C operand of the low-byte chain (starting that chain from zero
+    // and adding c_lo where tv[i] is formed frees them, but costs sixteen VALU instructions per step: measured
+    // as much as the fifth workgroup per CU returns)
+    v16i c_init;
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        c_init[i] = c_lo;
+    asm volatile("" : "+v"(c_init));
+
+    u4 ga;
+    uint32_t gb = 0;
     fetch(0, ga, gb);
     stage_write(s_stage[0], ga, gb);
     fetch(1, ga, gb);                                     // ntiles >= 1
@@ -238,6 +280,13 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
         const uint8_t *cur_buf = s_stage[t & 1];
         uint8_t *next_buf = s_stage[(t + 1) & 1];
         // ---- row pass of tile t (rows 32 t - 16 ...) ---------------------------------------------
+        // (the empty asm makes the table's address a new value in every step: the reads stay in the loop
+        //  instead of sixteen registers being held across it)
+        if (kFragLds)
+            asm volatile("" : "+v"(frag_tab));
+        const char *ftab = reinterpret_cast<const char *>(&s_frag[0][0]) + frag_tab;
+        const v4i BR0 = kFragLds ? *reinterpret_cast<const v4i *>(ftab) : brow[0];
+        const v4i BR1 = kFragLds ? *reinterpret_cast<const v4i *>(ftab + 1024) : brow[1];
         const v4i a0 = *reinterpret_cast<const v4i *>(cur_buf + frag_off);
         const v4i a1 = *reinterpret_cast<const v4i *>(cur_buf + frag_off + 32);
         v16i x = {};
@@ -248,8 +297,8 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
 #pragma unroll
             for (int j = 0; j < 4; j++)                   // (four word reads: conflict free at this stride)
                 vout[j] = (int)s_dst[(t + 1) & 1][tid >> 3][(tid & 7) * 4 + j];
-        x = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, brow[0], x, 0, 0, 0);
-        x = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, brow[1], x, 0, 0, 0);
+        x = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, BR0, x, 0, 0, 0);
+        x = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, BR1, x, 0, 0, 0);
 
         // ---- epilogue of output tile t-2: lane = output row nn (+ half hh), register i = column
         //      (i&3) + 8 (i>>2) + 4 hh ---------------------------------------------------------------
@@ -259,8 +308,11 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
 #pragma unroll
             for (int i = 15; i >= 0; i--) {
                 tv[i] = (yh[i] << 8) + yl[i];
-                if (HAS_BITS)
+                if (HAS_BITS) {
                     p = __builtin_amdgcn_alignbit(p, (uint32_t)tv[i], 31);
+                    if (i == 12 || i == 8 || i == 4)          // four columns, then the four of the other half row
+                        p <<= 4;
+                }
             }
             const int u = t - 2;                               // output tile of this epilogue
 #ifndef GMF_NO_DST_LDS                                    // (ablation build: no byte conversion, no LDS gather)
@@ -284,13 +336,12 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
             }
 #endif
             if (HAS_BITS) {
-                uint32_t wd = (p & 0xFu) | ((p & 0xF0u) << 4) | ((p & 0xF00u) << 8) | ((p & 0xF000u) << 12);
-                wd <<= 4 * hh;
+                const uint32_t wd = p << (4 * hh);
                 // lanes 0..31 receive the word of lane + 32 (v_permlane32_swap, no LDS trip)
                 const auto sw = __builtin_amdgcn_permlane32_swap(wd, wd, false, false);
                 if (hh == 0 && u >= 0)
                     s_bits[(u / kFlushTiles) & 1][(u % kFlushTiles) * 32 + nn][wave] =
-                        active ? (wd | sw[1]) & colmask : 0u;
+                        (wd | sw[1]) & colmask;
             }
         }
 
@@ -308,6 +359,8 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
             __builtin_amdgcn_raw_buffer_store_b128(vout, dst_rsrc, ok ? (uint32_t)(y * w + xb + c16) : kOob, 0, GMF_DST_AUX);
         }
 
+        const v4i BC0 = kFragLds ? *reinterpret_cast<const v4i *>(ftab + 2048) : bcol[0];
+        const v4i BC1 = kFragLds ? *reinterpret_cast<const v4i *>(ftab + 3072) : bcol[1];
         // ---- accumulator -> two i8 operand fragments -----------------------------------------
         v4i cur_hi, cur_lo;
 #pragma unroll
@@ -319,10 +372,10 @@ __global__ __launch_bounds__(kWaves * 64, 4) void gauss_mfma_kernel(
         }
 
         // ---- column pass for output rows 32 (t-1) ..., consumed by the next step ----------------
-        yh = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev_hi, bcol[0], v16i{}, 0, 0, 0);
-        yl = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev_lo, bcol[0], c_init, 0, 0, 0);
-        yh = __builtin_amdgcn_mfma_i32_32x32x32_i8(cur_hi, bcol[1], yh, 0, 0, 0);
-        yl = __builtin_amdgcn_mfma_i32_32x32x32_i8(cur_lo, bcol[1], yl, 0, 0, 0);
+        yh = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev_hi, BC0, v16i{}, 0, 0, 0);
+        yl = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev_lo, BC0, c_init, 0, 0, 0);
+        yh = __builtin_amdgcn_mfma_i32_32x32x32_i8(cur_hi, BC1, yh, 0, 0, 0);
+        yl = __builtin_amdgcn_mfma_i32_32x32x32_i8(cur_lo, BC1, yl, 0, 0, 0);
         prev_hi = cur_hi;
         prev_lo = cur_lo;
         lds_barrier();   // (not __syncthreads(): the fetch of tile t + 2 and the stores stay in flight)
@@ -396,14 +449,14 @@ int launch_gauss_mfma_u8(const uint8_t *src, uint8_t *dst, uint32_t *bits, int t
     const int bpf = cdiv(w, kTileCols);
     dim3 grid((unsigned)(8 * cdiv(n, 8) * bpf));
     if (mask8_maxval > 0)
-        gauss_mfma_kernel<true, false, true><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp,
+        gauss_mfma_kernel<true, false, true, kWgBytes><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp,
                                                                             mask8_maxval);
     else if (dst && bits)
-        gauss_mfma_kernel<true, true><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
+        gauss_mfma_kernel<true, true, false, kWgBytes><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
     else if (dst)
-        gauss_mfma_kernel<true, false><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
+        gauss_mfma_kernel<true, false, false, kWgBytes><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
     else
-        gauss_mfma_kernel<false, true><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
+        gauss_mfma_kernel<false, true, false, kWgBits><<<grid, kWaves * 64, 0, st>>>(src, dst, bits, thresh, h, w, w32, nstrips, bpf, n, tp);
     VA_LAUNCH_CHECK("gauss_mfma_kernel");
     return VA_OK;
 }
