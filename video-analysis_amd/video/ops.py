@@ -5,7 +5,7 @@ batched, device-resident path is :class:`video.engine.FrameEngine`.  Everything 
 the GPU through ``libvideoanalysis_hip.so`` -- nothing is computed with NumPy.
 """
 import ctypes as C
-
+import math
 import threading
 
 import numpy as np
@@ -73,6 +73,59 @@ def pool_clear():
         pass
 
 
+class _Lease(list):
+    """the pooled device buffers of one call (the list holds them).  Every buffer handed out goes back to the pool
+    when the block ends: after the call's downloads, which synchronise its stream, or on an exception as it is,
+    without a synchronisation of its own (none may be added to any path: the pool exists to keep them off the
+    per-call ops)"""
+    stream = None                       # the call's stream, for the ops that have one: _Lease.on(stream)
+
+    @classmethod
+    def on(cls, stream):
+        lease = cls()
+        lease.stream = stream
+        return lease
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _give(*self)
+
+    def take(self, nbytes):
+        """a buffer of at least `nbytes` bytes for an output or a workspace"""
+        buf = _take(nbytes)
+        self.append(buf)
+        return buf
+
+    def upload(self, arr):
+        """a buffer holding the array `arr`, copied on the call's stream; None (an optional operand left out) stays
+        None"""
+        if arr is None:
+            return None
+        buf = self.take(arr.nbytes)
+        buf.upload(arr, self.stream)
+        return buf
+
+
+def _ptr(buf):
+    return None if buf is None else buf.ptr
+
+
+# the one dtype -> VA_* table (TEMPORAL_DTYPES: what the temporal statistics take, which is all of it)
+_DTYPE_CODES = {np.dtype(np.uint8): _hip.VA_U8, np.dtype(np.int16): _hip.VA_I16,
+                np.dtype(np.float32): _hip.VA_F32, np.dtype(np.float64): _hip.VA_F64}
+TEMPORAL_DTYPES = _DTYPE_CODES
+_TARGET_DTYPES = (np.uint8, np.float32, np.float64)       # what normalize_any and gaussian_noise write
+
+
+def _as_mask(a, keep_uint8=False):
+    """contiguous uint8 mask, 1 where `a` is non-zero; keep_uint8: a uint8 array goes through with its own values"""
+    a = np.asarray(a)
+    if keep_uint8 and a.dtype == np.uint8:
+        return np.ascontiguousarray(a)
+    return np.ascontiguousarray(a != 0, np.uint8)
+
 
 def _as_batch(arr, frame_ndim):
     """returns (contiguous array, n, frame_shape, was_single)"""
@@ -93,6 +146,18 @@ def _hwc(frame_shape):
     raise ValueError("frames must be (H,W) or (H,W,C), got %r" % (frame_shape,))
 
 
+def _map(fn, arr, out_shape, out_dtype, *args):
+    """fn(src, dst, *args) from the uploaded `arr` into a buffer that comes back as an out_shape / out_dtype array"""
+    with _Lease() as d:
+        src, dst = d.upload(arr), d.take(math.prod(out_shape) * np.dtype(out_dtype).itemsize)
+        check(fn(src.ptr, dst.ptr, *args))
+        return dst.download(out_shape, out_dtype)
+
+
+def _pointwise_u8(fn, arr, out_shape, *args):
+    return _map(fn, arr, out_shape, np.uint8, *args)
+
+
 def gaussian_blur(frames, sigma, color=False, implementation=None, tap_rule="cv4"):
     """cv2.GaussianBlur(frame, (0,0), sigma) on uint8 or float32 frames
     (FilterBlur._process_frame, video/filters.py:388-392).
@@ -107,23 +172,19 @@ def gaussian_blur(frames, sigma, color=False, implementation=None, tap_rule="cv4
     arr, n, fshape, single = _as_batch(frames, 3 if color else 2)
     h, w, c = _hwc(fshape)
     L = _hip.lib()
-    src = _upload(arr)
-    dst = _take(arr.nbytes)
-    if arr.dtype == np.uint8:
-        if tap_rule != "cv4":
-            if implementation is not None:
-                raise ValueError("the implementation hooks run the default tap rule only")
-            fn = lambda *a: L.va_gaussian_u8_rule(*(a[:7] + (_hip.TAP_RULES[tap_rule],) + a[7:]))
-        else:
-            fn = {None: L.va_gaussian_u8, "generic": L.va_gaussian_u8_generic,
-                  "valu": L.va_gaussian_u8_valu}[implementation]
-    else:
+    if arr.dtype != np.uint8:
         fn = L.va_gaussian_f32
-    check(fn(src.ptr, dst.ptr, n, h, w, c, float(sigma), None))
-    out = dst.download(arr.shape, arr.dtype)
-    _give(src)
-    _give(dst)
-    return out
+    elif tap_rule != "cv4":
+        if implementation is not None:
+            raise ValueError("the implementation hooks run the default tap rule only")
+        fn = lambda *a: L.va_gaussian_u8_rule(*(a[:7] + (_hip.TAP_RULES[tap_rule],) + a[7:]))
+    else:
+        fn = getattr(L, {None: "va_gaussian_u8", "generic": "va_gaussian_u8_generic",
+                         "valu": "va_gaussian_u8_valu"}[implementation])
+    with _Lease() as d:                 # not through _map: the op that runs once per frame pays for no extra call
+        src, dst = d.upload(arr), d.take(arr.nbytes)
+        check(fn(src.ptr, dst.ptr, n, h, w, c, float(sigma), None))
+        return dst.download(arr.shape, arr.dtype)
 
 
 class BackgroundModel(object):
@@ -157,18 +218,14 @@ class BackgroundModel(object):
         if arr.shape[1:] != self.frame_shape:
             raise ValueError("frames of shape %r do not match %r" % (arr.shape[1:], self.frame_shape))
         n = arr.shape[0]
-        src = _upload(arr)
-        dst = _take(arr.nbytes) if want_diff else None
-        check(_hip.lib().va_bg_update(self.mode, _hip.VA_U8 if self.dtype == np.uint8 else _hip.VA_F32,
-                                      src.ptr, dst.ptr if dst else None, self._state.ptr,
-                                      self.n_seen, self.rate, n, self.px, None))
-        if self.mode != _hip.BG_STATIC:
-            self.n_seen += n
-        out = dst.download(arr.shape, arr.dtype) if dst else None
-        _give(src)
-        if dst:
-            _give(dst)
-        return out
+        with _Lease() as d:
+            src = d.upload(arr)
+            dst = d.take(arr.nbytes) if want_diff else None
+            check(_hip.lib().va_bg_update(self.mode, _DTYPE_CODES[self.dtype], src.ptr, _ptr(dst), self._state.ptr,
+                                          self.n_seen, self.rate, n, self.px, None))
+            if self.mode != _hip.BG_STATIC:
+                self.n_seen += n
+            return dst.download(arr.shape, arr.dtype) if dst else None
 
     @property
     def state(self):
@@ -177,10 +234,6 @@ class BackgroundModel(object):
     def set_state(self, state, n_seen):
         self._state.upload(np.ascontiguousarray(state, self.state_dtype).reshape(self.frame_shape))
         self.n_seen = int(n_seen)
-
-
-TEMPORAL_DTYPES = {np.dtype(np.uint8): _hip.VA_U8, np.dtype(np.int16): _hip.VA_I16,
-                   np.dtype(np.float32): _hip.VA_F32, np.dtype(np.float64): _hip.VA_F64}
 
 
 def _temporal_frames(frames):
@@ -199,18 +252,14 @@ def welford(frames, mean=None, m2=None, n_seen=0):
     px = int(np.prod(fshape))
     mean = np.zeros(fshape) if mean is None else np.ascontiguousarray(mean, np.float64)
     m2 = np.zeros(fshape) if m2 is None else np.ascontiguousarray(m2, np.float64)
-    src = _upload(arr)
-    dm = _upload(mean)
-    dq = _upload(m2)
-    if arr.dtype == np.uint8:
-        check(_hip.lib().va_welford_u8(src.ptr, dm.ptr, dq.ptr, int(n_seen), arr.shape[0], px, None))
-    else:
-        check(_hip.lib().va_welford_any(src.ptr, TEMPORAL_DTYPES[arr.dtype], dm.ptr, dq.ptr, int(n_seen),
-                                        arr.shape[0], px, None))
-    out = dm.download(fshape, np.float64), dq.download(fshape, np.float64)
-    for b in (src, dm, dq):
-        _give(b)
-    return out
+    with _Lease() as d:
+        src, dm, dq = d.upload(arr), d.upload(mean), d.upload(m2)
+        if arr.dtype == np.uint8:
+            check(_hip.lib().va_welford_u8(src.ptr, dm.ptr, dq.ptr, int(n_seen), arr.shape[0], px, None))
+        else:
+            check(_hip.lib().va_welford_any(src.ptr, _DTYPE_CODES[arr.dtype], dm.ptr, dq.ptr, int(n_seen),
+                                            arr.shape[0], px, None))
+        return dm.download(fshape, np.float64), dq.download(fshape, np.float64)
 
 
 def running_mean(frames, mean=None, n_seen=0):
@@ -220,12 +269,10 @@ def running_mean(frames, mean=None, n_seen=0):
     fshape = arr.shape[1:]
     px = int(np.prod(fshape))
     mean = np.zeros(fshape) if mean is None else np.ascontiguousarray(mean, np.float64)
-    src = _upload(arr)
-    dm = _upload(mean)
-    check(_hip.lib().va_mean_any(src.ptr, TEMPORAL_DTYPES[arr.dtype], dm.ptr, int(n_seen), arr.shape[0], px, None))
-    out = dm.download(fshape, np.float64)
-    _give(src, dm)
-    return out
+    with _Lease() as d:
+        src, dm = d.upload(arr), d.upload(mean)
+        check(_hip.lib().va_mean_any(src.ptr, _DTYPE_CODES[arr.dtype], dm.ptr, int(n_seen), arr.shape[0], px, None))
+        return dm.download(fshape, np.float64)
 
 
 def time_difference(this_frame, prev_frame):
@@ -234,23 +281,10 @@ def time_difference(this_frame, prev_frame):
     b = np.ascontiguousarray(prev_frame, np.uint8)
     if a.shape != b.shape:
         raise ValueError("frame shapes differ")
-    da, db = _upload(a), _upload(b)
-    do = _take(a.size * 2)
-    check(_hip.lib().va_time_difference_u8(da.ptr, db.ptr, do.ptr, a.size, None))
-    out = do.download(a.shape, np.int16)
-    for x in (da, db, do):
-        _give(x)
-    return out
-
-
-def _pointwise_u8(fn, arr, out_shape, *args):
-    src = _upload(arr)
-    dst = _take(int(np.prod(out_shape)))
-    check(fn(src.ptr, dst.ptr, *args))
-    out = dst.download(out_shape, np.uint8)
-    _give(src)
-    _give(dst)
-    return out
+    with _Lease() as d:
+        da, db, do = d.upload(a), d.upload(b), d.take(a.size * 2)
+        check(_hip.lib().va_time_difference_u8(da.ptr, db.ptr, do.ptr, a.size, None))
+        return do.download(a.shape, np.int16)
 
 
 def threshold(frames, thresh, maxval=255):
@@ -275,12 +309,7 @@ def rot90(frames, k=1, color=False):
     h, w, c = _hwc(fshape)
     k = int(k) % 4
     out_shape = ((w, h) if k & 1 else (h, w)) + ((c,) if color else ())
-    src = _upload(arr)
-    dst = _take(arr.nbytes)
-    check(_hip.lib().va_rot90(src.ptr, dst.ptr, n, h, w, c * arr.dtype.itemsize, k, None))
-    out = dst.download((n,) + out_shape, arr.dtype)
-    _give(src)
-    _give(dst)
+    out = _map(_hip.lib().va_rot90, arr, (n,) + out_shape, arr.dtype, n, h, w, c * arr.dtype.itemsize, k, None)
     return out[0] if single else out
 
 
@@ -308,19 +337,9 @@ def resize(frames, size, interpolation="linear", color=False):
     if dw < 1 or dh < 1:
         raise ValueError("target size must be positive, got %r" % (size,))
     out_shape = (n, dh, dw) + ((c,) if color else ())
-    src = _upload(arr)
-    dst = _take(int(np.prod(out_shape)) * arr.dtype.itemsize)
-    try:
-        fn = _hip.lib().va_resize_u8 if arr.dtype == np.uint8 else _hip.lib().va_resize_f32
-        check(fn(src.ptr, dst.ptr, n, h, w, c, dh, dw, INTERPOLATIONS[interpolation], None))
-        out = dst.download(out_shape, arr.dtype)
-    finally:
-        _give(src, dst)
+    fn = _hip.lib().va_resize_u8 if arr.dtype == np.uint8 else _hip.lib().va_resize_f32
+    out = _map(fn, arr, out_shape, arr.dtype, n, h, w, c, dh, dw, INTERPOLATIONS[interpolation], None)
     return out[0] if single else out
-
-
-_DTYPE_CODES = {np.dtype(np.uint8): _hip.VA_U8, np.dtype(np.float32): _hip.VA_F32,
-                np.dtype(np.float64): _hip.VA_F64}
 
 
 def normalize_any(frames, fmin, fmax, alpha, tmin, dtype):
@@ -328,32 +347,27 @@ def normalize_any(frames, fmin, fmax, alpha, tmin, dtype):
     (video/filters.py:126-132): clip, (f - fmin)*alpha + tmin in float64, astype(dtype)"""
     a = np.ascontiguousarray(frames)
     dtype = np.dtype(dtype)
-    if a.dtype not in (np.uint8, np.float32) or dtype not in _DTYPE_CODES:
+    if a.dtype not in (np.uint8, np.float32) or dtype not in _TARGET_DTYPES:
         raise TypeError("normalize: %s -> %s is not supported on the GPU path" % (a.dtype, dtype))
-    src = _upload(a)
-    dst = _take(a.size * dtype.itemsize)
-    try:
+    with _Lease() as d:
+        src, dst = d.upload(a), d.take(a.size * dtype.itemsize)
         check(_hip.lib().va_normalize(src.ptr, _DTYPE_CODES[a.dtype], dst.ptr, _DTYPE_CODES[dtype], a.size,
                                       float(fmin), float(fmax), float(alpha), float(tmin), None))
         return dst.download(a.shape, dtype)
-    finally:
-        _give(src, dst)
 
 
 def gaussian_noise(shape, dtype=np.float64, mean=0.0, std=1.0, seed=0, first_index=0):
     """`mean + std*randn(*shape)` produced on the GPU (VideoGaussianNoise, video/io/computed.py:36-41):
     sample i of the seeded stream is a function of (seed, first_index + i) only"""
     dtype = np.dtype(dtype)
-    if dtype not in _DTYPE_CODES:
+    if dtype not in _TARGET_DTYPES:
         raise TypeError("gaussian_noise: dtype %s is not supported on the GPU path" % dtype)
     count = int(np.prod(shape))
-    dst = _take(max(count, 1) * dtype.itemsize)
-    try:
+    with _Lease() as d:
+        dst = d.take(max(count, 1) * dtype.itemsize)
         check(_hip.lib().va_gaussian_noise(dst.ptr, _DTYPE_CODES[dtype], count, float(mean), float(std),
                                            int(seed) & (2 ** 64 - 1), int(first_index), None))
         return dst.download(tuple(shape), dtype)
-    finally:
-        _give(dst)
 
 
 def morph(frames, op, shape="rect", ksize=3, implementation=None):
@@ -367,25 +381,25 @@ def morph(frames, op, shape="rect", ksize=3, implementation=None):
                          _hip.SHAPES.get(shape, shape), int(ksize), None)
 
 
+def _label(d, arr, n, h, w, connectivity):
+    """label the (n, h, w) uint8 masks `arr` in buffers of the lease `d`; returns the (labels, counts) buffers"""
+    L = _hip.lib()
+    src, lab, cnt = d.upload(arr), d.take(arr.size * 4), d.take(max(n, 1) * 4)
+    ws_bytes = L.va_label_workspace_bytes(n, h, w)
+    ws = d.take(ws_bytes)
+    check(L.va_label_i32(src.ptr, lab.ptr, cnt.ptr, n, h, w, int(connectivity), ws.ptr, ws_bytes, None))
+    return lab, cnt
+
+
 def label(masks, connectivity=4):
     """ndimage.measurements.label (video/analysis/regions.py:162) for (H,W) or (N,H,W) masks.
     returns (labels int32, counts): counts is an int for a single mask, else an int32 array"""
-    m = np.asarray(masks)
-    if m.dtype != np.uint8:
-        m = (m != 0).astype(np.uint8)
-    arr, n, fshape, single = _as_batch(m, 2)
+    arr, n, fshape, single = _as_batch(_as_mask(masks, keep_uint8=True), 2)
     h, w = fshape
-    L = _hip.lib()
-    src = _upload(arr)
-    lab = _take(arr.size * 4)
-    cnt = _take(max(n, 1) * 4)
-    ws_bytes = L.va_label_workspace_bytes(n, h, w)
-    ws = _take(ws_bytes)
-    check(L.va_label_i32(src.ptr, lab.ptr, cnt.ptr, n, h, w, int(connectivity), ws.ptr, ws_bytes, None))
-    labels = lab.download(arr.shape, np.int32)
-    counts = cnt.download((n,), np.int32)
-    for b in (src, lab, cnt, ws):
-        _give(b)
+    with _Lease() as d:
+        lab, cnt = _label(d, arr, n, h, w, connectivity)
+        labels = lab.download(arr.shape, np.int32)
+        counts = cnt.download((n,), np.int32)
     if single:
         return labels, int(counts[0])
     return labels, counts
@@ -396,12 +410,10 @@ def region_stats(labels, max_labels):
     arr, n, fshape, single = _as_batch(np.asarray(labels, np.int32), 2)
     h, w = fshape
     max_labels = max(int(max_labels), 1)
-    src = _upload(arr)
-    st = _take(n * max_labels * _hip.STATS_STRIDE * 8)
-    check(_hip.lib().va_moments_i64(src.ptr, n, h, w, max_labels, st.ptr, None))
-    out = st.download((n, max_labels, _hip.STATS_STRIDE), np.int64)
-    _give(src)
-    _give(st)
+    with _Lease() as d:
+        src, st = d.upload(arr), d.take(n * max_labels * _hip.STATS_STRIDE * 8)
+        check(_hip.lib().va_moments_i64(src.ptr, n, h, w, max_labels, st.ptr, None))
+        out = st.download((n, max_labels, _hip.STATS_STRIDE), np.int64)
     return out[0] if single else out
 
 
@@ -411,35 +423,35 @@ def largest_region(mask, connectivity=4):
     m = np.asarray(mask)
     if m.ndim != 2:
         raise ValueError("mask must be 2-d")
-    if m.dtype != np.uint8:
-        m = (m != 0).astype(np.uint8)
-    m = np.ascontiguousarray(m)
+    m = _as_mask(m, keep_uint8=True)
     h, w = m.shape
     L = _hip.lib()
-    src = _upload(m)
-    lab = _take(m.size * 4)
-    cnt = _take(4)
-    ws_bytes = L.va_label_workspace_bytes(1, h, w)
-    ws = _take(ws_bytes)
-    check(L.va_label_i32(src.ptr, lab.ptr, cnt.ptr, 1, h, w, int(connectivity), ws.ptr, ws_bytes, None))
-    count = int(cnt.download((1,), np.int32)[0])
-    bufs = [src, lab, cnt, ws]
-    try:
+    with _Lease() as d:
+        lab, cnt = _label(d, m, 1, h, w, connectivity)
+        count = int(cnt.download((1,), np.int32)[0])
         if count == 0:
             return np.zeros(m.shape, bool), 0, 0
-        st = _take(count * _hip.STATS_STRIDE * 8)
-        big = _take(4)
-        area = _take(8)
-        sel = _take(m.size)
-        bufs += [st, big, area, sel]
+        st, big, area, sel = d.take(count * _hip.STATS_STRIDE * 8), d.take(4), d.take(8), d.take(m.size)
         check(L.va_moments_i64(lab.ptr, 1, h, w, count, st.ptr, None))
         check(L.va_largest_region(lab.ptr, cnt.ptr, st.ptr, 1, h, w, count, big.ptr, area.ptr,
                                   sel.ptr, None))
         out = sel.download(m.shape, np.uint8).astype(bool)
         return out, int(area.download((1,), np.int64)[0]), count
-    finally:
-        for b in bufs:
-            _give(b)
+
+
+DEFAULT_POINT_CAPACITY = 4096     # room for the points of a contour or a path when the caller names none
+
+
+def _with_room(max_points, run):
+    """run(capacity) launches with room for `capacity` points per item and returns (points buffer, counts found).
+    An explicit max_points truncates; otherwise a count beyond DEFAULT_POINT_CAPACITY (rare: a very long contour or
+    path) runs once more with room for the largest.  Returns (points buffer, counts kept, capacity)."""
+    cap = int(max_points) if max_points else DEFAULT_POINT_CAPACITY
+    pts, counts = run(cap)
+    if not max_points and counts.max(initial=0) > cap:
+        cap = int(counts.max())
+        pts, counts = run(cap)
+    return pts, np.minimum(counts, cap), cap
 
 
 def largest_contour(mask, max_points=None, moments=False):
@@ -450,39 +462,29 @@ def largest_contour(mask, max_points=None, moments=False):
     m = np.asarray(mask)
     if m.ndim != 2:
         raise ValueError("mask must be 2-d")
-    if m.dtype != np.uint8:
-        m = (m != 0).astype(np.uint8)
-    m = np.ascontiguousarray(m)
+    m = _as_mask(m, keep_uint8=True)
     h, w = m.shape
     L = _hip.lib()
-    cap = int(max_points) if max_points else 4096
-    src = _upload(m)
-    ws_bytes = L.va_contour_workspace_bytes(1, h, w)
-    ws = _take(ws_bytes)
-    npts, area, ncomp = _take(4), _take(8), _take(4)
-    bufs = [src, ws, npts, area, ncomp]
-    try:
-        while True:
-            pts = _take(cap * 8)
-            bufs.append(pts)
+    with _Lease() as d:
+        src = d.upload(m)
+        ws_bytes = L.va_contour_workspace_bytes(1, h, w)
+        ws = d.take(ws_bytes)
+        npts, area, ncomp = d.take(4), d.take(8), d.take(4)
+
+        def run(cap):
+            pts = d.take(cap * 8)
             check(L.va_largest_contour(src.ptr, 1, h, w, pts.ptr, cap, npts.ptr, area.ptr, ncomp.ptr,
                                        ws.ptr, ws_bytes, None))
-            n = int(npts.download((1,), np.int32)[0])
-            if n <= cap or max_points:
-                break
-            cap = n                       # rare: a very long contour, run again with room for it
+            return pts, npts.download((1,), np.int32)
+        pts, n, cap = _with_room(max_points, run)
         count = int(ncomp.download((1,), np.int32)[0])
-        points = pts.download((min(n, cap), 2), np.int32)
+        points = pts.download((int(n[0]), 2), np.int32)
         res = (points, float(area.download((1,), np.float64)[0]), count)
         if moments:
-            mom = _take(10 * 8)
-            bufs.append(mom)
+            mom = d.take(10 * 8)
             check(L.va_contour_moments(pts.ptr, npts.ptr, 1, cap, 0, mom.ptr, None))
             res += (mom.download((10,), np.float64),)
         return res
-    finally:
-        for b in bufs:
-            _give(b)
 
 
 # ------------------------------------------------------------------------ geodesic distance maps
@@ -513,7 +515,7 @@ def distance_map(fillable, start_points, end_points=None):
     filled; start_points: (x, y) points, one list per frame when batched; end_points likewise or
     None.  Returns int32 maps: 0 not fillable, 1 not reached, 2 + floor(distance) filled."""
     arr, n, fshape, single = _as_batch(np.asarray(fillable), 2)
-    arr = np.ascontiguousarray(arr != 0, np.uint8)
+    arr = _as_mask(arr)
     h, w = fshape
     if single:
         start_points = [start_points]
@@ -521,24 +523,16 @@ def distance_map(fillable, start_points, end_points=None):
     st, nst = _point_table(start_points, n)
     L = _hip.lib()
     ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
-    bufs = [_upload(arr), _upload(st), _upload(nst), _take(arr.size * 4), _take(ws_bytes)]
-    src, sb, nsb, out, ws = bufs
-    try:
-        eb = neb = None
-        me = 0
-        if end_points is not None:
-            et, net = _point_table(end_points, n)
-            eb, neb = _upload(et), _upload(net)
-            bufs += [eb, neb]
-            me = et.shape[1]
-        check(L.va_distance_map_i32(src.ptr, n, h, w, sb.ptr, nsb.ptr, st.shape[1], eb.ptr if eb else None,
-                                    neb.ptr if neb else None, me, out.ptr, ws.ptr, ws_bytes, None))
+    with _Lease() as d:
+        src, sb, nsb, out, ws = d.upload(arr), d.upload(st), d.upload(nst), d.take(arr.size * 4), d.take(ws_bytes)
+        et, net = (None, None) if end_points is None else _point_table(end_points, n)
+        eb, neb = d.upload(et), d.upload(net)
+        check(L.va_distance_map_i32(src.ptr, n, h, w, sb.ptr, nsb.ptr, st.shape[1], _ptr(eb), _ptr(neb),
+                                    0 if et is None else et.shape[1], out.ptr, ws.ptr, ws_bytes, None))
         return out.download(arr.shape, np.int32)
-    finally:
-        _give(*bufs)
 
 
-def _download_paths(pts, npath, n, cap):
+def _download_paths(pts, npath, cap, n):
     allp = pts.download((n, cap, 2), np.int32)
     return [allp[f, :npath[f]].astype(np.int64) for f in range(n)]
 
@@ -560,22 +554,15 @@ def distance_map_path(dmap, end_point, max_points=None):
     ends, _ = _point_table([[end_point]] if single else [[e] for e in end_point], n)
     L = _hip.lib()
     ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
-    cap = int(max_points) if max_points else 4096
-    src, eb, npb, ws = _upload(arr), _upload(ends[:, 0].copy()), _take(n * 4), _take(ws_bytes)
-    bufs = [src, eb, npb, ws]
-    try:
-        while True:
-            pts = _take(n * cap * 8)
-            bufs.append(pts)
+    with _Lease() as d:
+        src, eb, npb, ws = d.upload(arr), d.upload(ends[:, 0].copy()), d.take(n * 4), d.take(ws_bytes)
+
+        def run(cap):
+            pts = d.take(n * cap * 8)
             check(L.va_distance_map_path(src.ptr, n, h, w, eb.ptr, pts.ptr, cap, npb.ptr, ws.ptr, ws_bytes, None))
-            npath = npb.download((n,), np.int32)
-            if npath.max(initial=0) <= cap or max_points:
-                break
-            cap = int(npath.max())           # rare: a path longer than the buffer, run again with room
-        paths = _download_paths(pts, np.minimum(npath, cap), n, cap)
+            return pts, npb.download((n,), np.int32)
+        paths = _download_paths(*_with_room(max_points, run), n=n)
         return paths[0] if single else paths
-    finally:
-        _give(*bufs)
 
 
 def farthest_points(masks, p1=None, ret_path=False, max_points=None, ret_stats=False):
@@ -588,35 +575,27 @@ def farthest_points(masks, p1=None, ret_path=False, max_points=None, ret_stats=F
     ret_path the (K, 2) int64 paths from p2 instead (a list when batched).  ret_stats appends
     (distance value at p2 (N,), [maps built, sweeps] (N, 2)) as int32 arrays."""
     arr, n, fshape, single = _as_batch(np.asarray(masks), 2)
-    arr = np.ascontiguousarray(arr != 0, np.uint8)
+    arr = _as_mask(arr)
     h, w = fshape
     L = _hip.lib()
     ws_bytes = L.va_geodesic_workspace_bytes(n, h, w)
-    src, p1o, p2o, dist, rounds, npb, ws = (_upload(arr), _take(n * 8), _take(n * 8), _take(n * 4),
-                                            _take(n * 8), _take(n * 4), _take(ws_bytes))
-    bufs = [src, p1o, p2o, dist, rounds, npb, ws]
-    try:
+    with _Lease() as d:
+        src, p1o, p2o, dist, rounds, npb, ws = (d.upload(arr), d.take(n * 8), d.take(n * 8), d.take(n * 4),
+                                                d.take(n * 8), d.take(n * 4), d.take(ws_bytes))
         p1b = None
         if p1 is not None:
             given = [p1] if single else list(p1)
             tab, _ = _point_table([[q] for q in given], n)
-            p1b = _upload(tab[:, 0].copy())
-            bufs.append(p1b)
-        cap = int(max_points) if max_points else 4096
-        while True:
-            pts = _take(n * cap * 8) if ret_path else None
-            if pts is not None:
-                bufs.append(pts)
-            check(L.va_farthest_points(src.ptr, n, h, w, p1b.ptr if p1b else None, p1o.ptr, p2o.ptr, dist.ptr,
-                                       rounds.ptr, pts.ptr if pts is not None else None, cap, npb.ptr, ws.ptr, ws_bytes, None))
-            if not ret_path:
-                break
-            npath = npb.download((n,), np.int32)
-            if npath.max(initial=0) <= cap or max_points:
-                break
-            cap = int(npath.max())
+            p1b = d.upload(tab[:, 0].copy())
+
+        def run(cap):                 # without ret_path there is no list to outgrow the capacity: no counts are read
+            pts = d.take(n * cap * 8) if ret_path else None
+            check(L.va_farthest_points(src.ptr, n, h, w, _ptr(p1b), p1o.ptr, p2o.ptr, dist.ptr, rounds.ptr, _ptr(pts),
+                                       cap, npb.ptr, ws.ptr, ws_bytes, None))
+            return pts, npb.download((n,), np.int32) if ret_path else np.zeros(0, np.int32)
+        pts, npath, cap = _with_room(max_points, run)
         if ret_path:
-            res = _download_paths(pts, np.minimum(npath, cap), n, cap)
+            res = _download_paths(pts, npath, cap, n)
             res = (res[0] if single else res,)
         else:
             a, b = p1o.download((n, 2), np.int32).astype(np.int64), p2o.download((n, 2), np.int32).astype(np.int64)
@@ -628,11 +607,9 @@ def farthest_points(masks, p1=None, ret_path=False, max_points=None, ret_stats=F
                         a[f] = q
             res = (a[0], b[0]) if single else (a, b)
         if ret_stats:
-            d, r = dist.download((n,), np.int32), rounds.download((n, 2), np.int32)
-            res += (d[0], r[0]) if single else (d, r)
+            dv, rv = dist.download((n,), np.int32), rounds.download((n, 2), np.int32)
+            res += (dv[0], rv[0]) if single else (dv, rv)
         return res if len(res) > 1 else res[0]
-    finally:
-        _give(*bufs)
 
 
 def contour_moments(contour):
@@ -645,14 +622,10 @@ def contour_moments(contour):
         raise ValueError("contour must hold (x, y) points")
     is_float = 0 if np.issubdtype(c.dtype, np.integer) else 1
     c = np.ascontiguousarray(c.reshape(-1, 2), np.float32 if is_float else np.int32)
-    pts = _upload(c)
-    out = _take(10 * 8)
-    try:
+    with _Lease() as d:
+        pts, out = d.upload(c), d.take(10 * 8)
         check(_hip.lib().va_contour_moments(pts.ptr, None, 1, len(c), is_float, out.ptr, None))
         return out.download((10,), np.float64)
-    finally:
-        _give(pts)
-        _give(out)
 
 
 def detect_peaks(img, include_plateaus=True):
@@ -660,17 +633,8 @@ def detect_peaks(img, include_plateaus=True):
     a = np.ascontiguousarray(img)
     if a.dtype not in (np.uint8, np.float32) or a.ndim != 2:
         raise TypeError("detect_peaks expects a 2-d uint8 or float32 image on the GPU path")
-    if a.dtype == np.uint8:
-        out = _pointwise_u8(_hip.lib().va_detect_peaks_u8, a, a.shape, 1, a.shape[0], a.shape[1],
-                            1 if include_plateaus else 0, None)
-        return out.astype(bool)
-    src, dst = _upload(a), _take(a.size)
-    try:
-        check(_hip.lib().va_detect_peaks_f32(src.ptr, dst.ptr, 1, a.shape[0], a.shape[1],
-                                             1 if include_plateaus else 0, None))
-        return dst.download(a.shape, np.uint8).astype(bool)
-    finally:
-        _give(src, dst)
+    fn = _hip.lib().va_detect_peaks_u8 if a.dtype == np.uint8 else _hip.lib().va_detect_peaks_f32
+    return _pointwise_u8(fn, a, a.shape, 1, a.shape[0], a.shape[1], 1 if include_plateaus else 0, None).astype(bool)
 
 
 def mask_thinning(img):
@@ -680,14 +644,11 @@ def mask_thinning(img):
     if a.ndim != 2:
         raise ValueError("mask must be 2-d")
     h, w = a.shape
-    cur, tmp, skel = _upload(a), _take(a.size), _take(a.size)
     it = C.c_int()
-    try:
+    with _Lease() as d:
+        cur, tmp, skel = d.upload(a), d.take(a.size), d.take(a.size)
         check(_hip.lib().va_mask_thinning_u8(cur.ptr, tmp.ptr, skel.ptr, h, w, C.byref(it), None))
         return skel.download(a.shape, np.uint8), it.value
-    finally:
-        for b in (cur, tmp, skel):
-            _give(b)
 
 
 def image_statistics(img, kernel="box", ksize=5, prior=0.0, exclude_center=False, ret_var=True):
@@ -698,21 +659,13 @@ def image_statistics(img, kernel="box", ksize=5, prior=0.0, exclude_center=False
     if a.dtype not in (np.uint8, np.float32) or a.ndim != 2:
         raise TypeError("image_statistics expects a 2-d uint8 or float32 image on the GPU path")
     h, w = a.shape
-    src = _upload(a)
-    dm = _take(a.size * 8)
-    dv = _take(a.size * 8) if ret_var else None
-    try:
-        fn = _hip.lib().va_image_statistics_u8 if a.dtype == np.uint8 else _hip.lib().va_image_statistics_f32
-        check(fn(src.ptr, dm.ptr, dv.ptr if dv else None, 1, h, w,
-                                                {"box": 0, "ellipse": 1, "circle": 1}[kernel],
-                                                int(ksize), float(prior), 1 if exclude_center else 0,
-                                                None))
+    fn = _hip.lib().va_image_statistics_u8 if a.dtype == np.uint8 else _hip.lib().va_image_statistics_f32
+    with _Lease() as d:
+        src, dm, dv = d.upload(a), d.take(a.size * 8), (d.take(a.size * 8) if ret_var else None)
+        check(fn(src.ptr, dm.ptr, _ptr(dv), 1, h, w, {"box": 0, "ellipse": 1, "circle": 1}[kernel], int(ksize),
+                 float(prior), 1 if exclude_center else 0, None))
         mean = dm.download(a.shape, np.float64)
         return (mean, dv.download(a.shape, np.float64)) if ret_var else mean
-    finally:
-        for b in (src, dm, dv):
-            if b:
-                _give(b)
 
 
 # ------------------------------------------------------------------------ dense optical flow
@@ -730,15 +683,11 @@ def optical_flow_farneback(frames, pyr_scale=0.5, levels=3, winsize=2, iteration
     arr = np.asarray(frames)
     if arr.ndim != 3:
         raise ValueError("expected an (n, h, w) stack of single-channel frames, got shape %r" % (arr.shape,))
-    if arr.dtype == np.uint8:
-        dtype = _hip.VA_U8
-    elif arr.dtype == np.float32:
-        dtype = _hip.VA_F32
-    elif arr.dtype.kind in "biuf":
-        arr, dtype = arr.astype(np.float32), _hip.VA_F32
-    else:
-        raise TypeError("optical flow: frames of dtype %s are not supported" % arr.dtype)
-    arr = np.ascontiguousarray(arr)
+    if arr.dtype not in (np.uint8, np.float32):
+        if arr.dtype.kind not in "biuf":
+            raise TypeError("optical flow: frames of dtype %s are not supported" % arr.dtype)
+        arr = arr.astype(np.float32)
+    arr, dtype = np.ascontiguousarray(arr), _DTYPE_CODES[arr.dtype]
     n, h, w = arr.shape
     args = (float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n))
     L = _hip.lib()
@@ -753,17 +702,14 @@ def optical_flow_farneback(frames, pyr_scale=0.5, levels=3, winsize=2, iteration
     for a in range(0, n - 1, pairs):
         k = min(pairs, n - 1 - a)
         ws_bytes = ws_of(k + 1)
-        bufs = [_upload(arr[a:a + k + 1]), _take(k * h * w * 4), _take(k * h * w * 8) if ret_flow else None,
-                _take(ws_bytes)]
-        src, mb, fb, ws = bufs
-        try:
-            check(L.va_optical_flow_farneback(src.ptr, dtype, k + 1, h, w, *args, float(poly_sigma), 0,
-                                              fb.ptr if fb else None, mb.ptr, ws.ptr, ws_bytes, None))
+        with _Lease() as d:
+            src, mb, fb, ws = (d.upload(arr[a:a + k + 1]), d.take(k * h * w * 4),
+                               d.take(k * h * w * 8) if ret_flow else None, d.take(ws_bytes))
+            check(L.va_optical_flow_farneback(src.ptr, dtype, k + 1, h, w, *args, float(poly_sigma), 0, _ptr(fb),
+                                              mb.ptr, ws.ptr, ws_bytes, None))
             mag[a:a + k] = mb.download((k, h, w), np.float32)
             if ret_flow:
                 flow[a:a + k] = fb.download((k, h, w, 2), np.float32)
-        finally:
-            _give(*bufs)
     return (flow, mag) if ret_flow else mag
 
 
@@ -780,7 +726,7 @@ def _potential_stack(frames):
         arr = arr[None]
     if arr.ndim != 3:
         raise ValueError("expected an (h, w) potential or an (n, h, w) stack, got shape %r" % (arr.shape,))
-    return np.ascontiguousarray(arr), (_hip.VA_U8 if arr.dtype == np.uint8 else _hip.VA_F32)
+    return np.ascontiguousarray(arr), _DTYPE_CODES[arr.dtype]
 
 
 def potential_gradients(frames, sigma=0.0, stream=None):
@@ -792,21 +738,19 @@ def potential_gradients(frames, sigma=0.0, stream=None):
     n, h, w = arr.shape
     L = _hip.lib()
     fx, fy = DeviceBuffer(arr.nbytes * (8 // arr.itemsize)), DeviceBuffer(arr.nbytes * (8 // arr.itemsize))
-    src = _upload(arr, stream)
-    blur = None
     try:
-        if sigma > 0 and n:
-            blur = _take(arr.nbytes)
-            fn = L.va_gaussian_u8 if dtype == _hip.VA_U8 else L.va_gaussian_f32
-            check(fn(src.ptr, blur.ptr, n, h, w, 1, float(sigma), stream))
-        check(L.va_sobel5_f64((blur or src).ptr, dtype, fx.ptr, fy.ptr, n, h, w, stream))
-        check(L.va_stream_sync(stream))
-    except Exception:
+        with _Lease.on(stream) as d:
+            src, blur = d.upload(arr), None
+            if sigma > 0 and n:
+                blur = d.take(arr.nbytes)
+                fn = L.va_gaussian_u8 if dtype == _hip.VA_U8 else L.va_gaussian_f32
+                check(fn(src.ptr, blur.ptr, n, h, w, 1, float(sigma), stream))
+            check(L.va_sobel5_f64((blur or src).ptr, dtype, fx.ptr, fy.ptr, n, h, w, stream))
+            check(L.va_stream_sync(stream))
+    except Exception:                  # the caller never sees fx and fy: they are not pooled, free them here
         fx.free()
         fy.free()
         raise
-    finally:
-        _give(src, blur)
     return fx, fy, (n, h, w)
 
 
@@ -818,14 +762,10 @@ def sobel5_f64(frames, dx=True, dy=True):
     arr, dtype = _potential_stack(frames)
     n, h, w = arr.shape
     L = _hip.lib()
-    src = _upload(arr)
-    bx = _take(arr.size * 8) if dx else None
-    by = _take(arr.size * 8) if dy else None
-    try:
-        check(L.va_sobel5_f64(src.ptr, dtype, bx.ptr if bx else None, by.ptr if by else None, n, h, w, None))
+    with _Lease() as d:
+        src, bx, by = d.upload(arr), (d.take(arr.size * 8) if dx else None), (d.take(arr.size * 8) if dy else None)
+        check(L.va_sobel5_f64(src.ptr, dtype, _ptr(bx), _ptr(by), n, h, w, None))
         return tuple(b.download(arr.shape, np.float64).reshape(frames.shape) if b else None for b in (bx, by))
-    finally:
-        _give(src, bx, by)
 
 
 def active_contour(fx, fy, shape, points, npoints, frames, mats, mat_offsets, anchor_flags, anchor_vals, gamma,
@@ -841,23 +781,21 @@ def active_contour(fx, fy, shape, points, npoints, frames, mats, mat_offsets, an
     pts = np.ascontiguousarray(points, np.float64)
     m, max_points = pts.shape[:2]
     L = _hip.lib()
-    host = [pts, np.ascontiguousarray(npoints, np.int32), np.ascontiguousarray(frames, np.int32),
-            np.ascontiguousarray(mats, np.float64), np.ascontiguousarray(mat_offsets, np.int64)]
-    if anchor_flags is not None:
-        host += [np.ascontiguousarray(anchor_flags, np.uint8), np.ascontiguousarray(anchor_vals, np.float64)]
-    bufs = [_upload(a, stream) for a in host]
-    it_buf, tv_buf = _take(max(m, 1) * 4), _take(max(m, 1) * 8)
-    try:
-        pb, nb, fb, mb, ob = bufs[:5]
-        ab, vb = bufs[5:] if anchor_flags is not None else (None, None)
-        check(L.va_active_contour(fx.ptr, fy.ptr, n, h, w, m, max_points, nb.ptr, fb.ptr, mb.ptr, ob.ptr,
-                                  host[3].size, ab.ptr if ab else None, vb.ptr if vb else None, float(gamma),
-                                  float(tol_gamma), int(max_iterations), pb.ptr, it_buf.ptr, tv_buf.ptr, stream))
+    mats = np.ascontiguousarray(mats, np.float64)
+    anchored = anchor_flags is not None
+    with _Lease.on(stream) as d:
+        pb, nb, fb, mb, ob, ab, vb = (
+            d.upload(pts), d.upload(np.ascontiguousarray(npoints, np.int32)),
+            d.upload(np.ascontiguousarray(frames, np.int32)), d.upload(mats),
+            d.upload(np.ascontiguousarray(mat_offsets, np.int64)),
+            d.upload(np.ascontiguousarray(anchor_flags, np.uint8) if anchored else None),
+            d.upload(np.ascontiguousarray(anchor_vals, np.float64) if anchored else None))
+        it_buf, tv_buf = d.take(max(m, 1) * 4), d.take(max(m, 1) * 8)
+        check(L.va_active_contour(fx.ptr, fy.ptr, n, h, w, m, max_points, nb.ptr, fb.ptr, mb.ptr, ob.ptr, mats.size,
+                                  _ptr(ab), _ptr(vb), float(gamma), float(tol_gamma), int(max_iterations), pb.ptr,
+                                  it_buf.ptr, tv_buf.ptr, stream))
         return (pb.download(pts.shape, np.float64, stream), it_buf.download((m,), np.int32, stream),
                 tv_buf.download((m,), np.float64, stream))
-    finally:
-        _give(*bufs)
-        _give(it_buf, tv_buf)
 
 
 # ------------------------------------------------------------------------------------------ polygons
@@ -866,6 +804,29 @@ FILL_MAX_SIDE = 16384
 FILL_MAX_COORD = 1 << 20
 DT_MAX_WIDTH = 4096
 DT_MAX_HEIGHT = 16384
+
+
+def _pack_ragged(items):
+    """one flat buffer for m items of different sizes.  items: 2-d arrays, or their (h, w) shapes alone for
+    a call that has no input pixels.  Returns (flat, shapes int32 (m, 2), offsets int64 (m,), sizes int64 (m,),
+    total): item i is sizes[i] elements at offsets[i] of `total`; flat is the concatenated pixels (one placeholder
+    byte when there are none at all), None for shapes"""
+    m = len(items)
+    arrays = np.ndim(items[0]) == 2
+    shapes = np.array([a.shape for a in items] if arrays else items, np.int32).reshape(m, 2)
+    sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
+    offsets = np.zeros(m, np.int64)
+    offsets[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    flat = None
+    if arrays:
+        flat = np.concatenate([a.reshape(-1) for a in items]) if total else np.zeros(1, np.uint8)
+    return flat, shapes, offsets, sizes, total
+
+
+def _split_ragged(flat, shapes, offsets, sizes):
+    """the per-item (h, w) arrays of a flat result laid out by _pack_ragged"""
+    return [flat[o:o + s].reshape(hw) for o, s, hw in zip(offsets.tolist(), sizes.tolist(), shapes.tolist())]
 
 
 def _check_status(status, what):
@@ -907,22 +868,15 @@ def fill_polys(contours, boxes, dtype=np.uint8, stream=None):
     verts = np.ascontiguousarray(np.concatenate(polys), np.int32)
     vert_off = np.zeros(m + 1, np.int64)
     vert_off[1:] = np.cumsum([len(c) for c in polys])
-    sizes = bx[:, 2] * bx[:, 3]
-    out_off = np.zeros(m, np.int64)
-    out_off[1:] = np.cumsum(sizes)[:-1]
-    total = int(sizes.sum())
-    L = _hip.lib()
-    bufs = [_upload(verts, stream), _upload(vert_off, stream), _upload(bx.astype(np.int32), stream),
-            _upload(out_off, stream), _take(max(total, 1) * dtype.itemsize), _take(m * 4)]
-    vb, ob, bb, oob, out, st = bufs
-    try:
-        check(L.va_fill_poly(vb.ptr, ob.ptr, len(verts), bb.ptr, oob.ptr, total, m, dtype.itemsize, out.ptr, st.ptr,
-                             stream))
+    _, shapes, out_off, sizes, total = _pack_ragged(bx[:, [3, 2]])
+    with _Lease.on(stream) as d:
+        vb, ob, bb, oob, out, st = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)),
+                                    d.upload(out_off), d.take(max(total, 1) * dtype.itemsize), d.take(m * 4))
+        check(_hip.lib().va_fill_poly(vb.ptr, ob.ptr, len(verts), bb.ptr, oob.ptr, total, m, dtype.itemsize, out.ptr,
+                                      st.ptr, stream))
         _check_status(st.download((m,), np.int32, stream), "fill_polys")
         flat = out.download((total,), dtype, stream)
-    finally:
-        _give(*bufs)
-    return [flat[o:o + s].reshape(int(h), int(w)) for o, s, (h, w) in zip(out_off, sizes, bx[:, [3, 2]])]
+    return _split_ragged(flat, shapes, out_off, sizes)
 
 
 def distance_transform(masks, stream=None):
@@ -937,28 +891,19 @@ def distance_transform(masks, stream=None):
         if a.shape[1] > DT_MAX_WIDTH or a.shape[0] > DT_MAX_HEIGHT:
             raise ValueError("distance_transform: mask %d of shape %r exceeds %d rows x %d columns"
                              % (k, a.shape, DT_MAX_HEIGHT, DT_MAX_WIDTH))
-        arrs.append(np.ascontiguousarray(a != 0, np.uint8))
+        arrs.append(a)
     m = len(arrs)
     if m == 0:
         return []
-    shapes = np.array([a.shape for a in arrs], np.int32).reshape(m, 2)
-    sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
-    offsets = np.zeros(m, np.int64)
-    offsets[1:] = np.cumsum(sizes)[:-1]
-    total = int(sizes.sum())
-    flat = np.concatenate([a.reshape(-1) for a in arrs]) if total else np.zeros(1, np.uint8)
-    L = _hip.lib()
-    bufs = [_upload(flat, stream), _upload(shapes, stream), _upload(offsets, stream), _take(max(total, 1) * 4),
-            _take(m * 4)]
-    src, sb, ob, out, st = bufs
-    try:
-        check(L.va_distance_transform_l2_5(src.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()), out.ptr,
-                                           st.ptr, stream))
+    flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+    with _Lease.on(stream) as d:
+        src, sb, ob, out, st = (d.upload(_as_mask(flat)), d.upload(shapes), d.upload(offsets), d.take(max(total, 1) * 4),
+                                d.take(m * 4))
+        check(_hip.lib().va_distance_transform_l2_5(src.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()),
+                                                    out.ptr, st.ptr, stream))
         _check_status(st.download((m,), np.int32, stream), "distance_transform")
         res = out.download((max(total, 1),), np.float32, stream)
-    finally:
-        _give(*bufs)
-    return [res[o:o + s].reshape(a.shape) for o, s, a in zip(offsets, sizes, arrs)]
+    return _split_ragged(res, shapes, offsets, sizes)
 
 
 # ------------------------------------------------------------------------------------ Guo-Hall thinning
@@ -975,25 +920,17 @@ def _thin_words(shape):
 def _thin_resident(arrs, stream):
     """one va_guo_hall_thinning_batch call over 2-d uint8 arrays; (skeletons, int32 iterations)"""
     m = len(arrs)
-    shapes = np.array([a.shape for a in arrs], np.int32).reshape(m, 2)
-    sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
-    offsets = np.zeros(m, np.int64)
-    offsets[1:] = np.cumsum(sizes)[:-1]
-    total = int(sizes.sum())
-    flat = np.concatenate([a.reshape(-1) for a in arrs]) if total else np.zeros(1, np.uint8)
-    L = _hip.lib()
-    bufs = [_upload(flat, stream), _upload(shapes, stream), _upload(offsets, stream), _take(max(total, 1)),
-            _take(m * 4), _take(m * 4)]
-    src, sb, ob, out, it, st = bufs
-    try:
-        check(L.va_guo_hall_thinning_batch(src.ptr, sb.ptr, ob.ptr, total, m, max(_thin_words(a.shape) for a in arrs),
-                                           out.ptr, it.ptr, st.ptr, stream))
+    flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+    with _Lease.on(stream) as d:
+        src, sb, ob, out, it, st = (d.upload(flat), d.upload(shapes), d.upload(offsets), d.take(max(total, 1)),
+                                    d.take(m * 4), d.take(m * 4))
+        check(_hip.lib().va_guo_hall_thinning_batch(src.ptr, sb.ptr, ob.ptr, total, m,
+                                                    max(_thin_words(a.shape) for a in arrs), out.ptr, it.ptr, st.ptr,
+                                                    stream))
         _check_status(st.download((m,), np.int32, stream), "guo_hall_thinning")
         iters = it.download((m,), np.int32, stream)
         res = out.download((max(total, 1),), np.uint8, stream)
-    finally:
-        _give(*bufs)
-    return [res[o:o + n].reshape(a.shape) for o, n, a in zip(offsets, sizes, arrs)], iters
+    return _split_ragged(res, shapes, offsets, sizes), iters
 
 
 def _thin_tiled(stack, stream):
@@ -1004,14 +941,11 @@ def _thin_tiled(stack, stream):
     if need == 0:
         raise ValueError("guo_hall_thinning: a stack of shape %r is beyond the tiled path's limits" % (stack.shape,))
     iters = np.zeros(n, np.int32)
-    bufs = [_upload(stack, stream), _take(need), _take(stack.size)]
-    src, scratch, dst = bufs
-    try:
+    with _Lease.on(stream) as d:
+        src, scratch, dst = d.upload(stack), d.take(need), d.take(stack.size)
         check(L.va_guo_hall_thinning_u8(src.ptr, scratch.ptr, need, dst.ptr, n, h, w, int(THIN_TILED_SUB_ITERATIONS),
                                         int(THIN_TILED_POLL), iters.ctypes.data, None, stream))
         return dst.download(stack.shape, np.uint8, stream), iters
-    finally:
-        _give(*bufs)
 
 
 def guo_hall_thinning(masks, implementation=None, ret_iterations=False, stream=None):
