@@ -448,6 +448,53 @@ int va_guo_hall_thinning_u8(const uint8_t *src_dev, void *scratch_dev, size_t sc
                             int n, int h, int w, int sub_iterations, int poll_period, int32_t *iterations_out,
                             int32_t *stats_out, void *stream);
 
+/* ------------------------------------------------------------------ A15 affine warps and line scans
+ * replaces  cv2.warpAffine(img, matrix, dsize) of single-channel uint8 images (INTER_LINEAR, BORDER_CONSTANT 0) in
+ *           line_scan, video/analysis/image.py:102-106 (the strip and its mean over the rows), and
+ *           get_subimage, video/analysis/image.py:81-82
+ * The definition ("Affine warps and line scans") is the classical fixed-point path of OpenCV
+ * 2.4 .. 4.10, not the float kernels of 4.11 and later.  Unless VA_WARP_INVERSE_MAP is set, the forward 2x3
+ * float64 matrix M is inverted in float64 as cv::warpAffine does: D = M0 M4 - M1 M3; D = D != 0 ? 1/D : 0;
+ * A11 = M4 D; A22 = M0 D; M0 = A11; M1 *= -D; M3 *= -D; M4 = A22; b1 = -M0 M2 - M1 M5; b2 = -M3 M2 - M4 M5;
+ * M2 = b1; M5 = b2.  Destination pixel (x, y) then reads the source at (R: nearest integer, halves to even)
+ *   X = (R((M1 y + M2) 1024) + 16 + R(M0 x 1024)) >> 5,   Y = (R((M4 y + M5) 1024) + 16 + R(M3 x 1024)) >> 5,
+ *   sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31 (arithmetic shifts), and with v00, v01, v10, v11 the
+ *   source at (sy, sx), (sy, sx + 1), (sy + 1, sx), (sy + 1, sx + 1), 0 outside the image,
+ *   out = ((32 - fx)(32 - fy) v00 + fx (32 - fy) v01 + (32 - fx) fy v10 + fx fy v11 + 512) >> 10.
+ * Limits of one item (beyond them its status is VA_ERR_RANGE and nothing of it is written; the other items
+ * run): sides 0 .. VA_WARP_MAX_SIDE, and (|M0| (w - 1) + |M1| (h - 1) + |M2|) 1024 < VA_WARP_COORD_LIMIT for
+ * the inverted matrix and the destination's size, likewise for its second row (OpenCV saturates there); a
+ * frame index outside 0 .. n_frames - 1 or an output range outside 0 .. total_out are refused the same way.
+ * Frames: n_frames uint8 frames of h x w, fewer than 2^29 pixels each. */
+#define VA_WARP_MAX_SIDE 32767
+#define VA_WARP_COORD_LIMIT (1 << 30)
+#define VA_WARP_INVERSE_MAP 1 /* flag bit: the matrix maps destination to source (cv2.WARP_INVERSE_MAP) */
+#define VA_WARP_CHUNK 64      /* columns of a strip per work item of va_line_scan_u8 */
+#define VA_WARP_TILE_W 64     /* tile of va_warp_affine_u8 */
+#define VA_WARP_TILE_H 16
+/* m line scans in one launch.  Scan i warps frame frame_dev[i] (int32) with the forward matrix
+ * matrices_dev[6 i .. 6 i + 5] (float64) into a strip of shapes_dev[2 i] rows and shapes_dev[2 i + 1] columns
+ * (int32) that is never stored: sums_out_dev[out_off_dev[i] + x] (int32; out_off_dev int64, element offsets
+ * into total_out elements) receives the sum of column x over the rows, which is exact in any order; the
+ * profile of line_scan is that sum divided by the rows.  chunk_prefix_dev (int32, m entries): entry i is the
+ * number of work items before scan i, a scan of c columns having max(1, ceil(c / VA_WARP_CHUNK)) of them;
+ * total_chunks: their total.  A table that disagrees with the shapes leaves columns unwritten, never writes
+ * outside a scan's range.  status_dev[i] (int32): VA_OK or VA_ERR_RANGE.  Nothing is copied: the call
+ * enqueues one kernel on `stream`. */
+int va_line_scan_u8(const uint8_t *frames_dev, int n_frames, int h, int w, int m, const int32_t *frame_dev,
+                    const double *matrices_dev, const int32_t *shapes_dev, const int64_t *out_off_dev,
+                    const int32_t *chunk_prefix_dev, int total_chunks, int64_t total_out, int32_t *sums_out_dev,
+                    int32_t *status_dev, void *stream);
+/* m warps in one launch, the same per-item tables; shapes_dev[2 i], shapes_dev[2 i + 1] = (dh, dw) of
+ * destination i, written row-major as uint8 at byte offset out_off_dev[i] of out_dev (total_out bytes);
+ * flags_dev[i] (int32): VA_WARP_INVERSE_MAP or 0.  tile_prefix_dev (int32, m entries): the number of work
+ * items before item i, an item having max(1, ceil(dw / VA_WARP_TILE_W) * ceil(dh / VA_WARP_TILE_H)) of them;
+ * total_tiles: their total.  One kernel on `stream`, nothing copied. */
+int va_warp_affine_u8(const uint8_t *frames_dev, int n_frames, int h, int w, int m, const int32_t *frame_dev,
+                      const double *matrices_dev, const int32_t *shapes_dev, const int32_t *flags_dev,
+                      const int64_t *out_off_dev, const int32_t *tile_prefix_dev, int total_tiles, int64_t total_out,
+                      uint8_t *out_dev, int32_t *status_dev, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -353,6 +353,14 @@ int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const in
 size_t guo_hall_tiled_scratch_bytes(int n, int h, int w);
 int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
                        int32_t *iterations_out, int32_t *stats_out, hipStream_t st);
+// 8-bit affine warps (va_warp.hip): m line scans as int32 column sums, or m warped uint8 destinations, one launch
+int launch_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
+                        const double *mats, const int32_t *shapes, const int64_t *out_off, const int32_t *prefix,
+                        int total_chunks, int64_t total_out, int32_t *sums, int32_t *status, hipStream_t st);
+int launch_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
+                          const double *mats, const int32_t *shapes, const int32_t *flags, const int64_t *out_off,
+                          const int32_t *prefix, int total_tiles, int64_t total_out, uint8_t *out, int32_t *status,
+                          hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

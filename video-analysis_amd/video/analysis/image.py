@@ -1,6 +1,7 @@
 """Image operations: region properties from image moments, morphology, statistics.
 
-Reference: video/analysis/image.py -- subpixel(s) :23-57, set_image_border :205-210, regionprops :310-405.
+Reference: video/analysis/image.py -- subpixel(s) :23-57, get_subimage :61-85, line_scan :89-106,
+get_steepest_point :110-127, set_image_border :205-210, regionprops :310-405.
 The ten spatial moments are accumulated on the GPU from run segments (exact integers); the
 central / normalised moments and the derived scalars are the reference's formulas evaluated in
 float64 on the host (a few dozen flops per region).
@@ -55,6 +56,108 @@ def subpixels(img, pts):
             weight_tr * img[yi, xi + 1] +
             weight_bl * img[yi + 1, xi] +
             weight_br * img[yi + 1, xi + 1])
+
+
+def _round_half_away(x):
+    """Python 2's round(x), which the reference's get_subimage sizes its result with"""
+    x = float(x)
+    f = math.floor(abs(x))
+    if abs(x) - f >= 0.5:
+        f += 1.0
+    return math.copysign(f, x)
+
+
+def _uint8_image(img, what, ndims=(2,)):
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in ndims:
+        raise TypeError("%s: single-channel uint8 images only (float, int16 and colour images are not supported on "
+                        "the GPU path), got %s of shape %r" % (what, img.dtype, img.shape))
+    return img
+
+
+def get_subimage(img, slice_x, slice_y, width=None, height=None):
+    """extracts the subimage specified by `slice_x` and `slice_y`, optionally resampled to `width` x `height`
+    pixels (reference :61-85), through the batched cv2.warpAffine of the GPU path (ops.warp_affine; DESIGN.md §9,
+    "Affine warps and line scans").  The reference's transposed naming is kept: the result has int(round(width))
+    rows and int(round(height)) columns, `round` being Python 2's (halves away from zero).
+    Deviations: uint8 images only (TypeError otherwise); an empty result (a rounded side of 0) and a degenerate
+    slice raise ValueError, where OpenCV would warp to the source's size or return an arbitrary matrix."""
+    from .. import ops
+    img = _uint8_image(img, "get_subimage")
+    p1_x, p2_x = slice_x[:2]
+    p1_y, p2_y = slice_y[:2]
+
+    if width is None:
+        width = p2_x - p1_x
+
+    if height is None:
+        if p2_x == p1_x:
+            raise ValueError("get_subimage: slice_x is empty")
+        height = (p2_y - p1_y) * width / (p2_x - p1_x)
+
+    # get corresponding points between the two images
+    pts1 = np.array(((p1_x, p1_y), (p1_x, p2_y), (p2_x, p1_y)), np.float32)
+    pts2 = np.array(((0, 0), (height, 0), (0, width)), np.float32)
+
+    # determine and apply the affine transformation
+    matrix = ops.affine_transforms(pts1, pts2)
+    cols, rows = int(_round_half_away(height)), int(_round_half_away(width))
+    if cols < 1 or rows < 1:
+        raise ValueError("get_subimage: empty result (%d rows, %d columns)" % (rows, cols))
+    return ops.warp_affine(img, matrix, [(rows, cols)])[0]
+
+
+def line_scan(img, p1, p2, half_width=5):
+    """returns the average intensity of an image along a strip of a given half_width, ranging from point p1 to p2
+    (reference :89-106): the strip is cv2.warpAffine's, int(2*half_width) rows of int(length) columns, averaged
+    over its rows (ops.line_scans; DESIGN.md §9, "Affine warps and line scans").  One scan is one launch: many
+    scans of a frame or a stack belong in `line_scans`.
+    Deviations: uint8 images only (TypeError otherwise); an empty strip (length < 1 or 2*half_width < 1) and
+    p1 == p2 raise ValueError, where the reference returns the column means of a warp to the source's size."""
+    from .. import ops
+    return ops.line_scans(_uint8_image(img, "line_scan"), [p1], [p2], half_width)[0]
+
+
+def line_scans(img_or_stack, p1s, p2s, half_width=5):
+    """line_scan for many strips in one launch.  With one (h, w) image, p1s and p2s are (m, 2) points and the
+    result is the list of m profiles.  With an (n, h, w) stack they hold one (m_f, 2) array per frame, and the
+    result is one list of profiles per frame.  half_width: one number for all scans."""
+    from .. import ops
+    img = _uint8_image(img_or_stack, "line_scans", (2, 3))
+    if img.ndim == 2:
+        return ops.line_scans(img, p1s, p2s, half_width)
+    if len(p1s) != len(img) or len(p2s) != len(img):
+        raise ValueError("line_scans: a stack of %d frames needs %d point arrays" % (len(img), len(img)))
+    a = [np.asarray(p, np.float64).reshape(-1, 2) for p in p1s]
+    b = [np.asarray(p, np.float64).reshape(-1, 2) for p in p2s]
+    counts = [len(p) for p in a]
+    if counts != [len(p) for p in b]:
+        raise ValueError("line_scans: start and end points differ in number")
+    if sum(counts) == 0:
+        return [[] for _ in counts]
+    flat = ops.line_scans(img, np.concatenate(a), np.concatenate(b), half_width,
+                          frame_index=np.repeat(np.arange(len(img)), counts))
+    ends = np.cumsum(counts).tolist()
+    return [flat[e - c:e] for c, e in zip(counts, ends)]
+
+
+def get_steepest_point(profile, direction=1, smoothing=0):
+    """returns the index where the profile is steepest (reference :110-127; host arithmetic).
+
+    profile is a 1D array of intensities
+    direction determines whether ascending (direction=1) or descending (direction=-1) slopes are search for
+    smoothing determines the standard deviation of a Gaussian smoothing filter that is applied before looking
+        for the slope"""
+    if len(profile) < 2:
+        return np.nan
+
+    if smoothing > 0:
+        from scipy.ndimage import gaussian_filter1d
+        profile = gaussian_filter1d(profile, smoothing)
+
+    i_max = np.argmax(direction * np.diff(profile))
+
+    return i_max + 0.5
 
 
 def moments_from_spatial(spatial):

@@ -1003,3 +1003,172 @@ def guo_hall_thinning(masks, implementation=None, ret_iterations=False, stream=N
     if is_stack:
         out = np.stack(out) if m else np.zeros(masks.shape, np.uint8)
     return (out, iters) if ret_iterations else out
+
+
+# ------------------------------------------------------------------------- affine warps and line scans
+WARP_MAX_SIDE = 32767            # VA_WARP_MAX_SIDE .. VA_WARP_INVERSE_MAP, include/videoanalysis_hip.h
+WARP_CHUNK = 64
+WARP_TILE_W, WARP_TILE_H = 64, 16
+WARP_INVERSE_MAP = 1
+
+
+def affine_transforms(src_pts, dst_pts):
+    """cv2.getAffineTransform(src, dst) for a batch of point triples: (m, 3, 2) each (or one (3, 2) pair), cast to
+    float32 as cv2 takes them; returns (m, 2, 3) float64.  The 6x6 systems (rows i and i + 3 = (x_i, y_i, 1, 0, 0, 0
+    | X_i) and (0, 0, 0, x_i, y_i, 1 | Y_i)) are solved as cv::solve(DECOMP_LU) solves them, operation by operation
+    (DESIGN.md §9): the order is part of the definition, a closed form changes pixels.  Host arithmetic, vectorised
+    over the batch.  A pivot below 100 eps (collinear source points) raises ValueError."""
+    src = np.asarray(src_pts, np.float32).astype(np.float64).reshape(-1, 3, 2)
+    dst = np.asarray(dst_pts, np.float32).astype(np.float64).reshape(-1, 3, 2)
+    if len(src) != len(dst):
+        raise ValueError("affine_transforms: %d source and %d destination triples" % (len(src), len(dst)))
+    m = len(src)
+    a, b = np.zeros((m, 6, 6)), np.zeros((m, 6))
+    a[:, :3, 0:2], a[:, :3, 2] = src, 1.0
+    a[:, 3:, 3:5], a[:, 3:, 5] = src, 1.0
+    b[:, :3], b[:, 3:] = dst[:, :, 0], dst[:, :, 1]
+    idx = np.arange(m)
+    for i in range(6):
+        k = i + np.argmax(np.abs(a[:, i:, i]), axis=1)       # the first of the largest, as the scan with `>` finds it
+        bad = np.flatnonzero(~(np.abs(a[idx, k, i]) >= 100 * np.finfo(np.float64).eps))
+        if len(bad):
+            raise ValueError("affine_transforms: the source points of item %d are collinear" % bad[0])
+        row, rhs = a[idx, i].copy(), b[idx, i].copy()
+        a[idx, i], b[idx, i] = a[idx, k], b[idx, k]
+        a[idx, k], b[idx, k] = row, rhs
+        d = -1 / a[:, i, i]
+        for j in range(i + 1, 6):
+            alpha = a[:, j, i] * d
+            a[:, j, i + 1:] += alpha[:, None] * a[:, i, i + 1:]
+            b[:, j] += alpha * b[:, i]
+    for i in range(5, -1, -1):
+        s = b[:, i].copy()
+        for c in range(i + 1, 6):
+            s -= a[:, i, c] * b[:, c]
+        b[:, i] = s / a[:, i, i]
+    return b.reshape(m, 2, 3)
+
+
+def _warp_frames(frames, m, frame_index, what):
+    """(contiguous (n, h, w) uint8 stack, int32 frame index per item)"""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8:
+        raise TypeError("%s: single-channel uint8 frames only, got %s" % (what, frames.dtype))
+    arr, n, fshape, _ = _as_batch(frames, 2)
+    arr = arr.reshape((n,) + tuple(fshape))
+    if fshape[0] < 1 or fshape[1] < 1:
+        raise ValueError("%s: empty frames of shape %r" % (what, tuple(fshape)))
+    if frame_index is None:
+        if n != 1:
+            raise ValueError("%s: a stack of %d frames needs a frame_index per item" % (what, n))
+        fidx = np.zeros(m, np.int32)
+    else:
+        fidx = np.asarray(frame_index, np.int64).reshape(-1)
+        if len(fidx) != m or np.any(fidx < 0) or np.any(fidx >= n):
+            raise ValueError("%s: frame_index must hold %d entries in 0 .. %d" % (what, m, n - 1))
+        fidx = fidx.astype(np.int32)
+    return arr, fidx
+
+
+def _work_prefix(counts, what):
+    """(int32 exclusive prefix of the per-item work-item counts, their total)"""
+    total = int(counts.sum())
+    if total >= 2 ** 31:
+        raise ValueError("%s: %d work items in one call (fewer than 2^31 are supported)" % (what, total))
+    prefix = np.zeros(len(counts), np.int64)
+    prefix[1:] = np.cumsum(counts)[:-1]
+    return prefix.astype(np.int32), total
+
+
+def line_scan_tables(p1, p2, half_width=5):
+    """the host side of line_scan (video/analysis/image.py:95-103) for m scans: (matrices (m, 2, 3) float64, rows,
+    cols int64 (m,)).  length = hypot, angle = arctan2 in float64, p0 = (p1x + hw sin, p1y - hw cos); the triple
+    (p0, p1, p2) maps onto ((0, 0), (0, hw), (length, hw)); the strip has int(2 hw) rows and int(length) columns.
+    An empty strip or one beyond WARP_MAX_SIDE raises ValueError."""
+    p1 = np.asarray(p1, np.float64).reshape(-1, 2)
+    p2 = np.asarray(p2, np.float64).reshape(-1, 2)
+    m = len(p1)
+    if len(p2) != m:
+        raise ValueError("line_scans: %d start and %d end points" % (m, len(p2)))
+    hw = np.broadcast_to(np.asarray(half_width, np.float64), (m,)) if np.ndim(half_width) == 0 else \
+        np.asarray(half_width, np.float64).reshape(-1)
+    if len(hw) != m:
+        raise ValueError("line_scans: %d half widths for %d scans" % (len(hw), m))
+    dx, dy = p2[:, 0] - p1[:, 0], p2[:, 1] - p1[:, 1]
+    length, angle = np.hypot(dx, dy), np.arctan2(dy, dx)
+    if not (np.all(np.isfinite(length)) and np.all(np.isfinite(hw))):
+        raise ValueError("line_scans: points and half widths must be finite")
+    bad = np.flatnonzero((length < 1) | (2 * hw < 1))
+    if len(bad):
+        raise ValueError("line_scans: scan %d is empty (length %g, half width %g)" % (bad[0], length[bad[0]], hw[bad[0]]))
+    bad = np.flatnonzero((length >= WARP_MAX_SIDE + 1) | (2 * hw >= WARP_MAX_SIDE + 1))
+    if len(bad):
+        raise ValueError("line_scans: scan %d exceeds %d pixels a side" % (bad[0], WARP_MAX_SIDE))
+    src = np.stack([np.stack([p1[:, 0] + hw * np.sin(angle), p1[:, 1] - hw * np.cos(angle)], 1), p1, p2], 1)
+    dst = np.zeros((m, 3, 2))
+    dst[:, 1, 1], dst[:, 2, 0], dst[:, 2, 1] = hw, length, hw
+    return affine_transforms(src, dst), (2 * hw).astype(np.int64), length.astype(np.int64)
+
+
+def line_scans(frames, p1, p2, half_width=5, frame_index=None, stream=None, ret_sums=False):
+    """line_scan(img, p1, p2, half_width) (video/analysis/image.py:89-106) for m scans in one launch: the mean over
+    the width of the strip from p1 to p2 that cv2.warpAffine cuts out of the frame ("Affine warps and
+    line scans").  frames: one (h, w) uint8 frame or an (n, h, w) stack with frame_index (m,) naming each scan's
+    frame; p1, p2: (m, 2) (x, y) points; half_width: a number or (m,).  Returns the list of float64 profiles, each
+    the GPU's exact int32 column sums divided by the strip's rows; with ret_sums also the list of those sums."""
+    mats, rows, cols = line_scan_tables(p1, p2, half_width)
+    m = len(rows)
+    arr, fidx = _warp_frames(frames, m, frame_index, "line_scans")
+    if m == 0:
+        return ([], []) if ret_sums else []
+    n, h, w = arr.shape
+    _, shapes, offsets, sizes, total = _pack_ragged(np.stack([np.ones(m, np.int64), cols], 1))
+    prefix, chunks = _work_prefix(np.maximum(1, -(-cols // WARP_CHUNK)), "line_scans")
+    with _Lease.on(stream) as d:
+        fb, ib, mb, sb, ob, pb = (d.upload(arr), d.upload(fidx), d.upload(mats),
+                                  d.upload(np.stack([rows, cols], 1).astype(np.int32)), d.upload(offsets),
+                                  d.upload(prefix))
+        out, st = d.take(total * 4), d.take(m * 4)
+        check(_hip.lib().va_line_scan_u8(fb.ptr, n, h, w, m, ib.ptr, mb.ptr, sb.ptr, ob.ptr, pb.ptr, chunks, total,
+                                         out.ptr, st.ptr, stream))
+        _check_status(st.download((m,), np.int32, stream), "line_scans")
+        flat = out.download((total,), np.int32, stream)
+    sums = [s[0] for s in _split_ragged(flat, shapes, offsets, sizes)]
+    profiles = [s.astype(np.float64) / r for s, r in zip(sums, rows.tolist())]
+    return (profiles, sums) if ret_sums else profiles
+
+
+def warp_affine(frames, matrices, sizes, frame_index=None, inverse=False, stream=None):
+    """cv2.warpAffine(frame, matrix, (dw, dh)) with INTER_LINEAR and BORDER_CONSTANT 0 for m items in one launch
+    (get_subimage, video/analysis/image.py:81-82).  frames: one (h, w) uint8 frame or an (n, h, w)
+    stack with frame_index (m,); matrices: (m, 2, 3) float64 forward maps (or one (2, 3)); sizes: (m, 2) NumPy shapes
+    (dh, dw) of the destinations; inverse: True, or (m,) booleans, for matrices that map destination to source
+    (cv2.WARP_INVERSE_MAP).  Returns the list of (dh, dw) uint8 arrays.  An empty destination raises ValueError
+    (OpenCV would warp to the source's size)."""
+    mats = np.ascontiguousarray(matrices, np.float64).reshape(-1, 2, 3)
+    m = len(mats)
+    sz = np.asarray(sizes, np.int64).reshape(-1, 2)
+    if len(sz) != m:
+        raise ValueError("warp_affine: %d matrices and %d sizes" % (m, len(sz)))
+    bad = np.flatnonzero(np.any(sz < 1, axis=1))
+    if len(bad):
+        raise ValueError("warp_affine: destination %d is empty (%d x %d)" % (bad[0], sz[bad[0], 0], sz[bad[0], 1]))
+    if np.any(sz > WARP_MAX_SIDE):
+        raise ValueError("warp_affine: destinations are limited to %d pixels a side" % WARP_MAX_SIDE)
+    flags = np.broadcast_to(np.asarray(inverse, bool), (m,)).astype(np.int32) * WARP_INVERSE_MAP
+    arr, fidx = _warp_frames(frames, m, frame_index, "warp_affine")
+    if m == 0:
+        return []
+    n, h, w = arr.shape
+    _, shapes, offsets, sizes_, total = _pack_ragged(sz)
+    prefix, tiles = _work_prefix(np.maximum(1, (-(-sz[:, 0] // WARP_TILE_H)) * (-(-sz[:, 1] // WARP_TILE_W))),
+                                 "warp_affine")
+    with _Lease.on(stream) as d:
+        fb, ib, mb, sb, gb, ob, pb = (d.upload(arr), d.upload(fidx), d.upload(mats), d.upload(shapes),
+                                      d.upload(flags), d.upload(offsets), d.upload(prefix))
+        out, st = d.take(total), d.take(m * 4)
+        check(_hip.lib().va_warp_affine_u8(fb.ptr, n, h, w, m, ib.ptr, mb.ptr, sb.ptr, gb.ptr, ob.ptr, pb.ptr, tiles,
+                                           total, out.ptr, st.ptr, stream))
+        _check_status(st.download((m,), np.int32, stream), "warp_affine")
+        flat = out.download((total,), np.uint8, stream)
+    return _split_ragged(flat, shapes, offsets, sizes_)
