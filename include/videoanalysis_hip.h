@@ -363,6 +363,37 @@ int va_active_contour(const double *fx_dev, const double *fy_dev, int n, int h, 
                       const double *anchor_vals_dev, double gamma, double tol_gamma, int max_iterations,
                       double *pts_inout_dev, int32_t *iterations_out_dev, double *total_variation_out_dev,
                       void *stream);
+/* replaces  cv2.GaussianBlur(potential, (0, 0), sigma) and both cv2.Sobel calls of ActiveContour.set_potential,
+ *           video/analysis/active_contour.py:104-110, for the potentials of many polygons at once
+ *           (Polygon.get_centerline_optimized, video/analysis/shapes.py:735-743)
+ * m items of a ragged packed buffer, laid out as for va_distance_transform_l2_5: item i is (shapes_dev[2i],
+ * shapes_dev[2i + 1]) = (h, w) at element offset offsets_dev[i] (int64) of src_dev, and its two float64 planes
+ * go to the same element offset of fx_out_dev and fy_out_dev; every buffer holds `total` elements.  Each item
+ * is an image of its own: blur and Sobel reflect (BORDER_REFLECT_101) at the item's edges, and the Sobel
+ * reflects the blurred image ("Batched centre lines").  dtype: VA_F32, blurred as
+ * va_gaussian_f32 blurs when sigma > 0, or VA_U8 with sigma == 0 (the 8-bit blur is a different, fixed-point
+ * arithmetic: VA_U8 with sigma > 0 is VA_ERR_INVALID).  One workgroup keeps an item in LDS at 8 bytes per
+ * pixel; max_pixels is the largest h * w of the call (<= VA_GRAD_RESIDENT_MAX_PIXELS: 64 KiB; it sizes the
+ * LDS).  status_dev[i] (int32): VA_OK, or VA_ERR_RANGE for an item above max_pixels or outside `total` (not
+ * written); an empty item is VA_OK.  Nothing is copied: the call enqueues one kernel on `stream`. */
+#define VA_GRAD_RESIDENT_MAX_PIXELS 8192
+int va_potential_gradients_ragged(const void *src_dev, int dtype, const int32_t *shapes_dev,
+                                  const int64_t *offsets_dev, int64_t total, int m, int max_pixels, double sigma,
+                                  double *fx_out_dev, double *fy_out_dev, int32_t *status_dev, void *stream);
+/* replaces  the iteration of ActiveContour.find_contour, video/analysis/active_contour.py:160-191, on
+ *           potentials of different sizes
+ * va_active_contour on the planes va_potential_gradients_ragged writes: contour c runs on item item_dev[c]
+ * of the n_items items, whose plane starts at offsets_dev[item] with a row stride of its own w and is clipped
+ * to its own (w - 2, h - 2).  An item index out of range, an item with h < 2 or w < 2 or a plane that does not
+ * fit in `total` gives iterations -1 and leaves the contour untouched.  Everything else is as for
+ * va_active_contour. */
+int va_active_contour_ragged(const double *fx_dev, const double *fy_dev, const int32_t *shapes_dev,
+                             const int64_t *offsets_dev, int64_t total, int n_items, int m, int max_points,
+                             const int32_t *npts_dev, const int32_t *item_dev, const double *mats_dev,
+                             const int64_t *mat_offset_dev, int64_t mats_count, const uint8_t *anchor_flags_dev,
+                             const double *anchor_vals_dev, double gamma, double tol_gamma, int max_iterations,
+                             double *pts_inout_dev, int32_t *iterations_out_dev,
+                             double *total_variation_out_dev, void *stream);
 
 /* ------------------------------------------------------------------ A13 polygons
  * Limits of one polygon / mask of the two calls below (beyond them its status is VA_ERR_RANGE):

@@ -1141,9 +1141,64 @@ int va_active_contour(const double *fx, const double *fy, int n, int h, int w, i
     VA_REQUIRE(fx && fy && npts && frame && mats && mat_offset && pts_inout && iterations_out && total_variation_out,
                "va_active_contour: NULL argument");
     VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour: anchor flags without anchor values");
-    return launch_active_contour(fx, fy, n, h, w, m, max_points, npts, frame, mats, mat_offset, mats_count,
-                                 anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts_inout,
+    return launch_active_contour(fx, fy, nullptr, nullptr, 0, n, h, w, m, max_points, npts, frame, mats, mat_offset,
+                                 mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts_inout,
                                  iterations_out, total_variation_out, as_stream(stream));
+}
+
+int va_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
+                                  int64_t total, int m, int max_pixels, double sigma, double *fx_out, double *fy_out,
+                                  int32_t *status, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32,
+               "va_potential_gradients_ragged: items must be VA_U8 or VA_F32 (got dtype %d)", dtype);
+    VA_REQUIRE(sigma >= 0 && sigma == sigma, "va_potential_gradients_ragged: sigma must be >= 0 (got %g)", sigma);
+    VA_REQUIRE(dtype == VA_F32 || sigma == 0,
+               "va_potential_gradients_ragged: VA_U8 items take sigma == 0 only (the 8-bit blur is fixed-point)");
+    VA_REQUIRE(m >= 0 && total >= 0, "va_potential_gradients_ragged: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_pixels >= 0 && max_pixels <= kGradResidentMaxPixels,
+               "va_potential_gradients_ragged: max_pixels %d outside 0 .. %d", max_pixels, kGradResidentMaxPixels);
+    TapsF32 taps;
+    taps.ksize = 0;
+    if (sigma > 0) {
+        int rc = gauss_taps_f32(sigma, &taps.ksize, taps.t, kMaxTaps);
+        if (rc)
+            return rc;
+    }
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(shapes && offsets && status && ((src && fx_out && fy_out) || total == 0),
+               "va_potential_gradients_ragged: NULL argument");
+    return launch_potential_gradients_ragged(src, dtype, shapes, offsets, total, m, max_pixels, taps, fx_out, fy_out,
+                                             status, as_stream(stream));
+}
+
+int va_active_contour_ragged(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
+                             int64_t total, int n_items, int m, int max_points, const int32_t *npts,
+                             const int32_t *item, const double *mats, const int64_t *mat_offset, int64_t mats_count,
+                             const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
+                             int max_iterations, double *pts_inout, int32_t *iterations_out,
+                             double *total_variation_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n_items >= 0 && total >= 0, "va_active_contour_ragged: negative count (n_items %d, total %lld)",
+               n_items, (long long)total);
+    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
+               "va_active_contour_ragged: bad contour table (%d contours of up to %d points; at most %d points)", m,
+               max_points, kSnakeMaxN);
+    VA_REQUIRE(max_iterations >= 1, "va_active_contour_ragged: max_iterations must be >= 1 (got %d)", max_iterations);
+    VA_REQUIRE(mats_count >= 0, "va_active_contour_ragged: negative matrix table size");
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(fx && fy && shapes && offsets && npts && item && mats && mat_offset && pts_inout && iterations_out &&
+                   total_variation_out,
+               "va_active_contour_ragged: NULL argument");
+    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour_ragged: anchor flags without anchor values");
+    return launch_active_contour(fx, fy, shapes, offsets, total, n_items, 0, 0, m, max_points, npts, item, mats,
+                                 mat_offset, mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations,
+                                 pts_inout, iterations_out, total_variation_out, as_stream(stream));
 }
 
 int va_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,

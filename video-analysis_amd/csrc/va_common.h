@@ -326,11 +326,19 @@ int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, doub
 constexpr int kSnakeLdsMaxN = 128;
 constexpr int kSnakeMaxN = 1024;
 int launch_sobel5_f64(const void *src, int dtype, double *fx, double *fy, int n, int h, int w, hipStream_t st);
-int launch_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
-                          const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_off,
-                          int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
-                          double tol_gamma, int max_iterations, double *pts, int32_t *iterations,
-                          double *total_variation, hipStream_t st);
+// shapes, offsets, total: the planes are the items of a ragged buffer (n of them; h, w unused), null for a stack
+int launch_active_contour(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
+                          int64_t total, int n, int h, int w, int m, int max_points, const int32_t *npts,
+                          const int32_t *frame, const double *mats, const int64_t *mat_off, int64_t mats_count,
+                          const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
+                          int max_iterations, double *pts, int32_t *iterations, double *total_variation,
+                          hipStream_t st);
+// blur + Sobel of the items of a ragged buffer, one workgroup per item with the item in LDS (va_gradients.hip);
+// taps.ksize == 0: no blur
+constexpr int kGradResidentMaxPixels = VA_GRAD_RESIDENT_MAX_PIXELS;
+int launch_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
+                                      int64_t total, int m, int max_pixels, const TapsF32 &taps, double *fx,
+                                      double *fy, int32_t *status, hipStream_t st);
 // Polygons (va_polygon.hip): batched cv2.fillPoly and cv2.distanceTransform(DIST_L2, 5), one workgroup per item
 constexpr int kFillMaxVerts = VA_FILL_MAX_VERTS;
 constexpr int kPolyMaxSide = VA_FILL_MAX_SIDE;

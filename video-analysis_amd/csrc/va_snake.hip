@@ -12,7 +12,8 @@
 //                   antisymmetric  s = 0.0; s += 2*(S[y+1] - S[y-1]); s += S[y+2] - S[y-2]
 //          fx = column-smooth(row-derivative), fy = column-derivative(row-smooth); BORDER_REFLECT_101.
 // snake  : every iteration of every contour of a call in one launch (find_contour, :113-196); one
-//          workgroup owns one contour.  Per iteration: bilinear gather of fx, fy (image.subpixels),
+//          workgroup owns one contour, on its frame of an (n, h, w) stack or on its item of a ragged buffer
+//          (va_active_contour_ragged: base, row stride and clip bounds are the item's).  Per iteration: bilinear gather of fx, fy (image.subpixels),
 //          rhs = p + gamma*f, ps = Pinv @ rhs with acc = P[i,0]*rhs[0], acc += P[i,j]*rhs[j] in
 //          ascending j, anchors, residual, clip, and a workgroup-uniform stop.  The matrices arrive
 //          transposed (element (j, i) = Pinv[i, j]) so that the lanes of a wave read consecutive
@@ -135,6 +136,11 @@ constexpr int kSnakeBlock = 256;
 
 struct SnakeArgs {
     const double *fx, *fy;
+    // ragged planes (va_active_contour_ragged): item f is (shapes[2f], shapes[2f + 1]) at element offset offsets[f]
+    // of `total`; both null for an (n, h, w) stack
+    const int32_t *shapes;
+    const int64_t *offsets;
+    int64_t total;
     int n, h, w, m, max_points;
     const int32_t *npts, *frame;
     const double *mats;
@@ -190,7 +196,21 @@ snake_kernel(SnakeArgs a)
     const int tid = threadIdx.x, c = blockIdx.x;
     const int N = a.npts[c], f = a.frame[c];
     const int64_t off = a.mat_off[c];
-    if (N <= 2 || N > a.max_points || N > NMAX || f < 0 || f >= a.n || off < 0 ||
+    // the contour's plane, once per workgroup: (base, h, w) of its frame of the stack or of its ragged item
+    int h = a.h, w = a.w;
+    int64_t base = 0;
+    bool plane_ok = f >= 0 && f < a.n;
+    if (plane_ok) {
+        if (a.shapes) {
+            h = a.shapes[2 * f];
+            w = a.shapes[2 * f + 1];
+            base = a.offsets[f];
+            plane_ok = h >= 2 && w >= 2 && base >= 0 && base <= a.total - (int64_t)h * w;
+        } else {
+            base = (int64_t)f * h * w;
+        }
+    }
+    if (N <= 2 || N > a.max_points || N > NMAX || !plane_ok || off < 0 ||
         off > a.mats_count - (int64_t)N * N) {
         if (tid == 0) {                    // nothing to iterate (N <= 2) or an entry the host should not send
             a.iterations[c] = N <= 2 && N >= 0 && N <= a.max_points ? 0 : -1;
@@ -198,8 +218,8 @@ snake_kernel(SnakeArgs a)
         }
         return;
     }
-    const double xmax = a.w - 2, ymax = a.h - 2;
-    const double *gx = a.fx + (size_t)f * a.h * a.w, *gy = a.fy + (size_t)f * a.h * a.w;
+    const double xmax = w - 2, ymax = h - 2;
+    const double *gx = a.fx + base, *gy = a.fy + base;
     const double *PT = a.mats + off;
     double *pts = a.pts + (size_t)c * a.max_points * 2;
     const uint8_t *af = a.anchor_flags ? a.anchor_flags + (size_t)c * a.max_points : nullptr;
@@ -236,7 +256,7 @@ snake_kernel(SnakeArgs a)
             // trunc, as astype(int); the clamp only guards the reads (x, y are within the clip range)
             const int xi = (int)fmin(fmax(x, 0.0), xmax), yi = (int)fmin(fmax(y, 0.0), ymax);
             const double dx = x - xi, dy = y - yi;
-            const double fex = subpixel(gx, a.w, xi, yi, dx, dy), fey = subpixel(gy, a.w, xi, yi, dx, dy);
+            const double fex = subpixel(gx, w, xi, yi, dx, dy), fey = subpixel(gy, w, xi, yi, dx, dy);
             s_r[0][i] = x + a.gamma * fex;
             s_r[1][i] = y + a.gamma * fey;
         }
@@ -318,16 +338,17 @@ int launch_sobel5_f64(const void *src, int dtype, double *fx, double *fy, int n,
     return VA_OK;
 }
 
-int launch_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
-                          const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_off,
-                          int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
-                          double tol_gamma, int max_iterations, double *pts, int32_t *iterations,
-                          double *total_variation, hipStream_t st)
+int launch_active_contour(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
+                          int64_t total, int n, int h, int w, int m, int max_points, const int32_t *npts,
+                          const int32_t *frame, const double *mats, const int64_t *mat_off, int64_t mats_count,
+                          const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
+                          int max_iterations, double *pts, int32_t *iterations, double *total_variation,
+                          hipStream_t st)
 {
     if (m == 0)
         return VA_OK;
-    SnakeArgs a{fx, fy, n, h, w, m, max_points, npts, frame, mats, mat_off, mats_count, anchor_flags,
-                anchor_vals, gamma, tol_gamma, max_iterations, pts, iterations, total_variation};
+    SnakeArgs a{fx, fy, shapes, offsets, total, n, h, w, m, max_points, npts, frame, mats, mat_off, mats_count,
+                anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts, iterations, total_variation};
     // the widest contour of the call picks the instantiation; all of them compute the same numbers
     if (max_points <= 64)
         hipLaunchKernelGGL((snake_kernel<64, true>), dim3(m), dim3(kSnakeBlock), 0, st, a);

@@ -123,6 +123,9 @@ SIGNATURES = {
     "va_sobel5_f64": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "va_active_contour": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _d, _d, _i, _vp,
                                _vp, _vp, _vp]),
+    "va_potential_gradients_ragged": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, _vp, _vp]),
+    "va_active_contour_ragged": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _d, _d,
+                                      _i, _vp, _vp, _vp, _vp]),
     "va_fill_poly": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "va_distance_transform_l2_5": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "va_guo_hall_thinning_batch": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),

@@ -3,7 +3,8 @@ video/analysis/active_contour.py).
 
 set_potential blurs the potential and takes both 5-tap Sobel gradients on the GPU, and keeps the two
 float64 planes there; find_contours runs every iteration of every contour of a call in one kernel launch
-(va_snake.hip).  The host keeps the per-contour preparation: equidistant points, the point spacing, the
+(va_snake.hip).  The potential is one image, a stack of equal-sized frames, or a list of images of different
+shapes (the distance maps of many polygons), which is kept as one ragged buffer (va_gradients.hip).  The host keeps the per-contour preparation: equidistant points, the point spacing, the
 evolution matrix (NumPy, the reference's formula and np.linalg.inv, cached by (N, ds)) and the anchors.
 
 Arithmetic ("Active contours"): the forces, the update and the clip are the reference's; the
@@ -44,7 +45,8 @@ class ActiveContour(object):
         self.closed_loop = closed_loop
 
         self.clear_cache()  #< also initializes the cache
-        self._grad = None  #< (fx, fy, (n, h, w)) on the device
+        self._grad = None  #< (fx, fy, (n, h, w)) on the device; ragged: (fx, fy, (shapes, offsets))
+        self._ragged = False  #< the potential is a list of images of different shapes
         self._host = {}  #< downloaded planes
         self.info = {}
 
@@ -99,8 +101,14 @@ class ActiveContour(object):
     # ------------------------------------------------------------------------------- potential
     def set_potential(self, potential):
         """ sets the potential and calculates the associated derivatives.  `potential` is one (h, w)
-        image or an (n, h, w) stack, uint8 or float32; find_contour(..., frame=k) picks a frame """
+        image or an (n, h, w) stack, uint8 or float32; find_contour(..., frame=k) picks a frame.  A list or
+        tuple of 2-d potentials of different shapes (one dtype) is kept as it is: every item is blurred and
+        differentiated as an image of its own, fx and fy are then lists, and frame=k picks item k """
         from .. import ops
+        if isinstance(potential, (list, tuple)) and len(potential) > 0:
+            items = [np.asarray(q) for q in potential]
+            if all(q.ndim == 2 for q in items) and len(set(q.shape for q in items)) > 1:
+                return self._set_ragged_potential(items)
         p = np.asarray(potential)
         if p.dtype not in (np.uint8, np.float32):
             raise TypeError("ActiveContour: potentials must be uint8 or float32, got %s" % p.dtype)
@@ -117,16 +125,40 @@ class ActiveContour(object):
         self._grad = grad
         self._single = p.ndim == 2
 
+    def _set_ragged_potential(self, items):
+        from .. import ops
+        for q in items:
+            if q.dtype not in (np.uint8, np.float32):
+                raise TypeError("ActiveContour: potentials must be uint8 or float32, got %s" % q.dtype)
+            if q.shape[0] < 2 or q.shape[1] < 2:
+                raise ValueError("ActiveContour: the potential needs h, w >= 2 (got shape %r)" % (q.shape,))
+        self._set_gradients(*ops.potential_gradients_ragged(items, self.blur_radius if self.blur_radius > 0 else 0.0))
+
+    def _set_gradients(self, fx, fy, shapes, offsets):
+        """takes over the ragged gradient planes (fx, fy float64 DeviceBuffers, item k of shape shapes[k] at
+        element offset offsets[k]) as ops.potential_gradients_ragged / ops.centerline_gradients return them"""
+        self._release()
+        self._grad = (fx, fy, (np.asarray(shapes, np.int32).reshape(-1, 2), np.asarray(offsets, np.int64).reshape(-1)))
+        self._ragged = True
+        self._single = False
+
     def _release(self):
         if self._grad is not None:
             self._grad[0].free()
             self._grad[1].free()
         self._grad = None
+        self._ragged = False
         self._host = {}
 
     def _plane(self, k):
         if self._grad is None:
             return None
+        if k not in self._host and self._ragged:
+            shapes, offsets = self._grad[2]
+            sizes = shapes[:, 0].astype(np.int64) * shapes[:, 1]
+            flat = self._grad[k].download((int(sizes.sum()),), np.float64)
+            self._host[k] = [flat[o:o + s].reshape(hw) for o, s, hw in zip(offsets.tolist(), sizes.tolist(),
+                                                                           shapes.tolist())]
         if k not in self._host:
             n, h, w = self._grad[2]
             v = self._grad[k].download((n, h, w), np.float64)
@@ -135,8 +167,8 @@ class ActiveContour(object):
 
     @property
     def fx(self):
-        """the x gradient (h, w) -- or (n, h, w) for a stack -- float64, downloaded when read; None before
-        set_potential"""
+        """the x gradient (h, w) -- or (n, h, w) for a stack, a list of arrays for a list of potentials --
+        float64, downloaded when read; None before set_potential"""
         return self._plane(0)
 
     @property
@@ -186,7 +218,7 @@ class ActiveContour(object):
         if self._grad is None:
             raise RuntimeError('Potential must be set before the contour can be adapted.')
         fxb, fyb, shape = self._grad
-        n, h, w = shape
+        n = len(shape[0]) if self._ragged else shape[0]
         m = len(curves)
         frames = [0] * m if frames is None else [int(f) for f in frames]
         anchor_x = [None] * m if anchor_x is None else list(anchor_x)
@@ -230,8 +262,9 @@ class ActiveContour(object):
                     where[key] = sum(a.size for a in mats)
                     mats.append(np.ascontiguousarray(self._matrix(N, ds).T).reshape(-1))
                 offsets.append(where[key])
-            out, its, tvs = ops.active_contour(
-                fxb, fyb, shape, pts, [len(j[1]) for j in jobs], [frames[j[0]] for j in jobs],
+            planes = (fxb, fyb) + shape if self._ragged else (fxb, fyb, shape)
+            out, its, tvs = (ops.active_contour_ragged if self._ragged else ops.active_contour)(
+                *planes, pts, [len(j[1]) for j in jobs], [frames[j[0]] for j in jobs],
                 np.concatenate(mats), offsets, flags, vals, self.gamma, self.residual_tolerance * self.gamma,
                 self.max_iterations)
             if np.any(its < 0):

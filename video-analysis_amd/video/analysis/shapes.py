@@ -7,8 +7,10 @@ va_fill_poly), the skeleton (mask_thinning) and the centre lines.  The estimate 
 optimized centre line chains fill -> cv2.distanceTransform (va_distance_transform_l2_5) -> ActiveContour.  The
 equidistant resampling, the translations and the smoothing spline stay on the host, as in the reference.
 
-Batched forms: `get_masks` fills many polygons in one launch, and `get_centerline_estimates` runs the estimates of
-many polygons on padded stacks, one geodesic call per stack.
+Batched forms: `get_masks` fills many polygons in one launch, `get_centerline_estimates` runs the estimates of
+many polygons on padded stacks, one geodesic call per stack, and `get_centerlines_optimized` (with
+`get_centerlines_smoothed` and `get_centerlines` on top) keeps the masks, distance maps and gradient planes of
+many polygons on the device as ragged buffers and runs all their snakes in one launch.
 
 Deviations ("Polygons"):
   * `bounds` is a fresh Rectangle on every read.  The reference caches it and get_bounding_rect buffers it in
@@ -242,40 +244,9 @@ class Polygon(object):
         `skip_length` is the length that is skipped at either end of the center
             line when the smoothed variant is calculated
         """
-        from scipy import interpolate, spatial
         if points is None:
             points = self.get_centerline_optimized(spacing=spacing, **kwargs)
-
-        # get properties of the line
-        length = _curves.curve_length(points)
-        endpoints = points[0], points[-1]
-
-        # get the points to interpolate
-        points = _curves.make_curve_equidistant(points, spacing=spacing)
-        skip_points = int(skip_length / spacing)
-        points = points[skip_points:-skip_points]
-
-        # do spline fitting to smooth the line
-        try:
-            tck, _ = interpolate.splprep(np.transpose(points), k=3, s=length)
-        except (ValueError, TypeError):
-            # do not interpolate if there are problems
-            pass
-        else:
-            # extend the center line in both directions to make sure that it crosses the outline
-            overshoot = 20 * skip_length  #< absolute overshoot
-            num_points = (length + 2 * overshoot) / spacing
-            overshoot /= length  #< overshoot relative to total length
-            s = np.linspace(-overshoot, 1 + overshoot, int(num_points))
-            points = list(zip(*interpolate.splev(s, tck)))
-
-            # restrict center line to the section between the end points (the reference's LineString only
-            # wraps the point list)
-            dists = spatial.distance.cdist(endpoints, points)
-            ks = sorted(np.argmin(dists, axis=1))
-            points = np.array(points[ks[0]:ks[1] + 1])
-
-        return points
+        return smooth_centerline(points, spacing, skip_length)
 
     def get_centerline(self, method='smoothed', **kwargs):
         """ get the centerline of the polygon """
@@ -287,6 +258,44 @@ class Polygon(object):
             return self.get_centerline_estimate(**kwargs)
         else:
             raise ValueError('Unknown method `%s`' % method)
+
+
+def smooth_centerline(points, spacing=10, skip_length=90):
+    """ the spline part of get_centerline_smoothed (reference :775-810, host code): resamples the centre line
+    `points`, skips `skip_length` at either end, fits a smoothing spline and restricts it to the section between
+    the centre line's end points """
+    from scipy import interpolate, spatial
+
+    # get properties of the line
+    length = _curves.curve_length(points)
+    endpoints = points[0], points[-1]
+
+    # get the points to interpolate
+    points = _curves.make_curve_equidistant(points, spacing=spacing)
+    skip_points = int(skip_length / spacing)
+    points = points[skip_points:-skip_points]
+
+    # do spline fitting to smooth the line
+    try:
+        tck, _ = interpolate.splprep(np.transpose(points), k=3, s=length)
+    except (ValueError, TypeError):
+        # do not interpolate if there are problems
+        pass
+    else:
+        # extend the center line in both directions to make sure that it crosses the outline
+        overshoot = 20 * skip_length  #< absolute overshoot
+        num_points = (length + 2 * overshoot) / spacing
+        overshoot /= length  #< overshoot relative to total length
+        s = np.linspace(-overshoot, 1 + overshoot, int(num_points))
+        points = list(zip(*interpolate.splev(s, tck)))
+
+        # restrict center line to the section between the end points (the reference's LineString only
+        # wraps the point list)
+        dists = spatial.distance.cdist(endpoints, points)
+        ks = sorted(np.argmin(dists, axis=1))
+        points = np.array(points[ks[0]:ks[1] + 1])
+
+    return points
 
 
 # ---------------------------------------------------------------------------------------- batched
@@ -431,3 +440,64 @@ def get_centerline_estimates(polygons, end_points=None):
                 longest_path, length = path, path_len
         out[k] = longest_path
     return out
+
+
+def get_centerlines_optimized(polygons, alpha=1e3, beta=1e6, gamma=0.01, spacing=20, max_iterations=1000,
+                              endpoints=None):
+    """Polygon.get_centerline_optimized (reference :727-757) for every polygon of a list, as one batch: the masks
+    (margin 1), their distance transforms and the gradients of the blurred maps are computed back to back on the
+    device and stay there as ragged planes (ops.centerline_gradients), the estimates come from
+    get_centerline_estimates, and one find_contours call runs every snake, both ends anchored, each on its own
+    polygon's planes.  The equidistant resampling and the translations stay on the host.  endpoints: None, or one
+    entry per polygon as get_centerline_estimates takes them.  Returns the list of (K, 2) centre lines, each with
+    the bits the per-polygon method gives."""
+    from .. import ops
+    from .active_contour import ActiveContour
+    m = len(polygons)
+    eps = [None] * m if endpoints is None else list(endpoints)
+    if len(eps) != m:
+        raise ValueError("need one end-point entry per polygon (%d polygons, %d entries)" % (m, len(eps)))
+    ac = ActiveContour(blur_radius=1, alpha=alpha, beta=beta, gamma=gamma, closed_loop=False)
+    ac.max_iterations = max_iterations
+
+    # set the potentials from the distance maps
+    rects = [p.get_bounding_rect(margin=1) for p in polygons]
+    contours = [np.asarray(p.contour).astype(np.int64) for p in polygons]
+    ac._set_gradients(*ops.centerline_gradients(contours, rects, sigma=ac.blur_radius))
+    if m == 0:
+        return []
+    offsets = [(int(r[0]), int(r[1])) for r in rects]
+
+    # initialize the centerlines from the estimates, the end points anchored
+    curves, anchors = [], []
+    for points, offset in zip(get_centerline_estimates(polygons, eps), offsets):
+        points = _curves.make_curve_equidistant(points, spacing=spacing)
+        points = _curves.translate_points(points, -offset[0], -offset[1])
+        anchor = np.zeros(len(points), bool)
+        anchor[0] = anchor[-1] = True
+        curves.append(points)
+        anchors.append(anchor)
+
+    # find the best contours
+    found = ac.find_contours(curves, list(range(m)), anchors, anchors)
+    return [_curves.translate_points(_curves.make_curve_equidistant(points, spacing=spacing), *offset)
+            for points, offset in zip(found, offsets)]
+
+
+def get_centerlines_smoothed(polygons, spacing=10, skip_length=90, **kwargs):
+    """Polygon.get_centerline_smoothed(spacing=, skip_length=, **kwargs) for every polygon of a list: the batched
+    get_centerlines_optimized, then the smoothing spline of each centre line on the host"""
+    return [smooth_centerline(points, spacing, skip_length)
+            for points in get_centerlines_optimized(polygons, spacing=spacing, **kwargs)]
+
+
+def get_centerlines(polygons, method='smoothed', **kwargs):
+    """ Polygon.get_centerline(method, **kwargs) for every polygon of a list, batched """
+    if method == 'smoothed':
+        return get_centerlines_smoothed(polygons, **kwargs)
+    elif method == 'optimized':
+        return get_centerlines_optimized(polygons, **kwargs)
+    elif method == 'estimate':
+        return get_centerline_estimates(polygons, **kwargs)
+    else:
+        raise ValueError('Unknown method `%s`' % method)

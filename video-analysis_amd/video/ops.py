@@ -835,6 +835,36 @@ def _check_status(status, what):
         raise ValueError("%s: item %d is beyond the kernel's limits (status %d)" % (what, bad[0], status[bad[0]]))
 
 
+def _fill_tables(contours, boxes, what):
+    """the checked operands of va_fill_poly for m > 0 polygons: (verts int32 (k, 2), vert_off int64 (m + 1,), boxes
+    int64 (m, 4)); raises as fill_polys documents"""
+    m = len(contours)
+    bx = np.asarray(boxes, np.int64).reshape(-1, 4)
+    if len(bx) != m:
+        raise ValueError("%s: need one box per contour (%d contours, %d boxes)" % (what, m, len(bx)))
+    polys = []
+    for k, c in enumerate(contours):
+        c = np.asarray(c)
+        if not np.issubdtype(c.dtype, np.integer):
+            raise TypeError("%s: contour %d must hold integer vertices, got %s" % (what, k, c.dtype))
+        c = c.reshape(-1, 2).astype(np.int64)
+        if not 1 <= len(c) <= FILL_MAX_VERTS:
+            raise ValueError("%s: contour %d has %d vertices (1 .. %d are supported)"
+                             % (what, k, len(c), FILL_MAX_VERTS))
+        if np.any(np.abs(c - bx[k, :2]) > FILL_MAX_COORD) or np.any(np.abs(c) >= 2 ** 31):
+            raise ValueError("%s: contour %d has a vertex more than %d px from its box" % (what, k, FILL_MAX_COORD))
+        polys.append(c)
+    if np.any(bx[:, 2:] < 0):
+        raise ValueError("negative dimensions are not allowed")
+    if np.any(bx[:, 2:] > FILL_MAX_SIDE) or np.any(np.abs(bx[:, :2]) >= 2 ** 31):
+        raise ValueError("%s: boxes are limited to %d x %d px with int32 origins"
+                         % (what, FILL_MAX_SIDE, FILL_MAX_SIDE))
+    verts = np.ascontiguousarray(np.concatenate(polys), np.int32)
+    vert_off = np.zeros(m + 1, np.int64)
+    vert_off[1:] = np.cumsum([len(c) for c in polys])
+    return verts, vert_off, bx
+
+
 def fill_polys(contours, boxes, dtype=np.uint8, stream=None):
     """cv2.fillPoly(np.zeros((h, w), dtype), [contour], color=1, offset=(-x, -y)) for every polygon of a list, in
     one launch (Polygon.get_mask, video/analysis/shapes.py:586-592; lineType LINE_8, shift 0).  contours: (k, 2)
@@ -844,30 +874,9 @@ def fill_polys(contours, boxes, dtype=np.uint8, stream=None):
     if dtype not in (np.uint8, np.int32):
         raise TypeError("fill_polys: masks are uint8 or int32, got %s" % dtype)
     m = len(contours)
-    bx = np.asarray(boxes, np.int64).reshape(-1, 4) if m else np.zeros((0, 4), np.int64)
-    if len(bx) != m:
-        raise ValueError("fill_polys: need one box per contour (%d contours, %d boxes)" % (m, len(bx)))
     if m == 0:
         return []
-    polys = []
-    for k, c in enumerate(contours):
-        c = np.asarray(c)
-        if not np.issubdtype(c.dtype, np.integer):
-            raise TypeError("fill_polys: contour %d must hold integer vertices, got %s" % (k, c.dtype))
-        c = c.reshape(-1, 2).astype(np.int64)
-        if not 1 <= len(c) <= FILL_MAX_VERTS:
-            raise ValueError("fill_polys: contour %d has %d vertices (1 .. %d are supported)"
-                             % (k, len(c), FILL_MAX_VERTS))
-        if np.any(np.abs(c - bx[k, :2]) > FILL_MAX_COORD) or np.any(np.abs(c) >= 2 ** 31):
-            raise ValueError("fill_polys: contour %d has a vertex more than %d px from its box" % (k, FILL_MAX_COORD))
-        polys.append(c)
-    if np.any(bx[:, 2:] < 0):
-        raise ValueError("negative dimensions are not allowed")
-    if np.any(bx[:, 2:] > FILL_MAX_SIDE) or np.any(np.abs(bx[:, :2]) >= 2 ** 31):
-        raise ValueError("fill_polys: boxes are limited to %d x %d px with int32 origins" % (FILL_MAX_SIDE, FILL_MAX_SIDE))
-    verts = np.ascontiguousarray(np.concatenate(polys), np.int32)
-    vert_off = np.zeros(m + 1, np.int64)
-    vert_off[1:] = np.cumsum([len(c) for c in polys])
+    verts, vert_off, bx = _fill_tables(contours, boxes, "fill_polys")
     _, shapes, out_off, sizes, total = _pack_ragged(bx[:, [3, 2]])
     with _Lease.on(stream) as d:
         vb, ob, bb, oob, out, st = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)),
@@ -904,6 +913,203 @@ def distance_transform(masks, stream=None):
         _check_status(st.download((m,), np.int32, stream), "distance_transform")
         res = out.download((max(total, 1),), np.float32, stream)
     return _split_ragged(res, shapes, offsets, sizes)
+
+
+# ------------------------------------------------------------------------------- batched centre lines
+GRAD_RESIDENT_MAX_PIXELS = 8192  # VA_GRAD_RESIDENT_MAX_PIXELS: h * w of an item the resident blur + Sobel kernel takes
+GRAD_CLASSES = (2048, 4096, GRAD_RESIDENT_MAX_PIXELS)   # one launch per class: 16, 32 and 64 KiB of LDS a workgroup
+
+
+def _plan_ragged_gradients(d, shapes, offsets, sizes, resident):
+    """uploads the tables of the resident launches, one per size class of `resident` (the LDS of a launch is that
+    of its largest item, so one large item must not cost the small ones their occupancy): the items' shapes and
+    offsets in class order.  Returns (shapes buffer, offsets buffer, [(first entry, entries, largest item)])."""
+    classes = {}
+    for k in resident:
+        classes.setdefault(next(c for c in GRAD_CLASSES if sizes[k] <= c), []).append(k)
+    order = [k for cap in sorted(classes) for k in classes[cap]]
+    launches, first = [], 0
+    for cap in sorted(classes):
+        idx = classes[cap]
+        launches.append((first, len(idx), int(sizes[idx].max())))
+        first += len(idx)
+    if not order:
+        return None, None, launches
+    return d.upload(np.ascontiguousarray(shapes[order])), d.upload(np.ascontiguousarray(offsets[order])), launches
+
+
+def _enqueue_ragged_gradients(d, plan, src, code, shapes, offsets, sizes, total, sigma, resident, fx, fy, st_ptr,
+                              stream):
+    """blur + Sobel of the items of the ragged device buffer `src` (VA dtype `code`) into the float64 planes fx, fy;
+    everything is enqueued on `stream` and nothing is copied: the items of `resident` through
+    va_potential_gradients_ragged as `plan` (_plan_ragged_gradients) groups them, every other item on its own
+    through va_gaussian_* + va_sobel5_f64 at its offset of the same planes.  st_ptr: device address of an int32
+    status vector with room for len(resident) entries, written in the plan's order."""
+    L = _hip.lib()
+    itemsize = 1 if code == _hip.VA_U8 else 4
+    sb, ob, launches = plan
+    for first, count, max_pixels in launches:
+        check(L.va_potential_gradients_ragged(src.ptr, code, sb.ptr + 8 * first, ob.ptr + 8 * first, total, count,
+                                              max_pixels, float(sigma), fx.ptr, fy.ptr, st_ptr + 4 * first, stream))
+    blur = None
+    for k in sorted(set(range(len(sizes))) - set(resident)):
+        (h, w), o = (int(v) for v in shapes[k]), int(offsets[k])
+        if h * w == 0:
+            continue
+        item = src.ptr + o * itemsize
+        if sigma > 0:
+            blur = blur or d.take(int(sizes.max()) * itemsize)
+            fn = L.va_gaussian_u8 if code == _hip.VA_U8 else L.va_gaussian_f32
+            check(fn(item, blur.ptr, 1, h, w, 1, float(sigma), stream))
+            item = blur.ptr
+        check(L.va_sobel5_f64(item, code, fx.ptr + 8 * o, fy.ptr + 8 * o, 1, h, w, stream))
+
+
+def _grad_resident_items(sizes, code, sigma, implementation, what):
+    """indices of the items the resident kernel takes; implementation='resident' raises for the others"""
+    if implementation not in (None, "resident"):
+        raise ValueError("%s: unknown implementation %r" % (what, implementation))
+    if code == _hip.VA_U8 and sigma > 0:
+        ok = np.zeros(len(sizes), bool)
+    else:
+        ok = sizes <= GRAD_RESIDENT_MAX_PIXELS
+    if implementation == "resident" and not ok.all():
+        k = int(np.flatnonzero(~ok)[0])
+        raise ValueError("%s: the resident kernel does not take item %d (%d pixels; at most %d, and uint8 items "
+                         "only without a blur)" % (what, k, sizes[k], GRAD_RESIDENT_MAX_PIXELS))
+    return [int(k) for k in np.flatnonzero(ok)]
+
+
+def potential_gradients_ragged(potentials, sigma=0.0, implementation=None, stream=None):
+    """potential_gradients for a list of 2-d potentials of different shapes, all float32 or all uint8: each item is
+    blurred (sigma > 0) and differentiated as an image of its own, with BORDER_REFLECT_101 at its own edges, so
+    every item gets the bits potential_gradients gives it alone.  Items of up to GRAD_RESIDENT_MAX_PIXELS pixels
+    run in va_potential_gradients_ragged (one workgroup per item, the item in LDS); larger ones, and uint8 items
+    with sigma > 0 (a fixed-point blur), go one by one through va_gaussian_* + va_sobel5_f64.
+    implementation='resident' forces the kernel and raises ValueError for an item it cannot take.
+    Returns (fx, fy, shapes int32 (m, 2), offsets int64 (m,)): fx and fy are float64 DeviceBuffers that the caller
+    owns, item i's planes are shapes[i] at element offset offsets[i]."""
+    arrs = [np.asarray(a) for a in potentials]
+    for k, a in enumerate(arrs):
+        if a.dtype not in (np.uint8, np.float32):
+            raise TypeError("potential_gradients_ragged: potentials must be uint8 or float32, item %d is %s"
+                            % (k, a.dtype))
+        if a.dtype != arrs[0].dtype:
+            raise TypeError("potential_gradients_ragged: one dtype per call (item 0 is %s, item %d is %s)"
+                            % (arrs[0].dtype, k, a.dtype))
+        if a.ndim != 2:
+            raise ValueError("potential_gradients_ragged: item %d is not 2-d (shape %r)" % (k, a.shape))
+    if not sigma >= 0:
+        raise ValueError("potential_gradients_ragged: sigma must be >= 0, got %r" % (sigma,))
+    m = len(arrs)
+    if m == 0:
+        _hip.lib()
+        return DeviceBuffer(0), DeviceBuffer(0), np.zeros((0, 2), np.int32), np.zeros(0, np.int64)
+    flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+    code = _DTYPE_CODES[arrs[0].dtype]
+    resident = _grad_resident_items(sizes, code, sigma, implementation, "potential_gradients_ragged")
+    L = _hip.lib()
+    fx, fy = DeviceBuffer(total * 8), DeviceBuffer(total * 8)
+    try:
+        with _Lease.on(stream) as d:
+            src, st = d.upload(flat), d.take(m * 4)
+            plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
+            _enqueue_ragged_gradients(d, plan, src, code, shapes, offsets, sizes, total, sigma, resident, fx, fy,
+                                      st.ptr, stream)
+            if resident:
+                _check_status(st.download((len(resident),), np.int32, stream), "potential_gradients_ragged")
+            else:
+                check(L.va_stream_sync(stream))
+    except Exception:                  # the caller never sees fx and fy: they are not pooled, free them here
+        fx.free()
+        fy.free()
+        raise
+    return fx, fy, shapes, offsets
+
+
+def active_contour_ragged(fx, fy, shapes, offsets, points, npoints, items, mats, mat_offsets, anchor_flags, anchor_vals,
+                          gamma, tol_gamma, max_iterations, stream=None):
+    """active_contour on the ragged planes of potential_gradients_ragged / centerline_gradients: fx, fy, shapes,
+    offsets as they return them, items (m,) the item each contour runs on; everything else as active_contour takes
+    and returns it.  A contour whose item is out of range comes back untouched with -1 iterations."""
+    pts = np.ascontiguousarray(points, np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 2:
+        raise ValueError("active_contour_ragged: points must be (m, max_points, 2), got shape %r" % (pts.shape,))
+    m, max_points = pts.shape[:2]
+    shapes = np.ascontiguousarray(shapes, np.int32).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    npoints = np.ascontiguousarray(npoints, np.int32).reshape(-1)
+    items = np.ascontiguousarray(items, np.int32).reshape(-1)
+    mat_offsets = np.ascontiguousarray(mat_offsets, np.int64).reshape(-1)
+    if len(shapes) != len(offsets):
+        raise ValueError("active_contour_ragged: %d shapes and %d offsets" % (len(shapes), len(offsets)))
+    if not len(npoints) == len(items) == len(mat_offsets) == m:
+        raise ValueError("active_contour_ragged: npoints, items and mat_offsets need one entry per contour (%d)" % m)
+    total = int((shapes[:, 0].astype(np.int64) * shapes[:, 1]).sum())
+    L = _hip.lib()
+    if m == 0:
+        return pts.copy(), np.zeros(0, np.int32), np.zeros(0, np.float64)
+    mats = np.ascontiguousarray(mats, np.float64)
+    anchored = anchor_flags is not None
+    with _Lease.on(stream) as d:
+        pb, nb, fb, mb, ob, ab, vb, sb, gb = (
+            d.upload(pts), d.upload(npoints), d.upload(items), d.upload(mats), d.upload(mat_offsets),
+            d.upload(np.ascontiguousarray(anchor_flags, np.uint8) if anchored else None),
+            d.upload(np.ascontiguousarray(anchor_vals, np.float64) if anchored else None),
+            d.upload(shapes if len(shapes) else np.zeros((1, 2), np.int32)),
+            d.upload(offsets if len(offsets) else np.zeros(1, np.int64)))
+        it_buf, tv_buf = d.take(m * 4), d.take(m * 8)
+        check(L.va_active_contour_ragged(fx.ptr, fy.ptr, sb.ptr, gb.ptr, total, len(shapes), m, max_points, nb.ptr,
+                                         fb.ptr, mb.ptr, ob.ptr, mats.size, _ptr(ab), _ptr(vb), float(gamma),
+                                         float(tol_gamma), int(max_iterations), pb.ptr, it_buf.ptr, tv_buf.ptr, stream))
+        return (pb.download(pts.shape, np.float64, stream), it_buf.download((m,), np.int32, stream),
+                tv_buf.download((m,), np.float64, stream))
+
+
+def centerline_gradients(contours, boxes, sigma=1.0, stream=None):
+    """the dense part of Polygon.get_centerline_optimized (video/analysis/shapes.py:735-743) for m polygons: the
+    uint8 masks of fill_polys(contours, boxes), their distance transforms and the blurred distance maps' Sobel
+    planes, every table uploaded first and the kernels then back to back on one stream -- va_fill_poly,
+    va_distance_transform_l2_5, va_potential_gradients_ragged
+    (items above GRAD_RESIDENT_MAX_PIXELS one by one, as in potential_gradients_ragged).  Masks and distance maps
+    stay in leased device buffers, no pixel plane crosses to the host, and the status vectors are read once,
+    after the last launch.  contours, boxes as fill_polys takes them.  Returns (fx, fy, shapes, offsets) as
+    potential_gradients_ragged does."""
+    m = len(contours)
+    if not sigma >= 0:
+        raise ValueError("centerline_gradients: sigma must be >= 0, got %r" % (sigma,))
+    if m == 0:
+        _hip.lib()
+        return DeviceBuffer(0), DeviceBuffer(0), np.zeros((0, 2), np.int32), np.zeros(0, np.int64)
+    verts, vert_off, bx = _fill_tables(contours, boxes, "centerline_gradients")
+    _, shapes, offsets, sizes, total = _pack_ragged(bx[:, [3, 2]])
+    if shapes[:, 1].max() > DT_MAX_WIDTH or shapes[:, 0].max() > DT_MAX_HEIGHT:
+        raise ValueError("centerline_gradients: boxes are limited to %d rows x %d columns"
+                         % (DT_MAX_HEIGHT, DT_MAX_WIDTH))
+    resident = _grad_resident_items(sizes, _hip.VA_F32, sigma, None, "centerline_gradients")
+    L = _hip.lib()
+    fx, fy = DeviceBuffer(total * 8), DeviceBuffer(total * 8)
+    try:
+        with _Lease.on(stream) as d:
+            vb, vob, bb, sb, ob = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)), d.upload(shapes),
+                                   d.upload(offsets))
+            mask, dist, st = d.take(max(total, 1)), d.take(max(total, 1) * 4), d.take(3 * m * 4)
+            plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
+            check(L.va_fill_poly(vb.ptr, vob.ptr, len(verts), bb.ptr, ob.ptr, total, m, 1, mask.ptr, st.ptr, stream))
+            check(L.va_distance_transform_l2_5(mask.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()), dist.ptr,
+                                               st.ptr + 4 * m, stream))
+            # a mask or a map a status refuses is not written: what the later kernels make of it is discarded below
+            _enqueue_ragged_gradients(d, plan, dist, _hip.VA_F32, shapes, offsets, sizes, total, sigma, resident, fx, fy,
+                                      st.ptr + 8 * m, stream)
+            status = st.download((2 * m + len(resident),), np.int32, stream)
+            _check_status(status[:m], "centerline_gradients (fill)")
+            _check_status(status[m:2 * m], "centerline_gradients (distance transform)")
+            _check_status(status[2 * m:], "centerline_gradients (gradients)")
+    except Exception:
+        fx.free()
+        fy.free()
+        raise
+    return fx, fy, shapes, offsets
 
 
 # ------------------------------------------------------------------------------------ Guo-Hall thinning
