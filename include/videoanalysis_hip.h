@@ -22,11 +22,13 @@
  *   - bit masks ("bits") are (N, H, ceil(W/32)) uint32, pixel x <-> bit (x & 31) of word x>>5,
  *     padding bits are 0.
  *   - threads: one device per process (va_init fixes it; every entry point selects it for the
- *     calling thread).  The stand-alone entry points keep no state between calls: their device
- *     scratch is a stream-ordered allocation on the call's own `stream`, so different threads may
- *     call them concurrently on different streams (the reference's VideoPreprocessor workers,
- *     video/io/parallel.py:398-400).  A va_pipeline_t handle owns its scratch and background
- *     state and must be used by one thread / one stream at a time.
+ *     calling thread).  The stand-alone entry points keep no results between calls: each call
+ *     leases its device scratch for itself, and a returned block is cached for later calls on the
+ *     same `stream` only (va_trim and va_stream_destroy free it), so different threads may call
+ *     them concurrently on different streams (the reference's VideoPreprocessor workers,
+ *     video/io/parallel.py:398-400).  va_resize_u8 / va_resize_f32 upload their tables with a
+ *     blocking copy and wait for `stream` first.  A va_pipeline_t handle owns its scratch and
+ *     background state and must be used by one thread / one stream at a time.
  *   - sizes: frames of up to 2^29 - 1 pixels (the kernels address h*w*4 bytes through 32-bit
  *     buffer descriptors); larger frames are refused with VA_ERR_INVALID.
  */
@@ -102,7 +104,7 @@ int va_stream_sync(void *stream);
 /* streams and events, for hosts that overlap uploads, the chain and downloads (the role of the
  * reference's reader process / VideoPreprocessor threads, video/io/parallel.py:345-488) */
 int va_stream_create(void **stream_out);
-int va_stream_destroy(void *stream);
+int va_stream_destroy(void *stream);   /* waits for the stream, frees the scratch cached for it */
 int va_event_create(void **event_out);
 int va_event_destroy(void *event);
 int va_event_record(void *event, void *stream);

@@ -1010,6 +1010,49 @@ def test_two_streams_do_not_share_scratch(oracle):
     check(L.va_stream_destroy(s2))
 
 
+def test_resizes_back_to_back_on_a_created_stream(oracle):
+    """two resizes to the same target size, enqueued on one va_stream_create stream with nothing in between,
+    lease the same cached block for their tables (same target: same table sizes).  The second call writes
+    them from the host; that write must wait for the first call's kernel, which the busy stream has not
+    started yet.  The second source is the smaller one, so every index of its tables lies inside the first
+    call's frames.  Then the stream is destroyed (its cached blocks go with it) and a new one runs the pair
+    again."""
+    import ctypes as C
+    from video import _hip
+    from video._hip import DeviceBuffer, check
+    L = _hip.lib()
+    rng = np.random.default_rng(321)
+    busy = rng.integers(0, 256, (6, 301, 517), dtype=np.uint8)
+    dh, dw = 37, 53
+    d_busy, o_busy = DeviceBuffer.from_array(busy), DeviceBuffer(busy.nbytes)
+    buffers = [d_busy, o_busy]
+
+    def pair(stream, fn, ref_fn, dtype):
+        srcs = [rng.integers(0, 256, shape).astype(dtype) for shape in ((3, 48, 64), (3, 24, 32))]
+        refs = [np.asarray(ref_fn(s, (dw, dh), "linear")).reshape(3, dh, dw) for s in srcs]
+        dev = [DeviceBuffer.from_array(s) for s in srcs]
+        out = [DeviceBuffer(3 * dh * dw * np.dtype(dtype).itemsize) for _ in srcs]
+        buffers.extend(dev + out)
+        check(L.va_gaussian_u8_generic(d_busy.ptr, o_busy.ptr, 6, 301, 517, 1, 3.0, stream))
+        for s, d, o in zip(srcs, dev, out):
+            check(fn(d.ptr, o.ptr, 3, s.shape[1], s.shape[2], 1, dh, dw, 1, stream))
+        check(L.va_stream_sync(stream))
+        for o, ref in zip(out, refs):
+            assert np.array_equal(o.download((3, dh, dw), dtype), ref)
+
+    stream = C.c_void_p()
+    check(L.va_stream_create(C.byref(stream)))
+    pair(stream, L.va_resize_u8, oracle.resize_u8, np.uint8)
+    pair(stream, L.va_resize_f32, oracle.resize_f32, np.float32)
+    check(L.va_stream_destroy(stream))
+    stream = C.c_void_p()
+    check(L.va_stream_create(C.byref(stream)))
+    pair(stream, L.va_resize_u8, oracle.resize_u8, np.uint8)
+    check(L.va_stream_destroy(stream))
+    for buf in buffers:
+        buf.free()
+
+
 def test_pipeline_counts_only_skips_paint(oracle, ccl_mode):
     """counts without labels/stats: the label image is never painted (va_pipeline_run passes
     paint=false), on every labelling path, and the counts still match the oracle"""

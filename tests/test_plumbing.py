@@ -298,3 +298,25 @@ def test_video_preprocessor_dict_per_frame():
         raise ValueError("worker failed")
     with pytest.raises(ValueError):
         list(VideoPreprocessor(v, {"boom": boom}))
+
+
+def test_workspace_sizes_are_those_of_the_parent():
+    """the public size functions return, byte for byte, what they returned before every workspace got one
+    layout function (callers size their buffers with them); none of them touches a device.  Columns: label,
+    contour, geodesic, Farneback (pyr_scale 0.5, levels 3, winsize 2, iterations 3, poly_n 5), tiled
+    thinning; the last two rows are refused shapes"""
+    from video import _hip
+    L = _hip.load_library()
+    expected = {
+        (1, 1, 1): (152576, 153088, 154112, 0, 2560),
+        (3, 37, 53): (456960, 480768, 506624, 463616, 8192),
+        (8, 240, 320): (1304832, 3762688, 6374656, 58797824, 169984),
+        (2, 1080, 1920): (839168, 17428224, 35054592, 278653440, 1040896),
+        (0, 5, 5): (256, 256, 256, 0, 0),
+        (70000, 8, 8): (10615640064, 10634120192, 10656800512, 0, 0),
+    }
+    for shape, want in expected.items():
+        got = (L.va_label_workspace_bytes(*shape), L.va_contour_workspace_bytes(*shape),
+               L.va_geodesic_workspace_bytes(*shape), L.va_farneback_workspace_bytes(*shape, 0.5, 3, 2, 3, 5),
+               L.va_guo_hall_thinning_scratch_bytes(*shape))
+        assert got == want, shape

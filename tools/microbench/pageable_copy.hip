@@ -2,7 +2,8 @@
 // host layer issues them: upload, a kernel, download into a fresh array, hipStreamSynchronize, compare.
 //   hipcc --offload-arch=gfx950 -O2 pageable_copy.hip -o pageable_copy && ./pageable_copy
 // MI355X: no wrong word in either mode -- the span of zeros seen through video.ops needs more than
-// this pattern (there the call also leases scratch from the stream-ordered allocator before the download).
+// this pattern (there the call also took its scratch from hipMallocAsync / hipFreeAsync before the download; the
+// library has cached plain hipMalloc blocks per stream since).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

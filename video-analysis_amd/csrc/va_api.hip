@@ -1,15 +1,14 @@
 // va_api.hip -- the extern "C" surface of libvideoanalysis_hip.so (include/videoanalysis_hip.h)
 //
-// Host-side plumbing only: argument checks, scratch management, kernel sequencing for the
+// Host-side plumbing only: argument checks, workspace layouts, kernel sequencing for the
 // fused pipeline, lazy RCCL binding.  No exception crosses the ABI; every failure sets the
 // thread-local message returned by va_last_error().
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <vector>
 #include <new>
+#include <utility>
 
 #include "va_common.h"
 
@@ -25,91 +24,6 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 const char *get_error() { return g_err; }
-
-// Device scratch of the stand-alone entry points: one lease per call, nothing shared between concurrent calls --
-// the reference's concurrent callers (VideoPreprocessor's worker threads, video/io/parallel.py:398-400) may use one
-// stream each without seeing each other's intermediates -- and no call synchronises the device (unless the cache
-// below overflows).
-// Scratch of the stand-alone entry points.  A block is NOT handed back to the stream-ordered allocator when a call
-// returns: hipFreeAsync right behind the kernels, followed by a large asynchronous copy to pageable host memory,
-// made the next call of the same size return a partly unwritten result (a 28 MB span of zeros in a 531 MB blur;
-// leaking the block instead made it disappear: DESIGN.md 13.10).  Blocks are kept per stream -- the next call on
-// the same stream is ordered behind the kernels that still use the block -- and released by va_trim or when more
-// than kScratchCacheCap bytes are cached (then behind a stream synchronisation).
-struct ScratchBlock {
-    void *ptr;
-    size_t bytes;
-    hipStream_t st;
-};
-static std::mutex g_scratch_mu;
-static std::vector<ScratchBlock> g_scratch_free;
-static size_t g_scratch_cached = 0;
-constexpr size_t kScratchCacheCap = 6ull << 30;
-
-static void scratch_release_all_locked()
-{
-    for (const ScratchBlock &b : g_scratch_free)
-        (void)hipFree(b.ptr);
-    g_scratch_free.clear();
-    g_scratch_cached = 0;
-}
-
-struct ScratchLease {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    hipStream_t st = nullptr;
-    int acquire(size_t need, hipStream_t stream)
-    {
-        st = stream;
-        need = need ? need : 256;
-        {
-            std::lock_guard<std::mutex> lock(g_scratch_mu);
-            int best = -1;
-            for (int i = 0; i < (int)g_scratch_free.size(); i++) {
-                const ScratchBlock &b = g_scratch_free[i];
-                if (b.st == st && b.bytes >= need && (best < 0 || b.bytes < g_scratch_free[best].bytes))
-                    best = i;
-            }
-            if (best >= 0 && g_scratch_free[best].bytes <= 2 * need + (1u << 20)) {
-                ptr = g_scratch_free[best].ptr;
-                bytes = g_scratch_free[best].bytes;
-                g_scratch_cached -= bytes;
-                g_scratch_free.erase(g_scratch_free.begin() + best);
-                return VA_OK;
-            }
-        }
-        hipError_t e = hipMalloc(&ptr, need);
-        if (e != hipSuccess) {                       // make room: drop what is cached, once
-            (void)hipGetLastError();
-            (void)hipDeviceSynchronize();
-            {
-                std::lock_guard<std::mutex> lock(g_scratch_mu);
-                scratch_release_all_locked();
-            }
-            e = hipMalloc(&ptr, need);
-        }
-        if (e != hipSuccess) {
-            ptr = nullptr;
-            set_error("scratch: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-            return VA_ERR_NOMEM;
-        }
-        bytes = need;
-        return VA_OK;
-    }
-    ~ScratchLease()
-    {
-        if (!ptr)
-            return;
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        if (g_scratch_cached + bytes > kScratchCacheCap) {
-            (void)hipStreamSynchronize(st);          // (nothing uses the blocks any more)
-            (void)hipDeviceSynchronize();
-            scratch_release_all_locked();
-        }
-        g_scratch_free.push_back(ScratchBlock{ptr, bytes, st});
-        g_scratch_cached += bytes;
-    }
-};
 
 // One device per process (one process per GPU): va_init records it, and every
 // entry point that allocates or launches selects it for the calling thread first -- hipSetDevice
@@ -130,8 +44,6 @@ int enter_device()
         if (_rc)                     \
             return _rc;              \
     } while (0)
-
-static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) & ~(a - 1); }
 
 }  // namespace va
 
@@ -227,11 +139,6 @@ int va_init(int device)
                "va_init: this process already runs on device %d (one device per process)", g_device);
     VA_HIP(hipSetDevice(device));
     VA_HIP(hipFree(nullptr));  // force context creation
-    hipMemPool_t pool;
-    if (hipDeviceGetDefaultMemPool(&pool, device) == hipSuccess) {
-        uint64_t keep = ~(uint64_t)0;   // keep freed scratch in the pool instead of unmapping it
-        (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-    }
     g_device = device;
     tl_device = device;
     return VA_OK;
@@ -244,11 +151,7 @@ int va_trim(size_t keep_bytes)
     hipMemPool_t pool;
     VA_HIP(hipDeviceGetDefaultMemPool(&pool, g_device));
     VA_HIP(hipDeviceSynchronize());
-    {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);      // the cached scratch blocks of the stand-alone calls
-        if (g_scratch_cached > keep_bytes)
-            scratch_release_all_locked();
-    }
+    scratch_release_cached(keep_bytes);      // the cached scratch blocks of the stand-alone calls
     VA_HIP(hipMemPoolTrimTo(pool, keep_bytes));
     return VA_OK;
 }
@@ -360,8 +263,12 @@ int va_stream_create(void **stream_out)
 int va_stream_destroy(void *stream)
 {
     VA_ENTER();
-    if (stream)
-        VA_HIP(hipStreamDestroy(as_stream(stream)));
+    if (!stream)
+        return VA_OK;
+    // the cache is keyed by the handle, and a later stream may get the same one: its blocks go with it
+    VA_HIP(hipStreamSynchronize(as_stream(stream)));
+    scratch_purge_stream(as_stream(stream));
+    VA_HIP(hipStreamDestroy(as_stream(stream)));
     return VA_OK;
 }
 int va_event_create(void **event_out)
@@ -655,13 +562,15 @@ int va_morph_bits_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int 
     int rc = make_row_spans(shape, ksize, &se);
     if (rc)
         return rc;
-    size_t words = align_up((size_t)n * h * words_per_row(w) * sizeof(uint32_t));
+    Carve c;                                 // [b0 | b1]
+    const size_t words = (size_t)n * h * words_per_row(w) * sizeof(uint32_t);
+    const size_t o0 = c.take(words), o1 = c.take(words);
     hipStream_t st = as_stream(stream);
     ScratchLease scratch;
-    rc = scratch.acquire(2 * words, st);
+    rc = scratch.acquire(c.total, st);
     if (rc)
         return rc;
-    uint32_t *b0 = (uint32_t *)scratch.ptr, *b1 = (uint32_t *)((char *)scratch.ptr + words);
+    uint32_t *b0 = at<uint32_t>(scratch.ptr, o0), *b1 = at<uint32_t>(scratch.ptr, o1);
     if ((rc = launch_pack_bits(src, b0, n, h, w, 0, st)))
         return rc;
     if ((rc = launch_morph_bits(b0, b1, n, h, w, op, se, st)))
@@ -674,7 +583,7 @@ size_t va_label_workspace_bytes(int n, int h, int w)
 {
     if (n <= 0 || h <= 0 || w <= 0)
         return 256;
-    return ccl_workspace_bytes(n, h, w);
+    return ccl_layout(n, h, w).total;
 }
 
 int va_label_i32(const uint8_t *mask, int32_t *labels, int32_t *counts, int n, int h, int w,
@@ -691,13 +600,13 @@ int va_label_i32(const uint8_t *mask, int32_t *labels, int32_t *counts, int n, i
     if (n == 0)
         return VA_OK;
     hipStream_t st = as_stream(stream);
-    size_t bits_bytes = align_up((size_t)n * h * words_per_row(w) * sizeof(uint32_t));
-    uint32_t *bits = (uint32_t *)workspace;
+    const CclLayout L = ccl_layout(n, h, w);
+    uint32_t *bits = at<uint32_t>(workspace, L.bits);
     int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
     if (rc)
         return rc;
-    return launch_ccl(bits, labels, counts, n, h, w, connectivity, (char *)workspace + bits_bytes,
-                      workspace_bytes - bits_bytes, nullptr, 0, st);
+    return launch_ccl(bits, labels, counts, n, h, w, connectivity, at(workspace, L.rows), workspace_bytes - L.rows,
+                      nullptr, 0, st);
 }
 
 int va_moments_i64(const int32_t *labels, int n, int h, int w, int max_labels, int64_t *stats,
@@ -924,12 +833,24 @@ int va_image_statistics_u8(const uint8_t *src, double *mean_out, double *var_out
 }
 
 // ------------------------------------------------------------------------------ contour
+// [bits | labelling rows | forest | keys]
+namespace {
+struct ContourLayout { size_t bits, rows, rows_bytes, forest, keys, total; };
+ContourLayout contour_layout(int n, int h, int w)
+{
+    Carve c;
+    const CclLayout ccl = ccl_layout(n, h, w);
+    const size_t label = c.take(ccl.total);
+    return {label + ccl.bits, label + ccl.rows, ccl.rows_bytes, c.take((size_t)n * h * w * sizeof(int32_t)),
+            c.take((size_t)n * sizeof(unsigned long long)), c.total};
+}
+}  // namespace
+
 size_t va_contour_workspace_bytes(int n, int h, int w)
 {
     if (n <= 0 || h <= 0 || w <= 0)
         return 256;
-    return ccl_workspace_bytes(n, h, w) + align_up((size_t)n * h * w * sizeof(int32_t)) +
-           align_up((size_t)n * sizeof(unsigned long long));
+    return contour_layout(n, h, w).total;
 }
 
 int va_largest_contour(const uint8_t *mask, int n, int h, int w, int32_t *points, int max_points,
@@ -947,19 +868,15 @@ int va_largest_contour(const uint8_t *mask, int n, int h, int w, int32_t *points
     if (n == 0)
         return VA_OK;
     hipStream_t st = as_stream(stream);
-    char *ws = (char *)workspace;
-    const size_t bits_bytes = align_up((size_t)n * h * words_per_row(w) * sizeof(uint32_t));
-    const size_t rows_bytes = ccl_workspace_bytes(n, h, w) - bits_bytes;
-    uint32_t *bits = (uint32_t *)ws;
-    void *rows = ws + bits_bytes;
-    int32_t *forest = (int32_t *)(ws + bits_bytes + rows_bytes);
-    unsigned long long *keys =
-        (unsigned long long *)((char *)forest + align_up((size_t)n * h * w * sizeof(int32_t)));
+    const ContourLayout L = contour_layout(n, h, w);
+    uint32_t *bits = at<uint32_t>(workspace, L.bits);
+    int32_t *forest = at<int32_t>(workspace, L.forest);
+    unsigned long long *keys = at<unsigned long long>(workspace, L.keys);
     int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
     if (rc)
         return rc;
-    rc = launch_ccl(bits, forest, ncomponents, n, h, w, 8, rows, rows_bytes, nullptr, 0, st, nullptr,
-                    /*paint=*/false);
+    rc = launch_ccl(bits, forest, ncomponents, n, h, w, 8, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st,
+                    nullptr, /*paint=*/false);
     if (rc)
         return rc;
     return launch_largest_contour(bits, forest, n, h, w, keys, points, max_points, npoints, area, st);
@@ -976,21 +893,16 @@ struct GeoLayout {
 GeoLayout geo_layout(int n, int h, int w)
 {
     GeoLayout g;
-    size_t o = 0;
-    auto take = [&](size_t b) {
-        const size_t at = o;
-        o += align_up(b);
-        return at;
-    };
-    g.pairs = take(geodesic_pairs_bytes(n, h, w));
-    g.visited = take(geodesic_visited_bytes(n, h, w));
-    g.inv = take(geodesic_visited_bytes(n, h, w));
-    g.rows = take(ccl_rows_workspace_bytes(n, h));
-    g.edge = take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
-    g.keys = take((size_t)2 * n * sizeof(unsigned long long));
-    g.counts = take((size_t)2 * n * sizeof(int32_t));
-    g.p1 = take((size_t)2 * n * sizeof(int32_t));
-    g.total = o;
+    Carve c;
+    g.pairs = c.take(geodesic_pairs_bytes(n, h, w));
+    g.visited = c.take(geodesic_visited_bytes(n, h, w));
+    g.inv = c.take(geodesic_visited_bytes(n, h, w));
+    g.rows = c.take(ccl_rows_workspace_bytes(n, h));
+    g.edge = c.take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
+    g.keys = c.take((size_t)2 * n * sizeof(unsigned long long));
+    g.counts = c.take((size_t)2 * n * sizeof(int32_t));
+    g.p1 = c.take((size_t)2 * n * sizeof(int32_t));
+    g.total = c.total;
     return g;
 }
 }  // namespace
@@ -1386,14 +1298,14 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
         PIPE_MALLOC(p->blur, nb * p->px * esz);
     }
     if (masks) {
-        size_t bb = align_up(nb * cfg->height * p->w32 * sizeof(uint32_t));
+        size_t bb = Carve::up(nb * cfg->height * p->w32 * sizeof(uint32_t));
         p->bits_bytes = bb;
         PIPE_MALLOC(p->bits[0][0], bb);
         PIPE_MALLOC(p->bits[0][1], bb);
         if (cfg->connectivity) {
             p->ccl_ws_bytes = ccl_rows_workspace_bytes(cfg->max_batch, cfg->height);
             PIPE_MALLOC(p->ccl_ws[0], p->ccl_ws_bytes);
-            PIPE_MALLOC(p->counts_scratch, align_up(nb * sizeof(int32_t)));
+            PIPE_MALLOC(p->counts_scratch, Carve::up(nb * sizeof(int32_t)));
             // forest / label scratch for runs that do not ask for the label image (counts only:
             // sparse forest words, never painted; stats only: painted here).  Allocated now so
             // that an out-of-memory shows at create time and no run ever calls hipMalloc.
@@ -1557,12 +1469,7 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
     int rc;
     const void *cur = frames;
     StageProfiler *prof = (p->prof && p->prof->enabled && p->prof->runs++ % p->prof->every == 0) ? p->prof : nullptr;
-#define VA_MARK(nm)             \
-    do {                        \
-        if (prof)               \
-            prof->mark(nm, st); \
-    } while (0)
-    VA_MARK(nullptr);
+    mark(prof, nullptr, st);
 
     // float32 frames: background update, difference and row pass in one kernel, then the columns
     // (16-byte aligned frame pointers: a contract of float32 pipelines, see the header)
@@ -1592,7 +1499,7 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
             return rc;
         p->n_seen += n;
         cur = p->diff;
-        VA_MARK("bg");
+        mark(prof, "bg", st);
     }
 
     // Overlapped runs (va_pipeline_overlap): this batch's masks and run tables live in slot `slot`; the
@@ -1633,7 +1540,7 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
         rc = launch_pack_bits((const uint8_t *)cur, bits[0], n, c.height, c.width, c.thresh, st);
         if (rc)
             return rc;
-        VA_MARK("threshold_pack");
+        mark(prof, "threshold_pack", st);
     }
     // 4. morphology on bits (one fused kernel when the sequence allows it)
     int32_t *labels = nullptr;
@@ -1646,7 +1553,7 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
         if (rc)
             return rc;
         b ^= 1;
-        VA_MARK("morph_fused");
+        mark(prof, "morph_fused", st);
     } else {
         for (int i = 0; i < c.morph_count; i++) {
             rc = launch_morph_bits(bits[b], bits[b ^ 1], n, c.height, c.width, c.morph_op[i],
@@ -1654,14 +1561,14 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
             if (rc)
                 return rc;
             b ^= 1;
-            VA_MARK(c.morph_op[i] == VA_MORPH_DILATE ? "morph_dilate" : "morph_erode");
+            mark(prof, c.morph_op[i] == VA_MORPH_DILATE ? "morph_dilate" : "morph_erode", st);
         }
     }
     if (mask_out) {
         rc = launch_unpack_bits(bits[b], mask_out, n, c.height, c.width, c.maxval, st);
         if (rc)
             return rc;
-        VA_MARK("mask_unpack");
+        mark(prof, "mask_unpack", st);
     }
     // 5. labelling (+ statistics)
     if (want_ccl) {
@@ -1693,8 +1600,7 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
                 return rc;
             VA_HIP(hipEventRecord(p->ev_front, st));
             VA_HIP(hipStreamWaitEvent(p->side, p->ev_front, 0));
-            if (prof)
-                prof->mark(nullptr, p->side);            // (start of the side stream's part of this run)
+            mark(prof, nullptr, p->side);                // (start of the side stream's part of this run)
             plan.persistent_grid = p->paint_grid;
             rc = launch_ccl_paint(plan, p->side, prof);
             if (rc)
@@ -1708,7 +1614,6 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
             p->slot = slot ^ 1;
         }
     }
-#undef VA_MARK
     return VA_OK;
 }
 

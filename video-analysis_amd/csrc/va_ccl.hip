@@ -1864,8 +1864,6 @@ __global__ void longest_contour_start_kernel(const uint32_t *__restrict__ bits,
     p1[2 * f + 1] = e.y;
 }
 
-inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
 // the per-frame LDS kernel takes frames whose row table and row stages leave room for at least
@@ -1920,23 +1918,27 @@ bool ccl_frame_kernel_used(int n, int h, int w)
     return true;
 }
 
-// [row_cnt][row_off][run-label tables of the per-frame kernel][mode]
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t ccl_rows_workspace_bytes(int n, int h)
+// launch_ccl's workspace: the rows (the caller owns the bit mask)
+namespace {
+struct RowsLayout { size_t row_cnt, row_off, run_table, frame_mode, total; };   // run_table: of the per-frame kernel
+RowsLayout rows_layout(int n, int h)
 {
-    return 2 * up256((size_t)n * h * sizeof(int32_t)) + up256((size_t)n * kFrameLdsWords * sizeof(int32_t)) +
-           up256((size_t)n * sizeof(int32_t));
+    Carve c;
+    const size_t rows = (size_t)n * h * sizeof(int32_t);
+    return {c.take(rows), c.take(rows), c.take((size_t)n * kFrameLdsWords * sizeof(int32_t)),
+            c.take((size_t)n * sizeof(int32_t)), c.total};
+}
+}  // namespace
+
+size_t ccl_rows_workspace_bytes(int n, int h) { return rows_layout(n, h).total; }
+
+CclLayout ccl_layout(int n, int h, int w)   // with the bit mask of the u8 entry points in front
+{
+    Carve c;
+    const size_t rows_bytes = rows_layout(n, h).total;
+    return {c.take((size_t)n * h * words_per_row(w) * sizeof(uint32_t)), c.take(rows_bytes), rows_bytes, c.total};
 }
 
-size_t ccl_workspace_bytes(int n, int h, int w)
-{
-    // [bit mask for the u8 entry point][rows workspace]
-    size_t bits = (size_t)n * h * words_per_row(w) * sizeof(uint32_t);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return up(bits) + ccl_rows_workspace_bytes(n, h);
-}
-
-// workspace here = row_cnt + row_off only (the caller owns the bit mask)
 // The labelling proper: everything up to (not including) the write of the label image.  `plan`
 // (nullable: nobody will paint) receives what launch_ccl_paint needs, so that the caller may run the
 // store-bound paint pass on another stream, beside the next batch's VALU-bound stages.
@@ -1947,11 +1949,6 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
     const bool paint = plan != nullptr;
     if (plan)
         plan->n = 0;                             // (nothing to paint until the front has been enqueued)
-#define VA_MARK(nm)      \
-    do {                 \
-        if (prof)        \
-            prof->mark(nm, st); \
-    } while (0)
     VA_REQUIRE(connectivity == 4 || connectivity == 8, "label: connectivity must be 4 or 8 (got %d)",
                connectivity);
     VA_REQUIRE(bits && labels && workspace, "label: NULL argument");
@@ -1961,13 +1958,10 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
     if (n == 0 || h == 0 || w == 0)
         return VA_OK;
     const int w32 = words_per_row(w);
-    const size_t total_rows = (size_t)n * h;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    VA_REQUIRE(ws_bytes >= ccl_rows_workspace_bytes(n, h), "label: workspace too small");
-    int32_t *row_cnt = (int32_t *)workspace;
-    int32_t *row_off = (int32_t *)((char *)workspace + up(total_rows * sizeof(int32_t)));
-    int32_t *run_table = (int32_t *)((char *)workspace + 2 * up(total_rows * sizeof(int32_t)));
-    int32_t *frame_mode = (int32_t *)((char *)run_table + up((size_t)n * kFrameLdsWords * sizeof(int32_t)));
+    const RowsLayout L = rows_layout(n, h);
+    VA_REQUIRE(ws_bytes >= L.total, "label: workspace too small");
+    int32_t *row_cnt = at<int32_t>(workspace, L.row_cnt), *row_off = at<int32_t>(workspace, L.row_off);
+    int32_t *run_table = at<int32_t>(workspace, L.run_table), *frame_mode = at<int32_t>(workspace, L.frame_mode);
     bool table_mode = false;                 // set when the per-frame kernel hands its labels over as tables
     int table_stride = 0;
 
@@ -1977,23 +1971,23 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
         if (init) {
             ccl_init_kernel<<<sgrid, kBlock, 0, st>>>(bits, labels, h, w, w32, fl);
             VA_LAUNCH_CHECK("ccl_init_kernel");
-            VA_MARK("ccl_init");
+            mark(prof, "ccl_init", st);
         }
         if (connectivity == 8)
             ccl_link_kernel<true><<<sgrid, kBlock, 0, st>>>(bits, labels, h, w, w32, fl);
         else
             ccl_link_kernel<false><<<sgrid, kBlock, 0, st>>>(bits, labels, h, w, w32, fl);
         VA_LAUNCH_CHECK("ccl_link_kernel");
-        VA_MARK("ccl_link");
+        mark(prof, "ccl_link", st);
         ccl_flatten_kernel<<<sgrid, kBlock, 0, st>>>(bits, labels, row_cnt, h, w, w32, fl);
         VA_LAUNCH_CHECK("ccl_flatten_kernel");
-        VA_MARK("ccl_flatten");
+        mark(prof, "ccl_flatten", st);
         ccl_rowscan_kernel<<<nscan, kBlock, 0, st>>>(row_cnt, row_off, counts, h, fl);
         VA_LAUNCH_CHECK("ccl_rowscan_kernel");
-        VA_MARK("ccl_rowscan");
+        mark(prof, "ccl_rowscan", st);
         ccl_rank_kernel<<<sgrid, kBlock, 0, st>>>(bits, labels, row_off, h, w, w32, fl);
         VA_LAUNCH_CHECK("ccl_rank_kernel");
-        VA_MARK("ccl_rank");
+        mark(prof, "ccl_rank", st);
         return VA_OK;
     };
     if (ccl_frame_kernel_used(n, h, w)) {
@@ -2022,7 +2016,7 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
 #undef VA_FRAME_CASE
 #undef VA_FRAME_LAUNCH
         VA_LAUNCH_CHECK("ccl_frame_kernel");
-        VA_MARK("ccl_frame");
+        mark(prof, "ccl_frame", st);
     } else {
         int rc = chip_wide(sgrid_all, all, n, true);
         if (rc)
@@ -2044,17 +2038,11 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
     plan->frame_mode = frame_mode;
     plan->xcd_frames = table_mode ? cdiv(h, kRowsPerBlock) : 0;
     plan->persistent_grid = 0;
-#undef VA_MARK
     return VA_OK;
 }
 
 int launch_ccl_paint(const CclPaintPlan &pl, hipStream_t st, StageProfiler *prof)
 {
-#define VA_MARK(nm)      \
-    do {                 \
-        if (prof)        \
-            prof->mark(nm, st); \
-    } while (0)
     if (pl.n <= 0)
         return VA_OK;
     const int n = pl.n, h = pl.h, w = pl.w, w32 = words_per_row(pl.w);
@@ -2075,7 +2063,7 @@ int launch_ccl_paint(const CclPaintPlan &pl, hipStream_t st, StageProfiler *prof
         stats_init_kernel<<<cdiv((long long)entries * VA_STATS_STRIDE, kBlock), kBlock, 0, st>>>(
             pl.stats, entries, h, w);
         VA_LAUNCH_CHECK("stats_init_kernel");
-        VA_MARK("stats_init");
+        mark(prof, "stats_init", st);
         if (wide)
             VA_PAINT_LAUNCH(true, 2 * kWave, pl.stats, pl.max_labels);
         else
@@ -2088,8 +2076,7 @@ int launch_ccl_paint(const CclPaintPlan &pl, hipStream_t st, StageProfiler *prof
     }
 #undef VA_PAINT_LAUNCH
     VA_LAUNCH_CHECK("ccl_paint_kernel");
-    VA_MARK("ccl_paint");
-#undef VA_MARK
+    mark(prof, "ccl_paint", st);
     return VA_OK;
 }
 

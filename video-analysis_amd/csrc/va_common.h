@@ -75,9 +75,51 @@ struct StageProfiler {
         name[n++] = nm;
     }
 };
+// (prof == nullptr: nobody is timing)
+inline void mark(StageProfiler *prof, const char *nm, hipStream_t st) { if (prof) prof->mark(nm, st); }
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline int words_per_row(int w) { return (w + 31) / 32; }
+inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// Carves a workspace into regions that start on 256-byte boundaries.  Each workspace has one function that builds
+// a struct of offsets and `total` with this -- often as a braced list {c.take(..), .., c.total}, which is evaluated
+// left to right -- and both its size function and its launcher ask that struct.
+struct Carve {
+    static size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
+    size_t total = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t at = total;
+        total = up(total + bytes);
+        return at;
+    }
+};
+template <class T = void>
+inline T *at(void *base, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(base) + offset); }
+
+// Device scratch of the stand-alone entry points, cached per stream (va_scratch.hip states the contract)
+struct ScratchLease {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    hipStream_t st = nullptr;
+    int acquire(size_t need, hipStream_t stream);
+    ~ScratchLease();
+};
+void scratch_release_cached(size_t keep_bytes);   // frees the cache when it holds more than keep_bytes (va_trim)
+void scratch_purge_stream(hipStream_t st);        // frees the blocks cached for st (va_stream_destroy)
+
+#if defined(__HIPCC__)
+// BORDER_REFLECT_101 with repeated reflection (kernel wider than the image)
+__device__ __forceinline__ int reflect101(int p, int len)
+{
+    if (len == 1)
+        return 0;
+    while (p < 0 || p >= len)
+        p = p < 0 ? -p : 2 * (len - 1) - p;
+    return p;
+}
+#endif
 
 // ---- host-side kernels shared between translation units --------------------------------
 // Gaussian taps (host): OpenCV's 8-bit fixed-point / float definitions. Return 0 or VA_ERR_*.
@@ -238,7 +280,9 @@ int launch_morph_fused(const uint32_t *src, uint32_t *dst, int n, int h,
                        int w, const int *ops, const RowSpans *se, int count, hipStream_t st);
 
 // connected components on bit masks; labels doubles as the union-find forest
-size_t ccl_workspace_bytes(int n, int h, int w);
+// workspace of the entry points that label a u8 mask: its packed bits, then launch_ccl's workspace
+struct CclLayout { size_t bits, rows, rows_bytes, total; };
+CclLayout ccl_layout(int n, int h, int w);
 // true: launch_ccl labels with one workgroup per frame (forest in LDS); false: chip-wide
 // multi-pass path (large frames, small batches, or the test hook)
 bool ccl_frame_kernel_used(int n, int h, int w);

@@ -113,16 +113,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-// BORDER_REFLECT_101 with repeated reflection (kernel wider than the image)
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 // T = uint16_t while the row sums fit (tap sum <= 257: every OpenCV >= 4 tap set), uint32_t otherwise
 template <class T>
 __global__ void __launch_bounds__(kBlock)
@@ -263,11 +253,18 @@ static int planes_width(int h, int w, int c, const TapsQ8 &t)
         return wp;
     return 0;
 }
+// U8Planes scratch: [planes in | planes out]
+struct PlanesLayout { size_t in, out, total; };
+static PlanesLayout planes_layout(size_t n, int h, int wp, int c)
+{
+    Carve cv;
+    return {cv.take(n * c * h * wp), cv.take(n * c * h * wp), cv.total};
+}
 static int blur_u8_planes(const uint8_t *src, uint8_t *dst, int n, int h, int w, int wp, int c,
                           const TapsQ8 &t, void *scratch, hipStream_t st)
 {
-    const size_t plane_bytes = (size_t)n * c * h * wp;                   // multiple of 16
-    uint8_t *pin = (uint8_t *)scratch, *pout = pin + plane_bytes;        // both 16-byte aligned
+    const PlanesLayout L = planes_layout(n, h, wp, c);
+    uint8_t *pin = at<uint8_t>(scratch, L.in), *pout = at<uint8_t>(scratch, L.out);
     int rc = launch_channel_planes(src, pin, n, h, w, wp, c, true, st);
     if (rc)
         return rc;
@@ -306,7 +303,7 @@ size_t gauss_scratch_bytes(const GaussPlan &g, size_t n)
 {
     const size_t count = n * g.h * g.w * g.c;
     if (g.family == GaussFamily::U8Planes)
-        return 2 * n * g.c * g.h * g.wp;                                    // the planes in and out
+        return planes_layout(n, g.h, g.wp, g.c).total;
     if (g.family == GaussFamily::U8Generic)
         return count * (taps_sum(g.tq) <= 257 ? sizeof(uint16_t) : sizeof(uint32_t));     // row sums <= 255 * sum
     return g.dtype == VA_F32 && g.family != GaussFamily::None ? count * sizeof(float) : 0;   // (single pass: none)
@@ -330,8 +327,8 @@ int launch_gaussian(const GaussPlan &g, const void *src, void *dst, uint32_t *bi
     uint8_t *d8 = (uint8_t *)dst;
     float *df = (float *)dst, *scratch_f = (float *)scratch;
     auto marked = [&](int rc, const char *stage) {
-        if (rc == VA_OK && prof)
-            prof->mark(stage, st);
+        if (rc == VA_OK)
+            mark(prof, stage, st);
         return rc;
     };
     switch (g.family) {

@@ -23,15 +23,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 template <int C, int P>
 __global__ void __launch_bounds__(kBlock, 4)
 gauss_row_f32_kernel(const float *__restrict__ src, float *__restrict__ tmp, int w, TapsF32 taps,

@@ -43,15 +43,6 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 constexpr int kT = 256;        // threads per workgroup (4 waves, one per SIMD; 4 workgroups per CU)
 constexpr int kP = 15;         // outputs per thread and half (multiple of the channel count)
 constexpr int kNV = 7;         // float4 loads per thread and frame
@@ -1583,8 +1574,7 @@ int launch_gauss_f32_fused(const float *src, float *dst, float *scratch, const f
             ema_row_f32_kernel<3, false><<<grid, 2 * kT, lds1, st>>>(src, scratch, nullptr, nullptr, 0, 0.f, n, h, w, plan.L, taps);
     }
     VA_LAUNCH_CHECK("ema_row_f32_kernel");
-    if (prof)
-        prof->mark(bg ? "ema_row_f32" : "row_f32", st);
+    mark(prof, bg ? "ema_row_f32" : "row_f32", st);
     // radii of integer sigmas: the unrolled 15/16-rows-per-thread kernel (whichever wastes fewer rows
     // in the last step); any other radius: the 8-row kernel with its runtime tap loop
     const int waste16 = cdiv(h, 128) * 128 - h, waste15 = cdiv(h, 120) * 120 - h;
@@ -1597,8 +1587,7 @@ int launch_gauss_f32_fused(const float *src, float *dst, float *scratch, const f
         col_march_f32_kernel<<<(unsigned)((size_t)ncolt * 8 * cdiv(n, 8)), 256, lds2, st>>>(scratch, dst, h, rw, ncolt, taps, n);
     }
     VA_LAUNCH_CHECK("col_f32 kernel");
-    if (prof)
-        prof->mark("col_f32", st);
+    mark(prof, "col_f32", st);
     return VA_OK;
 }
 

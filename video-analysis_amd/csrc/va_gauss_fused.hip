@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
 // at least 32 x 32 here and the halo is 16, see gauss_fused_supported), branch-free.  Indices
 // further out belong to columns/rows whose results are never stored: they are only clamped
 // so that the load stays inside the frame.
-__device__ __forceinline__ int reflect101(int p, int len)
+__device__ __forceinline__ int clamp_reflect101(int p, int len)
 {
     p = p < 0 ? -p : p;
     p = p >= len ? 2 * (len - 1) - p : p;
@@ -101,7 +101,7 @@ gauss_fused_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     auto fetch = [&](int s, int v) -> uint4 {
         const int vrow = v / VPR, vcol = v % VPR;
         const int gx0 = X0 - kHalo + vcol * 16;
-        const int yy = reflect101(ROWS * s + vrow - RP, h);
+        const int yy = clamp_reflect101(ROWS * s + vrow - RP, h);
         const uint8_t *rowp = img + (size_t)yy * w;
         if (gx0 >= 0 && gx0 + 16 <= w)
             return ld16(rowp + gx0);

@@ -26,15 +26,6 @@ namespace {
 
 constexpr int kGradBlock = 256;
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 // both Sobel values of pixel (y, x) of the h x w plane A
 __device__ __forceinline__ void sobel_at(const float *A, int h, int w, int y, int x, double *gx, double *gy)
 {

@@ -519,8 +519,6 @@ morph_u8_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int 
     dst[e] = (uint8_t)best;
 }
 
-inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
 int launch_pack_bits(const uint8_t *src, uint32_t *bits, int n, int h, int w, int thresh,

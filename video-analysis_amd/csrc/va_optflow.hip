@@ -31,15 +31,6 @@ struct PolyConsts {
     double ig11, ig03, ig33, ig55;
 };
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // GaussianBlur row pass (SymmRowSmallFilter for ksize <= 5, RowFilter above), converting to float on the fly
@@ -359,8 +350,6 @@ struct OfLayout {
     std::vector<size_t> tab_img, tab_flow;     // per level: offsets of its resize tables (SIZE_MAX: none)
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 OfLayout of_layout(int n, int h, int w, const std::vector<OfLevel> &lv)
 {
     OfLayout L;
@@ -369,28 +358,23 @@ OfLayout of_layout(int n, int h, int w, const std::vector<OfLevel> &lv)
     for (const OfLevel &l : lv)
         if (l.h != h || l.w != w)
             img_px = img_px > (size_t)l.h * l.w ? img_px : (size_t)l.h * l.w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align256(o + bytes);
-        return at;
-    };
-    L.rows = take((size_t)n * px * 4);
-    L.blur = take((size_t)n * px * 4);
-    L.img = take((size_t)n * img_px * 4);
-    L.R = take((size_t)n * 5 * px * 4);
-    L.flow_prev = take(P * px * 8);
-    L.flow = take(P * px * 8);
-    L.M = take(P * 5 * px * 4);
-    L.V = take(P * 5 * px * 8);
-    L.tables = o;
+    Carve c;
+    L.rows = c.take((size_t)n * px * 4);
+    L.blur = c.take((size_t)n * px * 4);
+    L.img = c.take((size_t)n * img_px * 4);
+    L.R = c.take((size_t)n * 5 * px * 4);
+    L.flow_prev = c.take(P * px * 8);
+    L.flow = c.take(P * px * 8);
+    L.M = c.take(P * 5 * px * 4);
+    L.V = c.take(P * 5 * px * 8);
+    L.tables = c.total;
     for (size_t i = 0; i < lv.size(); i++) {
         const OfLevel &l = lv[i];
-        L.tab_img.push_back(l.h != h || l.w != w ? take(resize_scratch_bytes(h, w, l.h, l.w)) : SIZE_MAX);
+        L.tab_img.push_back(l.h != h || l.w != w ? c.take(resize_scratch_bytes(h, w, l.h, l.w)) : SIZE_MAX);
         const bool grow = i > 0 && (lv[i - 1].h != l.h || lv[i - 1].w != l.w);
-        L.tab_flow.push_back(grow ? take(resize_scratch_bytes(lv[i - 1].h, lv[i - 1].w, l.h, l.w)) : SIZE_MAX);
+        L.tab_flow.push_back(grow ? c.take(resize_scratch_bytes(lv[i - 1].h, lv[i - 1].w, l.h, l.w)) : SIZE_MAX);
     }
-    L.total = o + 256;
+    L.total = c.total + 256;
     return L;
 }
 

@@ -480,8 +480,6 @@ normalize_u8_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
     dst[i] = (uint8_t)iv;                          // wraps like NumPy for out-of-range targets
 }
 
-inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
 size_t bg_scratch_bytes(int n) { return sizeof(double) * (size_t)(n > 0 ? n : 1); }

@@ -444,8 +444,12 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
     auto push = [&](const void *host, size_t bytes, void **dev) -> int {
         used = (used + 15) & ~(size_t)15;
         *dev = base + used;
-        // (pageable source that dies with this call: a blocking copy -- complete on return; the destination is this
-        //  call's own scratch, nothing on the stream uses it yet)
+        // Pageable source that dies with this call: a blocking copy, complete on return.  It runs on the null
+        // stream, which does not wait for a non-blocking st, and the scratch may be a cached block that the
+        // previous call's kernel on st still reads its tables from: st drains before the first copy of the call
+        // (Upload: the caller has drained it).
+        if (stage == ResizeStage::Both && used == 0)
+            VA_HIP(hipStreamSynchronize(st));
         if (stage != ResizeStage::Launch)
             VA_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
         used += bytes;

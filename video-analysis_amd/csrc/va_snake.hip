@@ -28,15 +28,6 @@ namespace va {
 
 namespace {
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1)
-        return 0;
-    while (p < 0 || p >= len)
-        p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
 // ------------------------------------------------------------------------------------------- Sobel
 constexpr int kSobTW = 128, kSobTH = 32;          // output tile
 constexpr int kSobBlock = 256;                    // 64 lanes x 4 waves; a lane: 2 columns of its wave's rows

@@ -260,9 +260,14 @@ gh_tiled_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int
             out[frame + where[j]] = s[idx[j]];
 }
 
-size_t plane_bytes(int n, int h, int w)
+// scratch of the tiled path: two stacks of bit planes and a flag per pair of sub-iterations, poll and frame
+struct TiledLayout { size_t cur, nxt, flags, total; };
+TiledLayout tiled_layout(int n, int h, int w)
 {
-    return (((size_t)n * h * words_per_row(w) * sizeof(uint32_t)) + 255) & ~(size_t)255;
+    Carve c;
+    const size_t plane_bytes = (size_t)n * h * words_per_row(w) * sizeof(uint32_t);
+    return {c.take(plane_bytes), c.take(plane_bytes),
+            c.take((size_t)kThinMaxPoll * (kThinMaxK / 2) * n * sizeof(uint32_t)), c.total};
 }
 
 }  // namespace
@@ -288,7 +293,7 @@ int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const in
 
 size_t guo_hall_tiled_scratch_bytes(int n, int h, int w)
 {
-    return 2 * plane_bytes(n, h, w) + (size_t)kThinMaxPoll * (kThinMaxK / 2) * n * sizeof(uint32_t);
+    return tiled_layout(n, h, w).total;
 }
 
 int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
@@ -296,9 +301,9 @@ int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, i
 {
     const int wpr = words_per_row(w), per_launch = K / 2, per_poll = poll * per_launch;
     const int64_t rows = (int64_t)n * h;
-    uint32_t *cur = static_cast<uint32_t *>(scratch);
-    uint32_t *nxt = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + plane_bytes(n, h, w));
-    uint32_t *flags = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 2 * plane_bytes(n, h, w));
+    const TiledLayout L = tiled_layout(n, h, w);
+    uint32_t *cur = at<uint32_t>(scratch, L.cur), *nxt = at<uint32_t>(scratch, L.nxt);
+    uint32_t *flags = at<uint32_t>(scratch, L.flags);
     const bool fast = (w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0;
     const dim3 words_grid((unsigned)cdiv(rows * wpr, kThinBlock)), block(kThinBlock);
     if (fast)
