@@ -271,6 +271,42 @@ int va_largest_contour(const uint8_t *mask_dev, int n, int h, int w, int32_t *po
                        int32_t *ncomponents_dev, void *workspace_dev, size_t workspace_bytes,
                        void *stream);
 
+/* ------------------------------------------------------------------ A8 all outer contours
+ * replaces  contours = cv2.findContours(mask.astype(np.uint8), cv2.RETR_EXTERNAL,
+ *                                       cv2.CHAIN_APPROX_SIMPLE)[1]   used as a whole list:
+ *           video/analysis/regions.py:180-182, :229-231 (get_external_contour), :575-576,
+ *           video/io/composer.py:228
+ * Every outer contour of n frames of h x w uint8 (any non-zero byte is foreground) as one ragged list.
+ * A contour is the outer border (the walk of va_largest_contour, point for point) of an 8-connected
+ * component that lies in no hole of another: the 4-connected background component left of its first
+ * raster pixel reaches the frame edge, or that pixel is in column 0.  Within a frame the contours come
+ * in OpenCV's order, most recently found first = descending first-pixel index; frames follow each
+ * other, so contour k of frame f is global slot (sum of ncontours_dev[0 .. f)) + k.
+ *   ncontours_dev[n]                 contours of each frame
+ *   totals_dev[2]                    contours and points of the whole batch, always the true totals
+ *   info_dev[cap_contours]           one record per slot
+ *   point_off_dev[cap_contours + 1]  exclusive scan of the records' npoints: slot s owns the points
+ *                                    point_off[s] .. point_off[s + 1]
+ *   points_dev[cap_points][2]        int32 (x, y), 8-byte aligned
+ * Nothing is written beyond a capacity: slots 0 .. min(total, cap_contours) - 1 have their record and
+ * offsets, and a slot has its points when all of them lie below cap_points (such slots form a
+ * prefix).  Exceeding a capacity is no error: compare totals_dev with the capacities and call again
+ * with room.  Slots and positions come from counts and scans, never from the order of atomics: two
+ * calls write identical bytes.  Everything is enqueued on `stream`, in the caller's workspace only.
+ * Frames stay below 2^29 pixels, as for va_largest_contour. */
+typedef struct va_contour_info {
+    int32_t frame, npoints;                     /* frame index; points of the contour */
+    int32_t start_x, start_y;                   /* its first point = the component's first raster pixel */
+    int32_t rect_x, rect_y, rect_w, rect_h;     /* cv2.boundingRect */
+    double area;                                /* cv2.contourArea */
+    double perimeter;                           /* cv2.arcLength(contour, closed=True) */
+} va_contour_info;
+size_t va_find_contours_workspace_bytes(int n, int h, int w);
+int va_find_contours(const uint8_t *mask_dev, int n, int h, int w, int32_t *ncontours_dev, int64_t *totals_dev,
+                     va_contour_info *info_dev, int64_t *point_off_dev, int64_t cap_contours,
+                     int32_t *points_dev, int64_t cap_points, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+
 /* ------------------------------------------------------------------ A10 geodesic distance maps
  * 8-neighbour geodesics inside masks: straight steps cost 1, diagonal steps sqrt2 (a diagonal step may
  * pass between two wall pixels).  A distance d = a + b*sqrt2 is kept as the exact pair (a, b) and
@@ -540,6 +576,11 @@ int va_warp_affine_u8(const uint8_t *frames_dev, int n_frames, int h, int w, int
  * normalised moments follow on the host (completeMomentState). */
 int va_contour_moments(const void *points_dev, const int32_t *npoints_dev, int n, int max_points,
                        int is_float, double *moments_out_dev, void *stream);
+/* the same for m contours of a ragged list, contour i = points point_off_dev[i] .. point_off_dev[i + 1]
+ * (m + 1 offsets) -- the layout va_find_contours writes, so that the moments of every blob come from the
+ * device-resident points.  The same sequential per-contour code, one wave per contour. */
+int va_contour_moments_ragged(const void *points_dev, const int64_t *point_off_dev, int64_t m, int is_float,
+                              double *moments_out_dev, void *stream);
 
 /* ------------------------------------------------------------------ N2 small stencils
  * replaces  detect_peaks(img, include_plateaus), video/analysis/image.py:267-306:

@@ -882,6 +882,89 @@ int va_largest_contour(const uint8_t *mask, int n, int h, int w, int32_t *points
     return launch_largest_contour(bits, forest, n, h, w, keys, points, max_points, npoints, area, st);
 }
 
+// ------------------------------------------------------------------------------ all contours
+// [bits | labelling rows | forest | inverted bits | background labels | edge bits | counts | cells | frame_first |
+//  frame_pts | pt_first | starts | npts]
+namespace {
+struct FindContoursLayout {
+    size_t bits, rows, rows_bytes, forest, inv, bgl, edge, counts, cells, frame_first, frame_pts, pt_first, starts,
+        npts, total;
+};
+FindContoursLayout find_contours_layout(int n, int h, int w)
+{
+    FindContoursLayout g;
+    Carve c;
+    const CclLayout ccl = ccl_layout(n, h, w);
+    const size_t label = c.take(ccl.total), px = (size_t)n * h * w, slots = (size_t)n * max_contours_per_frame(h, w);
+    g.bits = label + ccl.bits;
+    g.rows = label + ccl.rows;
+    g.rows_bytes = ccl.rows_bytes;
+    g.forest = c.take(px * sizeof(int32_t));
+    g.inv = c.take((size_t)n * h * words_per_row(w) * sizeof(uint32_t));
+    g.bgl = c.take(px * sizeof(int32_t));
+    g.edge = c.take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
+    g.counts = c.take((size_t)2 * n * sizeof(int32_t));
+    g.cells = c.take((size_t)n * h * 8 * sizeof(int32_t));
+    g.frame_first = c.take(((size_t)n + 1) * sizeof(int64_t));
+    g.frame_pts = c.take((size_t)n * sizeof(int64_t));
+    g.pt_first = c.take(((size_t)n + 1) * sizeof(int64_t));
+    g.starts = c.take(slots * 8);
+    g.npts = c.take(slots * sizeof(int32_t));
+    g.total = c.total;
+    return g;
+}
+}  // namespace
+
+size_t va_find_contours_workspace_bytes(int n, int h, int w)
+{
+    if (n <= 0 || h <= 0 || w <= 0)
+        return 256;
+    return find_contours_layout(n, h, w).total;
+}
+
+int va_find_contours(const uint8_t *mask, int n, int h, int w, int32_t *ncontours, int64_t *totals,
+                     va_contour_info *info, int64_t *point_off, int64_t cap_contours, int32_t *points,
+                     int64_t cap_points, void *workspace, size_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_find_contours: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(mask && ncontours && totals && info && point_off && points && workspace,
+               "va_find_contours: NULL argument");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_find_contours: bad shape");
+    VA_REQUIRE(cap_contours >= 0 && cap_points >= 0, "va_find_contours: negative capacity (%lld contours, %lld points)",
+               (long long)cap_contours, (long long)cap_points);
+    VA_REQUIRE(aligned(points, 8) && aligned(info, 8) && aligned(point_off, 8) && aligned(totals, 8),
+               "va_find_contours: points, records, offsets and totals must be 8-byte aligned");
+    VA_REQUIRE(workspace_bytes >= va_find_contours_workspace_bytes(n, h, w),
+               "va_find_contours: workspace of %zu bytes < required %zu", workspace_bytes,
+               va_find_contours_workspace_bytes(n, h, w));
+    if (n == 0)
+        return VA_OK;
+    hipStream_t st = as_stream(stream);
+    const FindContoursLayout L = find_contours_layout(n, h, w);
+    uint32_t *bits = at<uint32_t>(workspace, L.bits), *inv = at<uint32_t>(workspace, L.inv);
+    int32_t *forest = at<int32_t>(workspace, L.forest), *bgl = at<int32_t>(workspace, L.bgl);
+    int32_t *counts = at<int32_t>(workspace, L.counts);
+    int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
+    if (!rc)
+        rc = launch_ccl(bits, forest, counts, n, h, w, 8, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st, nullptr,
+                        /*paint=*/false);
+    if (!rc)
+        rc = launch_invert_bits(bits, inv, n, h, w, st);
+    if (!rc)
+        rc = launch_ccl(inv, bgl, counts + n, n, h, w, 4, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st, nullptr,
+                        /*paint=*/true);
+    if (rc)
+        return rc;
+    const FindContoursScratch s = {at<uint32_t>(workspace, L.edge),       at<int32_t>(workspace, L.cells),
+                                   at<int64_t>(workspace, L.frame_first), at<int64_t>(workspace, L.frame_pts),
+                                   at<int64_t>(workspace, L.pt_first),    at(workspace, L.starts),
+                                   at<int32_t>(workspace, L.npts)};
+    return launch_find_contours(bits, forest, bgl, s, n, h, w, ncontours, totals, info, point_off, cap_contours, points,
+                                cap_points, st);
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited
@@ -1166,6 +1249,17 @@ int va_contour_moments(const void *points, const int32_t *npoints, int n, int ma
                max_points);
     return launch_contour_moments(points, npoints, n, max_points, is_float, moments_out,
                                   as_stream(stream));
+}
+
+int va_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float,
+                              double *moments_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0, "va_contour_moments_ragged: negative count (%lld contours)", (long long)m);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(points && point_off && moments_out, "va_contour_moments_ragged: NULL argument");
+    return launch_contour_moments_ragged(points, point_off, m, is_float, moments_out, as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------ pipeline

@@ -5,6 +5,8 @@
 //          areas = [np.sum(labels == l) ...]; argmax            video/analysis/regions.py:165-174
 //          find_bounding_box                                   video/analysis/regions.py:113-149
 //          cv2.moments(mask.astype(np.uint8)) spatial moments  video/analysis/image.py:353
+//          cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[1], the largest contour :178-197 and the whole
+//          list :180-182, :229-231, :575-576, video/io/composer.py:228 (A8, further down)
 //
 // Design (MI355X-first, not a pixel-per-thread port of a CPU two-pass labeller):
 //   * the mask is bit-packed, so a 1080p frame is 60 dwords per row; ONE WAVE OWNS ONE ROW
@@ -1864,6 +1866,246 @@ __global__ void longest_contour_start_kernel(const uint32_t *__restrict__ bits,
     p1[2 * f + 1] = e.y;
 }
 
+// ---- every outer contour of every frame (va_find_contours) -----------------------------------------
+// replaces  cv2.findContours(mask.astype(np.uint8), cv2.RETR_EXTERNAL, cv2.CHAIN_APPROX_SIMPLE)[1] used as a
+//           whole list: video/analysis/regions.py:180-182, :229-231, :575-576, video/io/composer.py:228
+// A contour starts at a forest root (its component's first raster pixel) that passes is_external.  OpenCV
+// lists the most recently found contour first, so contour k of frame f is the start with the k-th LARGEST pixel
+// index, at global slot frame_first[f] + k.  Slots are ranks: counts per cell (a lane's word span of a row, eight
+// per row, in raster order), one scan per frame, one scan over the frames -- no atomic decides a position, so two
+// runs write identical buffers.  The walks then run over the compacted start list, one lane per slot: a wave
+// holds 64 walks instead of the few that a lane-per-span grid finds.
+constexpr int kCellsPerRow = 8;   // span_ctx's word groups
+
+// fn(x, idx) for every external start of the lane's span, left to right
+template <class F>
+__device__ __forceinline__ void for_external_starts(const SpanCtx &c, const uint32_t *bits, const int32_t *forest,
+                                                    const int32_t *bg_labels, const uint32_t *edge_bits,
+                                                    int edge_words, int h, int w, int w32, F &&fn)
+{
+    const uint32_t *row = bits + c.row * w32;
+    const int32_t *L = forest + (size_t)c.f * h * w;
+    const int32_t *B = bg_labels + (size_t)c.f * h * w;
+    const uint32_t *E = edge_bits + (size_t)c.f * edge_words;
+    uint32_t prev = c.w0 > 0 ? row[c.w0 - 1] >> 31 : 0u;
+    for (int wi = c.w0; wi < c.w1; wi++) {
+        const uint32_t m = row[wi];
+        uint32_t s = m & ~((m << 1) | prev);
+        prev = m >> 31;
+        while (s) {
+            const int b = __ffs(s) - 1;
+            s &= s - 1;
+            const int x = (wi << 5) + b, idx = c.y * w + x;
+            const int v = L[idx];
+            if (v >= 0 || (-v & kNonRootBit))
+                continue;   // not a component's first pixel
+            if (is_external(B, E, w, x, c.y))
+                fn(x, idx);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+contour_cell_count_kernel(const uint32_t *__restrict__ bits, const int32_t *__restrict__ forest,
+                          const int32_t *__restrict__ bg_labels, const uint32_t *__restrict__ edge_bits,
+                          int edge_words, int32_t *__restrict__ cell_cnt, int h, int w, int w32, size_t total_rows)
+{
+    const SpanCtx c = span_ctx(h, w32, total_rows);
+    int cnt = 0;
+    if (c.valid)
+        for_external_starts(c, bits, forest, bg_labels, edge_bits, edge_words, h, w, w32, [&](int, int) { cnt++; });
+    if (c.row < total_rows)   // (a lane whose span is empty still owns its cell)
+        cell_cnt[c.row * kCellsPerRow + (c.lane >> 3)] = cnt;
+}
+
+// exclusive prefix of one value per thread over a kBlock workgroup (Hillis-Steele in LDS); *sum: the total
+__device__ __forceinline__ long long block_prefix(long long v, long long *part, long long *sum)
+{
+    const int t = threadIdx.x;
+    part[t] = v;
+    __syncthreads();
+    for (int o = 1; o < kBlock; o <<= 1) {
+        const long long x = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += x;
+        __syncthreads();
+    }
+    const long long r = part[t] - v;
+    *sum = part[kBlock - 1];
+    __syncthreads();
+    return r;
+}
+
+// in place, one workgroup per frame: cell counts -> exclusive prefix within the frame (ascending raster order)
+__global__ void __launch_bounds__(kBlock)
+contour_cell_scan_kernel(int32_t *__restrict__ cells, int32_t *__restrict__ ncontours, long long cells_per_frame)
+{
+    __shared__ long long part[kBlock];
+    int32_t *c = cells + (size_t)blockIdx.x * cells_per_frame;
+    const long long per = (cells_per_frame + kBlock - 1) / kBlock;
+    const long long i0 = min(cells_per_frame, threadIdx.x * per), i1 = min(cells_per_frame, i0 + per);
+    long long s = 0, sum;
+    for (long long i = i0; i < i1; i++)
+        s += c[i];
+    int run = (int)block_prefix(s, part, &sum);
+    for (long long i = i0; i < i1; i++) {
+        const int v = c[i];
+        c[i] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0)
+        ncontours[blockIdx.x] = (int32_t)sum;
+}
+
+// one workgroup: first[0 .. n] = exclusive scan of in[0 .. n), *total = first[n]
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+contour_frame_scan_kernel(const T *__restrict__ in, int n, long long *__restrict__ first,
+                          long long *__restrict__ total)
+{
+    __shared__ long long part[kBlock];
+    const int per = (n + kBlock - 1) / kBlock;
+    const int i0 = min(n, (int)threadIdx.x * per), i1 = min(n, i0 + per);
+    long long s = 0, sum;
+    for (int i = i0; i < i1; i++)
+        s += in[i];
+    long long run = block_prefix(s, part, &sum);
+    for (int i = i0; i < i1; i++) {
+        first[i] = run;
+        run += in[i];
+    }
+    if (threadIdx.x == 0) {
+        first[n] = sum;
+        *total = sum;
+    }
+}
+
+// starts[slot] = (frame, first-pixel index), descending within the frame
+__global__ void __launch_bounds__(kBlock)
+contour_list_kernel(const uint32_t *__restrict__ bits, const int32_t *__restrict__ forest,
+                    const int32_t *__restrict__ bg_labels, const uint32_t *__restrict__ edge_bits, int edge_words,
+                    const int32_t *__restrict__ cell_off, const int32_t *__restrict__ ncontours,
+                    const long long *__restrict__ frame_first, int2 *__restrict__ starts, int h, int w, int w32,
+                    size_t total_rows)
+{
+    const SpanCtx c = span_ctx(h, w32, total_rows);
+    if (!c.valid)
+        return;
+    long long slot = frame_first[c.f] + ncontours[c.f] - 1 - cell_off[c.row * kCellsPerRow + (c.lane >> 3)];
+    for_external_starts(c, bits, forest, bg_labels, edge_bits, edge_words, h, w, w32,
+                        [&](int, int idx) { starts[slot--] = make_int2(c.f, idx); });
+}
+
+struct RecordEmit {   // all that a contour's record holds, from one walk
+    AreaEmit a;
+    ArcEmit l;
+    int xmin = 0x7fffffff, ymin = 0x7fffffff, xmax = -1, ymax = -1;
+    __device__ __forceinline__ void operator()(int x, int y)
+    {
+        a(x, y);
+        l(x, y);
+        xmin = min(xmin, x);
+        ymin = min(ymin, y);
+        xmax = max(xmax, x);
+        ymax = max(ymax, y);
+    }
+};
+
+// count pass: one lane per slot of the compacted list (grid-stride: the host does not know the total)
+__global__ void __launch_bounds__(kWave)
+contour_count_kernel(const uint32_t *__restrict__ bits, const int2 *__restrict__ starts,
+                     const long long *__restrict__ totals, int32_t *__restrict__ npts,
+                     va_contour_info *__restrict__ info, long long cap_contours, int h, int w, int w32)
+{
+    const long long total = totals[0], stride = (long long)gridDim.x * kWave;
+    for (long long slot = (long long)blockIdx.x * kWave + threadIdx.x; slot < total; slot += stride) {
+        const int2 s = starts[slot];
+        const int x0 = s.y % w, y0 = s.y / w;
+        BitImage im{bits + (size_t)s.x * h * w32, h, w, w32};
+        RecordEmit e;
+        trace_outer_border(im, x0, y0, e);
+        npts[slot] = e.a.n;
+        if (slot < cap_contours) {
+            va_contour_info *r = info + slot;
+            r->frame = s.x;
+            r->npoints = e.a.n;
+            r->start_x = x0;
+            r->start_y = y0;
+            r->rect_x = e.xmin;
+            r->rect_y = e.ymin;
+            r->rect_w = e.xmax - e.xmin + 1;
+            r->rect_h = e.ymax - e.ymin + 1;
+            r->area = 0.5 * (double)e.a.twice_area();
+            r->perimeter = e.l.total();
+        }
+    }
+}
+
+// one workgroup per frame: the number of points of its contours
+__global__ void __launch_bounds__(kBlock)
+contour_frame_points_kernel(const int32_t *__restrict__ npts, const long long *__restrict__ frame_first,
+                            long long *__restrict__ frame_pts)
+{
+    __shared__ long long part[kBlock];
+    const long long a = frame_first[blockIdx.x], b = frame_first[blockIdx.x + 1];
+    long long s = 0, sum;
+    for (long long i = a + threadIdx.x; i < b; i += kBlock)
+        s += npts[i];
+    block_prefix(s, part, &sum);
+    if (threadIdx.x == 0)
+        frame_pts[blockIdx.x] = sum;
+}
+
+// one workgroup per frame: point_off[slot] for the slots within the capacity, and the end of the last one
+__global__ void __launch_bounds__(kBlock)
+contour_offsets_kernel(const int32_t *__restrict__ npts, const long long *__restrict__ frame_first,
+                       const long long *__restrict__ pt_first, const long long *__restrict__ totals,
+                       long long *__restrict__ point_off, long long cap_contours)
+{
+    __shared__ long long part[kBlock];
+    const long long a = frame_first[blockIdx.x], b = frame_first[blockIdx.x + 1], total = totals[0];
+    const long long per = (b - a + kBlock - 1) / kBlock;
+    const long long i0 = min(b, a + threadIdx.x * per), i1 = min(b, i0 + per);
+    long long s = 0, sum;
+    for (long long i = i0; i < i1; i++)
+        s += npts[i];
+    long long run = pt_first[blockIdx.x] + block_prefix(s, part, &sum);
+    for (long long i = i0; i < i1; i++) {
+        if (i <= cap_contours)
+            point_off[i] = run;
+        run += npts[i];
+        if (i == total - 1 && total <= cap_contours)
+            point_off[total] = run;
+    }
+    if (total == 0 && blockIdx.x == 0 && threadIdx.x == 0)
+        point_off[0] = 0;
+}
+
+struct RaggedPointEmit {
+    int2 *pts;
+    int n = 0;
+    __device__ __forceinline__ void operator()(int x, int y) { pts[n++] = make_int2(x, y); }
+};
+
+// emit pass: the same walk again, writing the points of every contour that fits whole
+__global__ void __launch_bounds__(kWave)
+contour_emit_kernel(const uint32_t *__restrict__ bits, const int2 *__restrict__ starts,
+                    const long long *__restrict__ totals, const int32_t *__restrict__ npts,
+                    const long long *__restrict__ point_off, long long cap_contours, int2 *__restrict__ points,
+                    long long cap_points, int h, int w, int w32)
+{
+    const long long total = min(totals[0], cap_contours), stride = (long long)gridDim.x * kWave;
+    for (long long slot = (long long)blockIdx.x * kWave + threadIdx.x; slot < total; slot += stride) {
+        const long long off = point_off[slot];
+        if (off + npts[slot] > cap_points)
+            continue;
+        const int2 s = starts[slot];
+        BitImage im{bits + (size_t)s.x * h * w32, h, w, w32};
+        RaggedPointEmit e{points + off};
+        trace_outer_border(im, s.y % w, s.y / w, e);
+    }
+}
+
 }  // namespace
 
 // the per-frame LDS kernel takes frames whose row table and row stages leave room for at least
@@ -2191,6 +2433,55 @@ int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, c
     VA_LAUNCH_CHECK("contour_perimeters_kernel");
     longest_contour_start_kernel<<<n, 64, 0, st>>>(bits, keys + n, h, w, w32, p1);
     VA_LAUNCH_CHECK("longest_contour_start_kernel");
+    return VA_OK;
+}
+
+size_t max_contours_per_frame(int h, int w) { return (size_t)((h + 1) / 2) * (size_t)((w + 1) / 2); }
+
+int launch_find_contours(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
+                         const FindContoursScratch &s, int n, int h, int w, int32_t *ncontours, int64_t *totals,
+                         va_contour_info *info, int64_t *point_off, int64_t cap_contours, int32_t *points,
+                         int64_t cap_points, hipStream_t st)
+{
+    VA_REQUIRE(bits && forest && bg_labels && ncontours && totals && info && point_off && points,
+               "find_contours: NULL argument");
+    if (n == 0)
+        return VA_OK;
+    const int w32 = words_per_row(w), ew = edge_label_words(h, w);
+    const size_t total_rows = (size_t)n * h;
+    long long *tot = (long long *)totals, *frame_first = (long long *)s.frame_first;
+    long long *frame_pts = (long long *)s.frame_pts, *pt_first = (long long *)s.pt_first;
+    int2 *starts = (int2 *)s.starts;
+    VA_HIP(hipMemsetAsync(s.edge_bits, 0, sizeof(uint32_t) * ew * (size_t)n, st));
+    edge_labels_kernel<<<dim3(cdiv(2ll * (w + h), kBlock), n), kBlock, 0, st>>>(bg_labels, s.edge_bits, h, w, ew);
+    VA_LAUNCH_CHECK("edge_labels_kernel");
+    const int sgrid = cdiv((long long)total_rows, kSparseRowsPerBlock);
+    contour_cell_count_kernel<<<sgrid, kBlock, 0, st>>>(bits, forest, bg_labels, s.edge_bits, ew, s.cells, h, w, w32,
+                                                        total_rows);
+    VA_LAUNCH_CHECK("contour_cell_count_kernel");
+    contour_cell_scan_kernel<<<n, kBlock, 0, st>>>(s.cells, ncontours, (long long)h * kCellsPerRow);
+    VA_LAUNCH_CHECK("contour_cell_scan_kernel");
+    contour_frame_scan_kernel<int32_t><<<1, kBlock, 0, st>>>(ncontours, n, frame_first, tot);
+    VA_LAUNCH_CHECK("contour_frame_scan_kernel");
+    contour_list_kernel<<<sgrid, kBlock, 0, st>>>(bits, forest, bg_labels, s.edge_bits, ew, s.cells, ncontours,
+                                                  frame_first, starts, h, w, w32, total_rows);
+    VA_LAUNCH_CHECK("contour_list_kernel");
+    // the walks: up to 64 waves per CU's worth of single-wave workgroups, each lane striding over the slots
+    const size_t worst = (size_t)n * max_contours_per_frame(h, w);
+    const size_t wblocks = (worst + kWave - 1) / kWave;
+    const int wgrid = wblocks < 8192 ? (int)wblocks : 8192;
+    contour_count_kernel<<<wgrid, kWave, 0, st>>>(bits, starts, tot, s.npts, info, cap_contours, h, w, w32);
+    VA_LAUNCH_CHECK("contour_count_kernel");
+    contour_frame_points_kernel<<<n, kBlock, 0, st>>>(s.npts, frame_first, frame_pts);
+    VA_LAUNCH_CHECK("contour_frame_points_kernel");
+    contour_frame_scan_kernel<long long><<<1, kBlock, 0, st>>>(frame_pts, n, pt_first, tot + 1);
+    VA_LAUNCH_CHECK("contour_frame_scan_kernel");
+    contour_offsets_kernel<<<n, kBlock, 0, st>>>(s.npts, frame_first, pt_first, tot, (long long *)point_off,
+                                                 cap_contours);
+    VA_LAUNCH_CHECK("contour_offsets_kernel");
+    contour_emit_kernel<<<wgrid, kWave, 0, st>>>(bits, starts, tot, s.npts, (const long long *)point_off, cap_contours,
+                                                 (int2 *)points, cap_points, h, w, w32);
+    VA_LAUNCH_CHECK("contour_emit_kernel");
     return VA_OK;
 }
 }  // namespace va

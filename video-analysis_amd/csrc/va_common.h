@@ -323,6 +323,22 @@ int launch_invert_bits(const uint32_t *bits, uint32_t *inv, int n, int h, int w,
 int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
                                   uint32_t *edge_bits, int n, int h, int w, unsigned long long *keys,
                                   int32_t *p1, hipStream_t st);
+// every RETR_EXTERNAL contour of every frame as one ragged list (va_find_contours states the outputs); forest and
+// bg_labels as for launch_longest_external_start.  Scratch: edge_bits edge_label_words words per frame; cells 8
+// int32 per row; frame_first, pt_first n + 1 and frame_pts n int64; starts (8 bytes) and npts (int32) one per
+// possible contour, n * max_contours_per_frame of them
+struct FindContoursScratch {
+    uint32_t *edge_bits;
+    int32_t *cells;
+    int64_t *frame_first, *frame_pts, *pt_first;
+    void *starts;
+    int32_t *npts;
+};
+size_t max_contours_per_frame(int h, int w);   // 8-connected components of a frame: every other row and column
+int launch_find_contours(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
+                         const FindContoursScratch &s, int n, int h, int w, int32_t *ncontours, int64_t *totals,
+                         va_contour_info *info, int64_t *point_off, int64_t cap_contours, int32_t *points,
+                         int64_t cap_points, hipStream_t st);
 // geodesic distance maps (va_geodesic.hip): pairs = geodesic_pairs_bytes, visited = geodesic_visited_bytes
 size_t geodesic_pairs_bytes(int n, int h, int w);
 size_t geodesic_visited_bytes(int n, int h, int w);
@@ -416,6 +432,9 @@ int launch_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, con
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);
+// the same over a ragged list: contour i = points point_off[i] .. point_off[i + 1]
+int launch_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float, double *out,
+                                  hipStream_t st);
 int launch_stats_from_labels(const int32_t *labels, int n, int h, int w, int max_labels,
                              int64_t *stats, hipStream_t st);
 int launch_largest_region(const int32_t *labels, const int32_t *counts, const int64_t *stats,

@@ -17,19 +17,12 @@
 namespace va {
 namespace {
 
+// the n points of one contour (first: its first point's index in `points`) -> o[0 .. 9]; one lane
 template <bool IS_FLOAT>
-__global__ __launch_bounds__(64) void contour_moments_kernel(const void *__restrict__ points,
-                                                             const int32_t *__restrict__ npoints,
-                                                             int max_points, double *__restrict__ out)
+__device__ void contour_moments_walk(const void *__restrict__ points, size_t first, int n, double *__restrict__ o)
 {
-    if (threadIdx.x != 0)
-        return;
-    const int f = blockIdx.x;
-    int n = npoints ? npoints[f] : max_points;
-    n = n < 0 ? 0 : (n > max_points ? max_points : n);
-    const int32_t *pi = (const int32_t *)points + (size_t)f * max_points * 2;
-    const float *pf = (const float *)points + (size_t)f * max_points * 2;
-    double *o = out + (size_t)f * 10;
+    const int32_t *pi = (const int32_t *)points + first * 2;
+    const float *pf = (const float *)points + first * 2;
     for (int k = 0; k < 10; k++)
         o[k] = 0.0;
     if (n == 0)
@@ -74,6 +67,33 @@ __global__ __launch_bounds__(64) void contour_moments_kernel(const void *__restr
     }
 }
 
+template <bool IS_FLOAT>
+__global__ __launch_bounds__(64) void contour_moments_kernel(const void *__restrict__ points,
+                                                             const int32_t *__restrict__ npoints,
+                                                             int max_points, double *__restrict__ out)
+{
+    if (threadIdx.x != 0)
+        return;
+    const int f = blockIdx.x;
+    int n = npoints ? npoints[f] : max_points;
+    n = n < 0 ? 0 : (n > max_points ? max_points : n);
+    contour_moments_walk<IS_FLOAT>(points, (size_t)f * max_points, n, out + (size_t)f * 10);
+}
+
+// contour i of a ragged list: points point_off[i] .. point_off[i + 1] (the layout va_find_contours writes)
+template <bool IS_FLOAT>
+__global__ __launch_bounds__(64) void contour_moments_ragged_kernel(const void *__restrict__ points,
+                                                                    const long long *__restrict__ point_off,
+                                                                    long long m, double *__restrict__ out)
+{
+    if (threadIdx.x != 0)
+        return;
+    for (long long i = blockIdx.x; i < m; i += gridDim.x) {
+        const long long a = point_off[i], b = point_off[i + 1];
+        contour_moments_walk<IS_FLOAT>(points, (size_t)a, (int)(b - a), out + (size_t)i * 10);
+    }
+}
+
 }  // namespace
 
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
@@ -87,6 +107,21 @@ int launch_contour_moments(const void *points, const int32_t *npoints, int n, in
     else
         contour_moments_kernel<false><<<n, 64, 0, st>>>(points, npoints, max_points, out);
     VA_LAUNCH_CHECK("contour_moments_kernel");
+    return VA_OK;
+}
+
+int launch_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float, double *out,
+                                  hipStream_t st)
+{
+    VA_REQUIRE(points && point_off && out && m >= 0, "contour_moments_ragged: bad argument");
+    if (m == 0)
+        return VA_OK;
+    const int grid = (int)(m < (1 << 20) ? m : (1 << 20));
+    if (is_float)
+        contour_moments_ragged_kernel<true><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, out);
+    else
+        contour_moments_ragged_kernel<false><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, out);
+    VA_LAUNCH_CHECK("contour_moments_ragged_kernel");
     return VA_OK;
 }
 

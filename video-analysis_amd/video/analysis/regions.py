@@ -3,7 +3,8 @@
 Reference: video/analysis/regions.py -- corners_to_rect :23-29, rect_to_corners :33-45,
 rect_to_slices :49-53, get_overlapping_slices :57-110, find_bounding_box :113-149,
 expand_rectangle :153-155, get_largest_region :159-174, triangle_area :430-451,
-make_distance_map :455-509, shortest_path_in_distance_map :513-565, get_farthest_points :568-611.
+make_distance_map :455-509, shortest_path_in_distance_map :513-565, get_farthest_points :568-611,
+get_external_contour :201-232 (and every cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) list: find_contours).
 """
 import numpy as np
 
@@ -130,6 +131,62 @@ def get_contour_from_largest_region(mask, ret_area=False):
     if ret_area:
         return contour, area
     return contour
+
+
+def find_contours(mask):
+    """cv2.findContours(mask.astype(np.uint8), cv2.RETR_EXTERNAL, cv2.CHAIN_APPROX_SIMPLE)[1]: the list of
+    (N, 1, 2) int32 outer contours in OpenCV's order (reference: video/analysis/regions.py:180-182, :229-231,
+    :575-576; video/io/composer.py:228).  A stack (n, h, w) gives one list per frame, from one call."""
+    from .. import ops
+    return ops.find_contours(mask)
+
+
+def external_contour_resolution(points):
+    """get_external_contour's default resolution: half the smallest non-zero distance of consecutive points, the
+    closing pair included, but at least a 2048th of the ring's longest side (reference :204-215)"""
+    p = np.asarray(points, np.double).reshape(-1, 2)
+    dist = np.hypot(*(p - np.roll(p, 1, axis=0)).T)
+    if not np.any(dist > 0):
+        raise ValueError("the points of the ring coincide: no resolution follows from them")
+    return max(0.5 * dist[dist > 0].min(), np.ptp(p, axis=0).max() / 2048)
+
+
+def get_external_contours(list_of_points, resolution=None):
+    """get_external_contour for every ring of a list: one fill launch and one contour launch for all of them.
+    resolution: None (each ring's own default), one number, or one per ring.  Every ring is filled into a box of
+    one common size (its own origin, zero padding to the right and below, which changes no contour), so that the
+    masks form a uniform stack.  Returns the list of (N, 2) float64 contours."""
+    from .. import ops
+    rings = [np.asarray(p, np.double).reshape(-1, 2) for p in list_of_points]
+    m = len(rings)
+    if m == 0:
+        return []
+    if resolution is None or np.ndim(resolution) == 0:
+        resolution = [resolution] * m
+    if len(resolution) != m:
+        raise ValueError("need one resolution per ring (%d rings, %d resolutions)" % (m, len(resolution)))
+    res = [external_contour_resolution(p) if r is None else float(r) for p, r in zip(rings, resolution)]
+    ints = [np.array(p / r, np.int64) for p, r in zip(rings, res)]         # truncation towards zero, as np.int
+    origin = np.array([c.min(axis=0) - 1 for c in ints])
+    size = np.max([np.ptp(c, axis=0) + 3 for c in ints], axis=0)
+    boxes = np.concatenate([origin, np.broadcast_to(size, (m, 2))], axis=1)
+    masks = np.stack(ops.fill_polys(ints, boxes))
+    out = []
+    for k, contours in enumerate(ops.find_contours(masks)):
+        if len(contours) != 1:
+            raise RuntimeError("ring %d filled into %d components" % (k, len(contours)))
+        out.append((contours[0].reshape(-1, 2) + origin[k]) * res[k])
+    return out
+
+
+def get_external_contour(points, resolution=None):
+    """approximation of the external contour of a linear ring `points`, which may intersect itself: the ring is
+    scaled to integers by `resolution` (default: external_contour_resolution), filled (cv2.fillPoly) into a mask
+    one pixel larger on every side, and the mask's outer contour scaled back; reference:
+    video/analysis/regions.py:201-232.  Returns an (N, 2) float64 array.  Deviation: a contour of one point is
+    (1, 2), where the reference's np.squeeze gives (2,).  More than ops.FILL_MAX_VERTS points raise the fill's
+    ValueError."""
+    return get_external_contours([points], resolution)[0]
 
 
 def make_distance_map(mask, start_points, end_points=None):

@@ -487,6 +487,69 @@ def largest_contour(mask, max_points=None, moments=False):
         return res
 
 
+DEFAULT_CONTOUR_CAPACITY = 4096          # contours / points of a find_contours batch the first launch has room for
+DEFAULT_CONTOUR_POINT_CAPACITY = 1 << 17
+# va_contour_info, include/videoanalysis_hip.h
+CONTOUR_INFO_DTYPE = np.dtype([("frame", np.int32), ("npoints", np.int32), ("start", np.int32, 2),
+                               ("rect", np.int32, 4), ("area", np.float64), ("perimeter", np.float64)])
+CONTOUR_RECORD_DTYPE = np.dtype([("area", np.float64), ("perimeter", np.float64), ("rect", np.int32, 4)])
+
+
+def find_contours(masks, ret_info=False, moments=False, stream=None):
+    """cv2.findContours(mask, cv2.RETR_EXTERNAL, cv2.CHAIN_APPROX_SIMPLE)[1] for one mask (h, w) or a stack
+    (n, h, w), foreground = non-zero (video/analysis/regions.py:180-182, :229-231, :575-576;
+    video/io/composer.py:228): the list of (N, 1, 2) int32 contours in OpenCV's order, one list per frame for a
+    stack.  ret_info appends, per frame, a structured array (CONTOUR_RECORD_DTYPE) of cv2.contourArea,
+    cv2.arcLength(c, True) and cv2.boundingRect (x, y, w, h) of its contours; moments appends the (k, 10) spatial
+    cv2.moments(contour) values per frame, computed from the points on the device.  The first launch has room for
+    DEFAULT_CONTOUR_CAPACITY contours and DEFAULT_CONTOUR_POINT_CAPACITY points in the batch; a batch that holds
+    more runs exactly once more, with exact room."""
+    arr, n, fshape, single = _as_batch(np.asarray(masks), 2)
+    extras = bool(ret_info) + bool(moments)
+    if n == 0:
+        return ([],) * (1 + extras) if extras else []
+    h, w = fshape
+    if h == 0 or w == 0:
+        raise ValueError("find_contours: frames of shape %r have no pixels" % (tuple(fshape),))
+    arr = _as_mask(arr, keep_uint8=True)
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        ws_bytes = L.va_find_contours_workspace_bytes(n, h, w)
+        src, ws, ncb, tot = d.upload(arr), d.take(ws_bytes), d.take(n * 4), d.take(16)
+
+        def run(capc, capp):
+            info, off, pts = d.take(max(capc, 1) * CONTOUR_INFO_DTYPE.itemsize), d.take((capc + 1) * 8), d.take(
+                max(capp, 1) * 8)
+            check(L.va_find_contours(src.ptr, n, h, w, ncb.ptr, tot.ptr, info.ptr, off.ptr, capc, pts.ptr, capp,
+                                     ws.ptr, ws_bytes, stream))
+            return info, off, pts, tot.download((2,), np.int64, stream)
+        capc, capp = DEFAULT_CONTOUR_CAPACITY, DEFAULT_CONTOUR_POINT_CAPACITY
+        info, off, pts, (k, npts) = run(capc, capp)
+        if k > capc or npts > capp:
+            info, off, pts, (k, npts) = run(int(k), int(npts))
+        k, npts = int(k), int(npts)
+        counts = ncb.download((n,), np.int32, stream)
+        offsets = off.download((k + 1,), np.int64, stream)
+        points = pts.download((npts, 2), np.int32, stream)
+        first = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        res = ([[points[offsets[s]:offsets[s + 1]].reshape(-1, 1, 2) for s in range(first[f], first[f + 1])]
+                for f in range(n)],)
+        if ret_info:
+            rec = info.download((k,), CONTOUR_INFO_DTYPE, stream)
+            out = np.empty(k, CONTOUR_RECORD_DTYPE)
+            for name in CONTOUR_RECORD_DTYPE.names:
+                out[name] = rec[name]
+            res += ([out[first[f]:first[f + 1]] for f in range(n)],)
+        if moments:
+            mom = d.take(max(k, 1) * 80)
+            check(L.va_contour_moments_ragged(pts.ptr, off.ptr, k, 0, mom.ptr, stream))
+            allm = mom.download((k, 10), np.float64, stream)
+            res += ([allm[first[f]:first[f + 1]] for f in range(n)],)
+    if single:
+        res = tuple(r[0] for r in res)
+    return res if len(res) > 1 else res[0]
+
+
 # ------------------------------------------------------------------------ geodesic distance maps
 _I32_MAX = 2 ** 31 - 1
 
