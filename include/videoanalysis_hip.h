@@ -517,6 +517,51 @@ int va_guo_hall_thinning_u8(const uint8_t *src_dev, void *scratch_dev, size_t sc
                             int n, int h, int w, int sub_iterations, int poll_period, int32_t *iterations_out,
                             int32_t *stats_out, void *stream);
 
+/* ------------------------------------------------------------------ A16 skeleton graphs
+ * replaces  MorphologicalGraph.from_skeleton(skeleton, post_process=False), video/analysis/morphological_graph.py:
+ *           287-378, by a definition that depends on no visiting order (the reference pops from a dict and a set)
+ * The definition ("Skeleton graphs"): foreground is img != 0, everything outside an item is
+ * background, pixel index i = y * w + x.  m-adjacency: two foreground pixels that share an edge are adjacent; two
+ * that touch only at a corner are adjacent iff neither of the two pixels that share an edge with both is
+ * foreground.  d(p) = number of pixels adjacent to p (0 .. 4).  Node pixels: d != 2, and the pixel of smallest
+ * index of a connected component whose pixels all have d == 2 (a pure ring).  A node is a maximal set of node
+ * pixels connected by adjacency; its anchor, which gives its coordinates, is its pixel of largest d, smallest
+ * index on ties; nodes of an item are numbered by ascending smallest pixel index.  Every other foreground pixel is
+ * a chain pixel (exactly two adjacent pixels).  An edge is a maximal path c1 .. ck (k >= 1) of chain pixels from a
+ * node pixel a adjacent to c1 to a node pixel b adjacent to ck; it starts at the end whose pair (index(a),
+ * index(c1)) is lexicographically smaller, and the edges of an item are ordered by that pair.  Its curve:
+ * anchor(A), a unless it is the anchor, c1 .. ck, b unless it is the anchor, anchor(B); its length: every segment
+ * the float32 sqrt(dx * dx + dy * dy) (correctly rounded), the roots summed in double in point order.
+ * Input: m uint8 items of a ragged packed buffer, laid out as for va_guo_hall_thinning_batch (an (n, h, w) stack
+ * is the same layout with equal shapes); offsets ascend and items do not overlap; total < 2^31 - 2 elements.
+ * An item of 2^29 elements or more, or one that would reach beyond `total`, is treated as empty (no nodes).
+ *   counts_dev[m][2]                 (nodes, edges) of each item
+ *   totals_dev[3]                    nodes, edges and points of the whole batch, always the true totals
+ *   nodes_dev[cap_nodes]             one record per node; item i's nodes follow those of items 0 .. i - 1
+ *   edges_dev[cap_edges]             one record per edge, in the same order; node_a, node_b are item-local numbers
+ *   point_off_dev[cap_edges + 1]     exclusive scan of the records' npoints
+ *   points_dev[cap_points][2]        int32 (x, y) in item coordinates, 8-byte aligned
+ * Nothing is written beyond a capacity: slots 0 .. min(total, cap) - 1 have their records and offsets, and an
+ * edge has its points when all of them lie below cap_points (such edges form a prefix).  Exceeding a capacity is
+ * no error: compare totals_dev with the capacities and call again with room.  Slots and positions come from
+ * counts and scans, never from the order of atomics: two calls write identical bytes.  Everything is enqueued on
+ * `stream`, in the caller's workspace only (va_skeleton_graph_workspace_bytes, 30 bytes per packed element). */
+typedef struct va_skeleton_node {
+    int32_t item, x, y;                         /* item index; the anchor */
+    int32_t degree;                             /* edge ends at the node (a loop counts twice) */
+    int32_t pixels;                             /* pixels of the node's set */
+} va_skeleton_node;
+typedef struct va_skeleton_edge {
+    int32_t item, node_a, node_b, npoints;      /* node numbers within the item, points of the curve */
+    double length;
+} va_skeleton_edge;
+size_t va_skeleton_graph_workspace_bytes(int64_t total, int m);
+int va_skeleton_graph(const uint8_t *masks_dev, const int32_t *shapes_dev, const int64_t *offsets_dev, int64_t total,
+                      int m, int32_t *counts_dev, int64_t *totals_dev, va_skeleton_node *nodes_dev,
+                      int64_t cap_nodes, va_skeleton_edge *edges_dev, int64_t *point_off_dev, int64_t cap_edges,
+                      int32_t *points_dev, int64_t cap_points, void *workspace_dev, size_t workspace_bytes,
+                      void *stream);
+
 /* ------------------------------------------------------------------ A15 affine warps and line scans
  * replaces  cv2.warpAffine(img, matrix, dsize) of single-channel uint8 images (INTER_LINEAR, BORDER_CONSTANT 0) in
  *           line_scan, video/analysis/image.py:102-106 (the strip and its mean over the rows), and

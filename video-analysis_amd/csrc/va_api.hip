@@ -965,6 +965,37 @@ int va_find_contours(const uint8_t *mask, int n, int h, int w, int32_t *ncontour
                                 cap_points, st);
 }
 
+// ------------------------------------------------------------------------------ skeleton graphs
+size_t va_skeleton_graph_workspace_bytes(int64_t total, int m)
+{
+    if (total < 0 || m < 0)
+        return 256;
+    return skeleton_layout(total, m).total;
+}
+
+int va_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
+                      int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
+                      va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
+                      int64_t cap_points, void *workspace, size_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_skeleton_graph: negative count (m %d, total %lld)", m, (long long)total);
+    VA_REQUIRE(total < ((int64_t)1 << 31) - 2, "va_skeleton_graph: 2^31 - 2 or more packed elements are not supported");
+    VA_REQUIRE(masks && shapes && offsets && counts && totals && nodes && edges && point_off && points && workspace,
+               "va_skeleton_graph: NULL argument");
+    VA_REQUIRE(cap_nodes >= 0 && cap_edges >= 0 && cap_points >= 0,
+               "va_skeleton_graph: negative capacity (%lld nodes, %lld edges, %lld points)", (long long)cap_nodes,
+               (long long)cap_edges, (long long)cap_points);
+    VA_REQUIRE(aligned(points, 8) && aligned(nodes, 4) && aligned(edges, 8) && aligned(point_off, 8) &&
+                   aligned(totals, 8) && aligned(counts, 4) && aligned(workspace, 8),
+               "va_skeleton_graph: points, edge records, offsets, totals and workspace must be 8-byte aligned");
+    VA_REQUIRE(workspace_bytes >= va_skeleton_graph_workspace_bytes(total, m),
+               "va_skeleton_graph: workspace of %zu bytes < required %zu", workspace_bytes,
+               va_skeleton_graph_workspace_bytes(total, m));
+    return launch_skeleton_graph(masks, shapes, offsets, total, m, counts, totals, nodes, cap_nodes, edges, point_off,
+                                 cap_edges, points, cap_points, workspace, as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited

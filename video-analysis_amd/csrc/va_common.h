@@ -421,6 +421,16 @@ int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const in
 size_t guo_hall_tiled_scratch_bytes(int n, int h, int w);
 int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
                        int32_t *iterations_out, int32_t *stats_out, hipStream_t st);
+// skeleton graphs (va_skeleton.hip): va_skeleton_graph's outputs from eleven chip-wide launches over the packed
+// pixels; the workspace holds per pixel the forest, the anchor key and the tally of its node (zeroed per call),
+// the adjacency and ownership masks, the point counts and the point offsets, then the scan's block sums
+struct SkeletonLayout { size_t zeroed, anchor, tally, zeroed_bytes, forest, adj, owned, npts, point_base, sums,
+                        first_node, total; };
+SkeletonLayout skeleton_layout(int64_t total, int m);
+int launch_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
+                          int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
+                          va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
+                          int64_t cap_points, void *ws, hipStream_t st);
 // 8-bit affine warps (va_warp.hip): m line scans as int32 column sums, or m warped uint8 destinations, one launch
 int launch_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
                         const double *mats, const int32_t *shapes, const int64_t *out_off, const int32_t *prefix,

@@ -77,3 +77,53 @@ def make_curve_equidistant(points, spacing=None, count=None):
         result = np.transpose((np.interp(sp, s, points[:, 0]), np.interp(sp, s, points[:, 1])))
 
     return result
+
+
+def merge_curves(points1, points2):
+    """one curve out of two that share an end point (curves.py:87-99): points1, turned so that it ends at the
+    shared point, followed by points2, turned so that it starts there; the shared point appears twice.  The pairs
+    of ends are tried in the order (last, first), (first, first), (first, last), (last, last), as the reference
+    tries them; ValueError if no pair coincides"""
+    a, b = np.asarray(points1), np.asarray(points2)
+    for a_end, b_end in ((-1, 0), (0, 0), (0, -1), (-1, -1)):
+        if np.allclose(a[a_end], b[b_end]):
+            return np.concatenate([a if a_end == -1 else a[::-1], b if b_end == 0 else b[::-1]])
+    raise ValueError("merge_curves: no end point of the first curve coincides with one of the second")
+
+
+def simplify_curve(points, epsilon=0):
+    """Ramer-Douglas-Peucker simplification of an (N, 2) curve (curves.py:22, the rdp of
+    external/simplify_polygon_rdp.py) with that module's arithmetic: a point's distance from the chord is
+    |det([x2 - x1, x1 - x0])| / |x2 - x1| (np.linalg.det and norm), or |x0[0] - x1[0]| when the chord's ends have
+    equal x; the first point of largest distance splits the curve when that distance exceeds epsilon.  Returns
+    the kept points, an array of the input's dtype.
+    One deviation: the module also measures the chord's own end point, whose distance is 0 in exact arithmetic;
+    where rounding makes it the largest distance above epsilon (float curves with epsilon = 0) the module recurses
+    without end, and this function does not test that point."""
+    M = np.asarray(points)
+    if M.ndim != 2 or len(M) == 0:
+        raise ValueError("simplify_curve: expected an (N, 2) curve, got shape %r" % (M.shape,))
+    keep = np.zeros(len(M), bool)
+    keep[0] = keep[-1] = True
+    todo = [(0, len(M) - 1)]
+    while todo:
+        i0, i1 = todo.pop()
+        if i1 - i0 < 2:
+            continue
+        x1, x2 = M[i0], M[i1]
+        x0 = M[i0 + 1:i1]                          # (the module also tests the chord's own end: see below)
+        if x1[0] == x2[0]:
+            d = np.abs(x0[:, 0] - x1[0])
+        else:
+            mats = np.empty((len(x0), 2, 2), np.result_type(M.dtype, np.float64))
+            mats[:, 0] = x2 - x1
+            mats[:, 1] = x1 - x0
+            d = np.abs(np.linalg.det(mats)) / np.linalg.norm(x2 - x1)
+        k = int(np.argmax(d))                      # the first of the largest
+        if d[k] > max(epsilon, 0.0):
+            keep[i0 + 1 + k] = True
+            todo.append((i0, i0 + 1 + k))
+            todo.append((i0 + 1 + k, i1))
+    if len(M) == 1:
+        return np.vstack((M[0], M[0]))             # the module returns both ends of the chord, here the same point
+    return M[keep]

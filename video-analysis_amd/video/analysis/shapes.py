@@ -203,6 +203,16 @@ class Polygon(object):
         y, x = np.nonzero(skeleton)
         return np.c_[x, y] + offset
 
+    def get_morphological_graph(self, simplify_epsilon=0.1, method="guo-hall"):
+        """the polygon's skeleton as a MorphologicalGraph in the polygon's own coordinates (reference :628-646):
+        the mask with a margin of 5 is thinned (`method` is mask_thinning's), MorphologicalGraph.from_skeleton
+        builds and post-processes the graph by the definition pinned in DESIGN.md §9, "Skeleton graphs", a
+        positive `simplify_epsilon` thins its curves, and the mask's offset is added"""
+        from .morphological_graph import MorphologicalGraph
+        skeleton, offset = self.get_skeleton(ret_offset=True, method=method)
+        graph = MorphologicalGraph.from_skeleton(skeleton, copy=False)
+        return _finish_morphological_graph(graph, simplify_epsilon, offset)
+
     def get_centerline_estimate(self, end_points=None):
         """ determines an estimate to a center line of the polygon (reference :649-724)
         `end_points` can either be None, a single point, two points or n points (the two of them whose path
@@ -501,3 +511,28 @@ def get_centerlines(polygons, method='smoothed', **kwargs):
         return get_centerline_estimates(polygons, **kwargs)
     else:
         raise ValueError('Unknown method `%s`' % method)
+
+
+# ------------------------------------------------------------------------------- morphological graphs
+def _finish_morphological_graph(graph, simplify_epsilon, offset):
+    """the last two steps of Polygon.get_morphological_graph: curves thinned by a positive epsilon, then the
+    mask's offset added"""
+    if simplify_epsilon > 0:
+        graph.simplify(simplify_epsilon)
+    graph.translate(*offset)
+    return graph
+
+
+def get_morphological_graphs(polygons, simplify_epsilon=0.1):
+    """Polygon.get_morphological_graph(simplify_epsilon, 'guo-hall') of every polygon of a list, as one batch: the
+    masks (margin 5), their Guo-Hall skeletons and the skeleton graphs are computed back to back on the device
+    (ops.polygon_skeleton_graphs); the post-processing, the simplification and the translation stay on the host.
+    Returns the list of MorphologicalGraphs, each with the bits the per-polygon method gives."""
+    from .. import ops
+    from .morphological_graph import MorphologicalGraph
+    rects = [p.get_bounding_rect(margin=5) for p in polygons]
+    contours = [np.asarray(p.contour).astype(np.int64) for p in polygons]
+    res = ops.polygon_skeleton_graphs(contours, rects) if polygons else []
+    return [_finish_morphological_graph(MorphologicalGraph.from_arrays(g.nodes, g.edges, g.curves),
+                                        simplify_epsilon, (int(r[0]), int(r[1])))
+            for g, r in zip(res, rects)]

@@ -1441,3 +1441,138 @@ def warp_affine(frames, matrices, sizes, frame_index=None, inverse=False, stream
         _check_status(st.download((m,), np.int32, stream), "warp_affine")
         flat = out.download((total,), np.uint8, stream)
     return _split_ragged(flat, shapes, offsets, sizes_)
+
+
+# ------------------------------------------------------------------------------------ skeleton graphs
+DEFAULT_SKELETON_NODE_CAPACITY = 1 << 16     # nodes / edges / points of a skeleton_graphs batch the first launch
+DEFAULT_SKELETON_EDGE_CAPACITY = 1 << 16     # has room for (4096 worm skeletons: 8192, 4096 and some 400 000)
+DEFAULT_SKELETON_POINT_CAPACITY = 1 << 20
+# va_skeleton_node, va_skeleton_edge, include/videoanalysis_hip.h
+SKELETON_NODE_DTYPE = np.dtype([("item", np.int32), ("x", np.int32), ("y", np.int32), ("degree", np.int32),
+                                ("pixels", np.int32)])
+SKELETON_EDGE_DTYPE = np.dtype([("item", np.int32), ("node_a", np.int32), ("node_b", np.int32),
+                                ("npoints", np.int32), ("length", np.float64)])
+
+
+class SkeletonGraph(tuple):
+    """the graph of one item: (nodes, edges, curves) -- SKELETON_NODE_DTYPE and SKELETON_EDGE_DTYPE records in the
+    definition's order, and one (npoints, 2) int32 array of (x, y) points per edge"""
+    __slots__ = ()
+    nodes = property(lambda self: self[0])
+    edges = property(lambda self: self[1])
+    curves = property(lambda self: self[2])
+
+
+def _skeleton_graph_run(d, src, sb, ob, total, m, stream):
+    """va_skeleton_graph on packed items that are on the device already (lease d): the first launch with the default
+    capacities and, if a total exceeds one, exactly one more with exact room; the m SkeletonGraphs"""
+    L = _hip.lib()
+    ws_bytes = L.va_skeleton_graph_workspace_bytes(total, m)
+    ws, cnt, tot = d.take(ws_bytes), d.take(m * 8), d.take(24)
+
+    def run(capn, cape, capp):
+        nodes, edges, off, pts = (d.take(max(capn, 1) * SKELETON_NODE_DTYPE.itemsize),
+                                  d.take(max(cape, 1) * SKELETON_EDGE_DTYPE.itemsize), d.take((cape + 1) * 8),
+                                  d.take(max(capp, 1) * 8))
+        check(L.va_skeleton_graph(src.ptr, sb.ptr, ob.ptr, total, m, cnt.ptr, tot.ptr, nodes.ptr, capn, edges.ptr,
+                                  off.ptr, cape, pts.ptr, capp, ws.ptr, ws_bytes, stream))
+        return nodes, edges, off, pts, tot.download((3,), np.int64, stream)
+    caps = (DEFAULT_SKELETON_NODE_CAPACITY, DEFAULT_SKELETON_EDGE_CAPACITY, DEFAULT_SKELETON_POINT_CAPACITY)
+    nodes, edges, off, pts, totals = run(*caps)
+    if any(int(t) > c for t, c in zip(totals, caps)):
+        nodes, edges, off, pts, totals = run(*(int(t) for t in totals))
+    nn, ne, npts = (int(t) for t in totals)
+    counts = cnt.download((m, 2), np.int32, stream).astype(np.int64)
+    node_rec = nodes.download((nn,), SKELETON_NODE_DTYPE, stream)
+    edge_rec = edges.download((ne,), SKELETON_EDGE_DTYPE, stream)
+    offsets = off.download((ne + 1,), np.int64, stream)
+    points = pts.download((npts, 2), np.int32, stream)
+    fn = np.concatenate([[0], np.cumsum(counts[:, 0])])
+    fe = np.concatenate([[0], np.cumsum(counts[:, 1])])
+    return [SkeletonGraph((node_rec[fn[i]:fn[i + 1]], edge_rec[fe[i]:fe[i + 1]],
+                           [points[offsets[s]:offsets[s + 1]] for s in range(fe[i], fe[i + 1])])) for i in range(m)]
+
+
+def skeleton_graphs(skeletons, stream=None):
+    """the skeleton graph of every image of a list of 2-d arrays of any shapes, of one 2-d array or of an (n, h, w)
+    stack (uint8 or bool, non-zero = foreground), in one va_skeleton_graph call: nodes, edges and branch curves by
+    the definition pinned in DESIGN.md §9, "Skeleton graphs" (m-adjacency; node pixels have degree != 2; an edge is
+    a chain of degree-2 pixels between two node pixels) -- what MorphologicalGraph.from_skeleton
+    (video/analysis/morphological_graph.py:287-378) walks on the host, without its dependence on a pop order.
+    Returns one SkeletonGraph per image (a single one for a 2-d array).  The first launch has room for
+    DEFAULT_SKELETON_NODE_CAPACITY nodes, DEFAULT_SKELETON_EDGE_CAPACITY edges and DEFAULT_SKELETON_POINT_CAPACITY
+    points in the batch; a batch that holds more runs exactly once more, with exact room."""
+    single = isinstance(skeletons, np.ndarray) and skeletons.ndim == 2
+    if isinstance(skeletons, np.ndarray) and skeletons.ndim not in (2, 3):
+        raise ValueError("skeleton_graphs: expected a list of 2-d images, one image or an (n, h, w) stack, got "
+                         "shape %r" % (skeletons.shape,))
+    arrs = []
+    for k, a in enumerate([skeletons] if single else skeletons):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 and a.dtype != np.bool_:
+            raise TypeError("skeleton_graphs: image %d has dtype %s (uint8 or bool are supported)" % (k, a.dtype))
+        if a.ndim != 2:
+            raise ValueError("skeleton_graphs: image %d is not 2-d (shape %r)" % (k, a.shape))
+        if a.size >= 2 ** 29:
+            raise ValueError("skeleton_graphs: image %d has %d pixels (fewer than 2^29 are supported)" % (k, a.size))
+        arrs.append(np.ascontiguousarray(a).view(np.uint8))
+    m = len(arrs)
+    if m == 0:
+        return []
+    flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+    if total >= 2 ** 31 - 2:
+        raise ValueError("skeleton_graphs: %d pixels in one call (fewer than 2^31 - 2 are supported)" % total)
+    with _Lease.on(stream) as d:
+        src, sb, ob = d.upload(flat), d.upload(shapes), d.upload(offsets)
+        res = _skeleton_graph_run(d, src, sb, ob, total, m, stream)
+    return res[0] if single else res
+
+
+def polygon_skeleton_graphs(contours, boxes, stream=None):
+    """the skeleton graphs of m polygons (Polygon.get_morphological_graph's pixel work, video/analysis/shapes.py:
+    631-637): the uint8 masks of fill_polys(contours, boxes), their Guo-Hall skeletons and the graphs of those,
+    every table uploaded first and the kernels then back to back on one stream -- va_fill_poly,
+    va_guo_hall_thinning_batch (one launch per size class, as guo_hall_thinning), va_skeleton_graph.  Masks and
+    skeletons stay in leased device buffers, no pixel plane crosses to the host.  Only a box above
+    THIN_RESIDENT_MAX_WORDS packed words takes the per-item path: fill_polys and guo_hall_thinning (its tiled
+    form) for that box alone, its skeleton copied into the batch's skeleton buffer before the graph kernel.
+    contours, boxes as fill_polys takes them.  Returns one SkeletonGraph per polygon, in box coordinates."""
+    m = len(contours)
+    if m == 0:
+        return []
+    verts, vert_off, bx = _fill_tables(contours, boxes, "polygon_skeleton_graphs")
+    _, shapes, offsets, sizes, total = _pack_ragged(bx[:, [3, 2]])
+    words = [_thin_words(s) for s in shapes]
+    large = [k for k, wd in enumerate(words) if wd > THIN_RESIDENT_MAX_WORDS]
+    large_skel = [np.ascontiguousarray(sk) for sk in guo_hall_thinning(
+        fill_polys([contours[k] for k in large], bx[large], stream=stream), stream=stream)] if large else []
+    if total >= 2 ** 31 - 2:
+        raise ValueError("polygon_skeleton_graphs: %d pixels in one call (fewer than 2^31 - 2 are supported)" % total)
+    classes = {}
+    for k, wd in enumerate(words):
+        if 0 < wd <= THIN_RESIDENT_MAX_WORDS:
+            classes.setdefault(0 if wd <= 1024 else 1 if wd <= 4096 else 2, []).append(k)
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        vb, vob, bb, sb, ob = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)), d.upload(shapes),
+                               d.upload(offsets))
+        tables = [(idx, d.upload(shapes[idx]), d.upload(offsets[idx])) for idx in classes.values()]
+        mask, skel, st, it = d.take(max(total, 1)), d.take(max(total, 1)), d.take(2 * m * 4), d.take(m * 4)
+        check(L.va_fill_poly(vb.ptr, vob.ptr, len(verts), bb.ptr, ob.ptr, total, m, 1, mask.ptr, st.ptr, stream))
+        at = m
+        for idx, csb, cob in tables:
+            check(L.va_guo_hall_thinning_batch(mask.ptr, csb.ptr, cob.ptr, total, len(idx),
+                                               max(words[k] for k in idx), skel.ptr, it.ptr + 4 * (at - m),
+                                               st.ptr + 4 * at, stream))
+            at += len(idx)
+        for k, sk in zip(large, large_skel):
+            check(L.va_memcpy_h2d(skel.ptr + int(offsets[k]), sk.ctypes.data, sk.nbytes, stream))   # (contiguous)
+        if large:
+            check(L.va_stream_sync(stream))    # pageable sources: the copies are complete before they go away
+        # an empty box has no pixels in either buffer; a mask a status refuses is not written, and what the later
+        # kernels make of it is discarded below: the statuses are read once, after the last launch
+        res = _skeleton_graph_run(d, skel, sb, ob, total, m, stream)
+        status = st.download((at,), np.int32, stream)
+        _check_status(status[:m], "polygon_skeleton_graphs (fill)")
+        _check_status(status[m:], "polygon_skeleton_graphs (thinning)")
+        return res
