@@ -762,6 +762,12 @@ int va_test_hook_gaussian_u8(int force_valu);
  * kernel, also for the radii (r = 4, 8, ... 36) that have an unrolled one; bit 1: the same for the
  * row pass (compile-time-radius kernels exist for the same radii) */
 int va_test_hook_gaussian_f32(int generic);
+/* byte = 0..255: from now on every block of library scratch (fresh or cached) is filled with that byte on the
+ * call's stream before the call uses it, and every plane a pipeline allocates (va_pipeline_create,
+ * va_pipeline_overlap) is filled before its own clears run: undefined memory that is not the zeros of a fresh
+ * page.  -1 = off (the default; the initial value is $VA_TEST_FILL, decimal 0..255).  Off costs one branch per
+ * scratch lease and per pipeline creation and nothing in va_pipeline_run. */
+int va_test_hook_fill(int byte);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL)
  * Frames shard across ranks with no data-path collective; the only exchange is the final

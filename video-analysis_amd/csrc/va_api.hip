@@ -428,6 +428,15 @@ int va_test_hook_gaussian_f32(int generic_columns)
     return VA_OK;
 }
 
+// test hook: -1 = off, 0..255 = every scratch lease and every plane of a pipeline created from now on starts
+// out filled with that byte (undefined memory that is not zero)
+int va_test_hook_fill(int byte)
+{
+    VA_REQUIRE(byte >= -1 && byte <= 255, "va_test_hook_fill: byte must be -1 (off) or 0..255");
+    g_test_fill = byte;
+    return VA_OK;
+}
+
 int va_gaussian_f32(const float *src, float *dst, int n, int h, int w, int c, double sigma,
                     void *stream)
 {
@@ -1388,6 +1397,8 @@ int va_pipeline_create(const va_config *cfg, va_pipeline_t **out)
             pipeline_free(p);                                                            \
             return VA_ERR_NOMEM;                                                         \
         }                                                                                \
+        if (g_test_fill >= 0)                                                            \
+            (void)hipMemset((ptr), g_test_fill, (bytes));                                \
     } while (0)
 
     if (cfg->sigma > 0)
@@ -1479,6 +1490,8 @@ int va_pipeline_overlap(va_pipeline_t *p, int enable)
                           hipGetErrorString(_e));                                           \
                 return VA_ERR_NOMEM;                                                        \
             }                                                                               \
+            if (g_test_fill >= 0)                                                           \
+                (void)hipMemset((ptr), g_test_fill, (bytes));                               \
         }                                                                                   \
     } while (0)
     OV_MALLOC(p->bits[1][0], p->bits_bytes);

@@ -108,6 +108,9 @@ struct ScratchLease {
 };
 void scratch_release_cached(size_t keep_bytes);   // frees the cache when it holds more than keep_bytes (va_trim)
 void scratch_purge_stream(hipStream_t st);        // frees the blocks cached for st (va_stream_destroy)
+// va_test_hook_fill: -1 (off), or the byte that every scratch lease and every plane a pipeline allocates is filled
+// with before use.  Initial value: $VA_TEST_FILL.
+extern int g_test_fill;
 
 #if defined(__HIPCC__)
 // BORDER_REFLECT_101 with repeated reflection (kernel wider than the image)

@@ -13,12 +13,31 @@
 //  * Blocks are freed by va_trim; by va_stream_destroy for its stream, behind a synchronisation of it (a later
 //    stream may get the same handle); and all of them, behind a device synchronisation, once more than
 //    kScratchCacheCap bytes are cached or a hipMalloc fails.  Otherwise no lease synchronises anything.
+//  * What a block holds when it is handed out is undefined.  Under va_test_hook_fill the whole block, fresh or
+//    cached, is set to the fill byte on the lease's stream first (stream order: no synchronisation added).
+#include <cstdlib>
 #include <mutex>
 #include <vector>
 
 #include "va_common.h"
 
 namespace va {
+namespace {
+
+int test_fill_from_env()                           // $VA_TEST_FILL: decimal 0..255, anything else is "off"
+{
+    const char *e = getenv("VA_TEST_FILL");
+    if (!e || !*e)
+        return -1;
+    char *end = nullptr;
+    long v = strtol(e, &end, 10);
+    return (*end == 0 && v >= 0 && v <= 255) ? (int)v : -1;
+}
+
+}  // namespace
+
+int g_test_fill = test_fill_from_env();
+
 namespace {
 
 struct ScratchBlock {
@@ -48,6 +67,19 @@ void release_locked(const hipStream_t *only = nullptr)
 
 }  // namespace
 
+// the test fill of a block just handed out (the one branch the mode costs a lease when it is off)
+static int fill_block(void *ptr, size_t bytes, hipStream_t st)
+{
+    if (g_test_fill < 0)
+        return VA_OK;
+    hipError_t e = hipMemsetAsync(ptr, g_test_fill, bytes, st);
+    if (e != hipSuccess) {
+        set_error("scratch: hipMemsetAsync(%zu) failed: %s", bytes, hipGetErrorString(e));
+        return VA_ERR_HIP;
+    }
+    return VA_OK;
+}
+
 int ScratchLease::acquire(size_t need, hipStream_t stream)
 {
     st = stream;
@@ -65,7 +97,7 @@ int ScratchLease::acquire(size_t need, hipStream_t stream)
             bytes = g_scratch_free[best].bytes;
             g_scratch_cached -= bytes;
             g_scratch_free.erase(g_scratch_free.begin() + best);
-            return VA_OK;
+            return fill_block(ptr, bytes, st);
         }
     }
     hipError_t e = hipMalloc(&ptr, need);
@@ -81,7 +113,7 @@ int ScratchLease::acquire(size_t need, hipStream_t stream)
         return VA_ERR_NOMEM;
     }
     bytes = need;
-    return VA_OK;
+    return fill_block(ptr, bytes, st);
 }
 
 ScratchLease::~ScratchLease()

@@ -6,6 +6,7 @@ shared library is missing, or no MI355X is visible, every filter/analysis call r
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -155,6 +156,7 @@ SIGNATURES = {
     "va_test_hook_labelling": (_i, [_i, _i]),
     "va_test_hook_gaussian_u8": (_i, [_i]),
     "va_test_hook_gaussian_f32": (_i, [_i]),
+    "va_test_hook_fill": (_i, [_i]),
     "va_morph_bits_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "va_comm_unique_id": (_i, [_vp]),
     "va_comm_init": (_i, [C.POINTER(_vp), _i, _i, _vp]),
@@ -227,13 +229,79 @@ def gpu_available():
         return False
 
 
+# ------------------------------------------------------------------------------------------ test fill mode
+# Undefined device memory that is not zero, and a guarded tail behind every buffer ("Hostile memory").
+# -1 = off; 0..255 = on: every DeviceBuffer is allocated with TAIL_BYTES more than asked for and filled with the
+# byte, and the library fills its own scratch and pipeline planes (va_test_hook_fill).  Initial value: $VA_TEST_FILL,
+# which the library reads too.
+TAIL_BYTES = 256
+
+
+def _fill_from_env():
+    text = os.environ.get("VA_TEST_FILL", "")
+    return int(text) if text.isdigit() and int(text) <= 255 else -1
+
+
+_fill_mode = _fill_from_env()
+_fill_watchers = []             # video.ops mirrors the value in a global of its own: called with each new value
+_guarded = weakref.WeakSet()    # every live DeviceBuffer made while the mode was on
+_violations = []                # what free() found (__del__ swallows exceptions): drained by check_guards()
+
+
+def fill_mode():
+    """the fill byte of the test fill mode, or -1 when it is off"""
+    return _fill_mode
+
+
+def set_fill_mode(byte):
+    """switch the test fill mode on (0..255) or off (-1), here and in the library where it has the hook (the
+    oracle's twin has no scratch of its own and no hook)"""
+    global _fill_mode
+    byte = int(byte)
+    if not -1 <= byte <= 255:
+        raise ValueError("the fill byte is -1 (off) or 0..255, got %d" % byte)
+    hook = getattr(load_library(), "va_test_hook_fill", None)
+    if hook is not None:
+        check(hook(byte))
+    _fill_mode = byte
+    for watcher in _fill_watchers:
+        watcher(byte)
+
+
+class GuardViolation(HipError):
+    """bytes behind the end of a device buffer were overwritten (test fill mode)"""
+
+    def __init__(self, message):
+        HipError.__init__(self, -14, message)
+
+
+def check_guards():
+    """the guarded ranges of every live DeviceBuffer, checked now, and what free() has recorded since the last
+    call: a list of messages, empty when nothing was written behind a buffer.  Each violation is reported once."""
+    found, _violations[:] = list(_violations), []
+    for buf in list(_guarded):
+        damage = buf.check_guard()
+        if damage:
+            found.append(damage)
+    return found
+
+
 class DeviceBuffer(object):
     """a hipMalloc'ed buffer with NumPy upload/download helpers"""
+    _fill = -1          # the byte this buffer and its tail were filled with; -1: made with the test fill mode off
+    _alloc = 0          # (test fill mode) bytes allocated: nbytes + TAIL_BYTES
+    _asked = 0          # (test fill mode) where the guarded range starts: nbytes, or what ops._take was asked for
 
     def __init__(self, nbytes):
         self.nbytes = int(nbytes)
         self._ptr = C.c_void_p()
-        check(lib().va_malloc(C.byref(self._ptr), max(self.nbytes, 1)))
+        if _fill_mode < 0:
+            check(lib().va_malloc(C.byref(self._ptr), max(self.nbytes, 1)))
+            return
+        self._fill, self._asked, self._alloc = _fill_mode, self.nbytes, self.nbytes + TAIL_BYTES
+        check(lib().va_malloc(C.byref(self._ptr), self._alloc))
+        self.refill()
+        _guarded.add(self)
 
     @property
     def ptr(self):
@@ -263,8 +331,35 @@ class DeviceBuffer(object):
         check(L.va_stream_sync(stream))
         return out
 
+    def refill(self, start=0):
+        """(test fill mode) set the allocation from byte `start` on, tail included, to the fill byte; synchronises"""
+        L = lib()
+        check(L.va_memset(self.ptr + start, self._fill, self._alloc - start, None))
+        check(L.va_stream_sync(None))
+
+    def check_guard(self):
+        """(test fill mode) None when every byte behind the size asked for still holds the fill byte; else a message
+        with the sizes, the first damaged offset and the number of damaged bytes, and the range is filled again (a
+        violation is reported once).  Synchronises.  A write of the fill byte itself cannot be seen."""
+        if _fill_mode < 0 or self._fill != _fill_mode or not self.ptr:      # (made with the mode off, or under another byte)
+            return None
+        tail = np.empty(self._alloc - self._asked, np.uint8)
+        L = lib()
+        check(L.va_memcpy_d2h(tail.ctypes.data, self.ptr + self._asked, tail.nbytes, None))
+        check(L.va_stream_sync(None))
+        bad = np.flatnonzero(tail != self._fill)
+        if not bad.size:
+            return None
+        self.refill(self._asked)
+        return ("buffer of %d bytes (%d allocated, fill 0x%02X): first damaged offset %d, %d byte(s) differ"
+                % (self._asked, self._alloc, self._fill, self._asked + int(bad[0]), bad.size))
+
     def free(self):
         if self._ptr is not None and self._ptr.value:
+            if _fill_mode >= 0:
+                damage = self.check_guard()
+                if damage:
+                    _violations.append("at free(): " + damage)
             load_library().va_free(self._ptr)
             self._ptr = C.c_void_p()
 

@@ -23,16 +23,50 @@ _POOL_LOCK = threading.Lock()       # VideoPreprocessor runs these ops from one 
 POOL_CAPACITY = 4 << 30
 
 
+_FILL = _hip.fill_mode()            # the test fill mode's byte, -1 when off: _hip.set_fill_mode keeps it current
+
+
+def _on_fill_mode(byte):
+    global _FILL
+    _FILL = byte
+
+
+_hip._fill_watchers.append(_on_fill_mode)
+
+
 def _take(nbytes):
     """a device buffer of at least `nbytes` bytes (recycled when one of its size class is free)"""
     global _POOL_BYTES
     size = max(256, 1 << max(int(nbytes) - 1, 1).bit_length())
+    if _FILL >= 0:
+        return _take_guarded(int(nbytes), size)
     with _POOL_LOCK:
         free = _POOL.get(size)
         if free:
             _POOL_BYTES -= size
             return free.pop()
     return DeviceBuffer(size)
+
+
+def _take_guarded(nbytes, size):
+    """_take in the test fill mode: the whole buffer holds the fill byte, a recycled one as much as a fresh one, and
+    its guarded range starts at the size asked for: the slack of the size class, then the tail"""
+    global _POOL_BYTES
+    buf = None
+    with _POOL_LOCK:
+        free = _POOL.get(size)
+        if free:
+            _POOL_BYTES -= size
+            buf = free.pop()
+    if buf is not None and buf._fill != _FILL:      # pooled under another setting of the mode
+        buf.free()
+        buf = None
+    if buf is None:
+        buf = DeviceBuffer(size)
+    else:
+        buf.refill()
+    buf._asked = nbytes
+    return buf
 
 
 def _upload(arr, stream=None):
@@ -45,6 +79,7 @@ def _upload(arr, stream=None):
 def _give(*bufs):
     """hand buffers back (every call below has synchronised its stream by then)"""
     global _POOL_BYTES
+    damage = _damage(bufs) if _FILL >= 0 else None
     for b in bufs:
         if b is None:
             continue
@@ -55,6 +90,18 @@ def _give(*bufs):
                 _POOL_BYTES += b.nbytes
         if not keep:
             b.free()
+    if damage:
+        raise _hip.GuardViolation(damage)
+
+
+def _damage(bufs):
+    """test fill mode: what the guarded ranges of a call's buffers show (this synchronises, which the mode may);
+    None when they all still hold the fill byte"""
+    found = [d for d in (b.check_guard() for b in bufs if b is not None) if d]
+    if not found:
+        return None
+    return ("a call with buffers of %s bytes wrote behind the end of %s"
+            % ([b._asked for b in bufs if b is not None], "; ".join(found)))
 
 
 def pool_clear():
