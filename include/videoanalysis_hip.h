@@ -31,6 +31,14 @@
  *     background state and must be used by one thread / one stream at a time.
  *   - sizes: frames of up to 2^29 - 1 pixels (the kernels address h*w*4 bytes through 32-bit
  *     buffer descriptors); larger frames are refused with VA_ERR_INVALID.
+ *   - shape envelope ("Shape envelope"): unless an entry point says otherwise it takes any n >= 0
+ *     (n = 0 enqueues nothing and writes nothing) and any h, w >= 1 below the pixel limit: a frame may be a single
+ *     pixel, row or column, narrower than the filter (borders reflect or clip as often as needed), or longer than
+ *     65535 rows or columns.  No launch puts more than 65535 into gridDim.y or gridDim.z: a longer batch goes out
+ *     in pieces of 65535 frames, a taller frame takes a kernel with a one-dimensional grid, and where neither is
+ *     possible the entry point states the limit and refuses beyond it with VA_ERR_INVALID and a message that names
+ *     it, before anything is enqueued or written.  Ragged entry points count their m items in gridDim.x: any
+ *     m >= 0 below 2^31.
  */
 #ifndef VIDEOANALYSIS_HIP_H
 #define VIDEOANALYSIS_HIP_H
@@ -116,11 +124,12 @@ int va_event_elapsed_ms(void *start_event, void *stop_event, float *ms_out);
  * replaces  cv2.GaussianBlur(frame.astype(np.uint8), (0, 0), sigma)
  *           FilterBlur._process_frame, video/filters.py:388-392
  * 8-bit: ksize = cvRound(6 sigma + 1)|1, unsigned 8.8 fixed-point taps, BORDER_REFLECT_101,
- * each of the `c` interleaved channels independently.  src != dst. */
+ * each of the `c` interleaved channels independently.  src != dst.
+ * Shape: any n >= 0, h, w >= 1 (frames smaller than the filter reflect repeatedly, as cv::borderInterpolate does). */
 int va_gaussian_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w, int c,
                    double sigma, void *stream);
 /* replaces  cv2.GaussianBlur(float_image, (0, 0), sigma), video/analysis/active_contour.py:108
- * ksize = cvRound(8 sigma + 1)|1, float32 taps and fmaf accumulation. */
+ * ksize = cvRound(8 sigma + 1)|1, float32 taps and fmaf accumulation.  Shape: any n >= 0, h, w >= 1. */
 int va_gaussian_f32(const float *src_dev, float *dst_dev, int n, int h, int w, int c,
                     double sigma, void *stream);
 /* the same with the tap set named explicitly (VA_TAPS_CV4 = va_gaussian_u8's, VA_TAPS_CV3 = the
@@ -139,7 +148,8 @@ int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacit
  * mode VA_BG_MEAN  : state = float64[px], n_seen = frames already folded into it
  * mode VA_BG_EMA   : state = float32[px], rate; the very first frame initialises bg = frame
  * mode VA_BG_STATIC: state = float64[px], read only
- * dtype VA_U8 (all modes) or VA_F32 (EMA only).  diff_out may be NULL (state update only). */
+ * dtype VA_U8 (all modes) or VA_F32 (EMA only).  diff_out may be NULL (state update only).
+ * Shape (this call and the three below): any n >= 0, px >= 1 (px = h*w*c: the frame's shape does not matter). */
 int va_bg_update(int mode, int dtype, const void *frames_dev, void *diff_out_dev,
                  void *state_dev, int64_t n_seen, double rate, int n, size_t px, void *stream);
 /* measure_mean / measure_mean_std over frames of any dtype the reference meets (video/analysis/video.py:26-55):
@@ -155,6 +165,8 @@ int va_welford_u8(const uint8_t *frames_dev, double *mean_dev, double *m2_dev, i
                   int n, size_t px, void *stream);
 
 /* ------------------------------------------------------------------ A3 / A4 / A5 pointwise
+ * Shape: the calls that take `count` or `pixels` see one flat array of any length >= 0; va_prepare_u8,
+ * va_rot90: any n >= 0 and frames of any h, w >= 1 (a crop must lie inside its source frame).
  * replaces  this_frame.astype(np.int16) - prev_frame, FilterTimeDifference._compare_frames,
  *           video/filters.py:564-568 */
 int va_time_difference_u8(const uint8_t *this_dev, const uint8_t *prev_dev, int16_t *out_dev,
@@ -207,7 +219,10 @@ int va_rot90(const void *src_dev, void *dst_dev, int n, int h, int w, int elem_b
  * float cell-overlap weights for other shrinks, linear with area-style positions when growing;
  * lanczos4 (video/filters.py:293-294) = 8 x 8 taps, 11-bit fixed point, int32 accumulation.  src != dst.
  * va_resize_f32: float32 frames (FilterResize takes the video's dtype): the float instantiations of the
- * same algorithms -- float coefficients, products summed from the first tap to the last, no rounding. */
+ * same algorithms -- float coefficients, products summed from the first tap to the last, no rounding.
+ * Shape: any n >= 0 (more than 65535 frames go out in pieces); source frames of any src_h, src_w >= 1; targets of
+ * dst_w >= 1 and 1 <= dst_h <= 65535 (the kernels count target rows in gridDim.y): a taller target is refused
+ * with VA_ERR_INVALID before the tables are uploaded. */
 #define VA_INTER_NEAREST 0
 #define VA_INTER_LINEAR 1
 #define VA_INTER_CUBIC 2
@@ -221,7 +236,9 @@ int va_resize_f32(const float *src_dev, float *dst_dev, int n, int src_h, int sr
 /* ------------------------------------------------------------------ A6 morphology
  * replaces  cv2.erode / cv2.dilate(img, cv2.getStructuringElement(shape, (k, k))),
  *           video/analysis/image.py:248-251; anchor = centre, pixels outside the image never
- *           win (OpenCV's default border).  src != dst.  (n, h, w) u8. */
+ *           win (OpenCV's default border).  src != dst.  (n, h, w) u8.
+ * Shape: any n >= 0, h, w >= 1, elements larger than the frame included (rows of whole dwords with h, n <= 65535
+ * take the four-samples-per-thread kernels, everything else the one-sample kernels: the same bytes). */
 int va_morph_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w, int op,
                 int shape, int ksize, void *stream);
 
@@ -230,7 +247,8 @@ int va_morph_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w, i
  * any non-zero mask byte is foreground; connectivity 4 (SciPy default) or 8; int32 labels
  * 1..L numbered in raster order of each component's first pixel; counts[f] = L of frame f.
  * labels_dev: (n,h,w) int32 (also used as the union-find forest while running).
- * workspace: va_label_workspace_bytes(n,h,w) bytes of device scratch. */
+ * workspace: va_label_workspace_bytes(n,h,w) bytes of device scratch.
+ * Shape: any n >= 0, h, w >= 1 below 2^29 pixels. */
 size_t va_label_workspace_bytes(int n, int h, int w);
 int va_label_i32(const uint8_t *mask_dev, int32_t *labels_dev, int32_t *counts_dev, int n,
                  int h, int w, int connectivity, void *workspace_dev, size_t workspace_bytes,
@@ -243,7 +261,8 @@ int va_label_i32(const uint8_t *mask_dev, int32_t *labels_dev, int32_t *counts_d
  * stats_dev: (n, max_labels, 16) int64, for label l at [l-1]:
  *   0 area(m00) 1 m10 2 m01 3 m20 4 m11 5 m02 6 m30 7 m21 8 m12 9 m03
  *   10 xmin 11 ymin 12 xmax 13 ymax 14,15 reserved
- * labels above max_labels are ignored (check counts against max_labels on the host). */
+ * labels above max_labels are ignored (check counts against max_labels on the host).
+ * Shape (va_moments_i64, va_largest_region): any n >= 0, h, w >= 1, max_labels >= 1. */
 int va_moments_i64(const int32_t *labels_dev, int n, int h, int w, int max_labels,
                    int64_t *stats_dev, void *stream);
 /* replaces  label_max = np.argmax(areas) + 1; labels == label_max,
@@ -264,7 +283,8 @@ int va_largest_region(const int32_t *labels_dev, const int32_t *counts_dev,
  * most-recent-first contour order for the argmax tie rule.
  * points_dev: (n, max_points, 2) int32 (x, y); npoints_dev[f] = points of the winning contour
  * (if > max_points only the first max_points were stored); area_dev[f] = cv2.contourArea of it;
- * ncomponents_dev[f] = number of 8-connected components (0 -> "Could not find any contour"). */
+ * ncomponents_dev[f] = number of 8-connected components (0 -> "Could not find any contour").
+ * Shape: any n >= 0 (the per-frame passes go out in pieces of 65535 frames), h, w >= 1 below 2^29 pixels. */
 size_t va_contour_workspace_bytes(int n, int h, int w);
 int va_largest_contour(const uint8_t *mask_dev, int n, int h, int w, int32_t *points_dev,
                        int max_points, int32_t *npoints_dev, double *area_dev,
@@ -293,7 +313,8 @@ int va_largest_contour(const uint8_t *mask_dev, int n, int h, int w, int32_t *po
  * prefix).  Exceeding a capacity is no error: compare totals_dev with the capacities and call again
  * with room.  Slots and positions come from counts and scans, never from the order of atomics: two
  * calls write identical bytes.  Everything is enqueued on `stream`, in the caller's workspace only.
- * Frames stay below 2^29 pixels, as for va_largest_contour. */
+ * Frames stay below 2^29 pixels, as for va_largest_contour.  Shape: any n >= 0 (pieces of 65535 frames where a
+ * pass counts frames in its grid), h, w >= 1. */
 typedef struct va_contour_info {
     int32_t frame, npoints;                     /* frame index; points of the contour */
     int32_t start_x, start_y;                   /* its first point = the component's first raster pixel */
@@ -311,7 +332,8 @@ int va_find_contours(const uint8_t *mask_dev, int n, int h, int w, int32_t *ncon
  * 8-neighbour geodesics inside masks: straight steps cost 1, diagonal steps sqrt2 (a diagonal step may
  * pass between two wall pixels).  A distance d = a + b*sqrt2 is kept as the exact pair (a, b) and
  * written as 2 + a + floor(b*sqrt2), the reference's int(2 + d); maps are relaxed to their fixpoint
- * with one workgroup per frame.  Frames up to 8192 columns wide.  All three entry points work only
+ * with one workgroup per frame.  Frames up to 8192 columns wide (wider: VA_ERR_INVALID), any h >= 1, any
+ * n >= 0 (the frame is the workgroup index, gridDim.x).  All three entry points work only
  * in `workspace_dev` (va_geodesic_workspace_bytes) and on `stream`. */
 size_t va_geodesic_workspace_bytes(int n, int h, int w);
 /* replaces  make_distance_map(mask, start_points, end_points), video/analysis/regions.py:455-509
@@ -368,7 +390,9 @@ size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int l
  * flow_out_dev (nullable): (n - 1, h, w, 2) float32 (dx, dy); mag_out_dev (nullable): (n - 1, h, w) float32
  * sqrt(dx^2 + dy^2); not both NULL.  pyr_scale in (0, 1), levels >= 0, winsize >= 1, iterations >= 1,
  * poly_n 5 or 7, flags 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not supported), else
- * VA_ERR_INVALID; a workspace smaller than va_farneback_workspace_bytes is VA_ERR_RANGE.  The call drains
+ * VA_ERR_INVALID; a workspace smaller than va_farneback_workspace_bytes is VA_ERR_RANGE.  Shape: 2 <= n, at most
+ * 65535 frames and at most 65535 rows in one call (both count in gridDim.y / gridDim.z of the pyramid kernels, and
+ * a pair needs both of its frames in one call), any w >= 1; beyond: VA_ERR_INVALID, nothing enqueued.  The call drains
  * `stream` before it uploads its resize tables, then enqueues its kernels on it. */
 int va_optical_flow_farneback(const void *frames_dev, int dtype, int n, int h, int w, double pyr_scale,
                               int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
@@ -380,12 +404,13 @@ int va_optical_flow_farneback(const void *frames_dev, int dtype, int n, int h, i
  *           ActiveContour.set_potential, video/analysis/active_contour.py:109-110
  * src_dev: (n, h, w) frames of dtype VA_U8 or VA_F32 (the blurred potential: va_gaussian_u8 / va_gaussian_f32
  * before it).  fx_out_dev, fy_out_dev (nullable, not both): (n, h, w) float64, OpenCV's FilterEngine
- * arithmetic with a CV_64F kernel and BORDER_REFLECT_101, -0.0 and +0.0 as it gives them. */
+ * arithmetic with a CV_64F kernel and BORDER_REFLECT_101, -0.0 and +0.0 as it gives them.
+ * Shape: any n >= 0 (pieces of 65535 frames), h, w >= 1. */
 int va_sobel5_f64(const void *src_dev, int dtype, double *fx_out_dev, double *fy_out_dev, int n, int h, int w,
                   void *stream);
 /* replaces  the iteration of ActiveContour.find_contour, video/analysis/active_contour.py:160-191
- * m contours on an (n, h, w) stack of float64 gradients (h, w >= 2), every iteration of every contour in one
- * launch.  Per contour c: npts_dev[c] points (<= max_points <= 1024; <= 2 leaves the contour as it is with
+ * m contours on an (n, h, w) stack of float64 gradients (h, w >= 2: smaller frames are VA_ERR_INVALID; any
+ * n >= 1, any m >= 0), every iteration of every contour in one launch.  Per contour c: npts_dev[c] points (<= max_points <= 1024; <= 2 leaves the contour as it is with
  * 0 iterations), frame_dev[c] its frame, mat_offset_dev[c] the element offset in mats_dev (mats_count
  * doubles) of its inverse evolution matrix stored TRANSPOSED (element (j, i) = Pinv[i, j]).
  * anchor_flags_dev (nullable): (m, max_points) u8, bit 0 = x fixed, bit 1 = y fixed, at the value in
@@ -615,7 +640,7 @@ int va_warp_affine_u8(const uint8_t *frames_dev, int n_frames, int h, int w, int
  *           video/analysis/shapes.py:527-533
  * Green's-theorem moments of n closed polygons, accumulated in float64 in OpenCV's point order
  * (bit-identical to its contourMoments; m00 >= 0 for either orientation; a degenerate contour
- * gives zeros).  points_dev: (n, max_points, 2) int32 (is_float == 0) or float32 (x, y) -- e.g.
+ * gives zeros; any n >= 0, one wave per contour in gridDim.x).  points_dev: (n, max_points, 2) int32 (is_float == 0) or float32 (x, y) -- e.g.
  * the output of va_largest_contour; npoints_dev[f] = points of contour f (NULL: max_points each).
  * moments_out_dev: (n, 10) float64 = m00 m10 m01 m20 m11 m02 m30 m21 m12 m03; the central and
  * normalised moments follow on the host (completeMomentState). */
@@ -631,7 +656,9 @@ int va_contour_moments_ragged(const void *points_dev, const int64_t *point_off_d
  * replaces  detect_peaks(img, include_plateaus), video/analysis/image.py:267-306:
  *           ndimage.maximum_filter(img, footprint=8-neighbourhood) == img, minus the
  *           binary_erosion(img == 0, 8-neighbourhood, border_value=1) background (plateaus), or
- *           img > maximum over the 8 neighbours.  dst: 0/1 u8 mask. */
+ *           img > maximum over the 8 neighbours.  dst: 0/1 u8 mask.
+ * Shape (all of this section): any n >= 0, h, w >= 1 -- one-dimensional grids over all pixels, except the
+ * four-samples-per-thread tail of va_mask_thinning_u8, which frames of more than 65535 rows do not take. */
 int va_detect_peaks_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w,
                        int include_plateaus, void *stream);
 /* the same on float32 maps (the reference calls it on distance / correlation maps): comparisons in float,
@@ -648,7 +675,8 @@ int va_mask_thinning_u8(uint8_t *img_dev, uint8_t *scratch_dev, uint8_t *skel_de
                         int *iterations_out, void *stream);
 /* replaces  get_image_statistics, video/analysis/image.py:131-201: local mean and variance in a
  *           (2*ksize+1)^2 box or ellipse window of (img - prior), zero border.
- * kernel: 0 box, 1 ellipse.  mean_out_dev / var_out_dev: (n,h,w) float64; var_out may be NULL. */
+ * kernel: 0 box, 1 ellipse.  mean_out_dev / var_out_dev: (n,h,w) float64; var_out may be NULL.
+ * ksize >= 0; a window of one sample (ksize 0) has the variance 0/0 = NaN, as in the reference. */
 int va_image_statistics_u8(const uint8_t *src_dev, double *mean_out_dev, double *var_out_dev, int n,
                            int h, int w, int kernel, int ksize, double prior, int exclude_center,
                            void *stream);
@@ -694,7 +722,9 @@ int va_pipeline_destroy(va_pipeline_t *p);
  *   mask_out_dev     : (n,H,W) u8 0/maxval after threshold + morphology
  *   labels_out_dev   : (n,H,W) int32
  *   counts_out_dev   : (n) int32 components per frame
- *   stats_out_dev    : (n,max_labels,16) int64 */
+ *   stats_out_dev    : (n,max_labels,16) int64
+ * Shape: width, height >= 1 (a chain on frames too small for the single-launch Gaussians runs the generic
+ * kernels: the same bytes), 0 <= n <= max_batch per run. */
 int va_pipeline_run(va_pipeline_t *p, const void *frames_dev, int n, void *filtered_out_dev,
                     uint8_t *mask_out_dev, int32_t *labels_out_dev, int32_t *counts_out_dev,
                     int64_t *stats_out_dev, void *stream);

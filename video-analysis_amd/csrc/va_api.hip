@@ -756,7 +756,9 @@ int va_guo_hall_thinning_u8(const uint8_t *src, void *scratch, size_t scratch_by
                             int32_t *stats_out, void *stream)
 {
     VA_ENTER();
-    VA_REQUIRE(n >= 0 && n <= 65535 && h > 0 && w > 0, "va_guo_hall_thinning_u8: bad shape (%d, %d, %d)", n, h, w);
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_guo_hall_thinning_u8: bad shape (%d, %d, %d)", n, h, w);
+    VA_REQUIRE(n <= kMaxGridYZ, "va_guo_hall_thinning_u8: %d frames, at most 65535 frames in one call are supported",
+               n);
     VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels,
                "va_guo_hall_thinning_u8: frames above 2^29 pixels are not supported");
     // grid.y = ceil(h / (64 - 2 K)) <= 65535 for every K, and the pack / unpack grids count words in 32 bits

@@ -2411,6 +2411,21 @@ int launch_invert_bits(const uint32_t *bits, uint32_t *inv, int n, int h, int w,
     return VA_OK;
 }
 
+// the frame index of edge_labels_kernel is gridDim.y, which holds at most 65535: longer batches go out in pieces
+// (frames are independent; every piece starts at its own frame's labels and edge words)
+static int launch_edge_labels(const int32_t *bg_labels, uint32_t *edge_bits, int n, int h, int w, int ew,
+                              hipStream_t st)
+{
+    const unsigned gx = (unsigned)cdiv(2ll * (w + h), kBlock);
+    for (int f0 = 0; f0 < n; f0 += kMaxGridYZ) {
+        const int k = n - f0 < kMaxGridYZ ? n - f0 : kMaxGridYZ;
+        edge_labels_kernel<<<dim3(gx, (unsigned)k), kBlock, 0, st>>>(bg_labels + (size_t)f0 * h * w,
+                                                                     edge_bits + (size_t)f0 * ew, h, w, ew);
+        VA_LAUNCH_CHECK("edge_labels_kernel");
+    }
+    return VA_OK;
+}
+
 int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
                                   uint32_t *edge_bits, int n, int h, int w, unsigned long long *keys,
                                   int32_t *p1, hipStream_t st)
@@ -2422,8 +2437,9 @@ int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, c
     const size_t total_rows = (size_t)n * h;
     VA_HIP(hipMemsetAsync(keys, 0, 2 * sizeof(unsigned long long) * n, st));
     VA_HIP(hipMemsetAsync(edge_bits, 0, sizeof(uint32_t) * ew * (size_t)n, st));
-    edge_labels_kernel<<<dim3(cdiv(2ll * (w + h), kBlock), n), kBlock, 0, st>>>(bg_labels, edge_bits, h, w, ew);
-    VA_LAUNCH_CHECK("edge_labels_kernel");
+    int rc = launch_edge_labels(bg_labels, edge_bits, n, h, w, ew, st);
+    if (rc)
+        return rc;
     const int sgrid = cdiv((long long)total_rows, 32);
     contour_perimeters_kernel<0><<<sgrid, 256, 0, st>>>(bits, forest, bg_labels, edge_bits, ew, keys, keys + n, h,
                                                          w, w32, total_rows);
@@ -2453,8 +2469,9 @@ int launch_find_contours(const uint32_t *bits, const int32_t *forest, const int3
     long long *frame_pts = (long long *)s.frame_pts, *pt_first = (long long *)s.pt_first;
     int2 *starts = (int2 *)s.starts;
     VA_HIP(hipMemsetAsync(s.edge_bits, 0, sizeof(uint32_t) * ew * (size_t)n, st));
-    edge_labels_kernel<<<dim3(cdiv(2ll * (w + h), kBlock), n), kBlock, 0, st>>>(bg_labels, s.edge_bits, h, w, ew);
-    VA_LAUNCH_CHECK("edge_labels_kernel");
+    int rc = launch_edge_labels(bg_labels, s.edge_bits, n, h, w, ew, st);
+    if (rc)
+        return rc;
     const int sgrid = cdiv((long long)total_rows, kSparseRowsPerBlock);
     contour_cell_count_kernel<<<sgrid, kBlock, 0, st>>>(bits, forest, bg_labels, s.edge_bits, ew, s.cells, h, w, w32,
                                                         total_rows);

@@ -46,6 +46,9 @@ constexpr int kWave = 64;  // CDNA wavefront width
 // largest frame the kernels take: per-frame byte offsets (4-byte labels) travel in the 32-bit
 // fields of raw buffer descriptors / uint32 arithmetic, so h*w*4 must stay below 2^31
 constexpr size_t kMaxFramePixels = (size_t)1 << 29;
+// largest gridDim.y / gridDim.z the library launches: a batch or a frame that would need more goes out in pieces,
+// takes a kernel with a one-dimensional grid, or is refused before anything is enqueued
+constexpr int kMaxGridYZ = 65535;
 
 // Optional per-stage timing with HIP events on the pipeline's own stream (bench.py's roofline
 // numbers come from here).  Events are only recorded, never waited for, inside a run.

@@ -1549,31 +1549,40 @@ int launch_gauss_f32_fused(const float *src, float *dst, float *scratch, const f
     // radii of common integer sigmas: the input-stationary kernel (one workgroup per CU)
     int p2 = is::kP2Max;
     const int Lis = g_f32_row_generic ? 0 : plan_rows_is(h, w, c, r, cus, taps, &p2);
-    bool rows_done = false;
-    if (Lis > 0) {
-        const long long total = (long long)h * rw;
-        const unsigned nwg2 = (unsigned)(((total + Lis - 1) / Lis + 1) / 2), ny = bg ? 1u : (unsigned)n;
-#define VA_ROW_IS_ARGS r, nwg2, ny, src, scratch, bg, bg_out, n_seen, (float)rate, n, h, w, Lis, taps, st
-        if (p2 == 13)
-            rows_done = c == 1 ? launch_row_is<1, 13>(VA_ROW_IS_ARGS) : launch_row_is<3, 13>(VA_ROW_IS_ARGS);
-        else
-            rows_done = c == 1 ? launch_row_is<1, 15>(VA_ROW_IS_ARGS) : launch_row_is<3, 15>(VA_ROW_IS_ARGS);
+    // the plain blur puts the frame index in gridDim.y, which holds at most kMaxGridYZ: a longer batch goes out in
+    // pieces (frames are independent).  With a background the frames are a loop inside one workgroup: one piece.
+    const size_t fstride = (size_t)h * rw;
+    const int piece = bg ? n : kMaxGridYZ;
+    for (int a = 0; a < n; a += piece) {
+        const int k = n - a < piece ? n - a : piece;
+        const float *src_a = src + (size_t)a * fstride;
+        float *tmp_a = scratch + (size_t)a * fstride;
+        bool rows_done = false;
+        if (Lis > 0) {
+            const long long total = (long long)h * rw;
+            const unsigned nwg2 = (unsigned)(((total + Lis - 1) / Lis + 1) / 2), ny = bg ? 1u : (unsigned)k;
+#define VA_ROW_IS_ARGS r, nwg2, ny, src_a, tmp_a, bg, bg_out, n_seen, (float)rate, k, h, w, Lis, taps, st
+            if (p2 == 13)
+                rows_done = c == 1 ? launch_row_is<1, 13>(VA_ROW_IS_ARGS) : launch_row_is<3, 13>(VA_ROW_IS_ARGS);
+            else
+                rows_done = c == 1 ? launch_row_is<1, 15>(VA_ROW_IS_ARGS) : launch_row_is<3, 15>(VA_ROW_IS_ARGS);
 #undef VA_ROW_IS_ARGS
+        }
+        if (rows_done) {
+        } else if (bg) {
+            if (c == 1)
+                ema_row_f32_kernel<1, true><<<nwg, 2 * kT, lds1, st>>>(src_a, tmp_a, bg, bg_out, n_seen, (float)rate, k, h, w, plan.L, taps);
+            else
+                ema_row_f32_kernel<3, true><<<nwg, 2 * kT, lds1, st>>>(src_a, tmp_a, bg, bg_out, n_seen, (float)rate, k, h, w, plan.L, taps);
+        } else {
+            const dim3 grid((unsigned)nwg, (unsigned)k);
+            if (c == 1)
+                ema_row_f32_kernel<1, false><<<grid, 2 * kT, lds1, st>>>(src_a, tmp_a, nullptr, nullptr, 0, 0.f, k, h, w, plan.L, taps);
+            else
+                ema_row_f32_kernel<3, false><<<grid, 2 * kT, lds1, st>>>(src_a, tmp_a, nullptr, nullptr, 0, 0.f, k, h, w, plan.L, taps);
+        }
+        VA_LAUNCH_CHECK("ema_row_f32_kernel");
     }
-    if (rows_done) {
-    } else if (bg) {
-        if (c == 1)
-            ema_row_f32_kernel<1, true><<<nwg, 2 * kT, lds1, st>>>(src, scratch, bg, bg_out, n_seen, (float)rate, n, h, w, plan.L, taps);
-        else
-            ema_row_f32_kernel<3, true><<<nwg, 2 * kT, lds1, st>>>(src, scratch, bg, bg_out, n_seen, (float)rate, n, h, w, plan.L, taps);
-    } else {
-        const dim3 grid((unsigned)nwg, (unsigned)n);
-        if (c == 1)
-            ema_row_f32_kernel<1, false><<<grid, 2 * kT, lds1, st>>>(src, scratch, nullptr, nullptr, 0, 0.f, n, h, w, plan.L, taps);
-        else
-            ema_row_f32_kernel<3, false><<<grid, 2 * kT, lds1, st>>>(src, scratch, nullptr, nullptr, 0, 0.f, n, h, w, plan.L, taps);
-    }
-    VA_LAUNCH_CHECK("ema_row_f32_kernel");
     mark(prof, bg ? "ema_row_f32" : "row_f32", st);
     // radii of integer sigmas: the unrolled 15/16-rows-per-thread kernel (whichever wastes fewer rows
     // in the last step); any other radius: the 8-row kernel with its runtime tap loop
