@@ -634,6 +634,49 @@ int va_warp_affine_u8(const uint8_t *frames_dev, int n_frames, int h, int w, int
                       const int64_t *out_off_dev, const int32_t *tile_prefix_dev, int total_tiles, int64_t total_out,
                       uint8_t *out_dev, int32_t *status_dev, void *stream);
 
+/* ------------------------------------------------------------------ A17 outline queries
+ * replaces  line_string.intersection(ray) and the choice of the nearest point in get_ray_hitpoint,
+ *           video/analysis/regions.py:353-391, once per ray of the angle loops of get_ray_intersections, :395-405,
+ *           and get_farthest_ray_intersection, :409-426, and
+ *           Polygon.contains (shapely's contains), video/analysis/shapes.py:552-554
+ * The definition is pinned in DESIGN.md §9, "Outline queries".  All arithmetic is float64, every product, sum and
+ * quotient rounded on its own.  Outlines: m of them in one packed buffer, points_dev[npoints][2] float64 (x, y);
+ * outline o owns points point_off_dev[o] .. point_off_dev[o + 1] - 1 (int64, m + 1 entries, ascending).  Query k
+ * names its outline in index_dev[k] (int32).  A group of `lanes` lanes takes one query and strides over the
+ * outline's edges: lanes = 8 or 64, or 0 for the library's choice (64 when the outlines hold
+ * VA_OUTLINE_WIDE_MIN_POINTS points or more on average, else 8); anything else is VA_ERR_INVALID.  Both widths
+ * write identical bytes.  Limits: an outline of at most 2^31 - 2 points; at most (2^31 - 1) * 256 / lanes
+ * queries (more: VA_ERR_INVALID).  A query whose index is outside 0 .. m - 1, whose outline's offsets are not
+ * inside 0 .. npoints in order, or whose outline has more points, is refused: it reads nothing else and writes
+ * the refused markers below; the other queries run.  q == 0 or m == 0 enqueues nothing and returns VA_OK; a NULL
+ * pointer with q > 0 is VA_ERR_INVALID.  Each call enqueues one kernel on `stream`, copies nothing and needs no
+ * workspace. */
+#define VA_OUTLINE_WIDE_MIN_POINTS 384
+/* q rays.  Ray k runs from A = anchors_dev[k] to F = fars_dev[k] (float64 (x, y) each), d = F - A.  Edge i of its
+ * outline runs from P = point i to Q = point i + 1; closed_dev[o] != 0 adds the edge from the last point to the
+ * first.  With e = Q - P and w = P - A:
+ *   den = d.x e.y - d.y e.x   tn = w.x e.y - w.y e.x   un = w.x d.y - w.y d.x   t = tn / den   u = un / den
+ * and edge i is hit iff den != 0, 0 <= t <= 1 and 0 <= u <= 1 (a NaN fails; -0.0 passes).  The ray's hit is the
+ * hitting edge with the smallest pair (t, i), -0.0 and +0.0 being equal:
+ *   t_out_dev[k] = its t, hits_out_dev[k] = (A.x + t d.x, A.y + t d.y), edge_out_dev[k] = i (int32),
+ *   count_out_dev[k] = the number of hitting edges (int32).
+ * Without a hit t and both coordinates are the quiet NaN 0x7FF8000000000000, edge = -1 and count = 0; a refused
+ * query has the same NaNs, edge = -1 and count = -1.  No root and no trigonometric function is evaluated:
+ * distances and the far points of the angle forms are the host's. */
+int va_ray_hits(const double *points_dev, const int64_t *point_off_dev, const uint8_t *closed_dev, int64_t npoints,
+                int m, const double *anchors_dev, const double *fars_dev, const int32_t *index_dev, int64_t q,
+                int lanes, double *t_out_dev, double *hits_out_dev, int32_t *edge_out_dev, int32_t *count_out_dev,
+                void *stream);
+/* q points.  Point k is X = query_dev[k] (float64 (x, y)); its outline is a ring, always closed.  For every edge
+ * P -> Q, c = (Q.x - P.x)(X.y - P.y) - (Q.y - P.y)(X.x - P.x).  If c == 0 and X lies in the edge's coordinate box
+ * (comparisons that a NaN fails), X is on the boundary and the result is 0.  Otherwise the edge toggles the
+ * answer iff (P.y > X.y) != (Q.y > X.y) and (c > 0 if Q.y > P.y, else c < 0).  inside_out_dev[k] (uint8) = 1 iff
+ * no edge reported the boundary and the number of toggles is odd, else 0; a ring of fewer than three points and a
+ * non-finite point give 0; a refused query gives 2. */
+int va_points_in_outlines(const double *points_dev, const int64_t *point_off_dev, int64_t npoints, int m,
+                          const double *query_dev, const int32_t *index_dev, int64_t q, int lanes,
+                          uint8_t *inside_out_dev, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

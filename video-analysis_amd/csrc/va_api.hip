@@ -1007,6 +1007,47 @@ int va_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t
                                  cap_edges, points, cap_points, workspace, as_stream(stream));
 }
 
+// ------------------------------------------------------------------------------ outline queries
+// the arguments the two outline calls share; `lanes` comes back as 8 or 64.  q == 0 and m == 0 are the caller's
+static int outline_check(const char *name, int64_t npoints, int m, int64_t q, int &lanes)
+{
+    VA_REQUIRE(npoints >= 0 && m >= 0 && q >= 0, "%s: negative count (npoints %lld, m %d, q %lld)", name,
+               (long long)npoints, m, (long long)q);
+    VA_REQUIRE(lanes == 0 || lanes == 8 || lanes == 64, "%s: lanes is 0 (the library's choice), 8 or 64, got %d", name,
+               lanes);
+    if (lanes == 0)
+        lanes = m > 0 && npoints / m >= VA_OUTLINE_WIDE_MIN_POINTS ? 64 : 8;
+    VA_REQUIRE(q <= (int64_t)0x7FFFFFFF * (256 / lanes), "%s: %lld queries are more than one launch of %d lanes takes",
+               name, (long long)q, lanes);
+    return VA_OK;
+}
+
+int va_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
+                const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes, double *t_out,
+                double *hits_out, int32_t *edge_out, int32_t *count_out, void *stream)
+{
+    VA_ENTER();
+    int rc = outline_check("va_ray_hits", npoints, m, q, lanes);
+    if (rc || q == 0 || m == 0)
+        return rc;
+    VA_REQUIRE(points && point_off && closed && anchors && fars && index && t_out && hits_out && edge_out && count_out,
+               "va_ray_hits: NULL argument");
+    return launch_ray_hits(points, point_off, closed, npoints, m, anchors, fars, index, q, lanes, t_out, hits_out,
+                           edge_out, count_out, as_stream(stream));
+}
+
+int va_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *query,
+                          const int32_t *index, int64_t q, int lanes, uint8_t *inside_out, void *stream)
+{
+    VA_ENTER();
+    int rc = outline_check("va_points_in_outlines", npoints, m, q, lanes);
+    if (rc || q == 0 || m == 0)
+        return rc;
+    VA_REQUIRE(points && point_off && query && index && inside_out, "va_points_in_outlines: NULL argument");
+    return launch_points_in_outlines(points, point_off, npoints, m, query, index, q, lanes, inside_out,
+                                     as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited

@@ -445,6 +445,14 @@ int launch_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, con
                           const double *mats, const int32_t *shapes, const int32_t *flags, const int64_t *out_off,
                           const int32_t *prefix, int total_tiles, int64_t total_out, uint8_t *out, int32_t *status,
                           hipStream_t st);
+// outline queries (va_outline.hip): q rays, or q points, each against one of m packed float64 outlines, a group of
+// `lanes` (8 or 64) lanes per query; one launch, no workspace
+int launch_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
+                    const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes,
+                    double *t_out, double *hits_out, int32_t *edge_out, int32_t *count_out, hipStream_t st);
+int launch_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m,
+                              const double *query, const int32_t *index, int64_t q, int lanes, uint8_t *inside_out,
+                              hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

@@ -4,7 +4,9 @@ Reference: video/analysis/regions.py -- corners_to_rect :23-29, rect_to_corners 
 rect_to_slices :49-53, get_overlapping_slices :57-110, find_bounding_box :113-149,
 expand_rectangle :153-155, get_largest_region :159-174, triangle_area :430-451,
 make_distance_map :455-509, shortest_path_in_distance_map :513-565, get_farthest_points :568-611,
-get_external_contour :201-232 (and every cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) list: find_contours).
+get_external_contour :201-232 (and every cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) list: find_contours),
+get_ray_hitpoint :353-391, get_ray_intersections :395-405, get_farthest_ray_intersection :409-426 (GPU; batched:
+ray_hits, ray_fans).
 """
 import numpy as np
 
@@ -245,3 +247,99 @@ def get_farthest_points(mask, p1=None, ret_path=False):
     if p1 is not None and rounds[0] == 1:     # never replaced: the caller's own start, as given
         return (int(p1[0]), int(p1[1])), (int(b[0]), int(b[1]))
     return (int(a[0]), int(a[1])), (int(b[0]), int(b[1]))
+
+
+# ------------------------------------------------------------------------------------------ rays onto outlines
+def _outline(shape):
+    """(points (n, 2) float64, closed) of an outline argument ("Outline queries"): one of our Polygons
+    is its contour, closed; an object with .coords is np.asarray(obj.coords), as given; anything else is an (N, 2)
+    array-like, an open line string as given"""
+    from .shapes import Polygon
+    if isinstance(shape, Polygon):
+        return shape.contour, True
+    if hasattr(shape, "coords"):
+        shape = shape.coords
+    pts = np.asarray(shape, np.float64)
+    return (pts.reshape(0, 2) if pts.size == 0 else pts), False
+
+
+def _hit_distances(hits, anchors):
+    """the pinned distance sqrt(dx dx + dy dy) of hit points from their anchors (NaN rows stay NaN)"""
+    with np.errstate(all="ignore"):
+        dx, dy = hits[:, 0] - anchors[:, 0], hits[:, 1] - anchors[:, 1]
+        return np.sqrt(dx * dx + dy * dy)
+
+
+def _far_points(anchor, angles, ray_length):
+    """the reference's far point of every angle, evaluated angle by angle as its loop does (:401-402)"""
+    return [(anchor[0] + ray_length * np.cos(angle), anchor[1] + ray_length * np.sin(angle)) for angle in angles]
+
+
+def ray_hits(outlines, anchors, fars, index=None):
+    """get_ray_hitpoint for q rays onto many outlines in one launch.  outlines: a list of outline arguments (see
+    get_ray_hitpoint); anchors, fars: (q, 2); index: the outline of each ray (None: the one outline for all rays,
+    else ray k onto outline k, which needs as many rays as outlines).  Returns (hits (q, 2) float64 with NaN rows
+    for the rays that hit nothing, distances (q,) float64, NaN likewise, edges (q,) int32, -1 likewise)."""
+    from .. import ops
+    pts, closed = zip(*[_outline(o) for o in outlines]) if len(outlines) else ((), ())
+    a = np.asarray(anchors, np.float64).reshape(-1, 2)
+    _, hits, edge, _ = ops.ray_hits(list(pts), list(closed), a, fars, index)
+    return hits, _hit_distances(hits, a), edge
+
+
+def ray_fans(outlines, anchors, angles, ray_length=1000):
+    """get_ray_intersections for many outlines in one launch: outline k gets the rays from anchors[k] at
+    angles[k] (a list of angles per outline, of any lengths).  Returns one (hits (k, 2), distances (k,)) pair per
+    outline, NaN where a ray hits nothing."""
+    if not len(outlines) == len(anchors) == len(angles):
+        raise ValueError("ray_fans: %d outlines, %d anchors and %d angle lists" % (len(outlines), len(anchors),
+                                                                                  len(angles)))
+    fars = [far for anchor, fan in zip(anchors, angles) for far in _far_points(anchor, fan, ray_length)]
+    counts = [len(fan) for fan in angles]
+    if not fars:
+        return [(np.zeros((0, 2)), np.zeros(0)) for _ in counts]
+    index = np.repeat(np.arange(len(counts)), counts)
+    hits, dist, _ = ray_hits(outlines, np.asarray(anchors, np.float64).reshape(-1, 2)[index], fars, index)
+    cuts = np.cumsum(counts)[:-1]
+    return list(zip(np.split(hits, cuts), np.split(dist, cuts)))
+
+
+def get_ray_hitpoint(point_anchor, point_far, line_string, ret_dist=False):
+    """the point where the ray from point_anchor to point_far first hits the outline line_string, as a tuple of
+    floats, or None; with ret_dist (point, distance) or (None, nan).  Reference: video/analysis/regions.py:353-391;
+    the definition is pinned in DESIGN.md §9, "Outline queries" (the hit of the smallest (t, edge); collinear
+    overlaps do not count).  line_string: an (N, 2) array-like, an open line string as given (a ring repeats its
+    first point); one of our Polygons, its contour closed; or an object with .coords."""
+    hits, dist, edge = ray_hits([line_string], [point_anchor], [point_far])
+    if edge[0] < 0:
+        return (None, np.nan) if ret_dist else None
+    point = (float(hits[0, 0]), float(hits[0, 1]))
+    return (point, float(dist[0])) if ret_dist else point
+
+
+def _ray_fan(point_anchor, angles, polygon, ray_length):
+    """(hit point or None, distance) per angle: one launch, none without angles"""
+    fars = _far_points(point_anchor, angles, ray_length)
+    if not fars:
+        return [], []
+    hits, dist, edge = ray_hits([polygon], [point_anchor] * len(fars), fars)
+    points = [(float(h[0]), float(h[1])) if e >= 0 else None for h, e in zip(hits, edge)]
+    return points, dist.tolist()
+
+
+def get_ray_intersections(point_anchor, angles, polygon, ray_length=1000):
+    """the hit point (or None) of a ray from point_anchor at every angle, of length ray_length; one launch for the
+    whole fan (reference: video/analysis/regions.py:395-405)"""
+    return _ray_fan(point_anchor, angles, polygon, ray_length)[0]
+
+
+def get_farthest_ray_intersection(point_anchor, angles, polygon, ray_length=1000):
+    """(hit point, its distance from point_anchor, its angle) of the farthest hit of the fan, (None, 0, None)
+    without one; a later ray replaces the best only on a strictly larger distance (reference:
+    video/analysis/regions.py:409-426)"""
+    points, dists = _ray_fan(point_anchor, angles, polygon, ray_length)
+    point_max, dist_max, angle_max = None, 0, None
+    for point, dist, angle in zip(points, dists, angles):
+        if dist > dist_max:
+            point_max, dist_max, angle_max = point, dist, angle
+    return point_max, dist_max, angle_max

@@ -162,6 +162,15 @@ class Polygon(object):
         c = self.contour
         return Rectangle.from_points((c[:, 0].min(), c[:, 1].min()), (c[:, 0].max(), c[:, 1].max()))
 
+    def contains(self, point):
+        """whether the point (x, y) lies strictly inside the polygon (reference :552-554, shapely's contains; the
+        definition is pinned in DESIGN.md §9, "Outline queries": the boundary is outside)"""
+        return bool(contains_points([self], [point])[0])
+
+    def contains_points(self, points):
+        """contains for (q, 2) points in one launch: a (q,) bool array"""
+        return contains_points([self], points)
+
     def get_bounding_rect(self, margin=0):
         """ returns the bounding rectangle of the polygon, (x, y, width, height) truncated to integers """
         bound_rect = self.bounds
@@ -309,6 +318,16 @@ def smooth_centerline(points, spacing=10, skip_length=90):
 
 
 # ---------------------------------------------------------------------------------------- batched
+def contains_points(polygons, points, index=None):
+    """Polygon.contains for many points and polygons in one launch.  polygons: Polygons, or (N, 2) rings (closed
+    with the edge from the last point to the first); points: (q, 2); index: the polygon of each point (None: the
+    one polygon for all points, else point k in polygon k, which needs as many points as polygons).  Returns a
+    (q,) bool array."""
+    from .. import ops
+    rings = [p.contour if isinstance(p, Polygon) else p for p in polygons]
+    return ops.points_in_outlines(rings, points, index)
+
+
 def get_masks(polygons, margin=0, dtype=np.uint8, ret_offset=False):
     """Polygon.get_mask(margin, dtype) of every polygon of a list, in one fill launch.  uint8 and int32 masks
     are written by the kernel; other dtypes are converted from uint8.  Returns the list of masks, and with

@@ -1623,3 +1623,137 @@ def polygon_skeleton_graphs(contours, boxes, stream=None):
         _check_status(status[:m], "polygon_skeleton_graphs (fill)")
         _check_status(status[m:], "polygon_skeleton_graphs (thinning)")
         return res
+
+
+# ------------------------------------------------------------------------------------ outline queries
+OUTLINE_LANES = {None: 0, "lanes8": 8, "lanes64": 64}
+# implementation=None: 64 lanes a query when the queries of the batch look at this many edges or more on average,
+# else 8 ("Outline queries": between 256 and 512 edges the 64-lane kernel overtakes the 8-lane one)
+OUTLINE_WIDE_MIN_EDGES = 384
+OUTLINE_MAX_POINTS = 2 ** 31 - 2
+
+
+def _pack_outlines(outlines, what):
+    """(points float64 flat, point offsets int64 (m + 1,), points per outline int64 (m,)) of m outlines, each an
+    (n, 2) array-like of any length; one without points may have any empty shape"""
+    arrs = []
+    for k, o in enumerate(outlines):
+        a = np.asarray(o, np.float64)
+        if a.size == 0 and a.ndim <= 2:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s: outline %d has shape %r, not (n, 2)" % (what, k, a.shape))
+        if len(a) > OUTLINE_MAX_POINTS:
+            raise ValueError("%s: outline %d has %d points (at most 2^31 - 2 are supported)" % (what, k, len(a)))
+        arrs.append(a)
+    if not arrs:
+        return np.zeros(1, np.float64), np.zeros(1, np.int64), np.zeros(0, np.int64)
+    flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+    return flat, np.append(offsets, total) // 2, shapes[:, 0].astype(np.int64)
+
+
+def _outline_index(index, m, q, what):
+    """the int32 outline index of q queries over m outlines, checked"""
+    if index is None:
+        if m == 1:
+            return np.zeros(q, np.int32)
+        if q != m:
+            raise ValueError("%s: without an index, %d outlines need %d queries, one each in order (got %d)"
+                             % (what, m, m, q))
+        return np.arange(m, dtype=np.int32)
+    idx = np.asarray(index, np.int64).reshape(-1)
+    if len(idx) != q:
+        raise ValueError("%s: %d index entries for %d queries" % (what, len(idx), q))
+    if np.any(idx < 0) or np.any(idx >= m):
+        raise ValueError("%s: index must lie in 0 .. %d" % (what, m - 1))
+    return idx.astype(np.int32)
+
+
+def _outline_lanes(edges, implementation, what):
+    """the lanes a query gets in the batch's one launch: those of a named implementation, or for None the rule over
+    the edge counts the batch's queries look at: 64 from a mean of OUTLINE_WIDE_MIN_EDGES on, else 8"""
+    if implementation not in OUTLINE_LANES:
+        raise ValueError("%s: implementation is None, 'lanes8' or 'lanes64', got %r" % (what, implementation))
+    if implementation is not None:
+        return OUTLINE_LANES[implementation]
+    return 64 if len(edges) and edges.mean() >= OUTLINE_WIDE_MIN_EDGES else 8
+
+
+def _query_points(points, what, name):
+    p = np.asarray(points, np.float64)
+    if p.size == 0 and p.ndim <= 2:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("%s: %s has shape %r, not (q, 2)" % (what, name, p.shape))
+    return p
+
+
+def ray_hits(outlines, closed, anchors, fars, index=None, implementation=None, stream=None):
+    """where q rays first hit their outlines (get_ray_hitpoint, video/analysis/regions.py:353-391, for every ray of
+    a batch; DESIGN.md §9, "Outline queries").  outlines: a list of m (n, 2) array-likes of (x, y) points of any
+    lengths, 0 and 1 included, converted to float64; closed: m flags, a true one adds the edge from the last point
+    to the first; anchors, fars: (q, 2), ray k runs from anchors[k] to fars[k]; index: (q,) the outline of each
+    ray.  index=None means the one outline for every ray when m == 1, else ray k onto outline k, which needs
+    q == m.  implementation: None (by the mean edge count of the batch's queries, OUTLINE_WIDE_MIN_EDGES),
+    'lanes8' or 'lanes64'; one launch, and all give the same bytes.  Returns (t (q,) float64, hits (q, 2) float64, edge (q,)
+    int32, count (q,) int32): the hitting edge with the smallest (t, edge), the hit point anchor + t (far - anchor)
+    and the number of hitting edges; without a hit t and the point are NaN, edge is -1 and count 0.  A bad index or
+    outline raises ValueError before anything is launched; a query the device refuses raises RuntimeError."""
+    what = "ray_hits"
+    flat, point_off, npts = _pack_outlines(outlines, what)
+    m = len(npts)
+    flags = np.asarray(closed, bool).reshape(-1)
+    if len(flags) != m:
+        raise ValueError("%s: %d closed flags for %d outlines" % (what, len(flags), m))
+    a, f = _query_points(anchors, what, "anchors"), _query_points(fars, what, "fars")
+    q = len(a)
+    if len(f) != q:
+        raise ValueError("%s: %d anchors and %d far points" % (what, q, len(f)))
+    idx = _outline_index(index, m, q, what)
+    edges = np.where(npts == 0, 0, np.where(flags, npts, npts - 1))[idx] if q else np.zeros(0, np.int64)
+    lanes = _outline_lanes(edges, implementation, what)
+    if q == 0:
+        return np.zeros(0), np.zeros((0, 2)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        pb, ob, cb, ab, fb, ib = (d.upload(flat), d.upload(point_off), d.upload(flags.astype(np.uint8)), d.upload(a),
+                                  d.upload(f), d.upload(idx))
+        out = d.take(32 * q)                   # t | hits | edge | count: one download
+        check(L.va_ray_hits(pb.ptr, ob.ptr, cb.ptr, int(point_off[-1]), m, ab.ptr, fb.ptr, ib.ptr, q, lanes, out.ptr,
+                            out.ptr + 8 * q, out.ptr + 24 * q, out.ptr + 28 * q, stream))
+        raw = out.download((32 * q,), np.uint8, stream)
+    t, hits = raw[:8 * q].view(np.float64), raw[8 * q:24 * q].view(np.float64).reshape(q, 2)
+    edge, count = raw[24 * q:28 * q].view(np.int32), raw[28 * q:].view(np.int32)
+    bad = np.flatnonzero(count < 0)
+    if len(bad):
+        raise RuntimeError("%s: the device refused ray %d" % (what, bad[0]))
+    return t.copy(), hits.copy(), edge.copy(), count.copy()
+
+
+def points_in_outlines(outlines, points, index=None, implementation=None, stream=None):
+    """whether q points lie inside their rings (Polygon.contains, video/analysis/shapes.py:552-554, for a batch;
+    DESIGN.md §9, "Outline queries").  outlines: a list of m (n, 2) array-likes of any lengths, converted to
+    float64, each closed with the edge from its last point to its first; points: (q, 2); index: (q,) the ring of
+    each point.  index=None means the one ring for every point when m == 1, else point k in ring k, which needs
+    q == m.  implementation as ray_hits takes it.  Returns (q,) bool: True strictly inside; the boundary, a ring of
+    fewer than three points and a non-finite point give False.  A bad index or outline raises ValueError before
+    anything is launched; a query the device refuses raises RuntimeError."""
+    what = "points_in_outlines"
+    flat, point_off, npts = _pack_outlines(outlines, what)
+    m = len(npts)
+    p = _query_points(points, what, "points")
+    q = len(p)
+    idx = _outline_index(index, m, q, what)
+    lanes = _outline_lanes(npts[idx] if q else np.zeros(0, np.int64), implementation, what)
+    if q == 0:
+        return np.zeros(0, bool)
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        pb, ob, xb, ib = d.upload(flat), d.upload(point_off), d.upload(p), d.upload(idx)
+        out = d.take(q)
+        check(L.va_points_in_outlines(pb.ptr, ob.ptr, int(point_off[-1]), m, xb.ptr, ib.ptr, q, lanes, out.ptr, stream))
+        inside = out.download((q,), np.uint8, stream)
+    bad = np.flatnonzero(inside > 1)
+    if len(bad):
+        raise RuntimeError("%s: the device refused point %d" % (what, bad[0]))
+    return inside != 0
