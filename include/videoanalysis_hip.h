@@ -677,6 +677,40 @@ int va_points_in_outlines(const double *points_dev, const int64_t *point_off_dev
                           const double *query_dev, const int32_t *index_dev, int64_t q, int lanes,
                           uint8_t *inside_out_dev, void *stream);
 
+/* ------------------------------------------------------------------ A18 equidistant curves
+ * replaces  make_curve_equidistant, video/analysis/curves.py:103-148, once per curve: the three calls per polygon
+ *           of Polygon.get_centerline_optimized, video/analysis/shapes.py:727-757, and the one per curve of
+ *           ActiveContour.find_contour, video/analysis/active_contour.py
+ * The definition is pinned in DESIGN.md §9, "Equidistant curves".  Curves: m of them in one packed buffer,
+ * points_dev[npoints][2] float64 (x, y); curve k owns points point_off_dev[k] .. point_off_dev[k + 1] - 1 (int64,
+ * m + 1 entries, ascending).  spacing_dev[k] (float64) > 0: the curve is walked and a point dropped every
+ * L / rint(L / spacing) of its float32-rule length L (L < spacing: the result is the input); spacing_dev[k] == 0:
+ * count_dev[k] (int32, >= 1) points at equal arc length (count_dev is read only for such curves, and may be NULL
+ * when there are none).  translate_dev: NULL, or (tx, ty) float64 per curve, added to every coordinate of the
+ * result, one rounded add each.
+ * Three launches on `stream`, one lane per curve, nothing copied, no workspace:
+ *   out_count_dev[k] (int32)   the number of points of curve k's result
+ *   out_off_dev[k]   (int64, m + 1 entries)  its first slot in out_points_dev; out_off_dev[m] = the total
+ *   in_length_dev[k] (float64) L in spacing mode, the arc total s[-1] in count mode
+ *   status_dev[k]    (int32)   VA_OK, or VA_ERR_RANGE for a curve that is not run: fewer than 2 or more than
+ *                    VA_CURVES_MAX_POINTS points, offsets out of order or outside 0 .. npoints, a negative or NaN
+ *                    spacing, a count < 1, rint(L / spacing) above VA_CURVES_MAX_STEPS, or a walk that drops more
+ *                    than 2 rint(L / spacing) + n + 2 points; such a curve has count 0 and lengths 0
+ *   totals_dev[0]    (int64)   the total number of points
+ *   out_points_dev[cap_points][2] (float64)  the results, curve after curve, written only when the total is at
+ *                    most cap_points: a caller that reads a larger total runs again with that much room
+ *   out_length_dev[k] (float64) the float32-rule length (cv2.arcLength of the float32 casts) of what was written
+ *                    for curve k, 0 when nothing was
+ * Two runs write identical bytes.  m == 0 enqueues nothing; a NULL pointer with m > 0 (translate_dev and, without
+ * a count-mode curve, count_dev apart), a negative count or capacity and a misaligned pointer are VA_ERR_INVALID. */
+#define VA_CURVES_MAX_POINTS (1 << 24)
+#define VA_CURVES_MAX_STEPS (1 << 20)
+int va_curves_equidistant(const double *points_dev, const int64_t *point_off_dev, int64_t npoints, int m,
+                          const double *spacing_dev, const int32_t *count_dev, const double *translate_dev,
+                          int32_t *out_count_dev, int64_t *out_off_dev, double *in_length_dev, int32_t *status_dev,
+                          int64_t *totals_dev, double *out_points_dev, int64_t cap_points, double *out_length_dev,
+                          void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

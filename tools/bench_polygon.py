@@ -44,6 +44,7 @@ ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
 ap.add_argument("--only-optimized", action="store_true", help="run the optimized_batch leg alone")
 ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polygon_bench.jsonl"))
+ap.add_argument("--tag", default="", help="written into every row as \"tree\": which tree or commit was measured")
 args = ap.parse_args()
 
 
@@ -364,4 +365,6 @@ if not args.no_cpu and not args.only_optimized:
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "a") as f:
     for row in rows:
+        if args.tag:
+            row["tree"] = args.tag
         f.write(json.dumps(row) + "\n")

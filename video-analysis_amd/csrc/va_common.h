@@ -453,6 +453,12 @@ int launch_ray_hits(const double *points, const int64_t *point_off, const uint8_
 int launch_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m,
                               const double *query, const int32_t *index, int64_t q, int lanes, uint8_t *inside_out,
                               hipStream_t st);
+// equidistant curves (va_curves.hip): va_curves_equidistant's outputs from three launches, one lane per curve
+int launch_curves_equidistant(const double *points, const int64_t *point_off, int64_t npoints, int m,
+                              const double *spacing, const int32_t *count, const double *translate,
+                              int32_t *out_count, int64_t *out_off, double *in_length, int32_t *status,
+                              int64_t *totals, double *out_points, int64_t cap_points, double *out_length,
+                              hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

@@ -4,8 +4,10 @@ video/analysis/active_contour.py).
 set_potential blurs the potential and takes both 5-tap Sobel gradients on the GPU, and keeps the two
 float64 planes there; find_contours runs every iteration of every contour of a call in one kernel launch
 (va_snake.hip).  The potential is one image, a stack of equal-sized frames, or a list of images of different
-shapes (the distance maps of many polygons), which is kept as one ragged buffer (va_gradients.hip).  The host keeps the per-contour preparation: equidistant points, the point spacing, the
-evolution matrix (NumPy, the reference's formula and np.linalg.inv, cached by (N, ds)) and the anchors.
+shapes (the distance maps of many polygons), which is kept as one ragged buffer (va_gradients.hip).  The
+equidistant points and the point spacing of all contours of a call come from one batched resampling
+(curves.resample_many); the host keeps the rest of the per-contour preparation: the evolution matrix (NumPy,
+the reference's formula and np.linalg.inv, cached by (N, ds)) and the anchors.
 
 Arithmetic ("Active contours"): the forces, the update and the clip are the reference's; the
 matrix-vector product sums in ascending column order, where the reference's np.dot goes through BLAS in an
@@ -214,7 +216,7 @@ class ActiveContour(object):
         per curve, each as find_contour takes it.  Returns a list of (N, 2) point arrays and sets
         info['iteration_count'] and info['total_variation'] to arrays with one entry per curve (0 for
         curves of two points or fewer, which come back equidistant and untouched) """
-        from .. import ops
+        from .. import _hip, ops
         if self._grad is None:
             raise RuntimeError('Potential must be set before the contour can be adapted.')
         fxb, fyb, shape = self._grad
@@ -226,12 +228,27 @@ class ActiveContour(object):
         if not len(frames) == len(anchor_x) == len(anchor_y) == m:
             raise ValueError("find_contours: frames and anchors need one entry per curve")
 
+        # every curve up to the first bad frame is resampled in one call; the checks then run curve by curve.  If a
+        # curve makes that call raise, each is resampled where the loop reaches it, so that the first failing curve
+        # raises after the checks of the curves before it, as it always did
+        good = next((k for k in range(m) if not 0 <= frames[k] < n), m)
+        inputs = [np.asarray(curves[k]) for k in range(good)]
+        try:
+            resampled, lengths = _curves.resample_many(inputs)
+        except _hip.HipError:                   # the device or the library is missing, or a call failed: an error
+            raise
+        except Exception:
+            resampled = lengths = None
         results, jobs = [], []
         for k in range(m):
             if not 0 <= frames[k] < n:
                 raise IndexError("find_contours: frame %d of a potential of %d frame(s)" % (frames[k], n))
-            curve = np.asarray(curves[k])
-            points = _curves.make_curve_equidistant(curve)
+            curve = inputs[k]
+            if resampled is not None:
+                points, length = resampled[k], float(lengths[k])
+            else:
+                points = _curves.make_curve_equidistant(curve)
+                length = float(_curves.curve_length(points))
             results.append(points)
             if len(points) <= 2:
                 continue
@@ -240,7 +257,7 @@ class ActiveContour(object):
             if len(points) > ops.SNAKE_MAX_POINTS:
                 raise ValueError("find_contours: curve %d has %d points; at most %d are supported"
                                  % (k, len(points), ops.SNAKE_MAX_POINTS))
-            jobs.append((k, points) + self._anchors(curve, points, anchor_x[k], anchor_y[k]))
+            jobs.append((k, points) + self._anchors(curve, points, anchor_x[k], anchor_y[k]) + (length,))
 
         iterations = np.zeros(m, np.int64)
         variation = np.zeros(m, np.float64)
@@ -250,13 +267,13 @@ class ActiveContour(object):
             flags = np.zeros((len(jobs), max_points), np.uint8) if any(j[2] is not None for j in jobs) else None
             vals = np.zeros((len(jobs), max_points, 2)) if flags is not None else None
             offsets, mats, where = [], [], {}
-            for r, (k, points, f, v) in enumerate(jobs):
+            for r, (k, points, f, v, length) in enumerate(jobs):
                 N = len(points)
                 pts[r, :N] = points
                 if f is not None:
                     flags[r, :N] = f
                     vals[r, :N] = v
-                ds = _curves.curve_length(points) / (N - 1)
+                ds = length / (N - 1)
                 key = (N, ds)
                 if key not in where:             # contours of equal (N, ds) share one matrix
                     where[key] = sum(a.size for a in mats)
@@ -269,7 +286,7 @@ class ActiveContour(object):
                 self.max_iterations)
             if np.any(its < 0):
                 raise RuntimeError("find_contours: the snake kernel refused a contour")
-            for r, (k, points, f, v) in enumerate(jobs):
+            for r, (k, points, f, v, length) in enumerate(jobs):
                 results[k] = out[r, :len(points)].copy()
                 iterations[k] = its[r]
                 variation[k] = tvs[r]

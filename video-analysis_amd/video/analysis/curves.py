@@ -1,6 +1,8 @@
 """Curve helpers that ActiveContour needs (reference: video/analysis/curves.py).
 
-Host NumPy: these run on at most a few hundred points per curve.  `curve_length` restates
+Host NumPy: these run on at most a few hundred points per curve.  The one batched exception is the equidistant
+resampling: make_curves_equidistant resamples many curves in one device call (ops.curves_equidistant, DESIGN.md §9,
+"Equidistant curves"), with the bits of make_curve_equidistant.  `curve_length` restates
 cv2.arcLength(float32 points, closed=False) (curves.py:66-71) without OpenCV: each segment is a float32
 dx*dx + dy*dy (two rounded products, one rounded sum), its float32 square root, and the roots are added
 in double in point order.  ActiveContour's point spacing -- and with it the evolution matrix and its
@@ -77,6 +79,39 @@ def make_curve_equidistant(points, spacing=None, count=None):
         result = np.transpose((np.interp(sp, s, points[:, 0]), np.interp(sp, s, points[:, 1])))
 
     return result
+
+
+def resample_many(curves, spacing=None, count=None, offsets=None):
+    """make_curve_equidistant(curve, spacing, count) of every curve of a list, then translate_points by its entry
+    of `offsets` (None: no translation): (list of (K, 2) float64 arrays, (m,) float64 curve_length of each).  This
+    is where the batched callers choose: one device call (ops.curves_equidistant) from ops.CURVES_DEVICE_MIN_BATCH
+    curves on, provided the host's np.linalg.norm is the form the device is pinned to (ops.host_norm_is_pinned);
+    else the per-curve loop on the host.  The results are the same bits either way.  spacing: None or one positive
+    finite number (anything else is a ValueError); count: None, one integer or one per curve."""
+    from .. import ops
+    curves = list(curves)
+    m = len(curves)
+    if spacing is not None and not (spacing > 0 and math.isfinite(spacing)):
+        raise ValueError("make_curves_equidistant: spacing must be a positive finite number, got %r" % (spacing,))
+    if m >= ops.CURVES_DEVICE_MIN_BATCH and ops.host_norm_is_pinned():
+        return ops.curves_equidistant(curves, spacing, count, offsets, ret_lengths=True)
+    counts = [count] * m if count is None or np.ndim(count) == 0 else list(count)
+    if len(counts) != m:
+        raise ValueError("make_curves_equidistant: %d count entries for %d curves" % (len(counts), m))
+    results, lengths = [], np.zeros(m, np.float64)
+    for k, curve in enumerate(curves):
+        points = np.asarray(make_curve_equidistant(curve, spacing=spacing, count=counts[k]), np.float64)
+        if offsets is not None:
+            points = translate_points(points, offsets[k][0], offsets[k][1])
+        results.append(points)
+        lengths[k] = curve_length(points)
+    return results, lengths
+
+
+def make_curves_equidistant(curves, spacing=None, count=None):
+    """make_curve_equidistant for every curve of a list, batched on the device: the list of (K, 2) float64 arrays,
+    each with the bits the per-curve function gives.  count may be one integer or one per curve."""
+    return resample_many(curves, spacing, count)[0]
 
 
 def merge_curves(points1, points2):

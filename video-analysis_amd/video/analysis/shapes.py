@@ -477,9 +477,9 @@ def get_centerlines_optimized(polygons, alpha=1e3, beta=1e6, gamma=0.01, spacing
     (margin 1), their distance transforms and the gradients of the blurred maps are computed back to back on the
     device and stay there as ragged planes (ops.centerline_gradients), the estimates come from
     get_centerline_estimates, and one find_contours call runs every snake, both ends anchored, each on its own
-    polygon's planes.  The equidistant resampling and the translations stay on the host.  endpoints: None, or one
-    entry per polygon as get_centerline_estimates takes them.  Returns the list of (K, 2) centre lines, each with
-    the bits the per-polygon method gives."""
+    polygon's planes.  Both equidistant resamplings are batched calls with the translations fused into them
+    (curves.resample_many).  endpoints: None, or one entry per polygon as get_centerline_estimates takes them.
+    Returns the list of (K, 2) float64 centre lines, each with the bits the per-polygon method gives."""
     from .. import ops
     from .active_contour import ActiveContour
     m = len(polygons)
@@ -498,19 +498,17 @@ def get_centerlines_optimized(polygons, alpha=1e3, beta=1e6, gamma=0.01, spacing
     offsets = [(int(r[0]), int(r[1])) for r in rects]
 
     # initialize the centerlines from the estimates, the end points anchored
-    curves, anchors = [], []
-    for points, offset in zip(get_centerline_estimates(polygons, eps), offsets):
-        points = _curves.make_curve_equidistant(points, spacing=spacing)
-        points = _curves.translate_points(points, -offset[0], -offset[1])
+    curves = _curves.resample_many(get_centerline_estimates(polygons, eps), spacing=spacing,
+                                   offsets=[(-x, -y) for x, y in offsets])[0]
+    anchors = []
+    for points in curves:
         anchor = np.zeros(len(points), bool)
         anchor[0] = anchor[-1] = True
-        curves.append(points)
         anchors.append(anchor)
 
     # find the best contours
     found = ac.find_contours(curves, list(range(m)), anchors, anchors)
-    return [_curves.translate_points(_curves.make_curve_equidistant(points, spacing=spacing), *offset)
-            for points, offset in zip(found, offsets)]
+    return _curves.resample_many(found, spacing=spacing, offsets=offsets)[0]
 
 
 def get_centerlines_smoothed(polygons, spacing=10, skip_length=90, **kwargs):

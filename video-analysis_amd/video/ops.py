@@ -1757,3 +1757,154 @@ def points_in_outlines(outlines, points, index=None, implementation=None, stream
     if len(bad):
         raise RuntimeError("%s: the device refused point %d" % (what, bad[0]))
     return inside != 0
+
+
+# ------------------------------------------------------------------------------------ equidistant curves
+CURVES_MAX_POINTS = 1 << 24      # VA_CURVES_MAX_POINTS, VA_CURVES_MAX_STEPS, include/videoanalysis_hip.h
+CURVES_MAX_STEPS = 1 << 20
+CURVES_MAX_COORD = 1e100         # a curve with a larger coordinate (or a non-finite one) is resampled on the host
+# the batched callers (video.analysis.curves.resample_many) go to the device from this many curves on; below it the
+# per-curve Python loop is quicker than a device round trip ("Equidistant curves": the crossover)
+CURVES_DEVICE_MIN_BATCH = 8
+CURVES_ROOM_SLACK = 3            # points a walked curve gets beyond the estimate of its result in the first launch
+
+# (dx, dy, sqrt(fma(dy, dy, dx * dx)), sqrt(dx * dx + dy * dy)): vectors on which the two forms differ
+_NORM_PROBES = (
+    ("0x1.33ef6c3c6472fp-2", "-0x1.b4bf2ef288857p-1", "0x1.cf177153ae392p-1", "0x1.cf177153ae391p-1"),
+    ("-0x1.24dfc42b81355p+1", "-0x1.1fdbb9ed7b8f3p+1", "0x1.9aa7b68af0f63p+1", "0x1.9aa7b68af0f64p+1"),
+    ("-0x1.880492c3cc3d2p+2", "0x1.3a5260ab86f1ap+1", "0x1.a65900c38e989p+2", "0x1.a65900c38e988p+2"),
+    ("0x1.e7d8a19827d10p+1", "-0x1.715a919dda321p+2", "0x1.baa11a0e9e82ep+2", "0x1.baa11a0e9e82dp+2"),
+    ("-0x1.f90c310f4b3b1p-1", "0x1.504291301551cp+2", "0x1.56228c0aa6030p+2", "0x1.56228c0aa602fp+2"),
+    ("0x1.a1fa05313cde3p+1", "-0x1.78034bce8cb5ap+2", "0x1.ae3027468bb1bp+2", "0x1.ae3027468bb1cp+2"),
+)
+_norm_pinned = None
+
+
+def host_norm_is_pinned():
+    """whether this host's np.linalg.norm of a 2-vector is sqrt(fma(dy, dy, dx * dx)), the form the device walk is
+    pinned to (NumPy's dot on a BLAS with FMA); checked once on _NORM_PROBES.  Where it is not, the batched
+    callers keep resampling on the host, so that they still equal the per-curve function on this host."""
+    global _norm_pinned
+    if _norm_pinned is None:
+        _norm_pinned = all(float(np.linalg.norm(np.array([float.fromhex(x), float.fromhex(y)]))) == float.fromhex(fused)
+                           for x, y, fused, _ in _NORM_PROBES)
+    return _norm_pinned
+
+
+def _per_curve(value, m, what, name):
+    """None, one value for every curve, or one per curve: a list of m entries"""
+    if value is None or np.ndim(value) == 0:
+        return [value] * m
+    value = list(value)
+    if len(value) != m:
+        raise ValueError("%s: %d %s entries for %d curves" % (what, len(value), name, m))
+    return value
+
+
+def _curve_on_host(curve, spacing, count, offset):
+    """one curve through the host function, translated: ((K, 2) float64, its float32-rule length)"""
+    from .analysis import curves as _curves
+    res = _curves.make_curve_equidistant(curve, spacing=spacing, count=count)
+    res = np.asarray(res, np.float64)
+    if offset is not None:
+        res = _curves.translate_points(res, offset[0], offset[1])
+    return res, float(_curves.curve_length(res))
+
+
+def curves_equidistant(curves, spacing=None, count=None, offsets=None, ret_lengths=False, stream=None):
+    """curves.make_curve_equidistant (video/analysis/curves.py:103-148) for every curve of a list in one
+    va_curves_equidistant call, bit for bit the per-curve function ("Equidistant curves").  curves: m
+    (n, 2) array-likes of any lengths, converted to float64.  spacing: None, one spacing or one per curve (None
+    entries allowed); a curve with a spacing is walked and a point dropped every L / rint(L / spacing).  A curve
+    without one gets `count` points at equal arc length: count is None (as many as the curve has), one integer or
+    one per curve.  offsets: None or one (xoff, yoff) per curve, added to every coordinate of the result
+    (curves.translate_points).  One packed upload, three launches, one download; the first launch has room for an
+    estimate of the result, a batch that holds more runs exactly once more, with exact room.
+    Curves of fewer than 2 points, with a non-finite coordinate or one beyond CURVES_MAX_COORD, with a count below
+    1, of another shape than (n, 2), and curves the device refuses (VA_CURVES_MAX_STEPS) go through the host
+    function one by one, in order.  A spacing that is not a positive finite number is a ValueError.
+    Returns the list of (K, 2) float64 arrays; ret_lengths appends the (m,) float64 curves.curve_length of each
+    result."""
+    what = "curves_equidistant"
+    curves = list(curves)
+    m = len(curves)
+    spacings, counts = _per_curve(spacing, m, what, "spacing"), _per_curve(count, m, what, "count")
+    for s in spacings:
+        if s is not None and not (s > 0 and math.isfinite(s)):
+            raise ValueError("%s: a spacing must be a positive finite number, got %r" % (what, s))
+    shifts = None
+    if offsets is not None:
+        shifts = np.asarray(offsets, np.float64).reshape(-1, 2)
+        if len(shifts) != m:
+            raise ValueError("%s: %d offsets for %d curves" % (what, len(shifts), m))
+    results, lengths = [None] * m, np.zeros(m, np.float64)
+
+    def on_host(k):
+        results[k], lengths[k] = _curve_on_host(curves[k], spacings[k], counts[k],
+                                                None if shifts is None else shifts[k])
+
+    # what the device takes -- (n, 2) with 2 <= n, finite coordinates within CURVES_MAX_COORD, a count it can hold --
+    # is kept; the rest goes through the host function now, in order
+    dev, arrs = [], []
+    for k in range(m):
+        a = np.asarray(curves[k], np.float64)
+        ct = counts[k]
+        if (a.ndim == 2 and a.shape[1] == 2 and 2 <= len(a) <= CURVES_MAX_POINTS
+                and (spacings[k] is not None or ct is None or 1 <= ct < 2 ** 31)
+                and bool((np.abs(a) <= CURVES_MAX_COORD).all())):                 # (a NaN fails the comparison)
+            dev.append(k)
+            arrs.append(a)
+        else:
+            on_host(k)
+    if dev:
+        md = len(dev)
+        flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+        npts, first = shapes[:, 0].astype(np.int64), np.append(offsets, total) // 2
+        sp = np.array([0.0 if spacings[k] is None else float(spacings[k]) for k in dev])
+        ct = np.array([n if counts[k] is None else int(counts[k]) for k, n in zip(dev, npts)], np.int64)
+        walked = sp > 0
+        # room of the first launch: the counts, and for a walked curve an estimate of its result from the float64
+        # polyline length (the sizes themselves come from the count pass; what the walk may not exceed bounds it)
+        xy = flat.reshape(-1, 2)
+        seg = np.append(np.hypot(*(xy[1:] - xy[:-1]).T), 0.0)
+        seg[first[1:] - 1] = 0.0
+        steps = np.minimum(np.add.reduceat(seg, first[:-1]) * (1 + 1e-5) / np.where(walked, sp, 1.0),
+                           2.0 * CURVES_MAX_STEPS)
+        room = int(np.where(walked, np.maximum(np.floor(steps).astype(np.int64) + CURVES_ROOM_SLACK, npts), ct).sum())
+        # one packed upload: [point offsets | spacings | translations | points | counts]
+        parts = {"off": first.astype(np.int64), "sp": sp,
+                 "tr": np.ascontiguousarray(shifts[dev]).reshape(-1) if shifts is not None else np.zeros(0),
+                 "pts": flat, "ct": np.where(walked, 0, ct).astype(np.int32)}
+        at, nbytes = {}, 0
+        for name, part in parts.items():
+            at[name], nbytes = nbytes, nbytes + part.nbytes
+        packed = np.concatenate([part.view(np.uint8) for part in parts.values()])
+        # one output buffer: [total | out offsets | in lengths | out lengths | counts | status | points]
+        o_total, o_off, o_lin, o_lout = 0, 8, 8 * md + 16, 16 * md + 16
+        o_cnt, o_st, head = 24 * md + 16, 28 * md + 16, 32 * md + 16
+        L = _hip.lib()
+        with _Lease.on(stream) as d:
+            src = d.upload(packed)
+
+            def run(cap):
+                out = d.take(head + 16 * max(cap, 1))
+                check(L.va_curves_equidistant(src.ptr + at["pts"], src.ptr + at["off"], total // 2, md,
+                                              src.ptr + at["sp"], src.ptr + at["ct"],
+                                              src.ptr + at["tr"] if shifts is not None else None,
+                                              out.ptr + o_cnt, out.ptr + o_off, out.ptr + o_lin, out.ptr + o_st,
+                                              out.ptr + o_total, out.ptr + head, cap, out.ptr + o_lout, stream))
+                raw = out.download((head + 16 * max(cap, 1),), np.uint8, stream)
+                return raw, int(raw[:8].view(np.int64)[0])
+            raw, found = run(room)
+            if found > room:                   # nothing was written: exactly once more, with exact room
+                raw, found = run(found)
+        out_off = raw[o_off:o_lin].view(np.int64)
+        out_len = raw[o_lout:o_cnt].view(np.float64)
+        status = raw[o_st:head].view(np.int32)
+        pts = raw[head:head + 16 * found].view(np.float64).reshape(found, 2).copy()
+        for j, k in enumerate(dev):
+            if status[j] != 0:                 # (VA_CURVES_MAX_STEPS: the reference's own walk, as slow as it is)
+                on_host(k)
+            else:
+                results[k], lengths[k] = pts[out_off[j]:out_off[j + 1]], out_len[j]
+    return (results, lengths) if ret_lengths else results
