@@ -711,6 +711,80 @@ int va_curves_equidistant(const double *points_dev, const int64_t *point_off_dev
                           int64_t *totals_dev, double *out_points_dev, int64_t cap_points, double *out_length_dev,
                           void *stream);
 
+/* ------------------------------------------------------------------ A19 composer
+ * replaces  VideoComposer, video/io/composer.py: set_frame's copy of a monochrome frame into a colour video
+ *           (:103-105, :119-123), highlight_mask (:131-154), add_image (:168-186), blend_image (:190-210) by
+ *           va_compose_layers_u8; cv2.drawContours (:236), cv2.polylines (:257), cv2.rectangle (:284) and
+ *           cv2.circle (:298), all with thickness 1 or, for the circle, -1, by va_draw_u8
+ * The definitions are pinned in DESIGN.md §9, "Composer".  Frames are uint8, (n, h, w) or (n, h, w, 3) with RGB
+ * interleaved.
+ *
+ * va_compose_layers_u8: dst frame f = src frame f (c_src channels; a monochrome source is copied into the three
+ * channels of a colour destination) with the layers layer_off_dev[f] .. layer_off_dev[f + 1] - 1 (int64, n + 1
+ * entries) of layers_dev applied in order.  A layer reads an image of image_channels (1, or 3 on a colour
+ * destination; a monochrome image counts for all three channels) at byte image_off of images_dev and, with
+ * mask_off >= 0, a (h, w) uint8 mask at byte mask_off of masks_dev: it changes the pixels whose mask byte is non-zero,
+ * every pixel with mask_off == -1.
+ *   VA_COMPOSE_HIGHLIGHT  v = (uint8) trunc((double) alpha + factor * v) in float64, product and sum rounded
+ *                         separately; on channel `channel` of a colour frame, on all three for channel == -1
+ *                         (alpha: the strength 0 .. 255, factor: (255 - strength) / 255; no image)
+ *   VA_COMPOSE_ADD        v = min(255, v + u)
+ *   VA_COMPOSE_BLEND      v = the float32 alpha * v + beta * u, two rounded products and one rounded sum, rounded
+ *                         to the nearest integer with ties to even and saturated to 0 .. 255
+ * One launch, 16 pixels of a row per lane; src_dev == dst_dev is allowed when c_src == c, and then a frame without
+ * layers is not touched.  A layer whose kind, channels or offsets are not valid for the buffers' sizes is not
+ * applied, and a frame whose layer range leaves the table gets none: nothing outside the buffers is read.
+ * n == 0, h == 0, w == 0, and nlayers == 0 in place enqueue nothing.  c_src, c outside {1, 3}, c_src > c, distinct
+ * pointers required for c_src != c, negative counts, NULL pointers and frames of 2^29 pixels or more are
+ * VA_ERR_INVALID.
+ *
+ * va_draw_u8: the commands cmd_off_dev[f] .. cmd_off_dev[f + 1] - 1 (int64, n + 1 entries) of cmds_dev drawn into
+ * frame f in order, one workgroup per frame: the final value of a pixel is the colour of the last command in list
+ * order that covers it.  Lines are 8-connected (clipLine, then the left-to-right LineIterator), thickness 1, shift 0.
+ *   VA_DRAW_POLYLINE  the points first .. first + count - 1 of points_dev[npoints][2] (int32 x, y): the segments
+ *                     v[i - 1] -> v[i], and v[count - 1] -> v[0] with flags & 1 (closed); a closed polyline of
+ *                     one point is that pixel, an open one and an empty one nothing
+ *   VA_DRAW_CIRCLE    OpenCV's integer Circle around (cx, cy): the outline, or the filled disc with flags & 1;
+ *                     radius 0 is one pixel, a negative radius nothing
+ * color: byte 0 on a monochrome frame, bytes 0, 1, 2 = R, G, B on a colour one.
+ * status_dev[f] (int32): VA_OK, or VA_ERR_RANGE for a frame that is left untouched: a command range outside
+ * 0 .. ncmds, an unknown kind, a point range outside 0 .. npoints, a coordinate beyond +-VA_FILL_MAX_COORD or a
+ * radius above it.  n == 0 and ncmds == 0 enqueue nothing (status_dev is not written).  c outside {1, 3}, negative
+ * counts, NULL pointers and frames of 2^29 pixels or more are VA_ERR_INVALID. */
+#define VA_COMPOSE_HIGHLIGHT 1
+#define VA_COMPOSE_ADD 2
+#define VA_COMPOSE_BLEND 3
+#define VA_DRAW_POLYLINE 1
+#define VA_DRAW_CIRCLE 2
+typedef struct va_compose_layer {
+    int32_t kind;           /* VA_COMPOSE_* */
+    int32_t image_channels; /* 1 or 3 (0 for a highlight) */
+    int32_t channel;        /* highlight: 0 .. 2, or -1 for all */
+    int32_t reserved;
+    int64_t image_off;      /* bytes into images_dev */
+    int64_t mask_off;       /* bytes into masks_dev, or -1 */
+    double factor;          /* highlight: (255 - strength) / 255 */
+    float alpha;            /* highlight: strength; blend: (float)(1 - weight) */
+    float beta;             /* blend: (float) weight */
+} va_compose_layer;         /* 48 bytes */
+typedef struct va_draw_cmd {
+    int32_t kind;   /* VA_DRAW_* */
+    int32_t flags;  /* bit 0: closed (polyline), filled (circle) */
+    uint32_t color; /* R | G << 8 | B << 16, or the grey value */
+    int32_t radius;
+    int32_t cx, cy;
+    int32_t count;  /* points of the polyline */
+    int32_t reserved;
+    int64_t first;  /* its first point in points_dev */
+} va_draw_cmd;      /* 40 bytes */
+int va_compose_layers_u8(const uint8_t *src_dev, int c_src, uint8_t *dst_dev, int n, int h, int w, int c,
+                         const va_compose_layer *layers_dev, const int64_t *layer_off_dev, int64_t nlayers,
+                         const uint8_t *images_dev, int64_t images_bytes, const uint8_t *masks_dev,
+                         int64_t masks_bytes, void *stream);
+int va_draw_u8(uint8_t *frames_dev, int n, int h, int w, int c, const va_draw_cmd *cmds_dev,
+               const int64_t *cmd_off_dev, int64_t ncmds, const int32_t *points_dev, int64_t npoints,
+               int32_t *status_dev, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -459,6 +459,13 @@ int launch_curves_equidistant(const double *points, const int64_t *point_off, in
                               int32_t *out_count, int64_t *out_off, double *in_length, int32_t *status,
                               int64_t *totals, double *out_points, int64_t cap_points, double *out_length,
                               hipStream_t st);
+// composer (va_compose.hip): the pixel layers of a stack in one pass; the drawing commands, one workgroup per frame
+int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
+                          const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,
+                          const uint8_t *images, int64_t images_bytes, const uint8_t *masks, int64_t masks_bytes,
+                          hipStream_t st);
+int launch_draw(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
+                int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

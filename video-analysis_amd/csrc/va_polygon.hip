@@ -15,6 +15,7 @@
 //             read in parallel from an LDS ring of three rows with the 2-pixel INIT_DIST0 border, and the
 //             tmp[j - 1] + HV (tmp[j + 1] + HV) chain is an exact int64 min-plus scan over the row.
 #include "va_common.h"
+#include "va_raster.h"
 
 namespace va {
 
@@ -36,80 +37,6 @@ struct FillArgs {
     int64_t out_elems;
     int32_t *status;
 };
-
-// OpenCV's clipLine (drawing.cpp) on int64 points: the corrections are computed in double and truncated
-__device__ bool clip_line(int64_t w, int64_t h, int64_t &x1, int64_t &y1, int64_t &x2, int64_t &y2)
-{
-    const int64_t right = w - 1, bottom = h - 1;
-    if (w <= 0 || h <= 0)
-        return false;
-    int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
-    int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
-    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-        int64_t a;
-        if (c1 & 12) {
-            a = c1 < 8 ? 0 : bottom;
-            x1 += (int64_t)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
-            y1 = a;
-            c1 = (x1 < 0) + (x1 > right) * 2;
-        }
-        if (c2 & 12) {
-            a = c2 < 8 ? 0 : bottom;
-            x2 += (int64_t)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
-            y2 = a;
-            c2 = (x2 < 0) + (x2 > right) * 2;
-        }
-        if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-            if (c1) {
-                a = c1 == 1 ? 0 : right;
-                y1 += (int64_t)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
-                x1 = a;
-                c1 = 0;
-            }
-            if (c2) {
-                a = c2 == 1 ? 0 : right;
-                y2 += (int64_t)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
-                x2 = a;
-                c2 = 0;
-            }
-        }
-    }
-    return (c1 | c2) == 0;
-}
-
-// Line(img, p1, p2, color, 8): LineIterator(img, p1, p2, 8, leftToRight = true)
-template <typename T>
-__device__ void draw_line8(T *img, int w, int h, int64_t x1, int64_t y1, int64_t x2, int64_t y2)
-{
-    if (x1 < 0 || x1 >= w || x2 < 0 || x2 >= w || y1 < 0 || y1 >= h || y2 < 0 || y2 >= h)
-        if (!clip_line(w, h, x1, y1, x2, y2))
-            return;
-    int64_t dx = x2 - x1, dy = y2 - y1;
-    if (dx < 0) {                          // left to right: start at the other end
-        dx = -dx;
-        dy = -dy;
-        x1 = x2;
-        y1 = y2;
-    }
-    const int64_t sy = dy < 0 ? -1 : 1;
-    dy = dy < 0 ? -dy : dy;
-    const bool steep = dy > dx;
-    const int64_t major = steep ? dy : dx, minor = steep ? dx : dy;
-    int64_t err = major - 2 * minor, x = x1, y = y1;
-    for (int64_t k = 0; k <= major; k++) {
-        if (x >= 0 && x < w && y >= 0 && y < h)          // always true after clipLine; kept as a guard
-            img[y * w + x] = (T)1;
-        const bool step_minor = err < 0;
-        err += -2 * minor + (step_minor ? 2 * major : 0);
-        if (steep) {
-            y += sy;
-            x += step_minor;
-        } else {
-            x += 1;
-            y += step_minor ? sy : 0;
-        }
-    }
-}
 
 template <typename T>
 __global__ void __launch_bounds__(kPolyBlock) fill_poly_kernel(FillArgs a, T *out)
@@ -200,7 +127,7 @@ __global__ void __launch_bounds__(kPolyBlock) fill_poly_kernel(FillArgs a, T *ou
     for (int i = tid; i < n; i += kPolyBlock) {
         const int j = i == 0 ? (int)n - 1 : i - 1;
         draw_line8(img, w, h, (int64_t)v[2 * j] - bx, (int64_t)v[2 * j + 1] - by, (int64_t)v[2 * i] - bx,
-                   (int64_t)v[2 * i + 1] - by);
+                   (int64_t)v[2 * i + 1] - by, (T)1);
     }
     if (tid == 0)
         a.status[p] = VA_OK;

@@ -124,7 +124,8 @@ class _Lease(list):
     """the pooled device buffers of one call (the list holds them).  Every buffer handed out goes back to the pool
     when the block ends: after the call's downloads, which synchronise its stream, or on an exception as it is,
     without a synchronisation of its own (none may be added to any path: the pool exists to keep them off the
-    per-call ops)"""
+    per-call ops).  The one exception is compose_layers(keep=True), which returns without a download: it
+    synchronises its stream once before its tables go back to the pool, because the launch still reads them."""
     stream = None                       # the call's stream, for the ops that have one: _Lease.on(stream)
 
     @classmethod
@@ -1908,3 +1909,306 @@ def curves_equidistant(curves, spacing=None, count=None, offsets=None, ret_lengt
             else:
                 results[k], lengths[k] = pts[out_off[j]:out_off[j + 1]], out_len[j]
     return (results, lengths) if ret_lengths else results
+
+
+# ------------------------------------------------------------------------------------------------ composer
+COMPOSE_CHANNELS = {0: 0, "r": 0, "red": 0, 1: 1, "g": 1, "green": 1, 2: 2, "b": 2, "blue": 2}   # composer.py:43-45
+COMPOSE_LAYER_DTYPE = np.dtype([("kind", np.int32), ("image_channels", np.int32), ("channel", np.int32),
+                                ("reserved", np.int32), ("image_off", np.int64), ("mask_off", np.int64),
+                                ("factor", np.float64), ("alpha", np.float32), ("beta", np.float32)])   # va_compose_layer
+DRAW_CMD_DTYPE = np.dtype([("kind", np.int32), ("flags", np.int32), ("color", np.uint32), ("radius", np.int32),
+                           ("cx", np.int32), ("cy", np.int32), ("count", np.int32), ("reserved", np.int32),
+                           ("first", np.int64)])                                                        # va_draw_cmd
+_COMPOSE_KINDS = {"highlight": 1, "add": 2, "blend": 3}      # VA_COMPOSE_*, VA_DRAW_*, include/videoanalysis_hip.h
+_DRAW_POLYLINE, _DRAW_CIRCLE = 1, 2
+DRAW_MAX_COORD = FILL_MAX_COORD
+
+
+class DeviceFrames(object):
+    """a uint8 frame stack (n, h, w) or (n, h, w, 3) that stays on the device between compose_layers and draw calls
+    (keep=True); download() copies it to the host, release() hands its buffer back to the pool (the caller has
+    synchronised by then: download() does)"""
+
+    def __init__(self, buf, n, h, w, c):
+        self.buf, self.n, self.h, self.w, self.c = buf, n, h, w, c
+
+    @property
+    def shape(self):
+        return (self.n, self.h, self.w) + ((3,) if self.c == 3 else ())
+
+    @property
+    def nbytes(self):
+        return self.n * self.h * self.w * self.c
+
+    @classmethod
+    def upload(cls, frames, stream=None):
+        arr, n, h, w, c = _frame_stack(frames, "DeviceFrames.upload")
+        buf = _take(max(arr.nbytes, 1))
+        try:
+            buf.upload(arr, stream)
+        except Exception:
+            _give(buf)
+            raise
+        return cls(buf, n, h, w, c)
+
+    def download(self, stream=None):
+        return self.buf.download(self.shape, np.uint8, stream)
+
+    def release(self):
+        buf, self.buf = self.buf, None
+        if buf is not None:
+            _give(buf)
+
+
+def _frame_stack(frames, what):
+    """(contiguous uint8 array, n, h, w, c) of a stack (n, h, w) or (n, h, w, 3)"""
+    arr = np.asarray(frames)
+    if arr.dtype != np.uint8:
+        raise TypeError("%s: frames are uint8, got %s" % (what, arr.dtype))
+    if not (arr.ndim == 3 or (arr.ndim == 4 and arr.shape[3] == 3)):
+        raise ValueError("%s: frames are a stack (n, h, w) or (n, h, w, 3), got shape %r" % (what, arr.shape))
+    return (np.ascontiguousarray(arr),) + tuple(arr.shape[:3]) + (1 if arr.ndim == 3 else 3,)
+
+
+class _BytePacker(object):
+    """byte planes of one call in one buffer, each at a 16-byte boundary; the same array object is stored once"""
+
+    def __init__(self):
+        self.parts, self.nbytes, self.seen = [], 0, {}
+
+    def add(self, arr, origin=None):
+        origin = arr if origin is None else origin           # what the caller handed in, of which arr is the bytes
+        key = id(origin)
+        if key not in self.seen:
+            flat = np.ascontiguousarray(arr, np.uint8).reshape(-1)
+            pad = -len(flat) % 16
+            self.seen[key] = (self.nbytes, origin)           # (the reference keeps the id alive)
+            self.parts += [flat, np.zeros(pad, np.uint8)] if pad else [flat]
+            self.nbytes += len(flat) + pad
+        return self.seen[key][0]
+
+    def packed(self):
+        return np.concatenate(self.parts) if self.parts else None
+
+
+def _compose_tables(layers, n, h, w, c, what):
+    """the checked operands of va_compose_layers_u8: (records, layer_off, images, masks), the last two packed byte
+    arrays or None; raises as compose_layers documents"""
+    if len(layers) != n:
+        raise ValueError("%s: need one layer list per frame (%d frames, %d lists)" % (what, n, len(layers)))
+    images, masks, recs = _BytePacker(), _BytePacker(), []
+    off = np.zeros(n + 1, np.int64)
+
+    def mask_of(mask):
+        if mask is None:
+            return -1
+        m = np.asarray(mask)
+        if m.shape != (h, w):
+            raise ValueError("%s: a mask of shape %r on frames of %r" % (what, m.shape, (h, w)))
+        origin = mask if isinstance(mask, np.ndarray) else m
+        if m.dtype != np.uint8:                  # non-zero is what counts; uint8 masks go as they are
+            m = (m != 0).view(np.uint8)
+        return masks.add(m, origin)
+
+    def image_of(image):
+        im = np.asarray(image)
+        if im.dtype != np.uint8:
+            raise TypeError("%s: images are uint8, got %s" % (what, im.dtype))
+        if im.shape[:2] != (h, w) or not (im.ndim == 2 or (im.ndim == 3 and im.shape[2] == 3)):
+            raise ValueError("The two images to be added must have the same size")
+        if im.ndim == 3 and c == 1:
+            raise ValueError("Cannot add a color image to a monochrome one")
+        return images.add(im, image if isinstance(image, np.ndarray) else im), (3 if im.ndim == 3 else 1)
+
+    for f, frame_layers in enumerate(layers):
+        for layer in frame_layers:
+            kind = layer[0]
+            rec = np.zeros((), COMPOSE_LAYER_DTYPE)
+            rec["mask_off"] = -1
+            if kind == "highlight":
+                _, mask, channel, strength = layer
+                if channel is None or (isinstance(channel, str) and channel == "all"):
+                    channel = -1
+                elif c == 1:
+                    raise ValueError("Highlighting a specific channel is only supported for color videos.")
+                else:
+                    try:
+                        channel = COMPOSE_CHANNELS[channel]
+                    except (KeyError, TypeError):
+                        raise ValueError("Unknown value `%s` for channel." % (channel,))
+                if isinstance(strength, (bool, np.bool_)) or int(strength) != strength or not 0 <= strength <= 255:
+                    raise ValueError("%s: the strength is an integer in 0 .. 255, got %r" % (what, strength))
+                if mask is None:
+                    raise ValueError("%s: a highlight needs a mask" % what)
+                rec["channel"], rec["alpha"] = channel, float(int(strength))
+                rec["factor"] = (255 - int(strength)) / 255
+                rec["mask_off"] = mask_of(mask)
+            elif kind == "add":
+                _, image, mask = layer
+                rec["image_off"], rec["image_channels"] = image_of(image)
+                rec["mask_off"] = mask_of(mask)
+            elif kind == "blend":
+                _, image, weight, mask = layer
+                weight = float(weight)
+                if not math.isfinite(weight):
+                    raise ValueError("%s: the weight must be finite, got %r" % (what, weight))
+                rec["image_off"], rec["image_channels"] = image_of(image)
+                rec["alpha"], rec["beta"] = np.float32(1 - weight), np.float32(weight)
+                rec["mask_off"] = mask_of(mask)
+            else:
+                raise ValueError("%s: unknown layer %r" % (what, kind))
+            rec["kind"] = _COMPOSE_KINDS[kind]
+            recs.append(rec)
+        off[f + 1] = len(recs)
+    table = np.array(recs, COMPOSE_LAYER_DTYPE) if recs else np.zeros(0, COMPOSE_LAYER_DTYPE)
+    return table, off, images.packed(), masks.packed()
+
+
+def compose_layers(frames, layers, color=None, keep=False, stream=None):
+    """the pixel layers of VideoComposer (video/io/composer.py:103-105, :131-210) on a whole stack in one
+    va_compose_layers_u8 launch ("Composer").  frames: uint8 (n, h, w) or (n, h, w, 3), or a
+    DeviceFrames of an earlier call.  layers: one list per frame of
+        ('highlight', mask, channel, strength)   channel None / 'all' or one of COMPOSE_CHANNELS; strength 0 .. 255
+        ('add', image, mask)                     saturating add; mask None: everywhere
+        ('blend', image, weight, mask)           cv2.addWeighted(frame, 1 - weight, image, weight, 0)
+    applied in order; masks (h, w), taken as non-zero; images uint8 (h, w) or (h, w, 3).  color: None keeps the
+    channels of the frames, True writes a colour stack (a monochrome frame is copied into the three channels first),
+    False asks for a monochrome one.  An array that appears in several layers is uploaded once.
+    ValueError, before anything is launched: a size mismatch, a colour image or colour frames on a monochrome
+    result, a channel on a monochrome stack, an unknown channel or layer, a strength outside 0 .. 255.
+    Returns the composed stack; keep=True returns a DeviceFrames instead (a DeviceFrames handed in with the same
+    channels is composed in place and returned; otherwise it is released)."""
+    what = "compose_layers"
+    dev = frames if isinstance(frames, DeviceFrames) else None
+    if dev is None:
+        arr, n, h, w, c_src = _frame_stack(frames, what)
+    else:
+        n, h, w, c_src = dev.n, dev.h, dev.w, dev.c
+    c = c_src if color is None else (3 if color else 1)
+    if c_src == 3 and c == 1:
+        raise ValueError("Cannot copy a color image into a monochrome video.")
+    table, off, images, masks = _compose_tables(list(layers), n, h, w, c, what)
+    if n == 0 or h == 0 or w == 0:
+        out = np.zeros((n, h, w) + ((3,) if c == 3 else ()), np.uint8)
+        if dev is not None:
+            dev.release()
+        return DeviceFrames.upload(out, stream) if keep else out
+    L = _hip.lib()
+    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
+    dst = src if c == c_src else DeviceFrames(_take(n * h * w * c), n, h, w, c)
+    try:
+        with _Lease.on(stream) as d:
+            tb, ob, ib, mb = (d.upload(table) if len(table) else None, d.upload(off), d.upload(images),
+                              d.upload(masks))
+            check(L.va_compose_layers_u8(src.buf.ptr, c_src, dst.buf.ptr, n, h, w, c, _ptr(tb), ob.ptr, len(table),
+                                         _ptr(ib), 0 if images is None else len(images), _ptr(mb),
+                                         0 if masks is None else len(masks), stream))
+            if keep:                       # the tables go back to the pool: the launch must have read them
+                check(L.va_stream_sync(stream))
+                out = dst
+            else:
+                out = dst.download(stream)
+    except Exception:
+        if dst is not src:
+            dst.release()
+        if dev is None:
+            src.release()
+        raise
+    if dst is not src:
+        src.release()
+    if not keep:
+        dst.release()
+    return out
+
+
+def _draw_color(color, c, what):
+    """the uint32 of a command's colour: one byte on a monochrome stack, R | G << 8 | B << 16 on a colour one"""
+    vals = [int(v) for v in np.atleast_1d(np.asarray(color)).reshape(-1)]
+    if len(vals) == 1 and c == 3:
+        vals = vals * 3
+    if len(vals) != c:
+        raise ValueError("%s: a colour of %d values on frames of %d channel(s)" % (what, len(vals), c))
+    if any(not 0 <= v <= 255 for v in vals):
+        raise ValueError("%s: colour values are 0 .. 255, got %r" % (what, color))
+    return sum(v << (8 * i) for i, v in enumerate(vals))
+
+
+def _draw_tables(commands, n, c, what):
+    """the checked operands of va_draw_u8: (records, cmd_off, points int32 (k, 2))"""
+    if len(commands) != n:
+        raise ValueError("%s: need one command list per frame (%d frames, %d lists)" % (what, n, len(commands)))
+    recs, pts, npts = [], [], 0
+    off = np.zeros(n + 1, np.int64)
+    for f, frame_cmds in enumerate(commands):
+        for cmd in frame_cmds:
+            rec = np.zeros((), DRAW_CMD_DTYPE)
+            if cmd[0] == "polyline":
+                _, points, closed, color = cmd
+                p = np.asarray(points)
+                if p.size and not np.issubdtype(p.dtype, np.integer):
+                    raise TypeError("%s: polylines hold integer points, got %s" % (what, p.dtype))
+                if p.size % 2:
+                    raise ValueError("%s: a polyline is (k, 2) or (k, 1, 2) points, got shape %r" % (what, p.shape))
+                p = p.reshape(-1, 2).astype(np.int64)
+                if p.size and np.abs(p).max() > DRAW_MAX_COORD:
+                    raise ValueError("%s: a coordinate is beyond +-%d" % (what, DRAW_MAX_COORD))
+                rec["kind"], rec["flags"], rec["first"], rec["count"] = _DRAW_POLYLINE, bool(closed), npts, len(p)
+                pts.append(p.astype(np.int32))
+                npts += len(p)
+            elif cmd[0] == "circle":
+                _, center, radius, filled, color = cmd
+                cx, cy, radius = int(center[0]), int(center[1]), int(radius)
+                if max(abs(cx), abs(cy), abs(radius)) > DRAW_MAX_COORD:
+                    raise ValueError("%s: a coordinate is beyond +-%d" % (what, DRAW_MAX_COORD))
+                rec["kind"], rec["flags"], rec["cx"], rec["cy"], rec["radius"] = _DRAW_CIRCLE, bool(filled), cx, cy, radius
+            else:
+                raise ValueError("%s: unknown command %r" % (what, cmd[0]))
+            rec["color"] = _draw_color(color, c, what)
+            recs.append(rec)
+        off[f + 1] = len(recs)
+    table = np.array(recs, DRAW_CMD_DTYPE) if recs else np.zeros(0, DRAW_CMD_DTYPE)
+    points = np.concatenate(pts) if npts else np.zeros((0, 2), np.int32)
+    return table, off, np.ascontiguousarray(points, np.int32)
+
+
+def draw(frames, commands, keep=False, stream=None):
+    """the thickness-1 drawing of VideoComposer (cv2.drawContours, polylines, rectangle, circle;
+    video/io/composer.py:236, :257, :284, :298) on a whole stack in one va_draw_u8 launch, one workgroup per frame
+    ("Composer").  frames: uint8 (n, h, w) or (n, h, w, 3), or a DeviceFrames.  commands: one list per
+    frame of
+        ('polyline', points, closed, color)           points (k, 2) or (k, 1, 2) integers, as find_contours returns
+        ('circle', center, radius, filled, color)     OpenCV's integer circle; a negative radius draws nothing
+    drawn in list order: the last command that covers a pixel decides it.  color: one value on a monochrome stack,
+    (r, g, b) on a colour one (one value counts for all three).
+    ValueError, before anything is launched: a coordinate or radius beyond +-DRAW_MAX_COORD, a colour outside
+    0 .. 255 or of the wrong length, an unknown command; RuntimeError: a frame the device refused.
+    Returns the stack; keep=True returns a DeviceFrames (the one handed in, drawn in place).  A DeviceFrames handed
+    in without keep is downloaded and released."""
+    what = "draw"
+    dev = frames if isinstance(frames, DeviceFrames) else None
+    if dev is None:
+        arr, n, h, w, c = _frame_stack(frames, what)
+    else:
+        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    table, off, points = _draw_tables(list(commands), n, c, what)
+    if len(table) == 0 and dev is None and not keep:
+        return arr.copy()
+    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
+    try:
+        if len(table):
+            with _Lease.on(stream) as d:
+                tb, ob, pb, st = d.upload(table), d.upload(off), d.upload(points) if len(points) else None, d.take(n * 4)
+                check(_hip.lib().va_draw_u8(src.buf.ptr, n, h, w, c, tb.ptr, ob.ptr, len(table), _ptr(pb), len(points),
+                                            st.ptr, stream))
+                status = st.download((n,), np.int32, stream)
+            bad = np.flatnonzero(status != 0)
+            if len(bad):
+                raise RuntimeError("%s: the device refused frame %d (status %d)" % (what, bad[0], status[bad[0]]))
+        out = src if keep else src.download(stream)
+    except Exception:
+        if dev is None:
+            src.release()
+        raise
+    if not keep:
+        src.release()
+    return out
