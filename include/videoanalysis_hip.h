@@ -785,6 +785,29 @@ int va_draw_u8(uint8_t *frames_dev, int n, int h, int w, int c, const va_draw_cm
                const int64_t *cmd_off_dev, int64_t ncmds, const int32_t *points_dev, int64_t npoints,
                int32_t *status_dev, void *stream);
 
+/* ------------------------------------------------------------------ A20 Motion-JPEG
+ * replaces  the frame-by-frame cv2.VideoWriter.write of VideoWriterOpenCV, video/io/backend_opencv.py:240-242, behind
+ *           write_video, video/io/file.py:50-64, by one baseline JFIF file per frame (the payload of an AVI's MJPG
+ *           stream, video/io/backend_mjpeg.py here)
+ * The stream is pinned in DESIGN.md §9, "Motion-JPEG": frames_dev uint8 (n, h, w) or (n, h, w, 3) RGB interleaved;
+ * 4:4:4 or monochrome, the Annex K Huffman tables, one restart interval per MCU row.  qtables_dev: 128 bytes, the
+ * luma and the chroma quantisation table in natural order (the chroma table is not read for c == 1).  header_dev:
+ * the header_bytes bytes SOI .. SOS that every frame's file starts with (video.ops.jpeg_header builds them).
+ *   sizes_out_dev[k]   (int64, n entries)      the bytes of frame k's file
+ *   offsets_out_dev[k] (int64, n + 1 entries)  where it starts in bytes_out_dev; offsets_out_dev[n] = the total
+ *   totals_dev[0]      (int64)                 the bytes needed, always
+ *   bytes_out_dev[cap_bytes]                   frame k's file is bytes offsets[k] .. offsets[k + 1] - 1, written only
+ *                      when the total is at most cap_bytes: a caller that reads a larger total runs again with that
+ *                      much room (bytes_out_dev may be NULL with cap_bytes == 0)
+ * Three launches on `stream` (count, scan, write), one workgroup per MCU row; every frame's bytes depend on that
+ * frame alone and two runs write identical bytes.  n == 0 enqueues nothing.  VA_ERR_INVALID, before anything is
+ * enqueued, in this order: a negative n or capacity, h, w or header_bytes below 1; c outside {1, 3}; a NULL
+ * pointer; an int64 buffer that is not 8-byte aligned; h or w above 65535 (SOF0 holds 16 bits); more than 2^31 - 1
+ * MCU rows in the stack. */
+int va_jpeg_encode_u8(const uint8_t *frames_dev, int n, int h, int w, int c, const uint8_t *qtables_dev,
+                      const uint8_t *header_dev, int header_bytes, int64_t *sizes_out_dev, int64_t *offsets_out_dev,
+                      int64_t *totals_dev, uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

@@ -1118,6 +1118,33 @@ int va_draw_u8(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *c
     return launch_draw(frames, n, h, w, c, cmds, cmd_off, ncmds, points, npoints, status, as_stream(stream));
 }
 
+// ------------------------------------------------------------------------------ Motion-JPEG
+int va_jpeg_encode_u8(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
+                      int header_bytes, int64_t *sizes_out, int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out,
+                      int64_t cap_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
+               "va_jpeg_encode_u8: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", n, h, w,
+               header_bytes, (long long)cap_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_encode_u8: channels must be 1 or 3, got %d", c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
+               "va_jpeg_encode_u8: NULL argument");
+    VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
+               "va_jpeg_encode_u8: the int64 buffers must be 8-byte aligned");
+    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_encode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
+    VA_REQUIRE((int64_t)n * ((h + 7) / 8) < ((int64_t)1 << 31),
+               "va_jpeg_encode_u8: the stack has too many MCU rows for one launch");
+    ScratchLease scratch;
+    int rc = scratch.acquire(jpeg_workspace_bytes(n, h), as_stream(stream));
+    if (rc)
+        return rc;
+    return launch_jpeg_encode(frames, n, h, w, c, qtables, header, header_bytes, sizes_out, offsets_out, totals,
+                              bytes_out, cap_bytes, scratch.ptr, as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited

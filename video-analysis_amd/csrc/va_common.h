@@ -466,6 +466,11 @@ int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, in
                           hipStream_t st);
 int launch_draw(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
                 int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, hipStream_t st);
+// Motion-JPEG (va_jpeg.hip): one baseline JFIF file per frame from three launches; ws: jpeg_workspace_bytes
+size_t jpeg_workspace_bytes(int n, int h);
+int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
+                       int header_bytes, int64_t *sizes, int64_t *offsets, int64_t *totals, uint8_t *out, int64_t cap,
+                       void *ws, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

@@ -1,0 +1,418 @@
+// va_jpeg.hip -- batched baseline JPEG encoding behind video.io.backend_mjpeg.VideoWriterMJPEG (the reference writes
+// its frames through cv2.VideoWriter, video/io/backend_opencv.py:240-242, behind write_video, video/io/file.py:50-64).
+// The stream is pinned in DESIGN.md §9, "Motion-JPEG"; the per-block arithmetic is va_jpeg_math.h, the same text the
+// host tests compile.
+//
+// One MCU row of one frame is an independent entropy segment (DRI = one MCU row), so the call has the library's
+// counts-then-scan shape over n * ceil(h / 8) segments, three launches on one stream:
+//   count  one workgroup per segment: encodes the segment and keeps only its byte length, stuffing included
+//   scan   one workgroup: the int64 exclusive prefix over [header | RSTm] + segment + [EOI] of every segment; the
+//          frames' offsets and sizes and the total
+//   write  one workgroup per segment: the same encoding again, stored at the segment's final offset.  Nothing is
+//          stored when the total exceeds the capacity.
+// The segment is encoded twice in place of keeping its coefficients: a frame is read twice (its bytes are a small
+// part of what the encoder computes) and the call needs no workspace that grows with the pixels.
+//
+// A segment is walked in chunks of 32 MCUs, so its length is not bounded by LDS.  Per chunk:
+//   A   each wave loads 8 MCUs, 8 (or 24) bytes of a pixel row per lane, converts colour and transforms block after
+//       block with one lane per sample: the row and column sums and the zigzag order are lane exchanges
+//   B1  one lane per coefficient: the length of its bit string (va_jpeg::coefficient_bits), summed per block
+//   --  a scan of the blocks' bit counts gives every block its bit position behind the chunk's carry
+//   B2  the same strings again, ORed into the chunk's bit buffer in LDS at block position + lane prefix
+//   E   the complete 32-bit words (all bytes, padded with 1-bits, in the last chunk) go out in tiles of 256 words:
+//       a workgroup scan of bytes + 0xFF counts places each word's stuffed bytes; the unfinished word is the next
+//       chunk's carry
+// The LDS atomics of B2 only OR disjoint bits into shared words: the result does not depend on their order, and
+// every byte written depends on its segment alone.
+#include "va_common.h"
+#include "va_jpeg_math.h"
+
+namespace va {
+
+namespace {
+
+constexpr int kJpegBlock = 256;
+constexpr int kJpegWaves = kJpegBlock / kWave;
+constexpr int kGroupMcus = 8;                          // MCUs a wave loads at once
+constexpr int kChunkMcus = kGroupMcus * kJpegWaves;    // MCUs of a chunk
+// a block has at most 22 + 63 * 26 bits: a DC string of 11 + 11, and an AC coefficient behind a run r adds at most
+// 11 (r / 16) + 26 bits over its r + 1 lanes
+constexpr int kMaxBlockBits = 22 + 63 * 26;
+// words of a chunk's bit buffer: its blocks, the carry, the padding, and put_bits' reach
+constexpr int bit_words(int c) { return (kChunkMcus * c * kMaxBlockBits + 31 + 7) / 32 + 3; }
+constexpr int kScanBlock = 256;
+constexpr int kScanPerThread = 4;
+
+struct JpegArgs {
+    const uint8_t *frames;
+    int n, h, w;
+    int nseg, mcus;                  // segments of a frame, MCUs of a segment
+    const uint8_t *qtables;          // [2][64], natural order
+    const uint8_t *header;
+    int header_bytes;
+    int32_t *seg_len;                // [n * nseg]
+    const int64_t *seg_start;        // [n * nseg + 1]
+    const int64_t *totals;
+    uint8_t *out;
+    int64_t cap;
+};
+
+__device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1)
+        v += __shfl_xor(v, d, kWave);
+    return v;
+}
+
+__device__ __forceinline__ int wave_inclusive(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int u = __shfl_up(v, d, kWave);
+        if (lane >= d)
+            v += u;
+    }
+    return v;
+}
+
+// the 8 pixels x0 .. x0 + 7 of row y as bytes; columns beyond the frame repeat the last one
+template <int C>
+__device__ __forceinline__ void load_pixels(const uint8_t *row, int x0, int w, uint32_t (&px)[2 * C])
+{
+    const uint8_t *p = row + (int64_t)x0 * C;
+    if (x0 + 8 <= w && ((uintptr_t)p & 7) == 0) {
+#pragma unroll
+        for (int i = 0; i < C; i++) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(p + 8 * i);
+            px[2 * i] = v.x;
+            px[2 * i + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2 * C; i++)
+            px[i] = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int x = x0 + i < w ? x0 + i : w - 1;
+#pragma unroll
+            for (int ch = 0; ch < C; ch++)
+                px[(i * C + ch) / 4] |= (uint32_t)row[(int64_t)x * C + ch] << (8 * ((i * C + ch) % 4));
+        }
+    }
+}
+
+template <int C, bool WRITE>
+__global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
+{
+    constexpr int kBitWords = bit_words(C);
+    __shared__ int16_t coef[kChunkMcus * C][64];
+    __shared__ uint32_t bitbuf[kBitWords];
+    __shared__ uint32_t huff_dc[2][16], huff_ac[2][256];
+    __shared__ uint8_t qt[2][64];
+    __shared__ int32_t block_bits[kChunkMcus * C];
+    __shared__ int32_t wave_total[kJpegWaves];
+    __shared__ int32_t pred[3];
+    __shared__ uint32_t chunk_end;
+
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t seg = blockIdx.x;
+    const int frame = (int)(seg / a.nseg), j = (int)(seg % a.nseg);
+    if (WRITE && a.totals[0] > a.cap)
+        return;
+
+    {
+        constexpr va_jpeg::HuffTables huff = va_jpeg::make_huff();
+        for (int i = tid; i < 32; i += kJpegBlock)
+            huff_dc[i / 16][i % 16] = huff.dc[i / 16][i % 16];
+        for (int i = tid; i < 512; i += kJpegBlock)
+            huff_ac[i / 256][i % 256] = huff.ac[i / 256][i % 256];
+    }
+    if (tid < 128)
+        qt[tid / 64][tid % 64] = a.qtables[tid];
+    for (int i = tid; i < kBitWords; i += kJpegBlock)
+        bitbuf[i] = 0;
+    if (tid < 3)
+        pred[tid] = 0;
+
+    // [header | RSTm] in front of the segment
+    int64_t out_at = 0, out_end = 0;
+    if (WRITE) {
+        out_at = a.seg_start[seg];
+        out_end = a.seg_start[seg + 1] - (j == a.nseg - 1 ? 2 : 0);
+        if (j == 0) {
+            for (int i = tid; i < a.header_bytes; i += kJpegBlock)
+                if (out_at + i < out_end)
+                    a.out[out_at + i] = a.header[i];
+            out_at += a.header_bytes;
+        } else {
+            if (tid < 2 && out_at + tid < out_end)
+                a.out[out_at + tid] = tid == 0 ? (uint8_t)0xFF : (uint8_t)(0xD0 + (j - 1) % 8);
+            out_at += 2;
+        }
+    }
+
+    // this lane's rows of T for the two passes, and where its zigzag coefficient comes from
+    int t_row[8], t_col[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        t_row[i] = va_jpeg::dct_at(lane & 7, i);
+        t_col[i] = va_jpeg::dct_at(lane >> 3, i);
+    }
+    const int zz_from = va_jpeg::zigzag_at(lane);
+    const int y_load = min(j * 8 + (lane >> 3), a.h - 1);
+    const uint8_t *row = a.frames + ((int64_t)frame * a.h + y_load) * a.w * C;
+
+    uint32_t carry_bits = 0;             // bits of bitbuf[0] that belong to the previous chunk
+    int64_t emitted = 0;                 // bytes of the segment so far
+    __syncthreads();
+
+    for (int m0 = 0; m0 < a.mcus; m0 += kChunkMcus) {
+        const int cm = min(kChunkMcus, a.mcus - m0), nblk = cm * C;
+        const bool last = m0 + kChunkMcus >= a.mcus;
+        // ---------------------------------------------------------------- A: transform
+        const int g = wave * kGroupMcus;
+        if (g < cm) {
+            uint32_t px[2 * C];          // the lane's 8 pixels of MCU g + (lane & 7), row lane >> 3
+            const int mcu = min(m0 + g + (lane & 7), a.mcus - 1);
+            load_pixels<C>(row, mcu * 8, a.w, px);
+            uint32_t comp[C][2];         // per component the 8 samples as bytes
+            if constexpr (C == 1) {
+                comp[0][0] = px[0], comp[0][1] = px[1];
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < C; ch++)
+                    comp[ch][0] = comp[ch][1] = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int r = (px[(3 * i) / 4] >> (8 * ((3 * i) % 4))) & 255;
+                    const int gg = (px[(3 * i + 1) / 4] >> (8 * ((3 * i + 1) % 4))) & 255;
+                    const int b = (px[(3 * i + 2) / 4] >> (8 * ((3 * i + 2) % 4))) & 255;
+                    int yy, cb, cr;
+                    va_jpeg::ycbcr(r, gg, b, yy, cb, cr);
+                    comp[0][i / 4] |= (uint32_t)yy << (8 * (i % 4));
+                    comp[1][i / 4] |= (uint32_t)cb << (8 * (i % 4));
+                    comp[2][i / 4] |= (uint32_t)cr << (8 * (i % 4));
+                }
+            }
+            const int blocks_here = min(kGroupMcus, cm - g);
+            for (int jj = 0; jj < blocks_here; jj++) {
+#pragma unroll
+                for (int ch = 0; ch < C; ch++) {
+                    // lane = 8 y + x of the block
+                    const int src = (lane & ~7) | jj;
+                    const uint32_t lo = __shfl(comp[ch][0], src, kWave), hi = __shfl(comp[ch][1], src, kWave);
+                    const int x = lane & 7;
+                    const int sample = (int)(((x < 4 ? lo : hi) >> (8 * (x & 3))) & 255u) - 128;
+                    int sum = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        sum += t_row[i] * __shfl(sample, (lane & ~7) | i, kWave);
+                    const int rows = va_jpeg::row_round(sum);            // lane = 8 y + k
+                    sum = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        sum += t_col[i] * __shfl(rows, 8 * i + (lane & 7), kWave);
+                    const int q = va_jpeg::quantise(sum, qt[ch ? 1 : 0][lane]);   // lane = 8 v + k
+                    coef[(g + jj) * C + ch][lane] = (int16_t)__shfl(q, zz_from, kWave);
+                }
+            }
+        }
+        __syncthreads();
+        // ---------------------------------------------------------------- B1: bits of every block
+        for (int q = wave; q < nblk; q += kJpegWaves) {
+            const int ch = q % C, tab = ch ? 1 : 0;
+            const int v = coef[q][lane];
+            const int p = q >= C ? coef[q - C][0] : pred[ch];
+            const uint64_t nonzero = __ballot(v != 0);
+            const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
+            const int total = wave_sum(b.len);
+            if (lane == 0)
+                block_bits[q] = total;
+        }
+        __syncthreads();
+        // the blocks' bit positions: an exclusive scan behind the carry (one wave, two entries a lane)
+        if (wave == 0) {
+            const int b0 = lane < nblk ? block_bits[lane] : 0, b1 = lane + 64 < nblk ? block_bits[lane + 64] : 0;
+            const int i0 = wave_inclusive(b0, lane), t0 = __shfl(i0, kWave - 1, kWave);
+            const int i1 = wave_inclusive(b1, lane), t1 = __shfl(i1, kWave - 1, kWave);
+            if (lane < nblk)
+                block_bits[lane] = (int)carry_bits + i0 - b0;
+            if (lane + 64 < nblk)
+                block_bits[lane + 64] = (int)carry_bits + t0 + i1 - b1;
+            if (lane == 0)
+                chunk_end = carry_bits + (uint32_t)(t0 + t1);
+        }
+        int next_pred = 0;
+        if (tid < C)
+            next_pred = coef[(cm - 1) * C + tid][0];
+        __syncthreads();
+        // ---------------------------------------------------------------- B2: the strings into the bit buffer
+        for (int q = wave; q < nblk; q += kJpegWaves) {
+            const int ch = q % C, tab = ch ? 1 : 0;
+            const int v = coef[q][lane];
+            const int p = q >= C ? coef[q - C][0] : pred[ch];
+            const uint64_t nonzero = __ballot(v != 0);
+            const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
+            const uint32_t pos = (uint32_t)(block_bits[q] + wave_inclusive(b.len, lane) - b.len);
+            va_jpeg::put_bits(pos, b, [&](uint32_t wi, uint32_t val) {
+                if (wi < (uint32_t)kBitWords)
+                    atomicOr(&bitbuf[wi], val);
+            });
+        }
+        __syncthreads();
+        if (tid < C)
+            pred[tid] = next_pred;
+        const uint32_t end = chunk_end;
+        if (last && tid == 0) {                                  // pad to a byte with 1-bits
+            const int pad = (int)(-end & 7u);
+            va_jpeg::put_bits(end, va_jpeg::Bits{(1ull << pad) - 1, pad},
+                              [&](uint32_t wi, uint32_t val) { bitbuf[wi] |= val; });
+        }
+        __syncthreads();
+        // ---------------------------------------------------------------- E: whole words out, stuffed
+        const int nbytes = last ? (int)((end + 7) >> 3) : (int)(end >> 5) * 4;
+        const int nwords = (nbytes + 3) >> 2;
+        for (int t0 = 0; t0 < nwords; t0 += kJpegBlock) {
+            const int wi = t0 + tid;
+            const int nvalid = min(max(nbytes - 4 * wi, 0), 4);
+            const uint32_t word = nvalid > 0 ? bitbuf[wi] : 0u;
+            const int mine = nvalid + va_jpeg::count_ff(word, nvalid);
+            const int incl = wave_inclusive(mine, lane);
+            if (lane == kWave - 1)
+                wave_total[wave] = incl;
+            __syncthreads();
+            int before = 0, tile = 0;
+#pragma unroll
+            for (int k = 0; k < kJpegWaves; k++) {
+                before += k < wave ? wave_total[k] : 0;
+                tile += wave_total[k];
+            }
+            if (WRITE) {
+                const int64_t at = out_at + emitted + before + incl - mine;
+                va_jpeg::put_stuffed(word, nvalid, [&](int i, uint8_t v) {
+                    if (at + i < out_end)
+                        a.out[at + i] = v;
+                });
+            }
+            emitted += tile;
+            __syncthreads();
+        }
+        // the unfinished word becomes word 0 of the next chunk
+        if (!last) {
+            const uint32_t wlast = end >> 5;
+            const uint32_t keep = bitbuf[wlast];
+            __syncthreads();
+            for (uint32_t i = tid; i <= wlast + 2 && i < (uint32_t)kBitWords; i += kJpegBlock)
+                bitbuf[i] = 0;
+            __syncthreads();
+            if (tid == 0)
+                bitbuf[0] = keep;
+            carry_bits = end & 31u;
+        }
+    }
+    if (!WRITE) {
+        if (tid == 0)
+            a.seg_len[seg] = (int32_t)emitted;
+    } else if (j == a.nseg - 1 && tid < 2) {
+        const int64_t at = out_at + emitted + tid;             // EOI
+        if (at < a.seg_start[seg + 1])
+            a.out[at] = tid == 0 ? (uint8_t)0xFF : (uint8_t)0xD9;
+    }
+}
+
+// seg_start[0 .. S] = exclusive prefix of [header | RST] + segment + [EOI]; offsets[f] = the start of frame f,
+// offsets[n] = totals[0] = the sum; sizes[f] = the bytes of frame f.  One workgroup, 1024 segments a round.
+__global__ void __launch_bounds__(kScanBlock)
+jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, int n, int header_bytes,
+                 int64_t *__restrict__ seg_start, int64_t *offsets, int64_t *__restrict__ sizes,
+                 int64_t *__restrict__ totals)
+{
+    __shared__ int64_t part[kScanBlock];
+    __shared__ int64_t carry;
+    const int t = (int)threadIdx.x;
+    if (t == 0)
+        carry = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < nsegs; base += kScanBlock * kScanPerThread) {
+        int64_t v[kScanPerThread], mine = 0;
+#pragma unroll
+        for (int i = 0; i < kScanPerThread; i++) {
+            const int64_t s = base + (int64_t)t * kScanPerThread + i;
+            v[i] = 0;
+            if (s < nsegs) {
+                const int j = (int)(s % nseg);
+                v[i] = (int64_t)seg_len[s] + (j == 0 ? header_bytes : 2) + (j == nseg - 1 ? 2 : 0);
+            }
+            mine += v[i];
+        }
+        part[t] = mine;
+        __syncthreads();
+        for (int d = 1; d < kScanBlock; d <<= 1) {
+            const int64_t add = t >= d ? part[t - d] : 0;
+            __syncthreads();
+            part[t] += add;
+            __syncthreads();
+        }
+        int64_t at = carry + part[t] - mine;
+#pragma unroll
+        for (int i = 0; i < kScanPerThread; i++) {
+            const int64_t s = base + (int64_t)t * kScanPerThread + i;
+            if (s < nsegs) {
+                seg_start[s] = at;
+                if (s % nseg == 0)
+                    offsets[s / nseg] = at;
+            }
+            at += v[i];
+        }
+        __syncthreads();
+        if (t == kScanBlock - 1)
+            carry += part[t];
+        __syncthreads();
+    }
+    if (t == 0) {
+        seg_start[nsegs] = carry;
+        offsets[n] = carry;
+        totals[0] = carry;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int f = t; f < n; f += kScanBlock)
+        sizes[f] = offsets[f + 1] - offsets[f];
+}
+
+}  // namespace
+
+size_t jpeg_workspace_bytes(int n, int h)
+{
+    const size_t nsegs = (size_t)n * ((h + 7) / 8);
+    return Carve::up(nsegs * sizeof(int32_t)) + Carve::up((nsegs + 1) * sizeof(int64_t));
+}
+
+int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
+                       int header_bytes, int64_t *sizes, int64_t *offsets, int64_t *totals, uint8_t *out, int64_t cap,
+                       void *ws, hipStream_t st)
+{
+    const int nseg = (h + 7) / 8;
+    const int64_t nsegs = (int64_t)n * nseg;
+    int32_t *seg_len = at<int32_t>(ws, 0);
+    int64_t *seg_start = at<int64_t>(ws, Carve::up((size_t)nsegs * sizeof(int32_t)));
+    const JpegArgs a{frames, n, h, w, nseg, (w + 7) / 8, qtables, header, header_bytes, seg_len, seg_start, totals, out, cap};
+    const dim3 grid((unsigned)nsegs), block(kJpegBlock);
+    if (c == 1)
+        hipLaunchKernelGGL((jpeg_segment_kernel<1, false>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, false>), grid, block, 0, st, a);
+    VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, header_bytes,
+                       seg_start, offsets, sizes, totals);
+    VA_LAUNCH_CHECK("jpeg_scan_kernel");
+    if (c == 1)
+        hipLaunchKernelGGL((jpeg_segment_kernel<1, true>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, true>), grid, block, 0, st, a);
+    VA_LAUNCH_CHECK("jpeg_segment_kernel (write)");
+    return VA_OK;
+}
+
+}  // namespace va

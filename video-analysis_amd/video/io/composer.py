@@ -2,9 +2,13 @@
 
 `VideoComposer` keeps the reference's method names and argument lists.  What differs, and why:
 
-* **Sink in place of the file name.**  The reference derives from a `VideoFileWriter` that its checkout does not
-  contain, so the first argument is a *sink*: ``None`` collects the frames (``.frames`` returns them as an array fit
-  for `VideoMemory`), an object with ``write_frame(frame)`` receives them, and so does a plain callable.
+* **File name or sink.**  The reference is a `VideoFileWriter`; here the first argument is a file name (a `str` or
+  `os.PathLike`), for which a `video.io.file.VideoFileWriter(filename, self.size, fps, is_color, **kwargs)` is
+  opened and closed with the composer, or a *sink*: ``None`` collects the frames (``.frames`` returns them as an
+  array fit for `VideoMemory`), an object with ``write_frame(frame)`` receives them, and so does a plain callable.
+  A sink with ``write_frames(stack)`` -- the file writer is one -- receives a flush's finished frames as one
+  `ops.DeviceFrames` where the flush needs no host copy of them: only what the sink makes of them crosses to the
+  host (for the file writer the compressed bytes).  The stack is the composer's: the sink uses it during the call.
 * **Deferred drawing.**  Calls are recorded per output frame and carried out for `batch` output frames at a time
   (default 32), on `close()`, and when `.frame` is read.  Everything a call is given is captured at call time, so a
   caller may reuse its arrays.  The order of the calls within a frame is kept: consecutive pixel layers
@@ -28,6 +32,7 @@ The ops are looked up on `video.ops` when a flush runs (`ops.compose_layers`, `o
 The pinned definitions are in DESIGN.md §9, "Composer".
 """
 import math
+import os
 
 import numpy as np
 
@@ -104,9 +109,10 @@ class VideoComposer(object):
     each frame.  See the module's docstring for the differences from the reference."""
 
     def __init__(self, sink, size, fps, is_color, output_period=1, zoom_factor=1, batch=32, **kwargs):
-        """`sink`: None, an object with write_frame(frame), or a callable.  `size` = (width, height) of the frames
-        handed to set_frame; the output is (int(width / zoom_factor), int(height / zoom_factor)).  `output_period`:
-        only every output_period-th frame is written.  `batch`: output frames composed per flush."""
+        """`sink`: a file name, None, an object with write_frame(frame), or a callable.  `size` = (width, height) of
+        the frames handed to set_frame; the output is (int(width / zoom_factor), int(height / zoom_factor)).
+        `output_period`: only every output_period-th frame is written.  `batch`: output frames composed per flush.
+        Further keyword arguments go to the file writer that a file name opens."""
         if batch < 1:
             raise ValueError("batch must be positive")
         self.sink, self.fps, self.is_color = sink, fps, bool(is_color)
@@ -120,6 +126,9 @@ class VideoComposer(object):
         self._pending = []
         self._collected = []
         self._last_capture = {}
+        if isinstance(sink, (str, os.PathLike)):
+            from .file import VideoFileWriter
+            self.sink = VideoFileWriter(sink, self.size, fps, self.is_color, **kwargs)
 
     # ------------------------------------------------------------------------------------------ bookkeeping
     def get_color(self, color):
@@ -342,6 +351,9 @@ class VideoComposer(object):
         else:
             self.sink(frame)
 
+    def _frame_shape(self):
+        return (self.size[1], self.size[0]) + ((3,) if self.is_color else ())
+
     def _resized(self, arrays, color):
         """ops.resize (linear) of every array of a list to self.size, one call per shape"""
         out, groups = [None] * len(arrays), {}
@@ -424,6 +436,9 @@ class VideoComposer(object):
                     r[-1].append(item)
                 runs.append(r)
             current = stack
+            # a sink that takes stacks gets the device stack itself when every frame of it is written now (nothing
+            # is kept for .frame): no host copy of the frames is needed then
+            direct = not keep_last and hasattr(self.sink, "write_frames")
             try:
                 for k in range(max(len(r) for r in runs)):
                     items = [r[k] if k < len(r) else [] for r in runs]
@@ -432,6 +447,11 @@ class VideoComposer(object):
                             current = ops.compose_layers(current, items, color=self.is_color, keep=True)
                     elif any(items):
                         current = ops.draw(current, items, keep=True)
+                if direct and isinstance(current, ops.DeviceFrames) and current.shape[1:] == self._frame_shape():
+                    self.sink.write_frames(current)
+                    self.frames_written += len(pending)
+                    self._pending = []
+                    return
                 out = current.download() if hasattr(current, "download") else np.asarray(current)
             finally:
                 if hasattr(current, "release"):

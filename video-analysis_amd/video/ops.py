@@ -2212,3 +2212,142 @@ def draw(frames, commands, keep=False, stream=None):
     if not keep:
         src.release()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ Motion-JPEG
+# ITU T.81 Annex K.1 / K.2 (natural order) and K.3 - K.6 as (BITS, HUFFVAL), keyed by the DHT byte Tc << 4 | Th
+_JPEG_BASE = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+     14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+     47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32)
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,
+                7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
+                39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_JPEG_AC_COMMON = (
+    0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a,
+    0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a,
+    0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a)
+_JPEG_AC_HIGH = (
+    0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+    0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda)
+JPEG_DHT = {
+    0x00: ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    0x10: ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+           (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
+            0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0,
+            0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a) + _JPEG_AC_COMMON + _JPEG_AC_HIGH
+           + (0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea,
+              0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    0x01: ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    0x11: ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+           (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
+            0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0,
+            0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+            0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a) + _JPEG_AC_COMMON[18:] + (0x82,)
+           + _JPEG_AC_HIGH + (0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea,
+                              0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+}
+JPEG_MAX_SIDE = 65535            # SOF0 holds 16-bit sizes
+JPEG_ROOM_DIVISOR = 4            # the first launch has room for the headers and a quarter of the raw bytes
+
+
+def jpeg_tables(quality):
+    """the (luma, chroma) quantisation tables of `quality` 1 .. 100 in natural order, uint8 (64,) each: the Annex K
+    base tables under the IJG scaling, clip((base * scale + 50) // 100, 1, 255) with scale = 5000 // q below 50 and
+    200 - 2 q from 50 on (host only)"""
+    if isinstance(quality, (bool, np.bool_)) or int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError("jpeg_tables: the quality is an integer in 1 .. 100, got %r" % (quality,))
+    q = int(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.array(base, np.int64) * scale + 50) // 100, 1, 255).astype(np.uint8)
+                 for base in _JPEG_BASE)
+
+
+def _jpeg_segment(marker, payload):
+    return bytes([0xFF, marker, (len(payload) + 2) >> 8, (len(payload) + 2) & 255]) + bytes(payload)
+
+
+def jpeg_header(h, w, c, quality):
+    """the bytes SOI .. SOS every frame's file starts with ("Motion-JPEG"): APP0 JFIF 1.01, one DQT per
+    table, SOF0 with 1 x 1 sampling, one DHT per Annex K table (DC0, AC0 and, in colour, DC1, AC1), DRI =
+    ceil(w / 8), SOS (host only)"""
+    h, w, c = int(h), int(w), int(c)
+    if not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
+        raise ValueError("jpeg_header: sides are 1 .. %d, got %d x %d" % (JPEG_MAX_SIDE, w, h))
+    if c not in (1, 3):
+        raise ValueError("jpeg_header: 1 or 3 components, got %d" % c)
+    tables = jpeg_tables(quality)
+    zz = list(_JPEG_ZIGZAG)
+    comps = [(1, 0)] if c == 1 else [(1, 0), (2, 1), (3, 1)]
+    out = b"\xff\xd8" + _jpeg_segment(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for t in range(1 if c == 1 else 2):
+        out += _jpeg_segment(0xDB, bytes([t]) + tables[t][zz].tobytes())
+    out += _jpeg_segment(0xC0, bytes([8, h >> 8, h & 255, w >> 8, w & 255, len(comps)])
+                         + b"".join(bytes([i, 0x11, t]) for i, t in comps))
+    for key in (0x00, 0x10) + ((0x01, 0x11) if c == 3 else ()):
+        bits, vals = JPEG_DHT[key]
+        out += _jpeg_segment(0xC4, bytes((key,) + bits + vals))
+    ri = (w + 7) // 8
+    out += _jpeg_segment(0xDD, bytes([ri >> 8, ri & 255]))
+    out += _jpeg_segment(0xDA, bytes([len(comps)]) + b"".join(bytes([i, 0x11 * t]) for i, t in comps)
+                         + bytes([0, 63, 0]))
+    return out
+
+
+def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
+    """one baseline JFIF file per frame of a stack in one va_jpeg_encode_u8 call ("Motion-JPEG"): 4:4:4
+    or monochrome, the Annex K Huffman tables, one restart interval per MCU row; the bytes are pinned and equal the
+    restatement's.  frames: uint8 (n, h, w) or (n, h, w, 3) RGB, or a DeviceFrames (it stays the caller's; nothing
+    is uploaded then).  color: None takes the channels from the shape; True / False say what a 3-dimensional array
+    is, one colour frame (h, w, 3) or a monochrome stack, and must agree with a 4-dimensional one.
+    One upload of the frames and one of [tables | header], one call, and the downloads of the sizes and of the used
+    bytes.  The first launch has room for the headers and 1 / JPEG_ROOM_DIVISOR of the raw bytes; a batch that
+    needs more runs exactly once more, with exact room.
+    Returns the list of n `bytes`; ret_packed: (uint8 blob, int64 offsets of n + 1 entries), frame k being
+    blob[offsets[k]:offsets[k + 1]]."""
+    what = "jpeg_encode"
+    dev = frames if isinstance(frames, DeviceFrames) else None
+    if dev is None:
+        arr = np.asarray(frames)
+        if arr.dtype != np.uint8:
+            raise TypeError("%s: frames are uint8, got %s" % (what, arr.dtype))
+        if color is not None and arr.ndim == (3 if color else 2):
+            arr = arr[None]
+        arr, n, h, w, c = _frame_stack(arr, what)
+    else:
+        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    if color is not None and (c == 3) != bool(color):
+        raise ValueError("%s: color=%r with frames of %d channel(s)" % (what, color, c))
+    if n and not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
+        raise ValueError("%s: sides are 1 .. %d, got %d x %d" % (what, JPEG_MAX_SIDE, w, h))
+    tables = jpeg_tables(quality)
+    if n == 0:
+        return (np.zeros(0, np.uint8), np.zeros(1, np.int64)) if ret_packed else []
+    head = np.frombuffer(jpeg_header(h, w, c, quality), np.uint8)
+    consts = np.concatenate([tables[0], tables[1], head])
+    nseg = (h + 7) // 8
+    room = n * (len(head) + 2 * nseg) + (n * h * w * c) // JPEG_ROOM_DIVISOR
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        src = dev.buf if dev is not None else d.upload(arr)
+        cb = d.upload(consts)
+        info = d.take(16 * n + 16)                  # [total | offsets (n + 1) | sizes (n)], int64
+
+        def run(cap):
+            out = d.take(max(cap, 1))
+            check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, cb.ptr, cb.ptr + 128, len(head), info.ptr + 16 + 8 * n,
+                                      info.ptr + 8, info.ptr, out.ptr, cap, stream))
+            meta = info.download((2 * n + 2,), np.int64, stream)
+            return out, meta
+        out, meta = run(room)
+        if meta[0] > room:                          # nothing was written: exactly once more, with exact room
+            out, meta = run(int(meta[0]))
+        blob = out.download((int(meta[0]),), np.uint8, stream)
+    offsets = meta[1:n + 2].copy()
+    if ret_packed:
+        return blob, offsets
+    raw = blob.tobytes()
+    return [raw[offsets[k]:offsets[k + 1]] for k in range(n)]
