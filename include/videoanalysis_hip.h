@@ -808,6 +808,47 @@ int va_jpeg_encode_u8(const uint8_t *frames_dev, int n, int h, int w, int c, con
                       const uint8_t *header_dev, int header_bytes, int64_t *sizes_out_dev, int64_t *offsets_out_dev,
                       int64_t *totals_dev, uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
 
+/* ------------------------------------------------------------------ A21 Motion-JPEG decoding
+ * replaces  the frame-by-frame cv2.VideoCapture.read of VideoOpenCV.get_frame, video/io/backend_opencv.py, behind
+ *           load_any_video, video/io/file.py:37-46, by one call per batch of stored baseline JPEG files (the chunks
+ *           of an AVI's MJPG stream, video/io/backend_mjpeg.py here)
+ * The decoder is pinned in DESIGN.md §9, "Motion-JPEG decoding".  All frames of a call share h, w, c, ri and the
+ * tables; video.ops.jpeg_decode parses the headers, refuses what the decoder does not take and groups the frames.
+ *   bytes_dev        the stored files, one behind the other
+ *   offsets_dev      int64 (n + 1): file k is bytes offsets[k] .. offsets[k + 1] - 1
+ *   scan_begin_dev   int64 (n): where file k's entropy data begins (the byte behind its SOS header), from the
+ *                    file's start; a value outside the file is clamped into it
+ *   c, ri            1 or 3 components (Y, or Y Cb Cr, all 1 x 1); the restart interval in MCUs, at least 1 (a
+ *                    stream without DRI: the MCUs of a frame); a frame has ceil(MCUs / ri) segments
+ *   qtables_dev      c * 64 bytes: the quantisation table of each component in natural order
+ *   huff_dev         2 * c tables of VA_JPEG_HUFF_DECODE_BYTES bytes: the DC and the AC table of each component as
+ *                    video.ops builds them from the DHT segments (va_jpeg_decode_math.h, HuffDecode); huff_bytes
+ *                    is their size.  Whatever they hold, nothing outside them is read.
+ *   frames_out_dev   uint8 (n, h, w) or (n, h, w, 3) RGB interleaved; every pixel is written, nothing else
+ *   status_out_dev   int32 (n): 0 or the VA_JPEG_STATUS_* bits; blocks at and behind an error in their segment, and
+ *                    the blocks of a missing segment, decode as zero coefficients (sample 128)
+ *   workspace_dev    workspace_bytes bytes, 16-byte aligned.  va_jpeg_decode_workspace_bytes(n, h, w, c, ri) holds the
+ *                    whole batch (2 bytes per padded sample and 16 bytes per segment; 0 for arguments the call would
+ *                    refuse); with less the call runs in chunks of as many frames as fit, with the same result.
+ * Three launches on `stream` per chunk (locate, entropy, reconstruct).  Nothing is read outside a file's bytes or
+ * written outside its pixels whatever the bytes are, a hostile stream costs no more than a valid one of its
+ * length, and two runs write identical bytes.  n == 0 enqueues nothing.  VA_ERR_INVALID, before anything is
+ * enqueued, in this order: a negative n or workspace_bytes, h, w or ri below 1; c outside {1, 3}; a NULL pointer;
+ * offsets_dev or scan_begin_dev not 8-byte, huff_dev or status_out_dev not 4-byte, workspace_dev not 16-byte
+ * aligned; h or w above 65535 (SOF0 holds 16 bits); huff_bytes other than 2 * c * VA_JPEG_HUFF_DECODE_BYTES.  Then
+ * VA_ERR_RANGE for a workspace that does not hold one frame. */
+#define VA_JPEG_STATUS_BAD_CODE 1  /* a code in no table, a DC category > 11, an AC size > 10, a DC value outside
+                                      -2048 .. 2047 */
+#define VA_JPEG_STATUS_OVERRUN 2   /* a coefficient index beyond 63 */
+#define VA_JPEG_STATUS_TRUNCATED 4 /* bits are needed beyond the segment's end */
+#define VA_JPEG_STATUS_MARKER 8    /* the scan did not end on EOI, or has another number of segments */
+#define VA_JPEG_HUFF_DECODE_BYTES 1416
+size_t va_jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri);
+int va_jpeg_decode_u8(const uint8_t *bytes_dev, const int64_t *offsets_dev, const int64_t *scan_begin_dev, int n, int h,
+                      int w, int c, int ri, const uint8_t *qtables_dev, const void *huff_dev, int huff_bytes,
+                      uint8_t *frames_out_dev, int32_t *status_out_dev, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

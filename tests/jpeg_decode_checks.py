@@ -1,0 +1,342 @@
+"""The Motion-JPEG decoder of DESIGN.md §9, "Motion-JPEG decoding", restated in NumPy: this file is the definition,
+and the device equals it byte for byte, status words included.  The header parse with its refusals, the segment
+splitter, the entropy decode with its status bits, the integer dequantiser and inverse transform, the fixed-point
+colour conversion; also the float64 decode of the same coefficients that the accuracy condition is stated against.
+Nothing here imports the package."""
+import struct
+
+import numpy as np
+
+import jpeg_checks as J
+
+BAD_CODE, OVERRUN, TRUNCATED, MARKER = 1, 2, 4, 8
+SHIFT1, SHIFT2 = 9, 17
+
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic sequential",
+              0xCA: "arithmetic progressive", 0xCB: "arithmetic lossless", 0xCD: "arithmetic differential",
+              0xCE: "arithmetic differential progressive", 0xCF: "arithmetic differential lossless"}
+
+
+# ------------------------------------------------------------------------------------------------ header
+def parse_header(data):
+    """what a stored file's header says, or ValueError naming what the decoder does not take: dict of h, w, c, ri
+    (the restart interval in MCUs; the MCUs of the frame where DRI is absent or 0), nseg, scan_begin, qtables
+    (c, 64) uint8 in natural order, huff: per component ((BITS, HUFFVAL) of its DC table, of its AC table)"""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("no SOI at the start")
+    i, qt, huff, sof, ri = 2, {}, {}, None, 0
+    while True:
+        if i + 4 > len(data):
+            raise ValueError("the file ends before SOS")
+        if data[i] != 0xFF:
+            raise ValueError("a marker is expected at byte %d, found %02x" % (i, data[i]))
+        m = data[i + 1]
+        if m == 0xFF:
+            i += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            i += 2
+            continue
+        if m in (0xD8, 0xD9):
+            raise ValueError("marker %02x before SOS" % m)
+        length = struct.unpack(">H", data[i + 2:i + 4])[0]
+        if length < 2 or i + 2 + length > len(data):
+            raise ValueError("the segment of marker %02x at byte %d leaves the file" % (m, i))
+        p = data[i + 4:i + 2 + length]
+        if m == 0xDB:
+            while p:
+                if p[0] >> 4:
+                    raise ValueError("a 16-bit quantisation table")
+                if len(p) < 65 or (p[0] & 15) > 3:
+                    raise ValueError("a damaged DQT segment")
+                table = np.zeros(64, np.uint8)
+                table[J.ZIGZAG] = list(p[1:65])
+                qt[p[0] & 15], p = table, p[65:]
+        elif m == 0xC4:
+            while p:
+                if len(p) < 17:
+                    raise ValueError("a damaged DHT segment")
+                bits = list(p[1:17])
+                n = sum(bits)
+                if (p[0] >> 4) > 1 or (p[0] & 15) > 3 or n > 256 or len(p) < 17 + n:
+                    raise ValueError("a damaged DHT segment")
+                code = 0
+                for length_ in range(1, 17):
+                    code += bits[length_ - 1]
+                    if code > (1 << length_):
+                        raise ValueError("a DHT segment with more codes of %d bits than there are" % length_)
+                    code <<= 1
+                huff[p[0]], p = (bits, list(p[17:17 + n])), p[17 + n:]
+        elif m in _SOF_NAMES or m == 0xC0:
+            if len(p) < 6:
+                raise ValueError("a damaged frame header")
+            precision, h, w, nc = struct.unpack(">BHHB", p[:6])
+            if precision != 8:
+                raise ValueError("sample precision %d: only 8-bit precision is decoded" % precision)
+            if m != 0xC0:
+                raise ValueError("%s mode (SOF%d): only baseline sequential is decoded" % (_SOF_NAMES[m], m - 0xC0))
+            if sof is not None:
+                raise ValueError("two frame headers")
+            if nc not in (1, 3) or len(p) < 6 + 3 * nc:
+                raise ValueError("%d components: 1 or 3 are decoded" % nc)
+            comps = [(p[6 + 3 * k], p[7 + 3 * k], p[8 + 3 * k]) for k in range(nc)]
+            for cid, hv, tq in comps:
+                if hv != 0x11 and nc > 1:
+                    raise ValueError("sampling factors %d x %d (chroma subsampling such as 4:2:0 or 4:2:2): only 1 x 1 "
+                                     "sampling is decoded" % (hv >> 4, hv & 15))
+            if h == 0:
+                raise ValueError("a frame height of 0 (DNL) is not decoded")
+            if w == 0:
+                raise ValueError("a frame width of 0")
+            sof = (h, w, comps)
+        elif m == 0xCC:
+            raise ValueError("arithmetic coding (DAC) is not decoded")
+        elif m == 0xDC:
+            raise ValueError("DNL is not decoded")
+        elif m == 0xDD:
+            if len(p) < 2:
+                raise ValueError("a damaged DRI segment")
+            ri = struct.unpack(">H", p[:2])[0]
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("SOS before the frame header")
+            h, w, comps = sof
+            ns = p[0] if p else 0
+            if len(p) < 1 + 2 * ns + 3:
+                raise ValueError("a damaged scan header")
+            if ns != len(comps) or [p[1 + 2 * k] for k in range(ns)] != [cid for cid, _, _ in comps]:
+                raise ValueError("more than one scan: this scan holds %d of the %d components" % (ns, len(comps)))
+            if (p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns]) != (0, 63, 0):
+                raise ValueError("a scan with Ss %d, Se %d, Ah/Al %02x is not baseline sequential"
+                                 % (p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns]))
+            tables = []
+            for k, (cid, _, tq) in enumerate(comps):
+                td, ta = p[2 + 2 * k] >> 4, p[2 + 2 * k] & 15
+                if tq not in qt:
+                    raise ValueError("quantisation table %d is not defined" % tq)
+                if td not in huff or (0x10 | ta) not in huff:
+                    raise ValueError("Huffman table %d / %d is not defined" % (td, ta))
+                tables.append((huff[td], huff[0x10 | ta]))
+            mcus = ((h + 7) // 8) * ((w + 7) // 8)
+            ri = ri if ri else mcus
+            return dict(h=h, w=w, c=len(comps), ri=ri, nseg=(mcus + ri - 1) // ri, scan_begin=i + 2 + length,
+                        qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
+        i += 2 + length
+
+
+# ------------------------------------------------------------------------------------------------ segments
+def split_segments(data, scan_begin, nseg):
+    """the entropy segments of a file whose scan data begins at scan_begin: ([(begin, end) or None] * nseg, the
+    marker-sequence bit).  The data is split at every FF xx with xx not 00 or FF; the k-th such marker ends segment
+    k and, when it is RST(k mod 8), begins segment k + 1; the first other one ends the scan.  Without one the last
+    segment ends with the file."""
+    b = np.frombuffer(bytes(data), np.uint8)
+    begin = min(max(int(scan_begin), 0), len(b))
+    marks = np.flatnonzero((b[:-1] == 0xFF) & (b[1:] != 0) & (b[1:] != 0xFF)) if len(b) > 1 else np.zeros(0, np.int64)
+    segs, term = [], None
+    for k, m in enumerate(int(m) for m in marks[marks >= begin]):
+        segs.append((begin, m))
+        if b[m + 1] != 0xD0 + k % 8:
+            term = int(b[m + 1])
+            break
+        begin = m + 2
+    else:
+        segs.append((begin, len(b)))
+    bad = term != 0xD9 or len(segs) != nseg
+    return (segs + [None] * nseg)[:nseg], MARKER if bad else 0
+
+
+def unstuffed(data, begin, end):
+    """the bytes of a segment: FF 00 inside it is the byte FF, every other byte is itself"""
+    raw = np.frombuffer(bytes(data[begin:end]), np.uint8)
+    keep = np.ones(len(raw), bool)
+    ff = np.flatnonzero(raw[:-1] == 0xFF) if len(raw) > 1 else np.zeros(0, np.int64)
+    keep[ff[raw[ff + 1] == 0] + 1] = False
+    return raw[keep].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ entropy decode
+_LUTS = {}
+
+
+def _lut(table):
+    """[the next 16 bits] -> length << 8 | symbol of the code that begins them, 0 where none does"""
+    bits, vals = table
+    key = (tuple(bits), tuple(vals))
+    if key not in _LUTS:
+        lut = np.zeros(65536, np.int64)
+        for sym, (code, length) in J.huffman_codes(bits, vals).items():
+            lut[code << (16 - length):(code + 1) << (16 - length)] = length << 8 | sym
+        _LUTS[key] = lut.tolist()
+    return _LUTS[key]
+
+
+class _Bits(object):
+    def __init__(self, raw):
+        self.raw, self.pos, self.nbits = raw + b"\0\0\0", 0, 8 * len(raw)
+
+    def peek16(self):
+        """the next 16 bits, zeros behind the end"""
+        i, raw = self.pos >> 3, self.raw
+        return ((raw[i] << 16 | raw[i + 1] << 8 | raw[i + 2]) >> (8 - (self.pos & 7))) & 0xFFFF if i < len(raw) - 3 else 0
+
+    def symbol(self, lut):
+        """(status, length, symbol) of the next code, not consumed.  A reader that takes bit after bit runs out of
+        bits exactly where no code begins fewer than 16 remaining bits, or the code is longer than what remains"""
+        left = self.nbits - self.pos
+        e = lut[self.peek16()]
+        if e == 0:
+            return (BAD_CODE if left >= 16 else TRUNCATED), 0, 0
+        return (TRUNCATED if (e >> 8) > left else 0), e >> 8, e & 255
+
+    def receive(self, size):
+        if size == 0:
+            return 0
+        v = self.peek16() >> (16 - size)
+        self.pos += size
+        return v if v >> (size - 1) else v - (1 << size) + 1
+
+
+def decode_block(bits, dc, ac, pred):
+    """(status, the 64 coefficients in natural order or None, the DC predictor) of the next block.  The checks come
+    in this order: the Huffman step, the symbol, the index, the magnitude bits, the DC range."""
+    st, length, sym = bits.symbol(dc)
+    if st:
+        return st, None, pred
+    if sym > 11:
+        return BAD_CODE, None, pred
+    if length + sym > bits.nbits - bits.pos:
+        return TRUNCATED, None, pred
+    bits.pos += length
+    pred += bits.receive(sym)
+    if not -2048 <= pred <= 2047:
+        return BAD_CODE, None, pred
+    block = [0] * 64
+    block[0] = pred
+    k = 1
+    while k < 64:
+        st, length, sym = bits.symbol(ac)
+        if st:
+            return st, None, pred
+        run, size = sym >> 4, sym & 15
+        if size == 0:
+            if run == 0:
+                bits.pos += length
+                break
+            if run != 15:
+                return BAD_CODE, None, pred
+            k += 16
+            if k > 64:
+                return OVERRUN, None, pred
+            bits.pos += length
+            continue
+        if size > 10:
+            return BAD_CODE, None, pred
+        k += run
+        if k > 63:
+            return OVERRUN, None, pred
+        if length + size > bits.nbits - bits.pos:
+            return TRUNCATED, None, pred
+        bits.pos += length
+        block[int(J.ZIGZAG[k])] = bits.receive(size)
+        k += 1
+    return 0, block, pred
+
+
+_ZZ = [int(v) for v in J.ZIGZAG]
+
+
+def decode_coefficients(data, head=None, ret_segments=False):
+    """((c, by, bx, 64) int64 quantised coefficients in natural order, the status word).  After an error in a
+    segment its block and the later blocks of the segment are zero; so are the blocks of a missing segment.
+    ret_segments: also the list per segment of None (missing) or (status bit or 0, the MCU of the error or None)"""
+    data = bytes(data)
+    head = head or parse_header(data)
+    h, w, c, ri = head["h"], head["w"], head["c"], head["ri"]
+    by, bx = (h + 7) // 8, (w + 7) // 8
+    segs, status = split_segments(data, head["scan_begin"], head["nseg"])
+    luts = [(_lut(dc), _lut(ac)) for dc, ac in head["huff"]]
+    coefs = np.zeros((c, by, bx, 64), np.int64)
+    report = []
+    for j, seg in enumerate(segs):
+        report.append(None if seg is None else (0, None))
+        if seg is None:
+            continue
+        bits, pred = _Bits(unstuffed(data, *seg)), [0] * c
+        dead = False
+        for m in range(j * ri, min((j + 1) * ri, by * bx)):
+            for ch in range(c):
+                st, block, pred[ch] = decode_block(bits, luts[ch][0], luts[ch][1], pred[ch])
+                if st:
+                    status |= st
+                    dead = True
+                    report[-1] = (st, m)
+                    break
+                coefs[ch, m // bx, m % bx] = block
+            if dead:
+                break
+    return (coefs, status, report) if ret_segments else (coefs, status)
+
+
+# ------------------------------------------------------------------------------------------------ reconstruction
+def dequantised(coefs, qtables):
+    """(clamp(coef * Q, -2048, 2047) as (c, by, bx, 8, 8) [v][k], whether the clamp was active)"""
+    raw = coefs * np.asarray(qtables, np.int64)[:, None, None, :]
+    f = np.clip(raw, -2048, 2047)
+    return f.reshape(f.shape[:3] + (8, 8)), bool((f != raw).any())
+
+
+def integer_planes(f):
+    """the pinned inverse transform: (c, by * 8, bx * 8) samples 0 .. 255"""
+    t, _ = J.dct_matrix()
+    g = (np.einsum("vy,cabvk->cabyk", t, f) + (1 << (SHIFT1 - 1))) >> SHIFT1
+    s = (np.einsum("kn,cabyk->cabyn", t, g) + (1 << (SHIFT2 - 1))) >> SHIFT2
+    c, by, bx = f.shape[:3]
+    return np.clip(s + 128, 0, 255).transpose(0, 1, 3, 2, 4).reshape(c, by * 8, bx * 8)
+
+
+def float_planes(f):
+    """the float64 IDCT of the same dequantised coefficients, rounded and clipped"""
+    _, a = J.dct_matrix()
+    x = np.einsum("vy,cabvk,kn->cabyn", a, f.astype(np.float64), a) + 128
+    c, by, bx = f.shape[:3]
+    return np.clip(np.rint(x), 0, 255).astype(np.int64).transpose(0, 1, 3, 2, 4).reshape(c, by * 8, bx * 8)
+
+
+def rgb_of(planes):
+    y, cb, cr = planes[0], planes[1] - 128, planes[2] - 128
+    return np.stack([np.clip(y + ((91881 * cr + 32768) >> 16), 0, 255),
+                     np.clip(y - ((22554 * cb + 46802 * cr + 32768) >> 16), 0, 255),
+                     np.clip(y + ((116130 * cb + 32768) >> 16), 0, 255)], axis=-1)
+
+
+def ideal_rgb_of(planes):
+    y, cb, cr = (p.astype(np.float64) for p in (planes[0], planes[1] - 128, planes[2] - 128))
+    rgb = np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], axis=-1)
+    return np.clip(np.rint(rgb), 0, 255)
+
+
+def decode(data, head=None):
+    """(the frame, uint8 (h, w) or (h, w, 3) RGB; the status word) of one stored file"""
+    head = head or parse_header(data)
+    coefs, status = decode_coefficients(data, head)
+    planes = integer_planes(dequantised(coefs, head["qtables"])[0])[:, :head["h"], :head["w"]]
+    frame = planes[0] if head["c"] == 1 else rgb_of(planes)
+    return frame.astype(np.uint8), status
+
+
+def ideal_decode(data, head=None):
+    """dequantise, float64 IDCT, round and clip, JFIF inverse matrix in float64, round and clip: what
+    jpeg_checks.ideal_decode computes, for any stream the decoder takes"""
+    head = head or parse_header(data)
+    coefs, _ = decode_coefficients(data, head)
+    planes = float_planes(dequantised(coefs, head["qtables"])[0])[:, :head["h"], :head["w"]]
+    return (planes[0] if head["c"] == 1 else ideal_rgb_of(planes)).astype(np.uint8)
+
+
+def header_key(head):
+    """what two frames must share to go into one call"""
+    return (head["h"], head["w"], head["c"], head["ri"], head["qtables"].tobytes(),
+            tuple((tuple(dc[0]), tuple(dc[1]), tuple(ac[0]), tuple(ac[1])) for dc, ac in head["huff"]))

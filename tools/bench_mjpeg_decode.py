@@ -1,0 +1,218 @@
+#!/usr/bin/env python3
+"""Time of the Motion-JPEG decoder on the GPU (va_jpeg_decode_u8, va_jpeg_decode.hip) and of the reader in front of it:
+  kernels   n x 1080p frames, monochrome and RGB, quality 90, the encoder's own streams resident on the device: the
+            call (locate + entropy + reconstruct per chunk) by HIP events, next to a device-to-device copy of its
+            output and to va_jpeg_encode_u8 on the same frames, all in the same run.  The ABI enqueues its three
+            launches together, so this leg cannot time them one by one; a run of this leg under
+            `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/bench_mjpeg_decode.py --legs kernels`
+            lists them per kernel.
+            Two contents: a smooth scene with mild noise and uniform noise
+  batch32   the same call on the first 32 frames: one lane per segment leaves most of the machine idle there
+  ops       ops.jpeg_decode from host bytes, wall clock with its upload and the download of the frames, and with
+            keep=True (no download), next to the upload of the raw pixels that it replaces
+  pillow    Pillow's decoder (libjpeg) on one core, a few frames, where Pillow exists
+  video     VideoMJPEG iteration end to end over an AVI file with the device decoder and, where Pillow exists, with
+            the default one
+Times are the median of the repetitions.  One JSON line per leg, appended to profiles/mjpeg_decode_bench.jsonl (or
+--out); a leg that did not run is written "not measured".
+Run on an MI355X:
+    python tools/bench_mjpeg_decode.py [--reps 15] [--frames 256]"""
+import argparse
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "video-analysis_amd"))
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=15)
+ap.add_argument("--frames", type=int, default=256)
+ap.add_argument("--height", type=int, default=1080)
+ap.add_argument("--width", type=int, default=1920)
+ap.add_argument("--quality", type=int, default=90)
+ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow leg (0: not measured)")
+ap.add_argument("--video-frames", type=int, default=64, help="frames of the VideoMJPEG leg")
+ap.add_argument("--legs", default="kernels,batch32,ops,pillow,video")
+ap.add_argument("--modes", default="mono,rgb")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mjpeg_decode_bench.jsonl"))
+args = ap.parse_args()
+LEGS = set(args.legs.split(","))
+N, H, W, Q = args.frames, args.height, args.width, args.quality
+
+
+def scene(n, h, w, c, rng, noise):
+    """n frames: uniform noise, or a smooth moving pattern with discs and +-4 of noise (the clips of bench_mjpeg.py)"""
+    shape = (n, h, w) + ((3,) if c == 3 else ())
+    if noise:
+        return rng.integers(0, 256, shape, dtype=np.uint8)
+    yy, xx = np.mgrid[:h, :w]
+    base = 128 + 60 * np.sin(xx / 97.0) * np.cos(yy / 71.0)
+    for _ in range(12):
+        cx, cy, r = rng.uniform(0, w), rng.uniform(0, h), rng.uniform(h / 40, h / 10)
+        base[(xx - cx) ** 2 + (yy - cy) ** 2 <= r * r] += rng.uniform(-60, 60)
+    out = np.empty(shape, np.uint8)
+    for t in range(n):
+        plane = np.roll(base, 3 * t, axis=1) + rng.integers(-4, 5, (h, w))
+        plane = np.clip(plane, 0, 255).astype(np.uint8)
+        out[t] = plane if c == 1 else np.stack([plane, np.roll(plane, 5, axis=0), 255 - plane], axis=-1)
+    return out
+
+
+def main():
+    import torch
+    dev = torch.device("cuda", 0)
+    S = torch.cuda.current_stream(dev).cuda_stream
+    from video import _hip, ops
+    from video.io.backend_mjpeg import VideoMJPEG, VideoWriterMJPEG
+    L, check = _hip.lib(), _hip.check
+    rng = np.random.default_rng(43)
+    rows = []
+
+    def emit(row):
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+
+    def events(call):
+        call()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = []
+        for _ in range(args.reps):
+            a.record()
+            call()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return min(ms), float(np.median(ms))
+
+    def wall(call, reps):
+        call()
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ms))
+
+    for c in [m for m in (1, 3) if ("rgb" if m == 3 else "mono") in args.modes.split(",")]:
+        for noise in (False, True):
+            name = "%s/%s" % ("rgb" if c == 3 else "mono", "noise" if noise else "smooth")
+            clip = scene(N, H, W, c, rng, noise)
+            raw = clip.nbytes
+            stack = ops.DeviceFrames.upload(clip)
+            blob, offsets = ops.jpeg_encode(stack, Q, ret_packed=True)
+            stack.release()
+            ops.pool_clear()
+            head = ops.jpeg_parse_header(blob[:offsets[1]].tobytes())
+            ri = head["ri"]
+            if LEGS & {"kernels", "batch32"}:
+                tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
+                consts = torch.from_numpy(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8).copy()).to(dev)
+                src = torch.from_numpy(blob).to(dev)
+                meta = torch.from_numpy(np.concatenate([offsets, np.full(N, head["scan_begin"], np.int64)])).to(dev)
+                out = torch.empty(raw, dtype=torch.uint8, device=dev)
+                status = torch.zeros(N, dtype=torch.int32, device=dev)
+                room = int(L.va_jpeg_decode_workspace_bytes(N, H, W, c, ri))
+                ws = torch.empty(room, dtype=torch.uint8, device=dev)
+
+                def decode(n):
+                    check(L.va_jpeg_decode_u8(src.data_ptr(), meta.data_ptr(), meta.data_ptr() + 8 * (N + 1), n, H, W,
+                                              c, ri, consts.data_ptr(), consts.data_ptr() + 64 * c, len(tables),
+                                              out.data_ptr(), status.data_ptr(), ws.data_ptr(), room, S))
+                if "kernels" in LEGS:
+                    best, med = events(lambda: decode(N))
+                    assert not bool(status.any())
+                    twin = torch.empty_like(out)
+                    _, copy_med = events(lambda: twin.copy_(out))
+                    del twin
+                    frames = torch.from_numpy(clip).to(dev)
+                    ehead = np.frombuffer(ops.jpeg_header(H, W, c, Q), np.uint8)
+                    econsts = torch.from_numpy(np.concatenate(ops.jpeg_tables(Q) + (ehead,))).to(dev)
+                    info = torch.zeros(2 * N + 2, dtype=torch.int64, device=dev)
+                    cap = raw + N * 4096
+                    eout = torch.empty(cap, dtype=torch.uint8, device=dev)
+                    _, enc_med = events(lambda: check(L.va_jpeg_encode_u8(
+                        frames.data_ptr(), N, H, W, c, econsts.data_ptr(), econsts.data_ptr() + 128, len(ehead),
+                        info.data_ptr() + 16 + 8 * N, info.data_ptr() + 8, info.data_ptr(), eout.data_ptr(), cap, S)))
+                    del frames, eout
+                    emit({"leg": "kernels/" + name, "frames": N, "h": H, "w": W, "quality": Q,
+                          "ms_per_call_min": round(best, 4), "ms_per_call_median": round(med, 4),
+                          "frames_per_s": round(N / med * 1e3, 1), "output_gb_per_s": round(raw / med / 1e6, 1),
+                          "bytes_in_per_frame": int(len(blob)) // N, "segments_per_call": N * head["nseg"],
+                          "workspace_bytes": room, "memcpy_same_output_ms_median": round(copy_med, 4),
+                          "times_the_memcpy": round(med / copy_med, 2), "encode_same_frames_ms_median": round(enc_med, 4),
+                          "note": "locate + entropy + reconstruct, one chunk"})
+                if "batch32" in LEGS:
+                    best, med = events(lambda: decode(min(32, N)))
+                    emit({"leg": "batch32/" + name, "frames": min(32, N), "ms_per_call_min": round(best, 4),
+                          "ms_per_call_median": round(med, 4), "frames_per_s": round(min(32, N) / med * 1e3, 1),
+                          "segments_per_call": min(32, N) * head["nseg"], "waves_of_the_entropy_launch":
+                          -(-min(32, N) * head["nseg"] // 64), "note": "one lane per segment"})
+                del src, out, ws
+            if "ops" in LEGS:
+                full = wall(lambda: ops.jpeg_decode((blob, offsets)), args.reps)
+
+                def kept():
+                    ops.jpeg_decode((blob, offsets), keep=True).release()
+                keep = wall(kept, args.reps)
+
+                def upload():
+                    ops.DeviceFrames.upload(clip).release()
+                    torch.cuda.synchronize()
+                up = wall(upload, args.reps)
+                emit({"leg": "ops/" + name, "frames": N, "h": H, "w": W, "quality": Q,
+                      "jpeg_decode_with_upload_and_download_ms_median": round(full, 2),
+                      "jpeg_decode_keep_with_upload_ms_median": round(keep, 2), "raw_upload_ms_median": round(up, 2),
+                      "bytes_uploaded": int(len(blob)), "raw_bytes": raw,
+                      "keep_frames_per_s": round(N / keep * 1e3, 1),
+                      "note": "wall clock from pageable host memory; header parse on the host included"})
+            if "pillow" in LEGS:
+                row = {"leg": "pillow/" + name, "frames": args.cpu_frames, "quality": Q}
+                try:
+                    from PIL import Image
+                except ImportError:
+                    Image = None
+                if Image is None or not args.cpu_frames:
+                    row["ms_per_frame"] = "not measured"
+                else:
+                    t0 = time.perf_counter()
+                    for k in range(args.cpu_frames):
+                        np.asarray(Image.open(io.BytesIO(blob[offsets[k]:offsets[k + 1]].tobytes())))
+                    row.update({"ms_per_frame": round((time.perf_counter() - t0) * 1e3 / args.cpu_frames, 2),
+                                "note": "libjpeg through Pillow, one core"})
+                emit(row)
+            if "video" in LEGS:
+                nv = min(args.video_frames, N)
+                with tempfile.TemporaryDirectory() as tmp:
+                    path = os.path.join(tmp, "bench.avi")
+                    with VideoWriterMJPEG(path, size=(W, H), fps=25, is_color=c == 3, quality=Q) as writer:
+                        for f in clip[:nv]:
+                            writer.write_frame(f)
+
+                    def iterate(decoder):
+                        with VideoMJPEG(path, {"decoder": decoder}) as video:
+                            return sum(int(f[0, 0].sum()) for f in video)
+                    device = wall(lambda: iterate("device"), 3)
+                    try:
+                        import PIL  # noqa: F401
+                        pillow = round(wall(lambda: iterate("pillow"), 1), 1)
+                    except ImportError:
+                        pillow = "not measured"
+                emit({"leg": "video/" + name, "frames": nv, "device_decoder_ms_median": round(device, 1),
+                      "device_decoder_frames_per_s": round(nv / device * 1e3, 1), "pillow_decoder_ms": pillow,
+                      "note": "VideoMJPEG iteration, wall clock: file reads, header parses, upload, decode, download "
+                              "and a copy per frame"})
+            del clip, blob
+            ops.pool_clear()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        for row in rows:
+            f.write(json.dumps(row) + "\n")
+
+
+main()

@@ -1145,6 +1145,43 @@ int va_jpeg_encode_u8(const uint8_t *frames, int n, int h, int w, int c, const u
                               bytes_out, cap_bytes, scratch.ptr, as_stream(stream));
 }
 
+size_t va_jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0)
+        return 0;
+    return jpeg_decode_workspace_bytes(n, h, w, c, ri);
+}
+
+int va_jpeg_decode_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w, int c,
+                      int ri, const uint8_t *qtables, const void *huff, int huff_bytes, uint8_t *frames_out,
+                      int32_t *status_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ri > 0 && workspace_bytes >= 0,
+               "va_jpeg_decode_u8: negative or zero size (n %d, h %d, w %d, ri %d, workspace %lld)", n, h, w, ri,
+               (long long)workspace_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_decode_u8: channels must be 1 or 3, got %d", c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
+               "va_jpeg_decode_u8: NULL argument");
+    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
+                   && aligned(workspace, 16),
+               "va_jpeg_decode_u8: offsets and scan_begin must be 8-byte aligned, the tables and the status 4-byte, "
+               "the workspace 16-byte");
+    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_decode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
+    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
+               "va_jpeg_decode_u8: the Huffman tables of %d component(s) are %d bytes, got %d", c,
+               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
+    if (jpeg_decode_chunk(n, h, w, c, ri, (size_t)workspace_bytes) < 1) {
+        set_error("va_jpeg_decode_u8: a workspace of %lld bytes does not hold one frame (%lld bytes)",
+                  (long long)workspace_bytes, (long long)jpeg_decode_workspace_bytes(1, h, w, c, ri));
+        return VA_ERR_RANGE;
+    }
+    return launch_jpeg_decode(bytes, offsets, scan_begin, n, h, w, c, ri, qtables, huff, frames_out, status_out,
+                              workspace, (size_t)workspace_bytes, as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited

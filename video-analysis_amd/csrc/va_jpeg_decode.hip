@@ -1,0 +1,402 @@
+// va_jpeg_decode.hip -- batched baseline JPEG decoding behind video.ops.jpeg_decode and
+// video.io.backend_mjpeg.VideoMJPEG (the reference reads its frames one by one through cv2.VideoCapture.read,
+// VideoOpenCV.get_frame, video/io/backend_opencv.py, behind load_any_video, video/io/file.py:37-46).  The decoder is
+// pinned in DESIGN.md §9, "Motion-JPEG decoding"; the serial arithmetic is va_jpeg_decode_math.h, the same text the
+// host tests compile.
+//
+// Every restart interval of every frame is an independent entropy segment, and everything behind the entropy decode
+// is per block, so a chunk of frames takes three launches on one stream:
+//   locate       one workgroup per frame walks the frame's entropy bytes in tiles of 2048, 8 bytes a lane: the
+//                markers FF xx (xx not 00, FF) get their rank in the frame from ballots' popcounts scanned over the
+//                workgroup; the k-th one ends segment k and, while it is RST(k mod 8), begins segment k + 1.  The
+//                first other marker ends the scan.  Fills the chunk's table of nseg (begin, end) byte ranges (-1: a
+//                missing segment) and stores the frame's status word, the marker-sequence bit or 0.
+//   entropy      one lane per segment: va_jpeg::decode_block over the segment's MCUs with a 64-bit bit buffer and the
+//                tables in LDS; the coefficients go to the workspace as int16 in natural order, [frame][component]
+//                [block row][block column][64], a zeroed block (16-byte stores) and then its non-zero entries.  An
+//                error zeroes its block and the rest of the segment and is ORed into the frame's status word.
+//   reconstruct  one lane per MCU: dequantise, both inverse passes and the colour conversion in registers; the lanes
+//                of a wave hold neighbouring MCUs of a block row, so each of the 8 pixel rows goes out as 8 (or 24)
+//                contiguous bytes a lane, 512 (1536) bytes a wave, where the row is complete and aligned, and
+//                bytewise at the frame's edges.
+// The only atomic is the OR into the status word, whose result does not depend on the order; every output byte
+// depends on its frame alone.  Loops over stream bytes end at the segment's end, loops over blocks at the segment's
+// MCU range.
+#include <limits.h>
+
+#include "va_common.h"
+#include "va_jpeg_decode_math.h"
+
+static_assert(sizeof(va_jpeg::HuffDecode) == VA_JPEG_HUFF_DECODE_BYTES, "the table size is part of the ABI");
+
+namespace va {
+
+namespace {
+
+constexpr int kLocBlock = 256;
+constexpr int kLocWaves = kLocBlock / kWave;
+constexpr int kLocPer = 8;                               // bytes a lane looks at
+constexpr int kLocTile = kLocBlock * kLocPer;
+constexpr int kEntBlock = kWave;
+constexpr int kRecBlock = 256;
+
+__device__ __forceinline__ int wave_inclusive_i(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int u = __shfl_up(v, d, kWave);
+        if (lane >= d)
+            v += u;
+    }
+    return v;
+}
+
+__device__ __forceinline__ long long wave_min_ll(long long v)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const long long u = __shfl_xor(v, d, kWave);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+// table[f][k] = (begin, end) of segment k of frame f as offsets into `bytes`; status[f] = the marker-sequence bit
+__global__ void __launch_bounds__(kLocBlock)
+jpeg_locate_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ offsets,
+                   const int64_t *__restrict__ scan_begin, int nseg, int64_t *__restrict__ table,
+                   int32_t *__restrict__ status)
+{
+    __shared__ int32_t wave_count[2][kLocWaves];
+    __shared__ long long wave_bad[2][kLocWaves];
+    __shared__ int32_t terminator;
+
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t f = blockIdx.x;
+    const int64_t fb = offsets[f], fe = offsets[f + 1] > fb ? offsets[f + 1] : fb;
+    int64_t sb = scan_begin[f];
+    sb = fb + (sb < 0 ? 0 : sb > fe - fb ? fe - fb : sb);
+    int64_t *tab = table + 2 * f * nseg;
+    for (int k = tid; k < nseg; k += kLocBlock) {
+        tab[2 * k] = k == 0 ? sb : -1;
+        tab[2 * k + 1] = -1;
+    }
+    if (tid == 0)
+        terminator = -1;
+    __syncthreads();
+
+    constexpr long long kNone = LLONG_MAX;
+    long long carry = 0, nfound = 0;                     // markers before this tile
+    bool stopped = false;
+    int par = 0;
+    for (int64_t base = sb; base < fe; base += kLocTile, par ^= 1) {
+        const int64_t p0 = base + (int64_t)kLocPer * tid;
+        uint32_t b[kLocPer + 1];
+#pragma unroll
+        for (int i = 0; i <= kLocPer; i++)
+            b[i] = p0 + i < fe ? bytes[p0 + i] : 0u;
+        uint32_t mask = 0;
+#pragma unroll
+        for (int i = 0; i < kLocPer; i++)
+            if (b[i] == 0xFFu && b[i + 1] != 0u && b[i + 1] != 0xFFu)
+                mask |= 1u << i;
+        const int mine = __popc(mask);
+        const int incl = wave_inclusive_i(mine, lane);
+        if (lane == kWave - 1)
+            wave_count[par][wave] = incl;
+        __syncthreads();
+        int before = 0, tile = 0;
+#pragma unroll
+        for (int k = 0; k < kLocWaves; k++) {
+            before += k < wave ? wave_count[par][k] : 0;
+            tile += wave_count[par][k];
+        }
+        if (tile == 0)
+            continue;
+        const long long first = carry + before + incl - mine;
+        long long bad = kNone, k = first;
+#pragma unroll
+        for (int i = 0; i < kLocPer; i++)
+            if (mask >> i & 1u) {
+                if (b[i + 1] != 0xD0u + (uint32_t)(k & 7) && bad == kNone)
+                    bad = k;
+                k++;
+            }
+        bad = wave_min_ll(bad);
+        if (lane == 0)
+            wave_bad[par][wave] = bad;
+        __syncthreads();
+        long long kbad = kNone;
+#pragma unroll
+        for (int i = 0; i < kLocWaves; i++)
+            kbad = wave_bad[par][i] < kbad ? wave_bad[par][i] : kbad;
+        k = first;
+#pragma unroll
+        for (int i = 0; i < kLocPer; i++)
+            if (mask >> i & 1u) {
+                if (k <= kbad) {
+                    if (k < nseg)
+                        tab[2 * k + 1] = p0 + i;
+                    if (k < kbad && k + 1 < nseg)
+                        tab[2 * (k + 1)] = p0 + i + 2;
+                    if (k == kbad)
+                        terminator = (int32_t)b[i + 1];
+                }
+                k++;
+            }
+        if (kbad != kNone) {
+            stopped = true;
+            nfound = kbad + 1;
+            break;
+        }
+        carry += tile;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (!stopped) {                                  // the file ends inside the last segment
+            nfound = carry + 1;
+            if (carry < nseg)
+                tab[2 * carry + 1] = fe;
+        }
+        const bool good = stopped && terminator == 0xD9 && nfound == nseg;
+        status[f] = good ? 0 : va_jpeg::kStatusMarker;
+    }
+}
+
+struct EntropyArgs {
+    const uint8_t *bytes;
+    const int64_t *table;
+    const va_jpeg::HuffDecode *huff;     // [c][2]: the DC and the AC table of each component
+    int16_t *coef;
+    int32_t *status;
+    int64_t nsegs;                       // segments of the chunk
+    int nseg, ri, bx, by;
+};
+
+template <int C>
+__global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
+{
+    __shared__ va_jpeg::HuffDecode tabs[2 * C];
+    static_assert(sizeof(va_jpeg::HuffDecode) % 4 == 0, "the tables are copied as words");
+    {
+        constexpr int words = 2 * C * (int)sizeof(va_jpeg::HuffDecode) / 4;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.huff);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(tabs);
+        for (int i = threadIdx.x; i < words; i += kEntBlock)
+            dst[i] = src[i];
+    }
+    __syncthreads();
+    const int64_t s = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
+    if (s >= a.nsegs)
+        return;
+    const int64_t f = s / a.nseg;
+    const int j = (int)(s % a.nseg);
+    const int64_t begin = a.table[2 * s], end = a.table[2 * s + 1];
+    const int64_t mcus = (int64_t)a.bx * a.by;
+    const int64_t m0 = (int64_t)j * a.ri, m1 = m0 + a.ri < mcus ? m0 + a.ri : mcus;
+    bool dead = begin < 0 || end < begin;
+    int32_t st = 0;
+    va_jpeg::BitReader r = va_jpeg::open_bits(a.bytes, dead ? 0 : begin, dead ? 0 : end);
+    int pred[C];
+#pragma unroll
+    for (int ch = 0; ch < C; ch++)
+        pred[ch] = 0;
+    for (int64_t m = m0; m < m1; m++) {
+        const int64_t row = m / a.bx, col = m % a.bx;
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) {
+            int16_t *blk = a.coef + ((((f * C + ch) * a.by + row) * a.bx + col) << 6);
+            uint4 *blk16 = reinterpret_cast<uint4 *>(blk);
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                blk16[i] = make_uint4(0, 0, 0, 0);
+            if (dead)
+                continue;
+            const int32_t e = va_jpeg::decode_block(r, tabs[2 * ch], tabs[2 * ch + 1], pred[ch],
+                                                    [&](int i, int v) { blk[i] = (int16_t)v; });
+            if (e) {
+                st = e;
+                dead = true;
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    blk16[i] = make_uint4(0, 0, 0, 0);
+            }
+        }
+    }
+    if (st)
+        atomicOr(&a.status[f], st);
+}
+
+struct ReconArgs {
+    const int16_t *coef;
+    const uint8_t *qtables;              // [c][64], natural order
+    uint8_t *out;
+    int64_t nmcus;                       // MCUs of the chunk
+    int h, w, bx, by;
+};
+
+struct BlockBytes {
+    uint32_t w[16];
+};
+
+// the 64 samples of one block as bytes in natural order.  Not inlined: a colour MCU calls it three times, and with the
+// three transforms scheduled into one another the kernel needs more registers than the vector file holds
+__device__ __noinline__ BlockBytes block_samples(const int16_t *__restrict__ coef, const uint8_t *q)
+{
+    const uint4 *src = reinterpret_cast<const uint4 *>(coef);
+    int16_t cf[64];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint4 v = src[i];
+        const uint32_t word[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            cf[8 * i + 2 * k] = (int16_t)(word[k] & 0xFFFFu);
+            cf[8 * i + 2 * k + 1] = (int16_t)(word[k] >> 16);
+        }
+    }
+    uint8_t smp[64];
+    va_jpeg::inverse_block(cf, q, smp);
+    BlockBytes out;
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        out.w[i] = (uint32_t)smp[4 * i] | (uint32_t)smp[4 * i + 1] << 8 | (uint32_t)smp[4 * i + 2] << 16
+                   | (uint32_t)smp[4 * i + 3] << 24;
+    return out;
+}
+
+template <int C>
+__global__ void __launch_bounds__(kRecBlock) jpeg_reconstruct_kernel(ReconArgs a)
+{
+    __shared__ uint8_t qt[C][64];
+    for (int i = threadIdx.x; i < C * 64; i += kRecBlock)
+        qt[i / 64][i % 64] = a.qtables[i];
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * kRecBlock + threadIdx.x;
+    if (idx >= a.nmcus)
+        return;
+    const int64_t per = (int64_t)a.bx * a.by;
+    const int64_t f = idx / per;
+    const int row = (int)((idx % per) / a.bx), col = (int)((idx % per) % a.bx);
+
+    uint32_t px[C][16];                  // per component the 64 samples as bytes, natural order
+#pragma unroll
+    for (int ch = 0; ch < C; ch++) {
+        const BlockBytes blk = block_samples(a.coef + ((((f * C + ch) * a.by + row) * a.bx + col) << 6), qt[ch]);
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            px[ch][i] = blk.w[i];
+    }
+
+    const int x0 = col * 8;
+    const bool complete = x0 + 8 <= a.w;
+#pragma unroll
+    for (int y = 0; y < 8; y++) {
+        const int gy = row * 8 + y;
+        if (gy >= a.h)
+            break;
+        uint8_t *dst = a.out + ((f * a.h + gy) * a.w + x0) * C;
+        uint32_t o[2 * C];
+        if constexpr (C == 1) {
+            o[0] = px[0][2 * y];
+            o[1] = px[0][2 * y + 1];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2 * C; i++)
+                o[i] = 0;
+#pragma unroll
+            for (int x = 0; x < 8; x++) {
+                const int sh = 8 * (x & 3), wi = 2 * y + (x >> 2);
+                int r, g, b;
+                va_jpeg::rgb_of((int)(px[0][wi] >> sh & 255u), (int)(px[1][wi] >> sh & 255u),
+                                (int)(px[2][wi] >> sh & 255u), r, g, b);
+                o[(3 * x) / 4] |= (uint32_t)r << (8 * ((3 * x) % 4));
+                o[(3 * x + 1) / 4] |= (uint32_t)g << (8 * ((3 * x + 1) % 4));
+                o[(3 * x + 2) / 4] |= (uint32_t)b << (8 * ((3 * x + 2) % 4));
+            }
+        }
+        if (complete && ((uintptr_t)dst & 7) == 0) {
+#pragma unroll
+            for (int i = 0; i < C; i++)
+                reinterpret_cast<uint2 *>(dst)[i] = make_uint2(o[2 * i], o[2 * i + 1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8 * C; i++)
+                if (x0 + i / C < a.w)
+                    dst[i] = (uint8_t)(o[i / 4] >> (8 * (i % 4)));
+        }
+    }
+}
+
+struct DecodeLayout {
+    size_t table, coef, total;
+};
+
+DecodeLayout decode_layout(int64_t n, int h, int w, int c, int ri)
+{
+    const int64_t mcus = (int64_t)((h + 7) / 8) * ((w + 7) / 8), nseg = (mcus + ri - 1) / ri;
+    Carve carve;
+    DecodeLayout l;
+    l.table = carve.take((size_t)n * nseg * 2 * sizeof(int64_t));
+    l.coef = carve.take((size_t)n * c * mcus * 64 * sizeof(int16_t));
+    l.total = carve.total;
+    return l;
+}
+
+}  // namespace
+
+size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri) { return decode_layout(n, h, w, c, ri).total; }
+
+// the frames of one chunk: as many as the workspace holds, and no more than one launch's grid takes
+int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, size_t workspace_bytes)
+{
+    const int64_t mcus = (int64_t)((h + 7) / 8) * ((w + 7) / 8);
+    const int64_t grid_cap = (((int64_t)1 << 31) - kRecBlock) / mcus;
+    const int64_t most = n < grid_cap ? n : grid_cap;
+    if (most < 1 || decode_layout(most, h, w, c, ri).total <= workspace_bytes)
+        return most;
+    // k frames need at most k times one frame's regions, and a little less: each region rounds up once
+    const size_t one = decode_layout(1, h, w, c, ri).total;
+    int64_t k = (int64_t)(workspace_bytes / one);
+    k = k < most ? k : most;
+    while (k < most && decode_layout(k + 1, h, w, c, ri).total <= workspace_bytes)
+        k++;
+    return k;
+}
+
+int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                       int c, int ri, const uint8_t *qtables, const void *huff, uint8_t *out, int32_t *status, void *ws,
+                       size_t workspace_bytes, hipStream_t st)
+{
+    const int by = (h + 7) / 8, bx = (w + 7) / 8;
+    const int64_t mcus = (int64_t)by * bx;
+    const int nseg = (int)((mcus + ri - 1) / ri);
+    const int64_t chunk = jpeg_decode_chunk(n, h, w, c, ri, workspace_bytes);
+    const DecodeLayout l = decode_layout(chunk, h, w, c, ri);
+    int64_t *table = at<int64_t>(ws, l.table);
+    int16_t *coef = at<int16_t>(ws, l.coef);
+    for (int64_t f0 = 0; f0 < n; f0 += chunk) {
+        const int64_t k = chunk < n - f0 ? chunk : n - f0;
+        hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
+                           scan_begin + f0, nseg, table, status + f0);
+        VA_LAUNCH_CHECK("jpeg_locate_kernel");
+        const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
+                            k * nseg, nseg, ri, bx, by};
+        const dim3 egrid((unsigned)((k * nseg + kEntBlock - 1) / kEntBlock));
+        if (c == 1)
+            hipLaunchKernelGGL(jpeg_entropy_kernel<1>, egrid, dim3(kEntBlock), 0, st, e);
+        else
+            hipLaunchKernelGGL(jpeg_entropy_kernel<3>, egrid, dim3(kEntBlock), 0, st, e);
+        VA_LAUNCH_CHECK("jpeg_entropy_kernel");
+        const ReconArgs r{coef, qtables, out + (size_t)f0 * h * w * c, k * mcus, h, w, bx, by};
+        const dim3 rgrid((unsigned)((k * mcus + kRecBlock - 1) / kRecBlock));
+        if (c == 1)
+            hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, rgrid, dim3(kRecBlock), 0, st, r);
+        else
+            hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, rgrid, dim3(kRecBlock), 0, st, r);
+        VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
+    }
+    return VA_OK;
+}
+
+}  // namespace va

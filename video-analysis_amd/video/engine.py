@@ -118,37 +118,36 @@ class FrameEngine(object):
             b = self._dev[name] = DeviceBuffer(nbytes)
         return b
 
-    def run(self, frames, want=("mask", "labels", "counts")):
-        """frames: (n, H, W[, C]) array; returns a dict with the requested outputs among
-        'filtered', 'mask', 'labels', 'counts', 'stats'"""
-        arr = np.ascontiguousarray(frames, self.dtype)
+    def _check_batch(self, shape, n, want):
         in_shape = self.prepare["src_shape"] if self.prepare else self.frame_shape
-        if arr.shape[1:] != in_shape:
-            raise ValueError("frames of shape %r do not match %r" % (arr.shape[1:], in_shape))
-        n = arr.shape[0]
+        if tuple(shape) != tuple(in_shape):
+            raise ValueError("frames of shape %r do not match %r" % (tuple(shape), in_shape))
         if n > self.max_batch:
             raise ValueError("batch of %d exceeds max_batch=%d" % (n, self.max_batch))
         want = set(want)
         unknown = want - {"filtered", "mask", "labels", "counts", "stats"}
         if unknown:
             raise ValueError("unknown outputs %r" % sorted(unknown))
+        return want
+
+    def _run_resident(self, raw_ptr, n, want):
+        """the chain on `n` source frames at device address `raw_ptr` (raw frames where the engine has prepare
+        stages: crop / monochrome / normalize run first, one device pass, no host round trip) and the downloads
+        of the outputs in `want`"""
         px = self.width * self.height
-        if self.prepare:                    # crop / monochrome / normalize: one device pass, no host round trip
+        frame_bytes = px * self.channels * self.dtype.itemsize
+        src_ptr = raw_ptr
+        if self.prepare:
             pr = self.prepare
-            raw = self._buf("raw", arr.nbytes)
-            raw.upload(arr)
-            src = self._buf("src", n * px * self.channels)
+            src = self._buf("src", n * frame_bytes)
             nm = pr["norm"] or (0.0, 0.0, 0.0, 0.0)
-            check(self._lib.va_prepare_u8(raw.ptr, src.ptr, n, pr["h0"], pr["w0"], pr["c0"], pr["rect"][0],
+            check(self._lib.va_prepare_u8(raw_ptr, src.ptr, n, pr["h0"], pr["w0"], pr["c0"], pr["rect"][0],
                                           pr["rect"][1], pr["rect"][2], pr["rect"][3], pr["mono"],
                                           1 if pr["norm"] else 0, nm[0], nm[1], nm[2], nm[3], None))
-            arr = np.empty((n,) + self.frame_shape, self.dtype)     # (shape of the prepared frames)
-        else:
-            src = self._buf("src", arr.nbytes)
-            src.upload(arr)
+            src_ptr = src.ptr
         ptr = {}
         if "filtered" in want:
-            ptr["filtered"] = self._buf("filtered", arr.nbytes)
+            ptr["filtered"] = self._buf("filtered", n * frame_bytes)
         if "mask" in want:
             ptr["mask"] = self._buf("mask", n * px)
         if "labels" in want:
@@ -158,12 +157,12 @@ class FrameEngine(object):
         if "stats" in want:
             ptr["stats"] = self._buf("stats", n * max(self.max_labels, 1) * _hip.STATS_STRIDE * 8)
         g = lambda k: ptr[k].ptr if k in ptr else None
-        self.run_device(src.ptr, n, g("filtered"), g("mask"), g("labels"), g("counts"), g("stats"))
+        self.run_device(src_ptr, n, g("filtered"), g("mask"), g("labels"), g("counts"), g("stats"))
         if getattr(self, "_overlap", False):
             self.fence(None)                # the downloads below read what the side stream writes
         out = {}
         if "filtered" in want:
-            out["filtered"] = ptr["filtered"].download(arr.shape, self.dtype)
+            out["filtered"] = ptr["filtered"].download((n,) + self.frame_shape, self.dtype)
         if "mask" in want:
             out["mask"] = ptr["mask"].download((n, self.height, self.width), np.uint8)
         if "labels" in want:
@@ -173,6 +172,24 @@ class FrameEngine(object):
         if "stats" in want:
             out["stats"] = ptr["stats"].download((n, self.max_labels, _hip.STATS_STRIDE), np.int64)
         return out
+
+    def run(self, frames, want=("mask", "labels", "counts")):
+        """frames: (n, H, W[, C]) array; returns a dict with the requested outputs among
+        'filtered', 'mask', 'labels', 'counts', 'stats'"""
+        arr = np.ascontiguousarray(frames, self.dtype)
+        want = self._check_batch(arr.shape[1:], arr.shape[0], want)
+        raw = self._buf("raw" if self.prepare else "src", arr.nbytes)
+        raw.upload(arr)
+        return self._run_resident(raw.ptr, arr.shape[0], want)
+
+    def run_frames(self, device_frames, want=("mask", "labels", "counts")):
+        """`run` on a stack that is already on the device (an `ops.DeviceFrames`, e.g. what `ops.jpeg_decode(...,
+        keep=True)` or `VideoMJPEG.get_device_frames` return): the same dict of outputs, and no pixel is uploaded.
+        The stack stays the caller's."""
+        if self.dtype != np.uint8:
+            raise TypeError("run_frames takes uint8 device frames, the engine works on %s" % self.dtype)
+        want = self._check_batch(device_frames.shape[1:], device_frames.n, want)
+        return self._run_resident(device_frames.buf.ptr, device_frames.n, want)
 
     # ------------------------------------------------------------------ per-stage timing
     def profile(self, enable=True, every=1):

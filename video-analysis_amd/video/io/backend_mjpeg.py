@@ -196,7 +196,17 @@ class VideoMJPEG(VideoBase):
 
     seekable = True
 
+    DEVICE_BATCH = 32                    # frames per decoder call with parameters={"decoder": "device"}
+
     def __init__(self, filename, parameters=None):
+        """parameters: {"decoder": "pillow"} (the default: get_frame decodes one frame on the host through Pillow) or
+        {"decoder": "device"}: get_frame and iteration serve frames from batches of DEVICE_BATCH frames decoded by
+        one ops.jpeg_decode call each, through a cache of one batch"""
+        parameters = dict(parameters or {})
+        self._decoder = parameters.pop("decoder", "pillow")
+        if self._decoder not in ("pillow", "device"):
+            raise ValueError("the decoder is 'pillow' or 'device', got %r" % (self._decoder,))
+        self._batch_start, self._batch = 0, None
         self.filename = os.fspath(filename)
         self._file = open(self.filename, "rb")
         try:
@@ -286,7 +296,41 @@ class VideoMJPEG(VideoBase):
         self._file.seek(pos)
         return self._file.read(size)
 
+    def _streams(self, start, stop):
+        count = len(self._frames)
+        start = 0 if start is None else start + count if start < 0 else start
+        stop = count if stop is None else stop + count if stop < 0 else stop
+        if not 0 <= start <= stop <= count:
+            raise IndexError("frames %r .. %r are out of range (the video has %d)" % (start, stop, count))
+        return [self.get_frame_bytes(i) for i in range(start, stop)]
+
+    def get_frames(self, start=None, stop=None):
+        """the frames start .. stop - 1 as one uint8 array (n, h, w) or (n, h, w, 3), decoded on the device by one
+        ops.jpeg_decode call (no Pillow); the frames are as stored, without `_process_frame`"""
+        from .. import ops
+        return ops.jpeg_decode(self._streams(start, stop), color=self.is_color)
+
+    def get_device_frames(self, start=None, stop=None):
+        """the frames start .. stop - 1 as an ops.DeviceFrames that stays on the device (the caller releases it): only
+        the stored bytes cross the bus"""
+        from .. import ops
+        return ops.jpeg_decode(self._streams(start, stop), color=self.is_color, keep=True)
+
+    def _device_frame(self, index):
+        count = len(self._frames)
+        index = index + count if index < 0 else index
+        if index < 0 or index >= count:
+            raise IndexError("frame %d is out of range" % index)
+        if self._batch is None or not self._batch_start <= index < self._batch_start + len(self._batch):
+            start = index - index % self.DEVICE_BATCH
+            self._batch = None
+            self._batch = self.get_frames(start, min(start + self.DEVICE_BATCH, count))
+            self._batch_start = start
+        return self._process_frame(self._batch[index - self._batch_start].copy())
+
     def get_frame(self, index):
+        if self._decoder == "device":
+            return self._device_frame(index)
         data = self.get_frame_bytes(index)
         try:
             from PIL import Image

@@ -2351,3 +2351,249 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
         return blob, offsets
     raw = blob.tobytes()
     return [raw[offsets[k]:offsets[k + 1]] for k in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------ Motion-JPEG decoding
+JPEG_STATUS_BAD_CODE, JPEG_STATUS_OVERRUN, JPEG_STATUS_TRUNCATED, JPEG_STATUS_MARKER = 1, 2, 4, 8    # VA_JPEG_STATUS_*
+_JPEG_STATUS_NAMES = ((JPEG_STATUS_BAD_CODE, "bad code"), (JPEG_STATUS_OVERRUN, "overrun"),
+                      (JPEG_STATUS_TRUNCATED, "truncated"), (JPEG_STATUS_MARKER, "marker sequence"))
+JPEG_HUFF_DECODE_BYTES = 1416                  # VA_JPEG_HUFF_DECODE_BYTES
+JPEG_DECODE_WORKSPACE_MAX = 1 << 30            # a batch whose coefficients need more is decoded in chunks of frames
+_JPEG_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+                   0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic sequential",
+                   0xCA: "arithmetic progressive", 0xCB: "arithmetic lossless", 0xCD: "arithmetic differential",
+                   0xCE: "arithmetic differential progressive", 0xCF: "arithmetic differential lossless"}
+
+
+def jpeg_parse_header(data):
+    """what the header of one stored JPEG file says, or a ValueError that names what the decoder does not take
+    ("Motion-JPEG decoding": baseline SOF0 with 8-bit samples, 1 component or 3 of 1 x 1 sampling,
+    8-bit DQT, any valid DHT, any DRI, one scan).  Returns a dict: h, w, c, ri (the restart interval in MCUs; the
+    MCUs of the frame where DRI is absent or 0), nseg, scan_begin (the byte behind the SOS header), qtables (c, 64)
+    uint8 in natural order, huff: per component ((BITS, HUFFVAL) of its DC table, of its AC table) (host only)"""
+    what = "jpeg_parse_header"
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("%s: no SOI at the start of the file" % what)
+    i, qt, huff, sof, ri = 2, {}, {}, None, 0
+    while True:
+        if i + 4 > len(data):
+            raise ValueError("%s: the file ends before SOS" % what)
+        if data[i] != 0xFF:
+            raise ValueError("%s: a marker is expected at byte %d, found %02x" % (what, i, data[i]))
+        m = data[i + 1]
+        if m == 0xFF:                               # a fill byte
+            i += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:          # markers without a segment
+            i += 2
+            continue
+        if m in (0xD8, 0xD9):
+            raise ValueError("%s: marker %02x before SOS" % (what, m))
+        length = (data[i + 2] << 8) | data[i + 3]
+        if length < 2 or i + 2 + length > len(data):
+            raise ValueError("%s: the segment of marker %02x at byte %d leaves the file" % (what, m, i))
+        p = data[i + 4:i + 2 + length]
+        if m == 0xDB:
+            while p:
+                if p[0] >> 4:
+                    raise ValueError("%s: a 16-bit quantisation table; 8-bit tables are decoded" % what)
+                if len(p) < 65 or (p[0] & 15) > 3:
+                    raise ValueError("%s: a damaged DQT segment" % what)
+                table = np.zeros(64, np.uint8)
+                table[list(_JPEG_ZIGZAG)] = np.frombuffer(p[1:65], np.uint8)
+                qt[p[0] & 15], p = table, p[65:]
+        elif m == 0xC4:
+            while p:
+                if len(p) < 17:
+                    raise ValueError("%s: a damaged DHT segment" % what)
+                bits = tuple(p[1:17])
+                n = sum(bits)
+                if (p[0] >> 4) > 1 or (p[0] & 15) > 3 or n > 256 or len(p) < 17 + n:
+                    raise ValueError("%s: a damaged DHT segment" % what)
+                code = 0
+                for k in range(16):
+                    code += bits[k]
+                    if code > (1 << (k + 1)):
+                        raise ValueError("%s: a DHT segment with more codes of %d bits than there are" % (what, k + 1))
+                    code <<= 1
+                huff[p[0]], p = (bits, tuple(p[17:17 + n])), p[17 + n:]
+        elif m == 0xC0 or m in _JPEG_SOF_NAMES:
+            if len(p) < 6:
+                raise ValueError("%s: a damaged frame header" % what)
+            precision, h, w, nc = p[0], (p[1] << 8) | p[2], (p[3] << 8) | p[4], p[5]
+            if precision != 8:
+                raise ValueError("%s: sample precision %d; only 8-bit precision is decoded" % (what, precision))
+            if m != 0xC0:
+                raise ValueError("%s: %s mode (SOF%d); only baseline sequential is decoded"
+                                 % (what, _JPEG_SOF_NAMES[m], m - 0xC0))
+            if sof is not None:
+                raise ValueError("%s: two frame headers" % what)
+            if nc not in (1, 3) or len(p) < 6 + 3 * nc:
+                raise ValueError("%s: %d components; 1 or 3 are decoded" % (what, nc))
+            comps = [(p[6 + 3 * k], p[7 + 3 * k], p[8 + 3 * k]) for k in range(nc)]
+            for _, hv, _ in comps:
+                if hv != 0x11 and nc > 1:
+                    raise ValueError("%s: sampling factors %d x %d (chroma subsampling such as 4:2:0 or 4:2:2); only "
+                                     "1 x 1 sampling is decoded" % (what, hv >> 4, hv & 15))
+            if h == 0:
+                raise ValueError("%s: a frame height of 0 (DNL) is not decoded" % what)
+            if w == 0:
+                raise ValueError("%s: a frame width of 0" % what)
+            sof = (h, w, comps)
+        elif m == 0xCC:
+            raise ValueError("%s: arithmetic coding (DAC) is not decoded" % what)
+        elif m == 0xDC:
+            raise ValueError("%s: DNL is not decoded" % what)
+        elif m == 0xDD:
+            if len(p) < 2:
+                raise ValueError("%s: a damaged DRI segment" % what)
+            ri = (p[0] << 8) | p[1]
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("%s: SOS before the frame header" % what)
+            h, w, comps = sof
+            ns = p[0] if p else 0
+            if len(p) < 1 + 2 * ns + 3:
+                raise ValueError("%s: a damaged scan header" % what)
+            if ns != len(comps) or [p[1 + 2 * k] for k in range(ns)] != [cid for cid, _, _ in comps]:
+                raise ValueError("%s: more than one scan: this scan holds %d of the %d components"
+                                 % (what, ns, len(comps)))
+            if (p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns]) != (0, 63, 0):
+                raise ValueError("%s: a scan with Ss %d, Se %d, Ah/Al %02x is not baseline sequential"
+                                 % (what, p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns]))
+            tables = []
+            for k, (_, _, tq) in enumerate(comps):
+                td, ta = p[2 + 2 * k] >> 4, p[2 + 2 * k] & 15
+                if tq not in qt:
+                    raise ValueError("%s: quantisation table %d is not defined" % (what, tq))
+                if td not in huff or (0x10 | ta) not in huff:
+                    raise ValueError("%s: Huffman table %d / %d is not defined" % (what, td, ta))
+                tables.append((huff[td], huff[0x10 | ta]))
+            mcus = ((h + 7) // 8) * ((w + 7) // 8)
+            ri = ri if ri else mcus
+            return dict(h=h, w=w, c=len(comps), ri=ri, nseg=(mcus + ri - 1) // ri, scan_begin=i + 2 + length,
+                        qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
+        i += 2 + length
+
+
+def _jpeg_decode_table(bits, vals):
+    """one Huffman table as the device reads it (va_jpeg_decode_math.h, HuffDecode): look[9 bits] = length << 8 |
+    symbol of the codes of at most 9 bits, maxcode[l] and valoff[l] of T.81 F.2.2.3 for the longer ones, the
+    symbols"""
+    look, maxcode = np.zeros(512, np.uint16), np.full(17, -1, np.int32)
+    valoff, symbols = np.zeros(17, np.int32), np.zeros(256, np.uint8)
+    symbols[:len(vals)] = vals
+    code = k = 0
+    for length in range(1, 17):
+        count = bits[length - 1]
+        if count:
+            valoff[length] = k - code
+            maxcode[length] = code + count - 1
+            if length <= 9:
+                for j in range(count):
+                    look[(code + j) << (9 - length):(code + j + 1) << (9 - length)] = (length << 8) | vals[k + j]
+            k, code = k + count, code + count
+        code <<= 1
+    out = look.tobytes() + maxcode.tobytes() + valoff.tobytes() + symbols.tobytes()
+    assert len(out) == JPEG_HUFF_DECODE_BYTES
+    return out
+
+
+def _jpeg_header_key(head):
+    return (head["h"], head["w"], head["c"], head["ri"], head["qtables"].tobytes(), tuple(head["huff"]))
+
+
+def jpeg_decode_groups(heads):
+    """[(first, stop)] of the runs of consecutive frames whose headers agree in size, components, restart interval
+    and tables: each run is one va_jpeg_decode_u8 call (host only)"""
+    groups, first = [], 0
+    keys = [_jpeg_header_key(head) for head in heads]
+    for k in range(1, len(keys) + 1):
+        if k == len(keys) or keys[k] != keys[first]:
+            groups.append((first, k))
+            first = k
+    return groups if keys else []
+
+
+def jpeg_status_text(status):
+    return " | ".join(name for bit, name in _JPEG_STATUS_NAMES if status & bit) or "ok"
+
+
+def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
+    """the frames of a batch of stored baseline JPEG files ("Motion-JPEG decoding"); the pixels are
+    pinned and equal the restatement's.  streams: a list of `bytes`, or the (blob, offsets) pair that
+    jpeg_encode(ret_packed=True) returns.  Every header is parsed on the host (jpeg_parse_header, with its
+    refusals); consecutive frames with identical headers go into one va_jpeg_decode_u8 call each, whose bytes are
+    uploaded once; all frames must have one shape (ValueError otherwise).  color: None takes the components from the
+    files; True / False must agree with them.
+    Returns the uint8 array (n, h, w) or (n, h, w, 3) RGB; keep=True: a DeviceFrames that is the caller's (nothing but
+    the status words is downloaded).  A frame whose status word is not 0 raises a ValueError that names the first
+    such frame and its bits; ret_status=True returns (frames, int32 status (n,)) in place of raising: blocks at and
+    behind an error in their segment decode as sample 128."""
+    what = "jpeg_decode"
+    if (isinstance(streams, tuple) and len(streams) == 2 and isinstance(streams[0], np.ndarray)
+            and streams[0].dtype == np.uint8):
+        blob = np.ascontiguousarray(streams[0]).ravel()
+        offsets = np.asarray(streams[1], np.int64).ravel()
+        if len(offsets) < 1 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > len(blob):
+            raise ValueError("%s: the offsets do not lie in the blob in ascending order" % what)
+    else:
+        files = [bytes(s) for s in streams]
+        blob = np.frombuffer(b"".join(files), np.uint8)
+        offsets = np.concatenate([[0], np.cumsum([len(s) for s in files])]).astype(np.int64)
+    n = len(offsets) - 1
+    heads = []
+    for k in range(n):
+        try:
+            heads.append(jpeg_parse_header(blob[offsets[k]:offsets[k + 1]].tobytes()))
+        except ValueError as err:
+            raise ValueError("%s: frame %d: %s" % (what, k, err))
+    if n == 0:
+        frames = np.zeros((0, 0, 0), np.uint8)
+        if keep:
+            frames = DeviceFrames(_take(1), 0, 0, 0, 1)
+        return (frames, np.zeros(0, np.int32)) if ret_status else frames
+    h, w, c = heads[0]["h"], heads[0]["w"], heads[0]["c"]
+    for k, head in enumerate(heads):
+        if (head["h"], head["w"], head["c"]) != (h, w, c):
+            raise ValueError("%s: mixed shapes: frame %d is %d x %d x %d, frame 0 is %d x %d x %d"
+                             % (what, k, head["w"], head["h"], head["c"], w, h, c))
+    if color is not None and (c == 3) != bool(color):
+        raise ValueError("%s: color=%r with files of %d component(s)" % (what, color, c))
+    frame_bytes = h * w * c
+    L = _hip.lib()
+    out = _take(max(n * frame_bytes, 1))
+    try:
+        with _Lease.on(stream) as d:
+            status_buf = d.take(4 * n)
+            for first, stop in jpeg_decode_groups(heads):
+                k, head = stop - first, heads[first]
+                base = int(offsets[first])
+                src = d.upload(blob[base:max(int(offsets[stop]), base + 1)])
+                meta = np.concatenate([offsets[first:stop + 1] - base,
+                                       np.array([hd["scan_begin"] for hd in heads[first:stop]], np.int64)])
+                mb = d.upload(meta)
+                tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
+                cb = d.upload(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8))
+                one = int(L.va_jpeg_decode_workspace_bytes(1, h, w, c, head["ri"]))
+                need = int(L.va_jpeg_decode_workspace_bytes(k, h, w, c, head["ri"]))
+                room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
+                ws = d.take(room)
+                check(L.va_jpeg_decode_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], cb.ptr,
+                                          cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes,
+                                          status_buf.ptr + 4 * first, ws.ptr, room, stream))
+            status = status_buf.download((n,), np.int32, stream)
+            if status.any() and not ret_status:
+                bad = int(np.flatnonzero(status)[0])
+                raise ValueError("%s: frame %d does not decode: %s (status %d); %d of %d frames have errors"
+                                 % (what, bad, jpeg_status_text(int(status[bad])), status[bad],
+                                    int(np.count_nonzero(status)), n))
+            frames = DeviceFrames(out, n, h, w, c) if keep else out.download(
+                (n, h, w) + ((3,) if c == 3 else ()), np.uint8, stream)
+    except Exception:
+        _give(out)
+        raise
+    if not keep:
+        _give(out)
+    return (frames, status) if ret_status else frames
