@@ -216,7 +216,8 @@ int launch_gaussian(const GaussPlan &g, const void *src, void *dst, uint32_t *bi
                     float *bg_out = nullptr, int64_t n_seen = 0, double rate = 0.0);
 
 // recip_scratch: bg_scratch_bytes(n) bytes of device memory for the per-frame reciprocals of the
-// division-free running mean of batches above 256 frames (nullptr: the plain-division kernel is used);
+// division-free running mean of batches above 256 frames (nullptr: the plain-division kernel is used, as it
+// is for n_seen + n > 2^53, where the division-free kernels' float64 frame counter stops being exact);
 // mean_in_u8_range: the caller vouches that the running-mean state lies in [0, 255] (saturation-free kernel)
 size_t bg_scratch_bytes(int n);
 int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, int64_t n_seen,

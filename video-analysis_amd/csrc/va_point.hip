@@ -119,63 +119,69 @@ __device__ __forceinline__ double clear_low9(double y)        // (uniform operan
     return __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, y) & ~0x1FFull);
 }
 
-// BOUNDED: the caller vouches that every mean lies in [0, 255] (true for a state that started at zero or
-// inside that range: a mean of uint8 values stays there up to rounding), so |frame - mean| < 256 and the
-// saturation of the difference -- one of the 14 operations per pixel -- can go
-// SPLIT (RECIP = RecipArgs only): the second quotient in two operations, see RecipArgs::lo
-template <int V, typename RECIP, bool BOUNDED, bool SPLIT = false>
-__global__ void __launch_bounds__(kBlock)
-bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__ diff,
-                       double *__restrict__ mean, const RECIP recip, long long n_seen, int n, size_t px)
+// The byte lanes of the frame and difference streams, written out so that they cost one vector instruction per
+// pixel going in (and / bfe / bfe / shift) and three per four pixels coming out (three byte permutes); a
+// uint8_t[V] + memcpy compiles to a chain of 16-bit shifts, bit-ops and a sub-dword or instead.
+__device__ __forceinline__ unsigned byte_lane(unsigned w, int k)
 {
-    size_t i0 = ((size_t)blockIdx.x * kBlock + threadIdx.x) * V;
-    if (i0 >= px)
-        return;
-    double m[V];
-#pragma unroll
-    for (int k = 0; k < V; k++)
-        m[k] = mean[i0 + k];
-    typedef unsigned int v2u __attribute__((ext_vector_type(V / 4)));
+    return k == 3 ? w >> 24 : (w >> (8 * k)) & 0xFFu;
+}
+__device__ __forceinline__ unsigned pack_bytes(const int *d)   // the low bytes of d[0..3], d[0] lowest
+{
+    // v_perm_b32: selectors 0-3 take bytes of the second operand, 4-7 of the first
+    const unsigned lo = __builtin_amdgcn_perm((unsigned)d[1], (unsigned)d[0], 0x0C0C0400u);
+    const unsigned hi = __builtin_amdgcn_perm((unsigned)d[3], (unsigned)d[2], 0x0C0C0400u);
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
+constexpr int kAhead = 8;   // frames per prefetch group, see bg_mean_u8_fast_kernel
+
+template <int V> struct BgGroup {
+    typedef unsigned int vec __attribute__((ext_vector_type(V / 4)));
+    vec v[kAhead];
     // frames and differences are one-touch streams: non-temporal loads/stores keep them out of L2.
-    // Frames are walked in groups of kAhead: the next group's loads are issued before this
-    // group's arithmetic (only 2 waves per SIMD exist at 16 px per thread), so a load has kAhead
-    // frame steps to arrive and a CU keeps 8 waves x 8 KB in flight (measured per 256 x 1080p:
-    // 4 frames 0.253 ms, 8 frames 0.241, 16 frames 0.250 -- registers cost the third wave).
-    constexpr int kAhead = 8;
-    const uint8_t *src = frames + i0;
-    v2u cur[kAhead], nxt[kAhead];
-#pragma unroll
-    for (int j = 0; j < kAhead; j++)
-        nxt[j] = __builtin_nontemporal_load(
-            reinterpret_cast<const v2u *>(src + (size_t)min(j, n - 1) * px));
-    for (int f0 = 0; f0 < n; f0 += kAhead) {
+    // CLAMP: the group may reach past the batch (its surplus slots re-read the last frame and are never used)
+    template <bool CLAMP>
+    __device__ __forceinline__ void load(const uint8_t *frames, size_t i0, size_t px, int f0, int n)
+    {
 #pragma unroll
         for (int j = 0; j < kAhead; j++)
-            cur[j] = nxt[j];
-        if (f0 + kAhead < n) {
+            v[j] = __builtin_nontemporal_load(reinterpret_cast<const vec *>(
+                frames + (size_t)(CLAMP ? min(f0 + j, n - 1) : f0 + j) * px + i0));
+    }
+};
+
+// The frames f0 .. f0 + cnt - 1 of one loaded group (FULL: cnt == kAhead, nothing to test per frame).  dn carries
+// the divisor n_seen + f as a double from frame to frame: + 1.0 is exact below 2^53 (launch_bg sees to that), and
+// a wave-uniform integer -> float64 conversion would run on the vector unit like everything else in float64.
+template <int V, typename RECIP, bool BOUNDED, bool SPLIT, bool DIFF, bool FULL>
+__device__ __forceinline__ void bg_mean_group(const BgGroup<V> &g, double (&m)[V], double &dn, const RECIP &recip,
+                                              int f0, int cnt, uint8_t *diff, size_t i0, size_t px)
+{
 #pragma unroll
-            for (int j = 0; j < kAhead; j++)
-                nxt[j] = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(
-                    src + (size_t)min(f0 + kAhead + j, n - 1) * px));
+    for (int j = 0; j < kAhead; j++) {
+        if (!FULL && j >= cnt)
+            break;
+        const int f = f0 + j;
+        const double dn1 = dn + 1.0;
+        const double y = recip[f];
+        double yh = 0.0, yl = 0.0;
+        if constexpr (SPLIT) {
+            yh = clear_low9(y);
+            yl = recip.lo[f];
         }
+        typename BgGroup<V>::vec out;
 #pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            const int f = f0 + j;
-            if (f >= n)
-                break;
-            uint8_t p[V], o[V];
-            memcpy(p, &cur[j], V);
-            const double dn = (double)(n_seen + f), dn1 = (double)(n_seen + f + 1);
-            const double y = recip[f];
-            double yh = 0.0, yl = 0.0;
-            if constexpr (SPLIT) {
-                yh = clear_low9(y);
-                yl = recip.lo[f];
-            }
+        for (int w = 0; w < V / 4; w++) {
+            int d[4];
 #pragma unroll
-            for (int k = 0; k < V; k++) {
-                const double fr = (double)p[k];
-                o[k] = BOUNDED ? (uint8_t)(int)fabs(fr - m[k]) : sat_u8_trunc(fabs(fr - m[k]));
+            for (int b = 0; b < 4; b++) {
+                const int k = 4 * w + b;
+                const double fr = (double)byte_lane(g.v[j][w], b);
+                if constexpr (DIFF) {
+                    const int a = (int)fabs(fr - m[k]);
+                    d[b] = BOUNDED ? a : min(a, 255);    // (sat_u8_trunc's saturation, on the integer side)
+                }
                 double q2;
                 if constexpr (SPLIT)
                     q2 = fma(fr, yl, fr * yh);
@@ -183,12 +189,59 @@ bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__
                     q2 = div_by_uniform(fr, dn1, y);
                 m[k] = div_by_uniform(m[k] * dn, dn1, y) + q2;
             }
-            if (diff) {
-                v2u v;
-                memcpy(&v, o, V);
-                __builtin_nontemporal_store(v, reinterpret_cast<v2u *>(diff + (size_t)f * px + i0));
-            }
+            if constexpr (DIFF)
+                out[w] = pack_bytes(d);
         }
+        if constexpr (DIFF)
+            __builtin_nontemporal_store(out, reinterpret_cast<typename BgGroup<V>::vec *>(diff + (size_t)f * px + i0));
+        dn = dn1;
+    }
+}
+
+// BOUNDED: the caller vouches that every mean lies in [0, 255] (true for a state that started at zero or
+// inside that range: a mean of uint8 values stays there up to rounding), so |frame - mean| < 256 and the
+// saturation of the difference -- one of the 14 operations per pixel -- can go
+// SPLIT (RECIP = RecipArgs only): the second quotient in two operations, see RecipArgs::lo
+// DIFF: the difference images are written (false: the state-only update, diff is not touched)
+// dn0 = (double)n_seen: launch_bg sends only |n_seen|, |n_seen + n| <= 2^53 here
+template <int V, typename RECIP, bool BOUNDED, bool SPLIT, bool DIFF>
+__global__ void __launch_bounds__(kBlock)
+bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__ diff,
+                       double *__restrict__ mean, const RECIP recip, double dn0, int n, size_t px)
+{
+    const size_t i0 = ((size_t)blockIdx.x * kBlock + threadIdx.x) * V;
+    if (i0 >= px)
+        return;
+    double m[V];
+#pragma unroll
+    for (int k = 0; k < V; k++)
+        m[k] = mean[i0 + k];
+    // Frames are walked in groups of kAhead: the next group's loads are issued before this
+    // group's arithmetic (only 2 waves per SIMD exist at 16 px per thread), so a load has kAhead
+    // frame steps to arrive and a CU keeps 8 waves x 8 KB in flight (measured per 256 x 1080p:
+    // 4 frames 0.253 ms, 8 frames 0.241, 16 frames 0.250 -- registers cost the third wave).
+    // Two register sets take turns (the first loop walks two groups per round), so nothing is
+    // copied between them, and its rounds neither test the frame index nor clamp a load address;
+    // what is left of the batch, fewer than three groups, goes through the second loop, which
+    // tests, clamps and copies.  So the first loop starts at batches of 24 frames: a shorter
+    // batch runs in the second loop alone.
+    double dn = dn0;
+    BgGroup<V> a, b;
+    a.template load<true>(frames, i0, px, 0, n);
+    int f0 = 0;
+    for (; f0 + 3 * kAhead <= n; f0 += 2 * kAhead) {
+        b.template load<false>(frames, i0, px, f0 + kAhead, n);
+        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(a, m, dn, recip, f0, kAhead, diff, i0, px);
+        a.template load<false>(frames, i0, px, f0 + 2 * kAhead, n);
+        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(b, m, dn, recip, f0 + kAhead, kAhead, diff, i0, px);
+    }
+    for (; f0 < n; f0 += kAhead) {
+        const bool more = f0 + kAhead < n;
+        if (more)
+            b.template load<true>(frames, i0, px, f0 + kAhead, n);
+        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, false>(a, m, dn, recip, f0, min(kAhead, n - f0), diff, i0, px);
+        if (more)
+            a = b;
     }
 #pragma unroll
     for (int k = 0; k < V; k++)
@@ -482,6 +535,21 @@ normalize_u8_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
 
 }  // namespace
 
+// one running-mean launch, V pixels per thread; without a difference image the kernel that writes none
+// (BOUNDED is a property of the difference alone, so it always comes with one: launch_bg sees to that)
+template <int V, typename RECIP, bool BOUNDED, bool SPLIT>
+static void launch_bg_fast(const uint8_t *fr, uint8_t *df, double *mean, const RECIP &recip, double dn0, int n,
+                           size_t px, hipStream_t st)
+{
+    const int grid = cdiv((long long)(px / V), kBlock);
+    if constexpr (BOUNDED)
+        bg_mean_u8_fast_kernel<V, RECIP, true, SPLIT, true><<<grid, kBlock, 0, st>>>(fr, df, mean, recip, dn0, n, px);
+    else if (df)
+        bg_mean_u8_fast_kernel<V, RECIP, BOUNDED, SPLIT, true><<<grid, kBlock, 0, st>>>(fr, df, mean, recip, dn0, n, px);
+    else
+        bg_mean_u8_fast_kernel<V, RECIP, BOUNDED, SPLIT, false><<<grid, kBlock, 0, st>>>(fr, df, mean, recip, dn0, n, px);
+}
+
 size_t bg_scratch_bytes(int n) { return sizeof(double) * (size_t)(n > 0 ? n : 1); }
 
 int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, int64_t n_seen,
@@ -500,7 +568,14 @@ int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, 
             // 16 px per thread when the streams allow 16-byte pieces (1 KB per wave instruction)
             // (8 px per thread, i.e. twice the waves with 8-byte accesses: 0.271-0.276 against 0.259-0.265 ms)
             const bool wide = px % 16 == 0 && aligned(fr, 16) && (!df || aligned(df, 16));
-            if (vec && n <= 256) {
+            // the fast kernels count the divisor up in float64, which is exact up to 2^53; beyond that the
+            // plain-division kernel converts every n_seen + f (no performance case)
+            const bool countable = n_seen >= -(1ll << 53) && n_seen <= (1ll << 53) - n;
+            // the saturation concerns the difference alone: a state-only update needs no vouching
+            const bool bounded = mean_in_u8_range && df;
+            const double dn0 = (double)n_seen;
+            double *mean = (double *)state;
+            if (vec && countable && n <= 256) {
                 RecipArgs ra;
                 for (int f = 0; f < 256; f++) {
                     const double d = (double)(n_seen + (f < n ? f : 0) + 1), y = 1.0 / d;
@@ -517,30 +592,23 @@ int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, 
 #else
                 const bool split = n_seen + n < (1ll << 40);         // where the two-operation quotient is proven
 #endif
-                if (wide && mean_in_u8_range && split)
-                    bg_mean_u8_fast_kernel<16, RecipArgs, true, true><<<cdiv((long long)(px / 16), kBlock), kBlock, 0, st>>>(
-                        fr, df, (double *)state, ra, n_seen, n, px);
-                else if (wide && mean_in_u8_range)
-                    bg_mean_u8_fast_kernel<16, RecipArgs, true><<<cdiv((long long)(px / 16), kBlock), kBlock, 0, st>>>(
-                        fr, df, (double *)state, ra, n_seen, n, px);
+                if (wide && bounded && split)
+                    launch_bg_fast<16, RecipArgs, true, true>(fr, df, mean, ra, dn0, n, px, st);
+                else if (wide && bounded)
+                    launch_bg_fast<16, RecipArgs, true, false>(fr, df, mean, ra, dn0, n, px, st);
                 else if (wide && split)
-                    bg_mean_u8_fast_kernel<16, RecipArgs, false, true><<<cdiv((long long)(px / 16), kBlock), kBlock, 0, st>>>(
-                        fr, df, (double *)state, ra, n_seen, n, px);
+                    launch_bg_fast<16, RecipArgs, false, true>(fr, df, mean, ra, dn0, n, px, st);
                 else if (wide)
-                    bg_mean_u8_fast_kernel<16, RecipArgs, false><<<cdiv((long long)(px / 16), kBlock), kBlock, 0, st>>>(
-                        fr, df, (double *)state, ra, n_seen, n, px);
+                    launch_bg_fast<16, RecipArgs, false, false>(fr, df, mean, ra, dn0, n, px, st);
                 else
-                    bg_mean_u8_fast_kernel<8, RecipArgs, false><<<grid, kBlock, 0, st>>>(fr, df, (double *)state, ra,
-                                                                                        n_seen, n, px);
-            } else if (vec && recip_scratch) {
+                    launch_bg_fast<8, RecipArgs, false, false>(fr, df, mean, ra, dn0, n, px, st);
+            } else if (vec && countable && recip_scratch) {
                 bg_reciprocals_kernel<<<cdiv(n, kBlock), kBlock, 0, st>>>(recip_scratch, n_seen, n);
                 VA_LAUNCH_CHECK("bg_reciprocals_kernel");
                 if (wide)
-                    bg_mean_u8_fast_kernel<16, const double *, false><<<cdiv((long long)(px / 16), kBlock), kBlock, 0, st>>>(
-                        fr, df, (double *)state, recip_scratch, n_seen, n, px);
+                    launch_bg_fast<16, const double *, false, false>(fr, df, mean, recip_scratch, dn0, n, px, st);
                 else
-                    bg_mean_u8_fast_kernel<8, const double *, false><<<grid, kBlock, 0, st>>>(
-                        fr, df, (double *)state, recip_scratch, n_seen, n, px);
+                    launch_bg_fast<8, const double *, false, false>(fr, df, mean, recip_scratch, dn0, n, px, st);
             } else if (vec)
                 bg_mean_u8_kernel<8><<<grid, kBlock, 0, st>>>(fr, df, (double *)state, n_seen, n, px);
             else
