@@ -849,6 +849,28 @@ int va_jpeg_decode_u8(const uint8_t *bytes_dev, const int64_t *offsets_dev, cons
                       uint8_t *frames_out_dev, int32_t *status_out_dev, void *workspace_dev, int64_t workspace_bytes,
                       void *stream);
 
+/* ------------------------------------------------------------------ A22 Motion-JPEG decoding, 4:2:0 and 4:2:2
+ * replaces  the same cv2.VideoCapture.read of VideoOpenCV.get_frame, video/io/backend_opencv.py, behind
+ *           load_any_video, video/io/file.py:37-46, for the files that cameras and other encoders write: chroma at
+ *           half resolution
+ * The arguments and the contract of va_jpeg_decode_u8, and behind ri the sampling factors of the luma component
+ * ("Subsampled Motion-JPEG decoding"):
+ *   luma_h, luma_v   1, 1: the bytes va_jpeg_decode_u8 writes.  2, 1 (4:2:2) or 2, 2 (4:2:0) with c == 3: Cb and Cr are
+ *                    1 x 1, an MCU covers 8 luma_h x 8 luma_v pixels and holds the Y blocks row by row, then Cb, Cr;
+ *                    ri and the segments count these MCUs; the chroma planes are upsampled with libjpeg's triangle
+ *                    filter in integers (replicated where the frame has at most 4 columns) before the colour
+ *                    conversion.  After an error the MCU's earlier blocks keep their coefficients.
+ *   workspace_dev    va_jpeg_decode_sampled_workspace_bytes(n, h, w, c, ri, luma_h, luma_v) holds the whole batch: as
+ *                    above, and for a subsampled file 1 byte per padded chroma sample more
+ * Four launches per chunk of subsampled frames (locate, entropy, chroma planes, pixels).  VA_ERR_INVALID in the order
+ * of va_jpeg_decode_u8, with sampling factors other than these three, or 2 x 1 / 2 x 2 with c == 1, refused behind
+ * "c outside {1, 3}"; then VA_ERR_RANGE. */
+size_t va_jpeg_decode_sampled_workspace_bytes(int n, int h, int w, int c, int ri, int luma_h, int luma_v);
+int va_jpeg_decode_sampled_u8(const uint8_t *bytes_dev, const int64_t *offsets_dev, const int64_t *scan_begin_dev, int n,
+                              int h, int w, int c, int ri, int luma_h, int luma_v, const uint8_t *qtables_dev,
+                              const void *huff_dev, int huff_bytes, uint8_t *frames_out_dev, int32_t *status_out_dev,
+                              void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

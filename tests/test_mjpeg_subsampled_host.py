@@ -1,0 +1,329 @@
+"""CPU: the decoder of 4:2:0 and 4:2:2 files ("Subsampled Motion-JPEG decoding") and its host layer.
+
+The restatement tests/jpeg_subsampled_checks.py against the fixture tests/golden/mjpeg_subsampled_v1.npz and against
+the ideal decode within the derived bounds, the upsampling's edge rules on hand-made planes, the header parser of
+video.ops with sampling="any" on the accepted and the refused streams and with its default on all of them, the
+grouping of layouts, the restated encoder, the C ABI's declarations and refusals, and va_jpeg_decode_math.h compiled
+into a stand-alone program under sanitizers."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import jpeg_decode_checks as D
+import jpeg_subsampled_checks as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "mjpeg_subsampled_v1.npz")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return S.fixture_cases(FIXTURE)
+
+
+@pytest.fixture(scope="module")
+def cases(golden):
+    return golden[0]
+
+
+# ------------------------------------------------------------------------------------------------ the definition
+def test_restatement_still_decodes_to_the_fixture(cases):
+    assert os.path.getsize(FIXTURE) < 400 * 1000
+    assert (len(cases["a"]), len(cases["b"]), len(cases["c"])) == (200, 30, 3)
+    bits = 0
+    for kind in "ab":
+        for name, data, want, want_status in cases[kind]:
+            got, status = S.decode(data)
+            assert status == want_status and got.dtype == np.uint8 and np.array_equal(got, want), name
+            bits |= status
+    assert bits == D.BAD_CODE | D.OVERRUN | D.TRUNCATED | D.MARKER
+    layouts = {S.parse_header(data)["sampling"] for _, data, _, _ in cases["a"]}
+    assert layouts == {(2, 1), (2, 2)}
+
+
+def test_accuracy_condition(golden):
+    """derived, not measured: the clamp is not active, every upsampled component sample is within 1 of the same
+    integer upsampling of the float64 IDCT's planes (samples within 1 go through weights that add up to 4 or 16
+    before the shift), every pixel within R 3, G 3, B 4 of the float64 colour matrix on those planes.  The recorded
+    distances to Pillow's decode are measurements: every component sample within 1, RGB within 3."""
+    cases, z = golden
+    for name, data, want, _ in cases["a"]:
+        head = S.parse_header(data)
+        coefs, status = S.decode_coefficients(data, head)
+        planes, clamped = S.integer_planes(coefs, head["qtables"])
+        ideal, _ = S.float_planes(coefs, head["qtables"])
+        assert status == 0 and not clamped, name
+        assert np.abs(S.full_planes(planes, head) - S.full_planes(ideal, head)).max() <= 1, name
+        d = np.abs(want.astype(int) - S.ideal_decode(data, head).astype(int))
+        assert (d <= np.array([3, 3, 4])).all(), name
+    assert z["worst_component"] <= 1 and (z["worst_rgb"] <= (3, 3, 4)).all()
+    assert (z["pillow_worst_ycc"] <= 1).all() and (z["pillow_worst_rgb"] <= 3).all()
+
+
+def test_variants_of_a_picture_decode_to_the_same_pixels(cases):
+    by_name = {name: want for name, _, want, _ in cases["a"]}
+    for name, want in by_name.items():
+        assert np.array_equal(want, by_name[name.rsplit("_", 1)[0] + "_plain"]), name
+    heads = {name: S.parse_header(data) for name, data, _, _ in cases["a"] if "q85_37x53" in name and "smooth" not in name}
+    assert (heads["420_q85_37x53_plain"]["ri"], heads["420_q85_37x53_plain"]["nseg"]) == (12, 1)
+    assert (heads["420_q85_37x53_rows"]["ri"], heads["420_q85_37x53_rows"]["nseg"]) == (4, 3)
+    assert (heads["420_q85_37x53_blocks3"]["ri"], heads["420_q85_37x53_blocks3"]["nseg"]) == (3, 4)
+    assert (heads["422_q85_37x53_plain"]["ri"], heads["422_q85_37x53_plain"]["nseg"]) == (20, 1)
+    assert (heads["422_q85_37x53_rows"]["ri"], heads["422_q85_37x53_rows"]["nseg"]) == (4, 5)
+    assert (heads["422_q85_37x53_blocks3"]["ri"], heads["422_q85_37x53_blocks3"]["nseg"]) == (3, 7)
+    assert heads["420_q85_37x53_optimized"]["huff"] != heads["420_q85_37x53_plain"]["huff"]
+
+
+def test_upsampling_on_hand_made_planes():
+    """the formulas of the definition written out sample by sample, with their clamps, and the cw > 2 rule"""
+    rng = np.random.default_rng(9)
+    for hv in S.LAYOUTS:
+        for h, w in ((1, 1), (2, 4), (5, 3), (3, 5), (4, 6), (7, 9), (16, 16), (17, 33)):
+            hh, vv = hv
+            chh, cw = -(-h // vv), -(-w // hh)
+            c = rng.integers(0, 256, (chh + 3, cw + 5))            # with padding that must never be used
+            want = np.zeros((h, w), np.int64)
+            at = lambda j, i: int(c[min(max(j, 0), chh - 1), min(max(i, 0), cw - 1)])
+            for y in range(h):
+                for x in range(w):
+                    j, i = y // vv, x // hh
+                    if cw <= 2:
+                        want[y, x] = at(j, i)
+                        continue
+                    di = 1 if x & 1 else -1
+                    if vv == 2:
+                        dj = 1 if y & 1 else -1
+                        s0, s1 = 3 * at(j, i) + at(j + dj, i), 3 * at(j, i + di) + at(j + dj, i + di)
+                        want[y, x] = (3 * s0 + s1 + (7 if x & 1 else 8)) >> 4
+                    else:
+                        want[y, x] = (3 * at(j, i) + at(j, i + di) + (2 if x & 1 else 1)) >> 2
+            assert np.array_equal(S.upsample(c, hv, h, w), want), (hv, h, w)
+    flat = np.full((4, 4), 77)
+    assert (S.upsample(flat, (2, 2), 8, 8) == 77).all() and (S.upsample(flat, (2, 1), 4, 8) == 77).all()
+
+
+def test_an_error_inside_an_mcu_keeps_its_earlier_blocks(cases):
+    shown = []
+    for name, data, want, want_status in cases["b"]:
+        head = S.parse_header(data)
+        hh, vv, my, mx, _, _ = S.geometry(head)
+        coefs, status, report = S.decode_coefficients(data, head, ret_segments=True)
+        walk = S.mcu_blocks((hh, vv))
+        for j, seg in enumerate(report):
+            if not seg or not seg[0]:
+                continue
+            _, m, k = seg
+            for mm in range(m, min((j + 1) * head["ri"], my * mx)):
+                for kk, (comp, v, u) in enumerate(walk):
+                    at = (0, (mm // mx) * vv + v, (mm % mx) * hh + u) if comp == 0 else (comp, mm // mx, mm % mx)
+                    block = coefs[at[0]][at[1], at[2]]
+                    if (mm, kk) >= (m, k):
+                        assert not block.any(), (name, j, mm, kk)
+                    elif block.any():
+                        shown.append(name)
+    assert {n for n in shown if n.endswith("cut_in_mcu")} == {"420_q50_37x53_rows_cut_in_mcu",
+                                                              "422_q50_37x53_rows_cut_in_mcu"}
+
+
+def test_restated_encoder_writes_what_pillow_and_the_restatement_read():
+    rng = np.random.default_rng(4)
+    for hv in S.LAYOUTS:
+        for h, w in ((1, 1), (16, 16), (19, 37)):
+            frame = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+            first = None
+            for ri in (None, 0, 3):
+                data = S.encode_frame(frame, 90, hv, ri)
+                head = S.parse_header(data)
+                hh, vv, my, mx, _, _ = S.geometry(head)
+                assert head["sampling"] == hv and (b"\xff\xdd" in data[:head["scan_begin"]]) == (ri != 0)
+                assert head["ri"] == (mx if ri is None else ri or my * mx)
+                pixels, status = S.decode(data, head)
+                assert status == 0
+                first = pixels if first is None else first
+                assert np.array_equal(pixels, first)
+            # quality 90 of noise loses the chroma detail; the luma stays close
+            luma = lambda p: p.astype(int) @ np.array([0.299, 0.587, 0.114])
+            assert np.abs(luma(first) - luma(frame)).mean() < 12
+    Image = pytest.importorskip("PIL.Image")
+    import io
+    data = S.encode_frame(rng.integers(0, 256, (19, 37, 3), dtype=np.uint8), 90, (2, 2), 0)
+    seen = np.asarray(Image.open(io.BytesIO(data)))
+    assert np.abs(seen.astype(int) - S.decode(data)[0]).max() <= 3
+
+
+# ------------------------------------------------------------------------------------------------ the parser
+def test_both_parsers_agree(cases):
+    from video import ops
+    for name, data, want, _ in cases["a"] + cases["b"]:
+        head, mine = S.parse_header(data), ops.jpeg_parse_header(data, sampling="any")
+        assert S.header_key(head) == S.header_key(mine) and head["scan_begin"] == mine["scan_begin"], name
+        assert mine["sampling"] == head["sampling"] == ((2, 2) if name.startswith("420") else (2, 1)), name
+        assert (mine["h"], mine["w"], mine["c"]) == want.shape and mine["nseg"] == head["nseg"], name
+        hh, vv, my, mx, _, _ = S.geometry(mine)
+        assert mine["nseg"] == -(-(my * mx) // mine["ri"])
+    for name, data, word in cases["c"]:
+        for parse in (lambda d: ops.jpeg_parse_header(d, sampling="any"), S.parse_header, ops.jpeg_parse_header,
+                      D.parse_header):
+            with pytest.raises(ValueError) as err:
+                parse(data)
+            assert word in str(err.value), (name, err.value)
+    with pytest.raises(ValueError):
+        ops.jpeg_parse_header(cases["a"][0][1], sampling="4:2:0")
+
+
+def test_the_default_parse_still_refuses_every_subsampled_stream(cases):
+    from video import ops
+    for name, data, _, _ in cases["a"]:
+        for parse in (ops.jpeg_parse_header, lambda d: ops.jpeg_parse_header(d, sampling="1x1"),
+                      lambda d: S.parse_header(d, sampling="1x1")):
+            with pytest.raises(ValueError) as err:
+                parse(data)
+            assert "sampling" in str(err.value), name
+    with pytest.raises(ValueError) as err:
+        ops.jpeg_parse_header(cases["a"][0][1])
+    assert str(err.value) == ("jpeg_parse_header: sampling factors 2 x 2 (chroma subsampling such as 4:2:0 or 4:2:2); "
+                              "only 1 x 1 sampling is decoded")
+
+
+def test_one_component_and_1x1_files_parse_as_before(cases):
+    from video import ops
+    dec = np.load(os.path.join(ROOT, "tests", "golden", "mjpeg_decode_v1.npz"), allow_pickle=False)
+    for name in list(dec["names_b"])[::5]:
+        data = dec["b_bytes_" + name].tobytes()
+        plain, any_ = ops.jpeg_parse_header(data), ops.jpeg_parse_header(data, sampling="any")
+        assert plain["sampling"] == any_["sampling"] == (1, 1)
+        assert ops._jpeg_header_key(plain) == ops._jpeg_header_key(any_) and plain["nseg"] == any_["nseg"]
+        assert S.header_key(S.parse_header(data)) == S.header_key(any_)
+    # a 1-component frame takes any factors and is decoded as 1 x 1
+    grey = dec["b_bytes_L_q85_37x53_rows"].tobytes()
+    sof = grey.index(b"\xff\xc0\x00\x0b\x08")
+    odd = bytearray(grey)
+    odd[sof + 11] = 0x22
+    for parse in (ops.jpeg_parse_header, lambda d: ops.jpeg_parse_header(d, sampling="any"), S.parse_header):
+        head = parse(bytes(odd))
+        assert head["sampling"] == (1, 1) and (head["ri"], head["nseg"]) == (7, 5)
+
+
+def test_layouts_of_one_shape_fall_into_different_groups(cases):
+    from video import ops
+    data = {name: d for name, d, _, _ in cases["a"]}["420_q85_37x53_rows"]
+    sof = data.index(b"\xff\xc0\x00\x11\x08")
+    as_422, as_444 = bytearray(data), bytearray(data)
+    as_422[sof + 11], as_444[sof + 11] = 0x21, 0x11
+    heads = [ops.jpeg_parse_header(bytes(d), sampling="any") for d in (data, data, as_444, as_444, as_422, data)]
+    assert [hd["sampling"] for hd in heads] == [(2, 2), (2, 2), (1, 1), (1, 1), (2, 1), (2, 2)]
+    assert len({(hd["h"], hd["w"], hd["c"], hd["ri"]) for hd in heads}) == 1           # only the sampling differs
+    assert ops.jpeg_decode_groups(heads) == [(0, 2), (2, 4), (4, 5), (5, 6)]
+    assert len({S.header_key(hd) for hd in heads}) == 3
+
+
+# ------------------------------------------------------------------------------------------------ the C ABI
+def test_abi_declarations_and_refusals():
+    import ctypes as C
+    from video import _hip
+    text = open(os.path.join(ROOT, "include", "videoanalysis_hip.h")).read()
+    assert "size_t va_jpeg_decode_sampled_workspace_bytes(int n, int h, int w, int c, int ri, int luma_h, int luma_v);" in text
+    assert "int va_jpeg_decode_sampled_u8(" in text and "Subsampled Motion-JPEG decoding" in text
+    res, args = _hip.SIGNATURES["va_jpeg_decode_sampled_u8"]
+    plain = _hip.SIGNATURES["va_jpeg_decode_u8"]
+    assert res is C.c_int and args == plain[1][:8] + [C.c_int, C.c_int] + plain[1][8:]
+    assert _hip.SIGNATURES["va_jpeg_decode_sampled_workspace_bytes"] == (C.c_size_t, [C.c_int] * 7)
+    L = _hip.load_library()
+    fn = L.va_jpeg_decode_sampled_u8
+    buf = np.zeros(64, np.int64)
+    p = buf.ctypes.data
+    names = ["bytes", "offsets", "scan", "n", "h", "w", "c", "ri", "lh", "lv", "qt", "huff", "huff_bytes", "out",
+             "status", "ws", "ws_bytes", "stream"]
+    ok = [p, p, p, 1, 16, 16, 3, 1, 2, 2, p, p, 6 * 1416, p, p, p, 1 << 20, None]
+
+    def call(**change):
+        a = list(ok)
+        for k, v in change.items():
+            a[names.index(k)] = v
+        return fn(*a), L.va_last_error().decode()
+    for change, word in ((dict(n=-1), "size"), (dict(h=0), "size"), (dict(ri=0), "size"), (dict(ws_bytes=-1), "size"),
+                         (dict(c=2), "channels"), (dict(lh=1, lv=2), "sampling"), (dict(lh=4, lv=1), "sampling"),
+                         (dict(lh=2, lv=3), "sampling"), (dict(lh=0, lv=0), "sampling"),
+                         (dict(c=1, huff_bytes=2 * 1416), "sampling"), (dict(c=1, lv=1), "sampling"),
+                         (dict(bytes=None), "NULL"), (dict(ws=None), "NULL"), (dict(offsets=p + 4), "aligned"),
+                         (dict(ws=p + 8), "aligned"), (dict(h=65536), "16-bit"), (dict(huff_bytes=1416), "tables")):
+        rc, message = call(**change)
+        assert rc == -22 and word in message and message.startswith("va_jpeg_decode_sampled_u8:"), (change, message)
+    # the order: sizes, channels, sampling, NULL, alignment, 16 bits, tables, then the workspace (VA_ERR_RANGE)
+    assert "size" in call(h=0, c=2)[1] and "channels" in call(c=2, lh=3)[1]
+    assert "sampling" in call(lh=3, bytes=None)[1] and "NULL" in call(bytes=None, offsets=p + 4)[1]
+    assert "aligned" in call(offsets=p + 4, h=65536)[1] and "16-bit" in call(h=65536, huff_bytes=7)[1]
+    assert "tables" in call(huff_bytes=7, ws_bytes=0)[1]
+    rc, message = call(ws_bytes=100)
+    assert rc == -34 and "one frame" in message
+    assert call(n=0, bytes=None, ws=None)[0] == 0 and call(n=0, lh=3)[0] == -22
+    assert not buf.any()
+    size, size11 = L.va_jpeg_decode_sampled_workspace_bytes, L.va_jpeg_decode_workspace_bytes
+    for a in ((1, 8, 8, 1, 1), (32, 1080, 1920, 3, 240), (5, 37, 53, 3, 7), (0, 8, 8, 1, 1), (1, 8, 8, 2, 1)):
+        assert size(*a + (1, 1)) == size11(*a)
+    # [16 bytes a segment | 128 bytes a block | 64 bytes a chroma block], each region rounded up to 256
+    assert size(1, 16, 16, 3, 1, 2, 2) == 256 + 6 * 128 + 256 and size(1, 16, 16, 3, 1, 2, 1) == 256 + 8 * 128 + 256
+    assert size(1, 16, 16, 1, 1, 2, 2) == 0 and size(1, 16, 16, 3, 1, 1, 2) == 0 and size(1, 16, 16, 3, 0, 2, 2) == 0
+    frame = 68 * 120 * (6 * 128 + 2 * 64) + 68 * 16                  # 1080p 4:2:0 with a restart interval per MCU row
+    assert 32 * frame <= size(32, 1080, 1920, 3, 120, 2, 2) < 32 * frame + 1024
+    # the plain entry keeps its messages
+    rc = L.va_jpeg_decode_u8(p, p, p, 1, 8, 8, 2, 1, p, p, 2 * 1416, p, p, p, 1 << 20, None)
+    assert rc == -22 and L.va_last_error().decode() == "va_jpeg_decode_u8: channels must be 1 or 3, got 2"
+
+
+# ------------------------------------------------------------------------------------------------ the header
+def test_subsampled_math_on_the_host_under_sanitizers(cases, tmp_path):
+    """va_jpeg_decode_math.h compiled for the host with -fsanitize=address,undefined into a stand-alone program that
+    decodes every fixture stream, the hostile ones included, and four cut ones, from heap buffers of exactly their
+    size; its status words and the hash of its pixels are the restatement's.  The program aborts where the
+    upsampling asks for a sample that is not a real one."""
+    from video import ops
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "llvm", "bin", "clang++")
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or (
+        rocm_clang if os.path.exists(rocm_clang) else None)
+    assert cxx is not None, "no host C++ compiler: neither g++, c++ or clang++ on the PATH nor %s" % rocm_clang
+    exe = str(tmp_path / "jpeg_subsampled_shim")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "video-analysis_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "jpeg_subsampled_shim.cpp"), "-o", exe])
+
+    def fnv(pixels):
+        h = 1469598103934665603
+        for v in pixels.tobytes():
+            h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+        return h
+
+    def record(data, head):
+        tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
+        return (struct.pack("<7i", head["h"], head["w"], head["ri"], head["scan_begin"], len(data), *head["sampling"])
+                + head["qtables"].tobytes() + tables + data)
+    everything = [c for c in cases["a"] + cases["b"]]
+    text = [record(data, ops.jpeg_parse_header(data, sampling="any")) for _, data, _, _ in everything]
+    # hand-made: files that are their header alone, and ones that end with FF
+    for name in ("420_q85_17x33_rows", "422_q100_37x53_plain"):
+        data = [c[1] for c in cases["a"] if c[0] == name][0]
+        head = ops.jpeg_parse_header(data, sampling="any")
+        for cut in (data[:head["scan_begin"]], data[:head["scan_begin"] + 1] + b"\xff"):
+            text.append(record(cut, head))
+            pixels, status = S.decode(cut, S.parse_header(data))
+            assert status & D.MARKER
+            everything = everything + [(name + " cut", cut, pixels, status)]
+    run = subprocess.run([exe], input=b"".join(text), capture_output=True)
+    assert run.returncode == 0, run.stderr.decode()[-2000:]
+    lines = run.stdout.decode().split("\n")[:-1]
+    assert len(lines) == len(everything) == 234
+    for (name, _, want, want_status), line in zip(everything, lines):
+        assert line == "%d %d" % (want_status, fnv(want)), name
+
+
+def test_product_does_not_import_the_restatement():
+    pkg = os.path.join(ROOT, "video-analysis_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                assert "jpeg_subsampled_checks" not in open(os.path.join(dirpath, f)).read(), f

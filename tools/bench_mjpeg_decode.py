@@ -13,6 +13,11 @@
   pillow    Pillow's decoder (libjpeg) on one core, a few frames, where Pillow exists
   video     VideoMJPEG iteration end to end over an AVI file with the device decoder and, where Pillow exists, with
             the default one
+  subsampled  n x 1080p RGB frames as Pillow (libjpeg) writes them at quality 90: 4:2:0 and 4:2:2 through
+            va_jpeg_decode_sampled_u8 (locate + entropy + chroma planes + pixels) and 4:4:4 of the same pictures
+            through va_jpeg_decode_u8, each with one restart interval per MCU row and with none (a frame is then one
+            segment, one lane), by HIP events in the same run; the launches one by one come from the same
+            rocprofv3 run as above with --legs subsampled.  Skipped with a message where Pillow is missing
 Times are the median of the repetitions.  One JSON line per leg, appended to profiles/mjpeg_decode_bench.jsonl (or
 --out); a leg that did not run is written "not measured".
 Run on an MI355X:
@@ -37,7 +42,8 @@ ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--quality", type=int, default=90)
 ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow leg (0: not measured)")
 ap.add_argument("--video-frames", type=int, default=64, help="frames of the VideoMJPEG leg")
-ap.add_argument("--legs", default="kernels,batch32,ops,pillow,video")
+ap.add_argument("--distinct", type=int, default=16, help="pictures of the subsampled leg, repeated to --frames")
+ap.add_argument("--legs", default="kernels,batch32,ops,pillow,video,subsampled")
 ap.add_argument("--modes", default="mono,rgb")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mjpeg_decode_bench.jsonl"))
 args = ap.parse_args()
@@ -99,9 +105,70 @@ def main():
             ms.append((time.perf_counter() - t0) * 1e3)
         return float(np.median(ms))
 
+    def subsampled():
+        try:
+            from PIL import Image
+        except ImportError:
+            print("the subsampled leg needs Pillow to write its streams: skipped", flush=True)
+            emit({"leg": "subsampled", "ms_per_call_median": "not measured", "note": "Pillow is not installed"})
+            return
+        pictures = scene(min(args.distinct, N), H, W, 3, np.random.default_rng(44), False)
+        raw = N * H * W * 3
+        out = torch.empty(raw, dtype=torch.uint8, device=dev)
+        status = torch.zeros(N, dtype=torch.int32, device=dev)
+        for restarts, kw in (("mcu_rows", {"restart_marker_rows": 1}), ("none", {})):
+            for layout, sub in (("444", 0), ("422", 1), ("420", 2)):
+                files = []
+                for picture in pictures:
+                    buf = io.BytesIO()
+                    Image.fromarray(picture).save(buf, "JPEG", quality=Q, subsampling=sub, **kw)
+                    files.append(buf.getvalue())
+                files = [files[k % len(files)] for k in range(N)]
+                heads = [ops.jpeg_parse_header(f, sampling="any") for f in files[:len(pictures)]]
+                head = heads[0]
+                assert len(ops.jpeg_decode_groups(heads)) == 1
+                lh, lv = head["sampling"]
+                ri = head["ri"]
+                tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
+                consts = torch.from_numpy(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8).copy()).to(dev)
+                src = torch.from_numpy(np.frombuffer(b"".join(files), np.uint8).copy()).to(dev)
+                offsets = np.concatenate([[0], np.cumsum([len(f) for f in files])]).astype(np.int64)
+                scans = np.array([heads[k % len(heads)]["scan_begin"] for k in range(N)], np.int64)
+                meta = torch.from_numpy(np.concatenate([offsets, scans])).to(dev)
+                room = int(L.va_jpeg_decode_sampled_workspace_bytes(N, H, W, 3, ri, lh, lv))
+                ws = torch.empty(room, dtype=torch.uint8, device=dev)
+                front = (src.data_ptr(), meta.data_ptr(), meta.data_ptr() + 8 * (N + 1), N, H, W, 3, ri)
+                back = (consts.data_ptr(), consts.data_ptr() + 192, len(tables), out.data_ptr(), status.data_ptr(),
+                        ws.data_ptr(), room, S)
+
+                def decode():
+                    if (lh, lv) == (1, 1):
+                        check(L.va_jpeg_decode_u8(*(front + back)))
+                    else:
+                        check(L.va_jpeg_decode_sampled_u8(*(front + (lh, lv) + back)))
+                reps, args.reps = args.reps, args.reps if restarts != "none" else min(args.reps, 3)
+                try:
+                    best, med = events(decode)
+                finally:
+                    args.reps = reps
+                assert not bool(status.any())
+                emit({"leg": "subsampled/%s/%s" % (layout, restarts), "frames": N, "h": H, "w": W, "quality": Q,
+                      "distinct_pictures": len(pictures), "ms_per_call_min": round(best, 4),
+                      "ms_per_call_median": round(med, 4), "frames_per_s": round(N / med * 1e3, 1),
+                      "output_gb_per_s": round(raw / med / 1e6, 1), "bytes_in_per_frame": int(offsets[-1]) // N,
+                      "restart_interval_mcus": ri, "segments_per_call": N * head["nseg"],
+                      "blocks_per_segment": ri * (lh * lv + 2), "workspace_bytes": room,
+                      "note": "Pillow-written; locate + entropy + %s, one chunk"
+                              % ("reconstruct" if (lh, lv) == (1, 1) else "chroma planes + pixels")})
+                del src, ws
+    if "subsampled" in LEGS:
+        subsampled()
+        ops.pool_clear()
     for c in [m for m in (1, 3) if ("rgb" if m == 3 else "mono") in args.modes.split(",")]:
         for noise in (False, True):
             name = "%s/%s" % ("rgb" if c == 3 else "mono", "noise" if noise else "smooth")
+            if not LEGS & {"kernels", "batch32", "ops", "pillow", "video"}:
+                continue
             clip = scene(N, H, W, c, rng, noise)
             raw = clip.nbytes
             stack = ops.DeviceFrames.upload(clip)

@@ -1149,37 +1149,74 @@ size_t va_jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri)
 {
     if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0)
         return 0;
-    return jpeg_decode_workspace_bytes(n, h, w, c, ri);
+    return jpeg_decode_workspace_bytes(n, h, w, c, ri, 1, 1);
 }
+
+namespace {
+bool jpeg_sampling_taken(int c, int lh, int lv)
+{
+    return (lh == 1 && lv == 1) || (c == 3 && lh == 2 && (lv == 1 || lv == 2));
+}
+
+// both decode entries: `what` names the one that was called
+int jpeg_decode_entry(const char *what, const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n,
+                      int h, int w, int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff,
+                      int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
+                      void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ri > 0 && workspace_bytes >= 0,
+               "%s: negative or zero size (n %d, h %d, w %d, ri %d, workspace %lld)", what, n, h, w, ri,
+               (long long)workspace_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
+    VA_REQUIRE(jpeg_sampling_taken(c, lh, lv),
+               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
+               what, lh, lv, c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
+               "%s: NULL argument", what);
+    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
+                   && aligned(workspace, 16),
+               "%s: offsets and scan_begin must be 8-byte aligned, the tables and the status 4-byte, "
+               "the workspace 16-byte", what);
+    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
+    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
+               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
+               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
+    if (jpeg_decode_chunk(n, h, w, c, ri, lh, lv, (size_t)workspace_bytes) < 1) {
+        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what,
+                  (long long)workspace_bytes, (long long)jpeg_decode_workspace_bytes(1, h, w, c, ri, lh, lv));
+        return VA_ERR_RANGE;
+    }
+    return launch_jpeg_decode(bytes, offsets, scan_begin, n, h, w, c, ri, lh, lv, qtables, huff, frames_out,
+                              status_out, workspace, (size_t)workspace_bytes, as_stream(stream));
+}
+}  // namespace
 
 int va_jpeg_decode_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w, int c,
                       int ri, const uint8_t *qtables, const void *huff, int huff_bytes, uint8_t *frames_out,
                       int32_t *status_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ri > 0 && workspace_bytes >= 0,
-               "va_jpeg_decode_u8: negative or zero size (n %d, h %d, w %d, ri %d, workspace %lld)", n, h, w, ri,
-               (long long)workspace_bytes);
-    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_decode_u8: channels must be 1 or 3, got %d", c);
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
-               "va_jpeg_decode_u8: NULL argument");
-    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
-                   && aligned(workspace, 16),
-               "va_jpeg_decode_u8: offsets and scan_begin must be 8-byte aligned, the tables and the status 4-byte, "
-               "the workspace 16-byte");
-    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_decode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
-    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
-               "va_jpeg_decode_u8: the Huffman tables of %d component(s) are %d bytes, got %d", c,
-               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
-    if (jpeg_decode_chunk(n, h, w, c, ri, (size_t)workspace_bytes) < 1) {
-        set_error("va_jpeg_decode_u8: a workspace of %lld bytes does not hold one frame (%lld bytes)",
-                  (long long)workspace_bytes, (long long)jpeg_decode_workspace_bytes(1, h, w, c, ri));
-        return VA_ERR_RANGE;
-    }
-    return launch_jpeg_decode(bytes, offsets, scan_begin, n, h, w, c, ri, qtables, huff, frames_out, status_out,
-                              workspace, (size_t)workspace_bytes, as_stream(stream));
+    return jpeg_decode_entry("va_jpeg_decode_u8", bytes, offsets, scan_begin, n, h, w, c, ri, 1, 1, qtables, huff,
+                             huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
+}
+
+size_t va_jpeg_decode_sampled_workspace_bytes(int n, int h, int w, int c, int ri, int luma_h, int luma_v)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0
+        || !jpeg_sampling_taken(c, luma_h, luma_v))
+        return 0;
+    return jpeg_decode_workspace_bytes(n, h, w, c, ri, luma_h, luma_v);
+}
+
+int va_jpeg_decode_sampled_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h,
+                              int w, int c, int ri, int luma_h, int luma_v, const uint8_t *qtables, const void *huff,
+                              int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    return jpeg_decode_entry("va_jpeg_decode_sampled_u8", bytes, offsets, scan_begin, n, h, w, c, ri, luma_h, luma_v,
+                             qtables, huff, huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------ geodesic

@@ -473,12 +473,13 @@ int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const 
                        int header_bytes, int64_t *sizes, int64_t *offsets, int64_t *totals, uint8_t *out, int64_t cap,
                        void *ws, hipStream_t st);
 // Motion-JPEG decoding (va_jpeg_decode.hip): locate, entropy and reconstruct per chunk of frames; the chunk is what
-// the workspace holds (jpeg_decode_chunk: 0 when it does not hold one frame)
-size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri);
-int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, size_t workspace_bytes);
+// the workspace holds (jpeg_decode_chunk: 0 when it does not hold one frame).  lh x lv is the sampling of the luma
+// component, 1 x 1, 2 x 1 or 2 x 2; behind a subsampled file the reconstruction is two launches (chroma planes, pixels)
+size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv);
+int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, size_t workspace_bytes);
 int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                       int c, int ri, const uint8_t *qtables, const void *huff, uint8_t *out, int32_t *status, void *ws,
-                       size_t workspace_bytes, hipStream_t st);
+                       int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
+                       int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

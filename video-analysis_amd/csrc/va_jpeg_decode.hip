@@ -19,6 +19,14 @@
 //                of a wave hold neighbouring MCUs of a block row, so each of the 8 pixel rows goes out as 8 (or 24)
 //                contiguous bytes a lane, 512 (1536) bytes a wave, where the row is complete and aligned, and
 //                bytewise at the frame's edges.
+// A 4:2:0 or 4:2:2 file ("Subsampled Motion-JPEG decoding": luma 2 x 2 or 2 x 1, an MCU of 6 or 4
+// blocks) takes four: locate as it is, entropy with the MCU walk of va_jpeg_decode_math.h into
+// [frame][Y: my V x mx H blocks | Cb: my x mx | Cr: my x mx][64], and the reconstruction in two, because the triangle
+// filter reads chroma samples of neighbouring MCUs:
+//   chroma planes  one lane per chroma block: its 64 samples as eight 8-byte rows of [frame][2][my 8][mx 8] bytes
+//   pixels         one lane per luma block, the lanes of a wave along a block row: the Y block's samples, the 6 x 6
+//                  (4:2:0) or 8 x 6 (4:2:2) chroma samples around its quarter or half of the chroma block, clamped to
+//                  the real samples, the upsampling and the colour conversion; the pixel rows go out as in reconstruct
 // The only atomic is the OR into the status word, whose result does not depend on the order; every output byte
 // depends on its frame alone.  Loops over stream bytes end at the segment's end, loops over blocks at the segment's
 // MCU range.
@@ -173,19 +181,24 @@ struct EntropyArgs {
     int nseg, ri, bx, by;
 };
 
+// the 2 * C tables into LDS, by the whole workgroup
+template <int C>
+__device__ __forceinline__ void stage_tables(va_jpeg::HuffDecode *tabs, const va_jpeg::HuffDecode *huff)
+{
+    static_assert(sizeof(va_jpeg::HuffDecode) % 4 == 0, "the tables are copied as words");
+    constexpr int words = 2 * C * (int)sizeof(va_jpeg::HuffDecode) / 4;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(huff);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(tabs);
+    for (int i = threadIdx.x; i < words; i += kEntBlock)
+        dst[i] = src[i];
+    __syncthreads();
+}
+
 template <int C>
 __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
 {
     __shared__ va_jpeg::HuffDecode tabs[2 * C];
-    static_assert(sizeof(va_jpeg::HuffDecode) % 4 == 0, "the tables are copied as words");
-    {
-        constexpr int words = 2 * C * (int)sizeof(va_jpeg::HuffDecode) / 4;
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.huff);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(tabs);
-        for (int i = threadIdx.x; i < words; i += kEntBlock)
-            dst[i] = src[i];
-    }
-    __syncthreads();
+    stage_tables<C>(tabs, a.huff);
     const int64_t s = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
     if (s >= a.nsegs)
         return;
@@ -213,6 +226,54 @@ __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
             if (dead)
                 continue;
             const int32_t e = va_jpeg::decode_block(r, tabs[2 * ch], tabs[2 * ch + 1], pred[ch],
+                                                    [&](int i, int v) { blk[i] = (int16_t)v; });
+            if (e) {
+                st = e;
+                dead = true;
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    blk16[i] = make_uint4(0, 0, 0, 0);
+            }
+        }
+    }
+    if (st)
+        atomicOr(&a.status[f], st);
+}
+
+// luma LH x LV, chroma 1 x 1; a.bx, a.by count MCUs of 8 LH x 8 LV pixels.  An error zeroes its block and every later
+// block of the segment; the MCU's earlier blocks keep their coefficients.
+template <int LH, int LV>
+__global__ void __launch_bounds__(kEntBlock) jpeg_entropy_sampled_kernel(EntropyArgs a)
+{
+    constexpr int kBlocks = va_jpeg::mcu_blocks(LH, LV);
+    __shared__ va_jpeg::HuffDecode tabs[6];
+    stage_tables<3>(tabs, a.huff);
+    const int64_t s = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
+    if (s >= a.nsegs)
+        return;
+    const int64_t f = s / a.nseg;
+    const int j = (int)(s % a.nseg);
+    const int64_t begin = a.table[2 * s], end = a.table[2 * s + 1];
+    const int64_t mcus = (int64_t)a.bx * a.by;
+    const int64_t m0 = (int64_t)j * a.ri, m1 = m0 + a.ri < mcus ? m0 + a.ri : mcus;
+    bool dead = begin < 0 || end < begin;
+    int32_t st = 0;
+    va_jpeg::BitReader r = va_jpeg::open_bits(a.bytes, dead ? 0 : begin, dead ? 0 : end);
+    int pred[3] = {0, 0, 0};
+    int16_t *frame = a.coef + ((f * kBlocks * mcus) << 6);
+    for (int64_t m = m0; m < m1; m++) {
+        const int64_t row = m / a.bx, col = m % a.bx;
+#pragma unroll
+        for (int k = 0; k < kBlocks; k++) {
+            int comp = 0;
+            int16_t *blk = frame + (va_jpeg::mcu_block_at(k, LH, LV, a.by, a.bx, row, col, comp) << 6);
+            uint4 *blk16 = reinterpret_cast<uint4 *>(blk);
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                blk16[i] = make_uint4(0, 0, 0, 0);
+            if (dead)
+                continue;
+            const int32_t e = va_jpeg::decode_block(r, tabs[2 * comp], tabs[2 * comp + 1], pred[comp],
                                                     [&](int i, int v) { blk[i] = (int16_t)v; });
             if (e) {
                 st = e;
@@ -328,51 +389,225 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_reconstruct_kernel(ReconArgs a
     }
 }
 
-struct DecodeLayout {
-    size_t table, coef, total;
+struct PlaneArgs {
+    const int16_t *coef;
+    const uint8_t *qtables;              // [3][64], natural order
+    uint8_t *planes;                     // [frame][2][by * 8][bx * 8]
+    int64_t nblocks;                     // chroma blocks of the chunk
+    int bx, by, luma;                    // MCUs of the frame, luma blocks of an MCU
 };
 
-DecodeLayout decode_layout(int64_t n, int h, int w, int c, int ri)
+__global__ void __launch_bounds__(kRecBlock) jpeg_chroma_planes_kernel(PlaneArgs a)
 {
-    const int64_t mcus = (int64_t)((h + 7) / 8) * ((w + 7) / 8), nseg = (mcus + ri - 1) / ri;
+    __shared__ uint8_t qt[2][64];
+    for (int i = threadIdx.x; i < 2 * 64; i += kRecBlock)
+        qt[i / 64][i % 64] = a.qtables[64 + i];
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * kRecBlock + threadIdx.x;
+    if (idx >= a.nblocks)
+        return;
+    const int64_t mcus = (int64_t)a.bx * a.by;
+    const int64_t f = idx / (2 * mcus);
+    const int comp = (int)((idx % (2 * mcus)) / mcus);
+    const int row = (int)((idx % mcus) / a.bx), col = (int)((idx % mcus) % a.bx);
+    const BlockBytes blk = block_samples(a.coef + (((f * (a.luma + 2) + a.luma + comp) * mcus + idx % mcus) << 6),
+                                         qt[comp]);
+    const int64_t stride = (int64_t)a.bx * 8;
+    uint8_t *dst = a.planes + ((f * 2 + comp) * a.by * 8 + row * 8) * stride + col * 8;
+#pragma unroll
+    for (int y = 0; y < 8; y++)
+        *reinterpret_cast<uint2 *>(dst + y * stride) = make_uint2(blk.w[2 * y], blk.w[2 * y + 1]);
+}
+
+struct PixelArgs {
+    const int16_t *coef;
+    const uint8_t *qtables;
+    const uint8_t *planes;
+    uint8_t *out;
+    int64_t nblocks;                     // luma blocks of the chunk
+    int h, w, bx, by;                    // bx, by: MCUs
+};
+
+// luma 2 x LV.  The lane of luma block (R, C) writes the pixels 8R .. 8R + 7 x 8C .. 8C + 7; their chroma samples are
+// the columns 4C .. 4C + 3 and the rows 4R .. 4R + 3 (LV == 2) or 8R .. 8R + 7 (LV == 1), and the triangle reads one
+// more on each side.  Every one is fetched as the nearest real sample, so the padding of the planes is never used.
+template <int LV>
+__global__ void __launch_bounds__(kRecBlock) jpeg_pixels_kernel(PixelArgs a)
+{
+    constexpr int kLuma = 2 * LV, kRows = LV == 2 ? 6 : 8;
+    __shared__ uint8_t qt[64];
+    for (int i = threadIdx.x; i < 64; i += kRecBlock)
+        qt[i] = a.qtables[i];
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * kRecBlock + threadIdx.x;
+    if (idx >= a.nblocks)
+        return;
+    const int lbx = a.bx * 2;
+    const int64_t mcus = (int64_t)a.bx * a.by, per = mcus * kLuma;
+    const int64_t f = idx / per;
+    const int row = (int)((idx % per) / lbx), col = (int)((idx % per) % lbx);
+    const BlockBytes luma = block_samples(a.coef + ((f * (kLuma + 2) * mcus + idx % per) << 6), qt);
+
+    const int cw = (a.w + 1) / 2, ch = (a.h + LV - 1) / LV;
+    const bool tri = va_jpeg::triangle_used(cw);
+    const int64_t stride = (int64_t)a.bx * 8;
+    // per component and chroma row the six samples of the columns 4C - 1 .. 4C + 4: four in lo, two in hi
+    uint32_t lo[2][kRows], hi[2][kRows];
+#pragma unroll
+    for (int comp = 0; comp < 2; comp++) {
+        const uint8_t *plane = a.planes + (f * 2 + comp) * a.by * 8 * stride;
+#pragma unroll
+        for (int k = 0; k < kRows; k++) {
+            const uint8_t *src = plane + va_jpeg::nearest_sample(LV == 2 ? 4 * row - 1 + k : 8 * row + k, ch) * stride;
+            const uint32_t mid = *reinterpret_cast<const uint32_t *>(src + 4 * col);
+            uint32_t s[6];
+            s[0] = src[va_jpeg::nearest_sample(4 * col - 1, cw)];
+#pragma unroll
+            for (int i = 1; i < 5; i++) {
+                s[i] = mid >> (8 * (i - 1)) & 255u;
+                if (4 * col - 1 + i > cw - 1)
+                    s[i] = s[i - 1];
+            }
+            s[5] = src[va_jpeg::nearest_sample(4 * col + 4, cw)];
+            lo[comp][k] = s[0] | s[1] << 8 | s[2] << 16 | s[3] << 24;
+            hi[comp][k] = s[4] | s[5] << 8;
+        }
+    }
+
+    const int x0 = col * 8;
+    const bool complete = x0 + 8 <= a.w;
+#pragma unroll
+    for (int y = 0; y < 8; y++) {
+        const int gy = row * 8 + y;
+        if (gy >= a.h)
+            break;
+        // the local chroma row of this pixel row and the one it blends with (LV == 2: the rows start at 4R - 1)
+        const int own = LV == 2 ? 1 + (y >> 1) : y, other = LV == 2 ? va_jpeg::blend_sample(y + 2, kRows, true) : y;
+        int s[2][6];
+#pragma unroll
+        for (int comp = 0; comp < 2; comp++) {
+            const uint32_t blo = tri ? lo[comp][other] : lo[comp][own], bhi = tri ? hi[comp][other] : hi[comp][own];
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const int sh = 8 * (i & 3);
+                const int v = (int)((i < 4 ? lo[comp][own] : hi[comp][own]) >> sh & 255u);
+                s[comp][i] = LV == 2 ? va_jpeg::upsample_rows(v, (int)((i < 4 ? blo : bhi) >> sh & 255u)) : v;
+            }
+        }
+        uint8_t *dst = a.out + ((f * a.h + gy) * a.w + x0) * 3;
+        uint32_t o[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int x = 0; x < 8; x++) {
+            const int mine = 1 + (x >> 1), next = va_jpeg::blend_sample(x + 2, 6, true);
+            const int cb = va_jpeg::upsample_columns(s[0][mine], tri ? s[0][next] : s[0][mine], x, LV);
+            const int cr = va_jpeg::upsample_columns(s[1][mine], tri ? s[1][next] : s[1][mine], x, LV);
+            int r, g, b;
+            va_jpeg::rgb_of((int)(luma.w[2 * y + (x >> 2)] >> (8 * (x & 3)) & 255u), cb, cr, r, g, b);
+            o[(3 * x) / 4] |= (uint32_t)r << (8 * ((3 * x) % 4));
+            o[(3 * x + 1) / 4] |= (uint32_t)g << (8 * ((3 * x + 1) % 4));
+            o[(3 * x + 2) / 4] |= (uint32_t)b << (8 * ((3 * x + 2) % 4));
+        }
+        if (complete && ((uintptr_t)dst & 7) == 0) {
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+                reinterpret_cast<uint2 *>(dst)[i] = make_uint2(o[2 * i], o[2 * i + 1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 24; i++)
+                if (x0 + i / 3 < a.w)
+                    dst[i] = (uint8_t)(o[i / 4] >> (8 * (i % 4)));
+        }
+    }
+}
+
+// [segment table | coefficients | chroma planes (subsampled files only)]
+struct DecodeLayout {
+    size_t table, coef, planes, total;
+};
+
+DecodeLayout decode_layout(int64_t n, int h, int w, int c, int ri, int lh, int lv)
+{
+    const int64_t mcus = (int64_t)((h + 8 * lv - 1) / (8 * lv)) * ((w + 8 * lh - 1) / (8 * lh));
+    const int64_t nseg = (mcus + ri - 1) / ri, blocks = c == 1 ? 1 : lh * lv + 2;
     Carve carve;
     DecodeLayout l;
     l.table = carve.take((size_t)n * nseg * 2 * sizeof(int64_t));
-    l.coef = carve.take((size_t)n * c * mcus * 64 * sizeof(int16_t));
+    l.coef = carve.take((size_t)n * blocks * mcus * 64 * sizeof(int16_t));
+    l.planes = carve.total;
+    if (lh * lv > 1)
+        l.planes = carve.take((size_t)n * 2 * mcus * 64);
     l.total = carve.total;
     return l;
 }
 
 }  // namespace
 
-size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri) { return decode_layout(n, h, w, c, ri).total; }
-
-// the frames of one chunk: as many as the workspace holds, and no more than one launch's grid takes
-int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, size_t workspace_bytes)
+size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv)
 {
-    const int64_t mcus = (int64_t)((h + 7) / 8) * ((w + 7) / 8);
-    const int64_t grid_cap = (((int64_t)1 << 31) - kRecBlock) / mcus;
+    return decode_layout(n, h, w, c, ri, lh, lv).total;
+}
+
+// the frames of one chunk: as many as the workspace holds, and no more than one launch's grid takes (the largest
+// grid has one lane per 8 x 8 block of the frame)
+int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, size_t workspace_bytes)
+{
+    const int64_t mcus = (int64_t)((h + 8 * lv - 1) / (8 * lv)) * ((w + 8 * lh - 1) / (8 * lh));
+    const int64_t grid_cap = (((int64_t)1 << 31) - kRecBlock) / (mcus * lh * lv);
     const int64_t most = n < grid_cap ? n : grid_cap;
-    if (most < 1 || decode_layout(most, h, w, c, ri).total <= workspace_bytes)
+    if (most < 1 || decode_layout(most, h, w, c, ri, lh, lv).total <= workspace_bytes)
         return most;
     // k frames need at most k times one frame's regions, and a little less: each region rounds up once
-    const size_t one = decode_layout(1, h, w, c, ri).total;
+    const size_t one = decode_layout(1, h, w, c, ri, lh, lv).total;
     int64_t k = (int64_t)(workspace_bytes / one);
     k = k < most ? k : most;
-    while (k < most && decode_layout(k + 1, h, w, c, ri).total <= workspace_bytes)
+    while (k < most && decode_layout(k + 1, h, w, c, ri, lh, lv).total <= workspace_bytes)
         k++;
     return k;
 }
 
-int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                       int c, int ri, const uint8_t *qtables, const void *huff, uint8_t *out, int32_t *status, void *ws,
-                       size_t workspace_bytes, hipStream_t st)
+namespace {
+
+// a chunk of 4:2:0 or 4:2:2 frames behind its locate launch
+int launch_sampled_chunk(const uint8_t *bytes, const int64_t *table, int64_t k, int h, int w, int ri, int lv,
+                         const uint8_t *qtables, const void *huff, int16_t *coef, uint8_t *planes, uint8_t *out,
+                         int32_t *status, hipStream_t st)
 {
-    const int by = (h + 7) / 8, bx = (w + 7) / 8;
+    const int my = (h + 8 * lv - 1) / (8 * lv), mx = (w + 15) / 16;
+    const int64_t mcus = (int64_t)my * mx;
+    const int nseg = (int)((mcus + ri - 1) / ri);
+    const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status, k * nseg, nseg, ri,
+                        mx, my};
+    const dim3 egrid((unsigned)((k * nseg + kEntBlock - 1) / kEntBlock));
+    if (lv == 2)
+        hipLaunchKernelGGL((jpeg_entropy_sampled_kernel<2, 2>), egrid, dim3(kEntBlock), 0, st, e);
+    else
+        hipLaunchKernelGGL((jpeg_entropy_sampled_kernel<2, 1>), egrid, dim3(kEntBlock), 0, st, e);
+    VA_LAUNCH_CHECK("jpeg_entropy_sampled_kernel");
+    const PlaneArgs c{coef, qtables, planes, k * 2 * mcus, mx, my, 2 * lv};
+    hipLaunchKernelGGL(jpeg_chroma_planes_kernel, dim3((unsigned)((c.nblocks + kRecBlock - 1) / kRecBlock)),
+                       dim3(kRecBlock), 0, st, c);
+    VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
+    const PixelArgs p{coef, qtables, planes, out, k * mcus * 2 * lv, h, w, mx, my};
+    const dim3 pgrid((unsigned)((p.nblocks + kRecBlock - 1) / kRecBlock));
+    if (lv == 2)
+        hipLaunchKernelGGL(jpeg_pixels_kernel<2>, pgrid, dim3(kRecBlock), 0, st, p);
+    else
+        hipLaunchKernelGGL(jpeg_pixels_kernel<1>, pgrid, dim3(kRecBlock), 0, st, p);
+    VA_LAUNCH_CHECK("jpeg_pixels_kernel");
+    return VA_OK;
+}
+
+}  // namespace
+
+int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                       int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
+                       int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st)
+{
+    const int by = (h + 8 * lv - 1) / (8 * lv), bx = (w + 8 * lh - 1) / (8 * lh);
     const int64_t mcus = (int64_t)by * bx;
     const int nseg = (int)((mcus + ri - 1) / ri);
-    const int64_t chunk = jpeg_decode_chunk(n, h, w, c, ri, workspace_bytes);
-    const DecodeLayout l = decode_layout(chunk, h, w, c, ri);
+    const int64_t chunk = jpeg_decode_chunk(n, h, w, c, ri, lh, lv, workspace_bytes);
+    const DecodeLayout l = decode_layout(chunk, h, w, c, ri, lh, lv);
     int64_t *table = at<int64_t>(ws, l.table);
     int16_t *coef = at<int16_t>(ws, l.coef);
     for (int64_t f0 = 0; f0 < n; f0 += chunk) {
@@ -380,6 +615,14 @@ int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64
         hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
                            scan_begin + f0, nseg, table, status + f0);
         VA_LAUNCH_CHECK("jpeg_locate_kernel");
+        if (lh * lv > 1) {
+            const int rc = launch_sampled_chunk(bytes, table, k, h, w, ri, lv, qtables, huff, coef,
+                                                at<uint8_t>(ws, l.planes), out + (size_t)f0 * h * w * 3, status + f0,
+                                                st);
+            if (rc)
+                return rc;
+            continue;
+        }
         const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
                             k * nseg, nseg, ri, bx, by};
         const dim3 egrid((unsigned)((k * nseg + kEntBlock - 1) / kEntBlock));

@@ -1,7 +1,7 @@
 // va_jpeg_decode_math.h -- the serial pieces of the baseline JPEG decoder ("Motion-JPEG decoding") as
 // plain inline C++ that compiles for the host and for the device: the bit reader with the stuffing removed, the
-// Huffman step, the decode of one block with its status, the dequantiser, the 8-point inverse pass and the colour
-// conversion.  va_jpeg_decode.hip runs the entropy decode with one lane per segment and the reconstruction with one
+// Huffman step, the decode of one block with its status, the dequantiser, the 8-point inverse pass, the colour
+// conversion, and for 4:2:0 and 4:2:2 files the MCU walk and the chroma upsampling.  va_jpeg_decode.hip runs the entropy decode with one lane per segment and the reconstruction with one
 // lane per MCU; tests/jpeg_decode_shim.cpp compiles the same text with the host compiler (under sanitizers) into a
 // serial decoder whose pixels and status words are the NumPy restatement's (tests/jpeg_decode_checks.py).
 //
@@ -210,6 +210,67 @@ VA_JPEG_FN void rgb_of(int y, int cb, int cr, int &r, int &g, int &b)
     r = clip8(y + ((91881 * cr + 32768) >> 16));
     g = clip8(y - ((22554 * cb + 46802 * cr + 32768) >> 16));
     b = clip8(y + ((116130 * cb + 32768) >> 16));
+}
+
+// ------------------------------------------------------------------------------------------------ subsampled chroma
+// DESIGN.md §9, "Subsampled Motion-JPEG decoding": the luma component has H x V = 2 x 1 (4:2:2) or 2 x 2 (4:2:0)
+// blocks in an MCU of 8H x 8V pixels, Cb and Cr one each.
+
+VA_JPEG_FN constexpr int mcu_blocks(int lh, int lv) { return lh * lv + 2; }
+
+// Block k of the MCU (row, col) of a frame of my x mx MCUs, in coding order: Y (V rows of H blocks, row by row), Cb,
+// Cr.  Returns the block's index in the frame's coefficients [Y: my V x mx H blocks | Cb: my x mx | Cr: my x mx]
+// and sets its component.
+VA_JPEG_FN int64_t mcu_block_at(int k, int lh, int lv, int64_t my, int64_t mx, int64_t row, int64_t col, int &comp)
+{
+    const int luma = lh * lv;
+    if (k < luma) {
+        comp = 0;
+        return (row * lv + k / lh) * (mx * lh) + col * lh + k % lh;
+    }
+    comp = 1 + k - luma;
+    return (int64_t)k * my * mx + row * mx + col;           // the Y planes hold lh * lv * my * mx blocks
+}
+
+// libjpeg's triangle filter is used on a chroma plane of more than 2 real columns; a narrower plane (a frame of at
+// most 4 columns) is replicated in both directions
+VA_JPEG_FN bool triangle_used(int cw) { return cw > 2; }
+
+// the real sample nearest to sample i of 0 .. n - 1
+VA_JPEG_FN int nearest_sample(int i, int n) { return i < 0 ? 0 : i > n - 1 ? n - 1 : i; }
+
+// the sample that pixel g of a doubled direction blends its own sample g >> 1 with: the one before for an even g,
+// behind for an odd g, clamped to the real samples; its own sample where the plane is replicated
+VA_JPEG_FN int blend_sample(int g, int n, bool triangle)
+{
+    return triangle ? nearest_sample((g >> 1) + ((g & 1) ? 1 : -1), n) : g >> 1;
+}
+
+// V = 2, the vertical step: four times the sample of a pixel row from its own chroma row and the blended one
+VA_JPEG_FN int upsample_rows(int own, int other) { return 3 * own + other; }
+
+// the horizontal step at pixel column g: `own` and `other` are the values of blend_sample's two columns, 4 times
+// the sample after upsample_rows (lv == 2) or the samples themselves (lv == 1)
+VA_JPEG_FN int upsample_columns(int own, int other, int g, int lv)
+{
+    const int sum = 3 * own + other;
+    if (lv == 2)
+        return (sum + ((g & 1) ? 7 : 8)) >> 4;
+    return (sum + ((g & 1) ? 2 : 1)) >> 2;
+}
+
+// the upsampled sample of pixel (gy, gx) of a chroma plane with ch x cw real samples, read through c(row, column);
+// H = 2
+template <class Fetch>
+VA_JPEG_FN int upsampled_at(Fetch c, int gy, int gx, int lv, int ch, int cw)
+{
+    const bool tri = triangle_used(cw);
+    const int i = gx >> 1, i2 = blend_sample(gx, cw, tri);
+    if (lv == 2) {
+        const int j = gy >> 1, j2 = blend_sample(gy, ch, tri);
+        return upsample_columns(upsample_rows(c(j, i), c(j2, i)), upsample_rows(c(j, i2), c(j2, i2)), gx, 2);
+    }
+    return upsample_columns(c(gy, i), c(gy, i2), gx, 1);
 }
 
 }  // namespace va_jpeg

@@ -201,7 +201,9 @@ class VideoMJPEG(VideoBase):
     def __init__(self, filename, parameters=None):
         """parameters: {"decoder": "pillow"} (the default: get_frame decodes one frame on the host through Pillow) or
         {"decoder": "device"}: get_frame and iteration serve frames from batches of DEVICE_BATCH frames decoded by
-        one ops.jpeg_decode call each, through a cache of one batch"""
+        one ops.jpeg_decode call each, through a cache of one batch.  The device decoder (also behind get_frames
+        and get_device_frames) reads monochrome and 4:4:4 files and the 4:2:0 and 4:2:2 files of cameras and other
+        encoders; every frame of the file must have one shape"""
         parameters = dict(parameters or {})
         self._decoder = parameters.pop("decoder", "pillow")
         if self._decoder not in ("pillow", "device"):

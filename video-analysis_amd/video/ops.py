@@ -2365,13 +2365,18 @@ _JPEG_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "loss
                    0xCE: "arithmetic differential progressive", 0xCF: "arithmetic differential lossless"}
 
 
-def jpeg_parse_header(data):
+def jpeg_parse_header(data, sampling="1x1"):
     """what the header of one stored JPEG file says, or a ValueError that names what the decoder does not take
     ("Motion-JPEG decoding": baseline SOF0 with 8-bit samples, 1 component or 3 of 1 x 1 sampling,
-    8-bit DQT, any valid DHT, any DRI, one scan).  Returns a dict: h, w, c, ri (the restart interval in MCUs; the
-    MCUs of the frame where DRI is absent or 0), nseg, scan_begin (the byte behind the SOS header), qtables (c, 64)
-    uint8 in natural order, huff: per component ((BITS, HUFFVAL) of its DC table, of its AC table) (host only)"""
+    8-bit DQT, any valid DHT, any DRI, one scan).  sampling="any" also takes the 3-component layouts of "Subsampled
+    Motion-JPEG decoding": luma 2 x 1 (4:2:2) or 2 x 2 (4:2:0) with Cb and Cr 1 x 1.  Returns a dict: h, w, c,
+    sampling (H, V) of the luma component ((1, 1) for one component), ri (the restart interval in MCUs of 8H x 8V
+    pixels; the MCUs of the frame where DRI is absent or 0), nseg, scan_begin (the byte behind the SOS header),
+    qtables (c, 64) uint8 in natural order, huff: per component ((BITS, HUFFVAL) of its DC table, of its AC table)
+    (host only)"""
     what = "jpeg_parse_header"
+    if sampling not in ("1x1", "any"):
+        raise ValueError("%s: sampling is '1x1' or 'any', got %r" % (what, sampling))
     data = bytes(data)
     if data[:2] != b"\xff\xd8":
         raise ValueError("%s: no SOI at the start of the file" % what)
@@ -2432,15 +2437,23 @@ def jpeg_parse_header(data):
             if nc not in (1, 3) or len(p) < 6 + 3 * nc:
                 raise ValueError("%s: %d components; 1 or 3 are decoded" % (what, nc))
             comps = [(p[6 + 3 * k], p[7 + 3 * k], p[8 + 3 * k]) for k in range(nc)]
-            for _, hv, _ in comps:
+            luma = (1, 1)
+            for k, (_, hv, _) in enumerate(comps):
                 if hv != 0x11 and nc > 1:
+                    if sampling == "any" and k == 0 and hv in (0x21, 0x22):
+                        luma = (hv >> 4, hv & 15)
+                        continue
+                    if sampling == "any":
+                        raise ValueError("%s: sampling factors %d x %d of %s; luma 1 x 1, 2 x 1 (4:2:2) or 2 x 2 "
+                                         "(4:2:0) with 1 x 1 chroma sampling is decoded"
+                                         % (what, hv >> 4, hv & 15, "a chroma component" if k else "the luma component"))
                     raise ValueError("%s: sampling factors %d x %d (chroma subsampling such as 4:2:0 or 4:2:2); only "
                                      "1 x 1 sampling is decoded" % (what, hv >> 4, hv & 15))
             if h == 0:
                 raise ValueError("%s: a frame height of 0 (DNL) is not decoded" % what)
             if w == 0:
                 raise ValueError("%s: a frame width of 0" % what)
-            sof = (h, w, comps)
+            sof = (h, w, comps, luma)
         elif m == 0xCC:
             raise ValueError("%s: arithmetic coding (DAC) is not decoded" % what)
         elif m == 0xDC:
@@ -2452,7 +2465,7 @@ def jpeg_parse_header(data):
         elif m == 0xDA:
             if sof is None:
                 raise ValueError("%s: SOS before the frame header" % what)
-            h, w, comps = sof
+            h, w, comps, luma = sof
             ns = p[0] if p else 0
             if len(p) < 1 + 2 * ns + 3:
                 raise ValueError("%s: a damaged scan header" % what)
@@ -2470,10 +2483,10 @@ def jpeg_parse_header(data):
                 if td not in huff or (0x10 | ta) not in huff:
                     raise ValueError("%s: Huffman table %d / %d is not defined" % (what, td, ta))
                 tables.append((huff[td], huff[0x10 | ta]))
-            mcus = ((h + 7) // 8) * ((w + 7) // 8)
+            mcus = -(-h // (8 * luma[1])) * -(-w // (8 * luma[0]))
             ri = ri if ri else mcus
-            return dict(h=h, w=w, c=len(comps), ri=ri, nseg=(mcus + ri - 1) // ri, scan_begin=i + 2 + length,
-                        qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
+            return dict(h=h, w=w, c=len(comps), sampling=luma, ri=ri, nseg=(mcus + ri - 1) // ri,
+                        scan_begin=i + 2 + length, qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
         i += 2 + length
 
 
@@ -2501,12 +2514,13 @@ def _jpeg_decode_table(bits, vals):
 
 
 def _jpeg_header_key(head):
-    return (head["h"], head["w"], head["c"], head["ri"], head["qtables"].tobytes(), tuple(head["huff"]))
+    return (head["h"], head["w"], head["c"], head["ri"], head["qtables"].tobytes(), tuple(head["huff"]),
+            tuple(head["sampling"]))
 
 
 def jpeg_decode_groups(heads):
-    """[(first, stop)] of the runs of consecutive frames whose headers agree in size, components, restart interval
-    and tables: each run is one va_jpeg_decode_u8 call (host only)"""
+    """[(first, stop)] of the runs of consecutive frames whose headers agree in size, components, sampling, restart
+    interval and tables: each run is one va_jpeg_decode_u8 or va_jpeg_decode_sampled_u8 call (host only)"""
     groups, first = [], 0
     keys = [_jpeg_header_key(head) for head in heads]
     for k in range(1, len(keys) + 1):
@@ -2521,12 +2535,15 @@ def jpeg_status_text(status):
 
 
 def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
-    """the frames of a batch of stored baseline JPEG files ("Motion-JPEG decoding"); the pixels are
-    pinned and equal the restatement's.  streams: a list of `bytes`, or the (blob, offsets) pair that
-    jpeg_encode(ret_packed=True) returns.  Every header is parsed on the host (jpeg_parse_header, with its
-    refusals); consecutive frames with identical headers go into one va_jpeg_decode_u8 call each, whose bytes are
-    uploaded once; all frames must have one shape (ValueError otherwise).  color: None takes the components from the
-    files; True / False must agree with them.
+    """the frames of a batch of stored baseline JPEG files ("Motion-JPEG decoding" and "Subsampled
+    Motion-JPEG decoding"); the pixels are pinned and equal the restatement's.  Decoded are monochrome files, 4:4:4
+    files, and 4:2:2 and 4:2:0 files (luma 2 x 1 or 2 x 2, Cb and Cr 1 x 1: what cameras, libjpeg and Pillow write by
+    default), whose chroma is upsampled with libjpeg's triangle filter.  streams: a list of `bytes`, or the (blob,
+    offsets) pair that jpeg_encode(ret_packed=True) returns.  Every header is parsed on the host (jpeg_parse_header
+    with sampling="any", with its refusals); consecutive frames with identical headers go into one va_jpeg_decode_u8
+    call each (va_jpeg_decode_sampled_u8 for the subsampled layouts), whose bytes are uploaded once; all frames must
+    have one shape (ValueError otherwise).  color: None takes the components from the files; True / False must agree
+    with them.
     Returns the uint8 array (n, h, w) or (n, h, w, 3) RGB; keep=True: a DeviceFrames that is the caller's (nothing but
     the status words is downloaded).  A frame whose status word is not 0 raises a ValueError that names the first
     such frame and its bits; ret_status=True returns (frames, int32 status (n,)) in place of raising: blocks at and
@@ -2543,12 +2560,17 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
         blob = np.frombuffer(b"".join(files), np.uint8)
         offsets = np.concatenate([[0], np.cumsum([len(s) for s in files])]).astype(np.int64)
     n = len(offsets) - 1
-    heads = []
+    heads, last = [], (None, None)                   # last: a header's bytes up to the scan, and what they say
     for k in range(n):
+        data = blob[offsets[k]:offsets[k + 1]].tobytes()
+        if last[0] is not None and data.startswith(last[0]):     # the frames of a file mostly repeat one header
+            heads.append(last[1])
+            continue
         try:
-            heads.append(jpeg_parse_header(blob[offsets[k]:offsets[k + 1]].tobytes()))
+            heads.append(jpeg_parse_header(data, sampling="any"))
         except ValueError as err:
             raise ValueError("%s: frame %d: %s" % (what, k, err))
+        last = (data[:heads[-1]["scan_begin"]], heads[-1])
     if n == 0:
         frames = np.zeros((0, 0, 0), np.uint8)
         if keep:
@@ -2576,13 +2598,24 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
                 mb = d.upload(meta)
                 tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
                 cb = d.upload(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8))
-                one = int(L.va_jpeg_decode_workspace_bytes(1, h, w, c, head["ri"]))
-                need = int(L.va_jpeg_decode_workspace_bytes(k, h, w, c, head["ri"]))
+                luma = tuple(head["sampling"])
+                if luma == (1, 1):
+                    one = int(L.va_jpeg_decode_workspace_bytes(1, h, w, c, head["ri"]))
+                    need = int(L.va_jpeg_decode_workspace_bytes(k, h, w, c, head["ri"]))
+                else:
+                    one = int(L.va_jpeg_decode_sampled_workspace_bytes(1, h, w, c, head["ri"], *luma))
+                    need = int(L.va_jpeg_decode_sampled_workspace_bytes(k, h, w, c, head["ri"], *luma))
                 room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
                 ws = d.take(room)
-                check(L.va_jpeg_decode_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], cb.ptr,
-                                          cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes,
-                                          status_buf.ptr + 4 * first, ws.ptr, room, stream))
+                if luma == (1, 1):
+                    check(L.va_jpeg_decode_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], cb.ptr,
+                                              cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes,
+                                              status_buf.ptr + 4 * first, ws.ptr, room, stream))
+                else:
+                    check(L.va_jpeg_decode_sampled_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"],
+                                                      luma[0], luma[1], cb.ptr, cb.ptr + 64 * c, len(tables),
+                                                      out.ptr + first * frame_bytes, status_buf.ptr + 4 * first,
+                                                      ws.ptr, room, stream))
             status = status_buf.download((n,), np.int32, stream)
             if status.any() and not ret_status:
                 bad = int(np.flatnonzero(status)[0])
