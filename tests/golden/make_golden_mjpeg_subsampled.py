@@ -61,7 +61,7 @@ def hostile(data):
     """[(name, bytes)] of the hostile variants of a stream with one restart interval per MCU row: the family of
     make_golden_mjpeg_decode.py's (c), on the first three segments"""
     data = bytes(data)
-    head = S.parse_header(data)
+    head = D.parse_header(data, sampling="any")
     segs, bit = D.split_segments(data, head["scan_begin"], head["nseg"])
     assert bit == 0 and len(segs) >= 3
     out = [("cut_mid", data[:(segs[1][0] + segs[1][1]) // 2])]
@@ -86,10 +86,10 @@ def hostile(data):
 
 def cut_in_mcu(data):
     """the stream cut at the first byte of its third segment where the error falls behind the first block of an MCU"""
-    head = S.parse_header(data)
+    head = D.parse_header(data, sampling="any")
     segs, _ = D.split_segments(data, head["scan_begin"], head["nseg"])
     for cut in range(segs[2][0] + 1, segs[2][1]):
-        coefs, status, report = S.decode_coefficients(data[:cut], head, ret_segments=True)
+        coefs, status, report = D.decode_coefficients(data[:cut], head, ret_segments=True)
         if report[2] and report[2][0] and report[2][2] >= 1:
             return data[:cut]
     raise AssertionError("no cut of segment 2 ends inside an MCU")
@@ -98,9 +98,9 @@ def cut_in_mcu(data):
 def check_kept_blocks(name, data):
     """an error at block k of MCU m zeroes block k and what follows; the blocks 0 .. k - 1 of m stay: whether one
     case shows kept coefficients"""
-    head = S.parse_header(data)
+    head = D.parse_header(data, sampling="any")
     hh, vv, my, mx, _, _ = S.geometry(head)
-    coefs, status, report = S.decode_coefficients(data, head, ret_segments=True)
+    coefs, status, report = D.decode_coefficients(data, head, ret_segments=True)
     walk, shown = S.mcu_blocks((hh, vv)), False
     for j, seg in enumerate(report):
         if not seg or not seg[0]:
@@ -135,9 +135,9 @@ def main():
             for variant, kw in A_VARIANTS:
                 name = base + "_" + variant
                 data = written(frame, q, subsampling, **kw)
-                head = S.parse_header(data)
+                head = D.parse_header(data, sampling="any")
                 assert head["sampling"] == hv and head["c"] == 3, name
-                coefs, status = S.decode_coefficients(data, head)
+                coefs, status = D.decode_coefficients(data, head)
                 planes, clamped = S.integer_planes(coefs, head["qtables"])
                 ideal_planes, _ = S.float_planes(coefs, head["qtables"])
                 assert status == 0 and not clamped, name
@@ -167,14 +167,14 @@ def main():
             pillow_a.append(first[1].ravel())
             dpx_a.append(d.astype(np.int8).ravel())
     by_name = dict(zip(names_a, streams_a))
-    head = S.parse_header(by_name["420_q85_37x53_blocks3"])
+    head = D.parse_header(by_name["420_q85_37x53_blocks3"], sampling="any")
     assert head["ri"] == 3 and head["nseg"] == 4 and (3 * 4) % 3 == 0
-    head = S.parse_header(by_name["422_q85_37x53_blocks3"])
+    head = D.parse_header(by_name["422_q85_37x53_blocks3"], sampling="any")
     assert head["ri"] == 3 and head["nseg"] == 7 and (5 * 4) % 3 != 0
-    assert S.parse_header(by_name["420_q85_37x53_plain"])["nseg"] == 1
-    assert S.parse_header(by_name["420_q85_37x53_rows"])["nseg"] == 3
-    assert (S.header_key(S.parse_header(by_name["420_q85_37x53_optimized"]))[5]
-            != S.header_key(S.parse_header(by_name["420_q85_37x53_plain"]))[5])
+    assert D.parse_header(by_name["420_q85_37x53_plain"], sampling="any")["nseg"] == 1
+    assert D.parse_header(by_name["420_q85_37x53_rows"], sampling="any")["nseg"] == 3
+    assert (D.header_key(D.parse_header(by_name["420_q85_37x53_optimized"], sampling="any"))[5]
+            != D.header_key(D.parse_header(by_name["420_q85_37x53_plain"], sampling="any"))[5])
     store["names_a"], store["bases_a"] = np.array(names_a), np.array(bases_a)
     store["a_blob"] = np.frombuffer(b"".join(streams_a), np.uint8)
     store["a_offsets"] = np.concatenate([[0], np.cumsum([len(s) for s in streams_a])]).astype(np.int64)
@@ -187,9 +187,9 @@ def main():
         intact, _ = S.decode(by_name[source])
         for variant, data in hostile(by_name[source]) + [("cut_in_mcu", cut_in_mcu(by_name[source]))]:
             name = source + "_" + variant
-            head = S.parse_header(data)
+            head = D.parse_header(data, sampling="any")
             pixels, status = S.decode(data, head)
-            assert status == S.decode_coefficients(data, head)[1]
+            assert status == D.decode_coefficients(data, head)[1]
             shown = check_kept_blocks(name, data)
             kept += shown
             assert shown or variant != "cut_in_mcu", name
@@ -213,7 +213,7 @@ def main():
         bad = bytearray(good)
         bad[sof + 11 + 3 * comp] = factors
         try:
-            S.parse_header(bytes(bad))
+            D.parse_header(bytes(bad), sampling="any")
         except ValueError as err:
             assert word in str(err), (name, err)
         else:

@@ -1,9 +1,13 @@
 """The Motion-JPEG decoder of DESIGN.md §9, "Motion-JPEG decoding", restated in NumPy: this file is the definition,
-and the device equals it byte for byte, status words included.  The header parse with its refusals, the segment
-splitter, the entropy decode with its status bits, the integer dequantiser and inverse transform, the fixed-point
-colour conversion; also the float64 decode of the same coefficients that the accuracy condition is stated against.
+and the device equals it byte for byte, status words included.  The header parse of every sampling layout with its
+refusals, the segment splitter, the entropy decode over the MCUs of every layout with its status bits, the integer
+dequantiser and inverse transform, the fixed-point colour conversion (what only 4:2:0 and 4:2:2 files need is
+jpeg_subsampled_checks.py); also the float64 decode of the same coefficients that the accuracy condition is stated against.
 Nothing here imports the package."""
+import os
+import shutil
 import struct
+import subprocess
 
 import numpy as np
 
@@ -19,10 +23,15 @@ _SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless"
 
 
 # ------------------------------------------------------------------------------------------------ header
-def parse_header(data):
-    """what a stored file's header says, or ValueError naming what the decoder does not take: dict of h, w, c, ri
-    (the restart interval in MCUs; the MCUs of the frame where DRI is absent or 0), nseg, scan_begin, qtables
-    (c, 64) uint8 in natural order, huff: per component ((BITS, HUFFVAL) of its DC table, of its AC table)"""
+def parse_header(data, sampling="1x1"):
+    """what a stored file's header says, or ValueError naming what the decoder does not take: dict of h, w, c,
+    sampling (H, V) of the luma component, ri (the restart interval in MCUs of 8H x 8V pixels; the MCUs of the frame
+    where DRI is absent or 0), nseg, scan_begin, qtables (c, 64) uint8 in natural order, huff: per component ((BITS,
+    HUFFVAL) of its DC table, of its AC table).  sampling="1x1" takes 1 component (of any factors, decoded as 1 x 1)
+    or 3 of 1 x 1; "any" also takes 3 components whose luma is 2 x 1 (4:2:2) or 2 x 2 (4:2:0) and whose chroma
+    components are 1 x 1 ("Subsampled Motion-JPEG decoding")."""
+    if sampling not in ("1x1", "any"):
+        raise ValueError("sampling is '1x1' or 'any', got %r" % (sampling,))
     data = bytes(data)
     if data[:2] != b"\xff\xd8":
         raise ValueError("no SOI at the start")
@@ -82,15 +91,25 @@ def parse_header(data):
             if nc not in (1, 3) or len(p) < 6 + 3 * nc:
                 raise ValueError("%d components: 1 or 3 are decoded" % nc)
             comps = [(p[6 + 3 * k], p[7 + 3 * k], p[8 + 3 * k]) for k in range(nc)]
-            for cid, hv, tq in comps:
-                if hv != 0x11 and nc > 1:
+            luma = (1, 1)
+            for k, (cid, hv, tq) in enumerate(comps):
+                if hv == 0x11 or nc == 1:
+                    continue
+                if sampling == "1x1":
                     raise ValueError("sampling factors %d x %d (chroma subsampling such as 4:2:0 or 4:2:2): only 1 x 1 "
                                      "sampling is decoded" % (hv >> 4, hv & 15))
+                if k:
+                    raise ValueError("sampling factors %d x %d of a chroma component: only 1 x 1 chroma sampling is "
+                                     "decoded" % (hv >> 4, hv & 15))
+                if hv not in (0x21, 0x22):
+                    raise ValueError("sampling factors %d x %d of the luma component: 1 x 1, 2 x 1 (4:2:2) and 2 x 2 (4:2:0) "
+                                     "are decoded" % (hv >> 4, hv & 15))
+                luma = (hv >> 4, hv & 15)
             if h == 0:
                 raise ValueError("a frame height of 0 (DNL) is not decoded")
             if w == 0:
                 raise ValueError("a frame width of 0")
-            sof = (h, w, comps)
+            sof = (h, w, comps, luma)
         elif m == 0xCC:
             raise ValueError("arithmetic coding (DAC) is not decoded")
         elif m == 0xDC:
@@ -102,7 +121,7 @@ def parse_header(data):
         elif m == 0xDA:
             if sof is None:
                 raise ValueError("SOS before the frame header")
-            h, w, comps = sof
+            h, w, comps, luma = sof
             ns = p[0] if p else 0
             if len(p) < 1 + 2 * ns + 3:
                 raise ValueError("a damaged scan header")
@@ -119,10 +138,10 @@ def parse_header(data):
                 if td not in huff or (0x10 | ta) not in huff:
                     raise ValueError("Huffman table %d / %d is not defined" % (td, ta))
                 tables.append((huff[td], huff[0x10 | ta]))
-            mcus = ((h + 7) // 8) * ((w + 7) // 8)
+            mcus = -(-h // (8 * luma[1])) * -(-w // (8 * luma[0]))
             ri = ri if ri else mcus
-            return dict(h=h, w=w, c=len(comps), ri=ri, nseg=(mcus + ri - 1) // ri, scan_begin=i + 2 + length,
-                        qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
+            return dict(h=h, w=w, c=len(comps), sampling=luma, ri=ri, nseg=(mcus + ri - 1) // ri,
+                        scan_begin=i + 2 + length, qtables=np.stack([qt[tq] for _, _, tq in comps]), huff=tables)
         i += 2 + length
 
 
@@ -248,35 +267,51 @@ def decode_block(bits, dc, ac, pred):
 _ZZ = [int(v) for v in J.ZIGZAG]
 
 
+def mcu_blocks(hv, c=3):
+    """the blocks of an MCU in coding order: [(component, block row in the MCU, block column in the MCU)]; the MCU of
+    a 1-component frame is its one block"""
+    if c == 1:
+        return [(0, 0, 0)]
+    return [(0, v, u) for v in range(hv[1]) for u in range(hv[0])] + [(1, 0, 0), (2, 0, 0)]
+
+
 def decode_coefficients(data, head=None, ret_segments=False):
-    """((c, by, bx, 64) int64 quantised coefficients in natural order, the status word).  After an error in a
-    segment its block and the later blocks of the segment are zero; so are the blocks of a missing segment.
-    ret_segments: also the list per segment of None (missing) or (status bit or 0, the MCU of the error or None)"""
+    """(the int64 quantised coefficients in natural order, the status word).  The coefficients of a 1 x 1 or
+    1-component frame are one (c, by, bx, 64) array; those of luma H x V are [Y (my * V, mx * H, 64), Cb (my, mx, 64),
+    Cr (my, mx, 64)].  After an error the block where it happened and every later block of the segment are zero,
+    earlier blocks of the same MCU keep their coefficients; the blocks of a missing segment are zero.
+    ret_segments: also per segment None (missing) or (status bit or 0, the MCU of the error or None, the index of
+    the block in that MCU or None)"""
     data = bytes(data)
     head = head or parse_header(data)
-    h, w, c, ri = head["h"], head["w"], head["c"], head["ri"]
-    by, bx = (h + 7) // 8, (w + 7) // 8
+    c, ri, (hh, vv) = head["c"], head["ri"], head["sampling"]
+    my, mx = -(-head["h"] // (8 * vv)), -(-head["w"] // (8 * hh))
     segs, status = split_segments(data, head["scan_begin"], head["nseg"])
     luts = [(_lut(dc), _lut(ac)) for dc, ac in head["huff"]]
-    coefs = np.zeros((c, by, bx, 64), np.int64)
-    report = []
+    coefs = [np.zeros((my * vv, mx * hh, 64), np.int64)] + [np.zeros((my, mx, 64), np.int64) for _ in range(c - 1)]
+    walk, report = mcu_blocks((hh, vv), c), []
     for j, seg in enumerate(segs):
-        report.append(None if seg is None else (0, None))
+        report.append(None if seg is None else (0, None, None))
         if seg is None:
             continue
         bits, pred = _Bits(unstuffed(data, *seg)), [0] * c
         dead = False
-        for m in range(j * ri, min((j + 1) * ri, by * bx)):
-            for ch in range(c):
-                st, block, pred[ch] = decode_block(bits, luts[ch][0], luts[ch][1], pred[ch])
+        for m in range(j * ri, min((j + 1) * ri, my * mx)):
+            row, col = m // mx, m % mx
+            for k, (comp, v, u) in enumerate(walk):
+                st, block, pred[comp] = decode_block(bits, luts[comp][0], luts[comp][1], pred[comp])
                 if st:
                     status |= st
                     dead = True
-                    report[-1] = (st, m)
+                    report[-1] = (st, m, k)
                     break
-                coefs[ch, m // bx, m % bx] = block
+                if comp == 0:
+                    coefs[0][row * vv + v, col * hh + u] = block
+                else:
+                    coefs[comp][row, col] = block
             if dead:
                 break
+    coefs = np.stack(coefs) if (hh, vv) == (1, 1) else coefs
     return (coefs, status, report) if ret_segments else (coefs, status)
 
 
@@ -339,4 +374,43 @@ def ideal_decode(data, head=None):
 def header_key(head):
     """what two frames must share to go into one call"""
     return (head["h"], head["w"], head["c"], head["ri"], head["qtables"].tobytes(),
-            tuple((tuple(dc[0]), tuple(dc[1]), tuple(ac[0]), tuple(ac[1])) for dc, ac in head["huff"]))
+            tuple((tuple(dc[0]), tuple(dc[1]), tuple(ac[0]), tuple(ac[1])) for dc, ac in head["huff"]),
+            tuple(head["sampling"]))
+
+
+# ------------------------------------------------------------------------------------------------ the host shim
+def build_shim(root, out_dir):
+    """tests/jpeg_decode_shim.cpp compiled for the host with -fsanitize=address,undefined into a stand-alone program:
+    its path"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "llvm", "bin", "clang++")
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or (
+        rocm_clang if os.path.exists(rocm_clang) else None)
+    assert cxx is not None, "no host C++ compiler: neither g++, c++ or clang++ on the PATH nor %s" % rocm_clang
+    exe = os.path.join(str(out_dir), "jpeg_decode_shim")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(root, "video-analysis_amd", "csrc"),
+                           os.path.join(root, "tests", "jpeg_decode_shim.cpp"), "-o", exe])
+    return exe
+
+
+def shim_record(data, head, table):
+    """one record of the shim's input: `data` under the header `head`; table(BITS, HUFFVAL) is a HuffDecode's bytes"""
+    tables = b"".join(table(*dc) + table(*ac) for dc, ac in head["huff"])
+    return (struct.pack("<8i", head["h"], head["w"], head["c"], head["ri"], head["scan_begin"], len(data),
+                        *head["sampling"]) + head["qtables"].tobytes() + tables + data)
+
+
+def run_shim(exe, records):
+    """the lines the program prints for the records, one each"""
+    run = subprocess.run([exe], input=b"".join(records), capture_output=True)
+    assert run.returncode == 0, run.stderr.decode()[-2000:]
+    return run.stdout.decode().split("\n")[:-1]
+
+
+def shim_line(pixels, status):
+    """the line of a record that decodes to these pixels and this status word: the status and the 64-bit FNV-1a hash"""
+    h = 1469598103934665603
+    for v in pixels.tobytes():
+        h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return "%d %d" % (status, h)

@@ -1,9 +1,9 @@
 """The decoder of 4:2:0 and 4:2:2 files of DESIGN.md §9, "Subsampled Motion-JPEG decoding", restated in NumPy: this
 file is the definition, and the device equals it byte for byte, status words included.  Everything shared with the
 1 x 1 decoder (segments, entropy decode, status bits, dequantiser, the inverse passes, the colour formula) is
-jpeg_decode_checks'; here are the header parse that takes the two layouts, the MCU walk into per-component coefficient
-planes, libjpeg's integer triangle upsampling with its edge rules, and a small encoder that writes such streams as
-inputs for tests.  Nothing here imports the package."""
+jpeg_decode_checks', the header parse (parse_header(data, sampling="any")) and the MCU walk into per-component
+coefficient planes included; here are libjpeg's integer triangle upsampling with its edge rules, the decode of the two
+layouts through it, and a small encoder that writes such streams as inputs for tests.  Nothing here imports the package."""
 import struct
 
 import numpy as np
@@ -14,119 +14,14 @@ import jpeg_decode_checks as D
 LAYOUTS = ((2, 1), (2, 2))              # (H, V) of the luma component: 4:2:2, 4:2:0
 
 
-# ------------------------------------------------------------------------------------------------ header
-def _walk(data):
-    """[(marker, offset of the payload, payload length)] up to and including SOS, as far as the bytes allow"""
-    out, i = [], 2
-    while i + 4 <= len(data) and data[i] == 0xFF:
-        m = data[i + 1]
-        if m == 0xFF:
-            i += 1
-            continue
-        if m == 0x01 or 0xD0 <= m <= 0xD7:
-            i += 2
-            continue
-        length = struct.unpack(">H", data[i + 2:i + 4])[0]
-        if m in (0xD8, 0xD9) or length < 2 or i + 2 + length > len(data):
-            break
-        out.append((m, i + 4, length - 2))
-        if m == 0xDA:
-            break
-        i += 2 + length
-    return out
-
-
-def parse_header(data, sampling="any"):
-    """jpeg_decode_checks.parse_header with `sampling` = (H, V) of the luma component in the dict.  "1x1" refuses
-    what that parser refuses; "any" also takes a 3-component frame whose luma is 2 x 1 or 2 x 2 and whose chroma
-    components are 1 x 1: an MCU then covers 8H x 8V pixels, and ri and nseg count those MCUs."""
-    data = bytes(data)
-    if sampling == "1x1":
-        return dict(D.parse_header(data), sampling=(1, 1))
-    if sampling != "any":
-        raise ValueError("sampling is '1x1' or 'any', got %r" % (sampling,))
-    segs = _walk(data)
-    sofs = [(at, n) for m, at, n in segs if m == 0xC0]
-    hv = (1, 1)
-    if len(sofs) == 1 and sofs[0][1] >= 15 and data[sofs[0][0]] == 8 and data[sofs[0][0] + 5] == 3:
-        at = sofs[0][0] + 6
-        luma, cb, cr = (data[at + 3 * k + 1] for k in range(3))
-        for chroma in (cb, cr):
-            if chroma != 0x11:
-                raise ValueError("sampling factors %d x %d of a chroma component: only 1 x 1 chroma sampling is "
-                                 "decoded" % (chroma >> 4, chroma & 15))
-        if luma not in (0x11, 0x21, 0x22):
-            raise ValueError("sampling factors %d x %d of the luma component: 1 x 1, 2 x 1 (4:2:2) and 2 x 2 (4:2:0) "
-                             "are decoded" % (luma >> 4, luma & 15))
-        hv = (luma >> 4, luma & 15)
-        patched = bytearray(data)
-        patched[at + 1] = 0x11
-        data = bytes(patched)
-    head = dict(D.parse_header(data), sampling=hv)
-    if hv != (1, 1):
-        ri = 0
-        for m, at, n in segs:
-            if m == 0xDD:
-                ri = struct.unpack(">H", data[at:at + 2])[0]
-        mcus = -(-head["h"] // (8 * hv[1])) * -(-head["w"] // (8 * hv[0]))
-        head["ri"] = ri if ri else mcus
-        head["nseg"] = -(-mcus // head["ri"])
-    return head
-
-
-def mcu_blocks(hv):
-    """the blocks of an MCU in coding order: [(component, block row in the MCU, block column in the MCU)]"""
-    return [(0, v, u) for v in range(hv[1]) for u in range(hv[0])] + [(1, 0, 0), (2, 0, 0)]
+# ------------------------------------------------------------------------------------------------ geometry
+mcu_blocks = D.mcu_blocks               # [(component, block row in the MCU, block column in the MCU)] in coding order
 
 
 def geometry(head):
     """(H, V, my, mx, ch, cw): the MCU grid and the real samples of a chroma plane"""
     hh, vv = head["sampling"]
     return hh, vv, -(-head["h"] // (8 * vv)), -(-head["w"] // (8 * hh)), -(-head["h"] // vv), -(-head["w"] // hh)
-
-
-def header_key(head):
-    """what two frames must share to go into one call"""
-    return D.header_key(head) + (tuple(head["sampling"]),)
-
-
-# ------------------------------------------------------------------------------------------------ entropy decode
-def decode_coefficients(data, head=None, ret_segments=False):
-    """([Y (my * V, mx * H, 64), Cb (my, mx, 64), Cr (my, mx, 64)] int64 quantised coefficients in natural order, the
-    status word).  After an error the block where it happened and every later block of the segment are zero; earlier
-    blocks of the same MCU keep their coefficients.  ret_segments: also per segment None (missing) or (status bit or
-    0, the MCU of the error or None, the index of the block in that MCU or None)"""
-    data = bytes(data)
-    head = head or parse_header(data)
-    hh, vv, my, mx, _, _ = geometry(head)
-    ri = head["ri"]
-    segs, status = D.split_segments(data, head["scan_begin"], head["nseg"])
-    luts = [(D._lut(dc), D._lut(ac)) for dc, ac in head["huff"]]
-    coefs = [np.zeros((my * vv, mx * hh, 64), np.int64), np.zeros((my, mx, 64), np.int64),
-             np.zeros((my, mx, 64), np.int64)]
-    walk, report = mcu_blocks((hh, vv)), []
-    for j, seg in enumerate(segs):
-        report.append(None if seg is None else (0, None, None))
-        if seg is None:
-            continue
-        bits, pred = D._Bits(D.unstuffed(data, *seg)), [0, 0, 0]
-        dead = False
-        for m in range(j * ri, min((j + 1) * ri, my * mx)):
-            row, col = m // mx, m % mx
-            for k, (comp, v, u) in enumerate(walk):
-                st, block, pred[comp] = D.decode_block(bits, luts[comp][0], luts[comp][1], pred[comp])
-                if st:
-                    status |= st
-                    dead = True
-                    report[-1] = (st, m, k)
-                    break
-                if comp == 0:
-                    coefs[0][row * vv + v, col * hh + u] = block
-                else:
-                    coefs[comp][row, col] = block
-            if dead:
-                break
-    return (coefs, status, report) if ret_segments else (coefs, status)
 
 
 # ------------------------------------------------------------------------------------------------ reconstruction
@@ -181,10 +76,10 @@ def full_planes(planes, head):
 
 def decode(data, head=None):
     """(the frame, uint8 (h, w, 3) RGB or (h, w); the status word) of one stored file"""
-    head = head or parse_header(data)
+    head = head or D.parse_header(data, sampling="any")
     if head["c"] == 1 or tuple(head["sampling"]) == (1, 1):
         return D.decode(data, head)
-    coefs, status = decode_coefficients(data, head)
+    coefs, status = D.decode_coefficients(data, head)
     planes, _ = integer_planes(coefs, head["qtables"])
     return D.rgb_of(full_planes(planes, head)).astype(np.uint8), status
 
@@ -192,10 +87,10 @@ def decode(data, head=None):
 def ideal_decode(data, head=None):
     """dequantise, float64 IDCT, round and clip, the same integer upsampling, the JFIF inverse matrix in float64,
     round and clip"""
-    head = head or parse_header(data)
+    head = head or D.parse_header(data, sampling="any")
     if head["c"] == 1 or tuple(head["sampling"]) == (1, 1):
         return D.ideal_decode(data, head)
-    coefs, _ = decode_coefficients(data, head)
+    coefs, _ = D.decode_coefficients(data, head)
     planes, _ = float_planes(coefs, head["qtables"])
     return D.ideal_rgb_of(full_planes(planes, head)).astype(np.uint8)
 

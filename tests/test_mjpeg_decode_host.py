@@ -4,11 +4,9 @@ The restatement tests/jpeg_decode_checks.py against the fixture tests/golden/mjp
 decode within the IDCT bounds, the header parser of video.ops on the accepted and the refused streams, the grouping
 of mixed headers, the segment splitter on hand-made bytes, the device's Huffman tables as the host builds them, the
 C ABI's declaration and refusals, VideoMJPEG with its default decoder, and va_jpeg_decode_math.h compiled into a
-stand-alone program under sanitizers."""
+stand-alone program under sanitizers (tests/jpeg_decode_shim.cpp, the one shim of every sampling layout), on this
+fixture and on records of this and the subsampled fixture alternating in one run."""
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -360,49 +358,49 @@ def test_run_frames_refuses_before_it_touches_the_device():
 
 
 # ------------------------------------------------------------------------------------------------ the header
+def _with_cuts(everything, sources, decode):
+    """`everything` and, hand-made from each of `sources`: a file that is its header alone, and one that ends with FF.
+    [(name, bytes, expected pixels, expected status, the header to decode under)]"""
+    from video import ops
+    out = [(name, data, want, status, ops.jpeg_parse_header(data, sampling="any")) for name, data, want, status in everything]
+    for name, data, _, _ in sources:
+        head = ops.jpeg_parse_header(data, sampling="any")
+        for cut in (data[:head["scan_begin"]], data[:head["scan_begin"] + 1] + b"\xff"):
+            pixels, status = decode(cut, D.parse_header(data, sampling="any"))
+            assert status & D.MARKER
+            out.append((name + " cut", cut, pixels, status, head))
+    return out
+
+
+def _check_shim(exe, everything):
+    from video import ops
+    lines = D.run_shim(exe, [D.shim_record(data, head, ops._jpeg_decode_table) for _, data, _, _, head in everything])
+    assert len(lines) == len(everything)
+    for (name, _, want, want_status, _), line in zip(everything, lines):
+        assert line == D.shim_line(want, want_status), name
+
+
 def test_decode_math_header_on_the_host_under_sanitizers(cases, tmp_path):
     """va_jpeg_decode_math.h compiled for the host with -fsanitize=address,undefined into a stand-alone program that
     decodes every fixture stream, the hostile ones included, from a heap buffer of exactly the stream's size; its
     status words and the hash of its pixels are the restatement's"""
-    from video import ops
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "llvm", "bin", "clang++")
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or (
-        rocm_clang if os.path.exists(rocm_clang) else None)
-    assert cxx is not None, "no host C++ compiler: neither g++, c++ or clang++ on the PATH nor %s" % rocm_clang
-    exe = str(tmp_path / "jpeg_decode_shim")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "video-analysis_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "jpeg_decode_shim.cpp"), "-o", exe])
+    everything = _with_cuts(cases["a"] + cases["b"] + cases["c"], (cases["a"][5], cases["a"][-1]), D.decode)
+    assert len(everything) == 120 + 96 + 28 + 4
+    _check_shim(D.build_shim(ROOT, tmp_path), everything)
 
-    def fnv(pixels):
-        h = 1469598103934665603
-        for v in pixels.tobytes():
-            h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return h
-    everything = cases["a"] + cases["b"] + cases["c"]
-    text = []
-    for name, data, _, _ in everything:
-        head = ops.jpeg_parse_header(data)
-        tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
-        text.append(struct.pack("<6i", head["h"], head["w"], head["c"], head["ri"], head["scan_begin"], len(data))
-                    + head["qtables"].tobytes() + tables + data)
-    # hand-made: a file that is its header alone, and one that ends with FF
-    for name, data, _, _ in (cases["a"][5], cases["a"][-1]):
-        head = ops.jpeg_parse_header(data)
-        for cut in (data[:head["scan_begin"]], data[:head["scan_begin"] + 1] + b"\xff"):
-            tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
-            text.append(struct.pack("<6i", head["h"], head["w"], head["c"], head["ri"], head["scan_begin"], len(cut))
-                        + head["qtables"].tobytes() + tables + cut)
-            pixels, status = D.decode(cut, head)
-            assert status & D.MARKER
-            everything = everything + [(name + " cut", cut, pixels, status)]
-    run = subprocess.run([exe], input=b"".join(text), capture_output=True)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    lines = run.stdout.decode().split("\n")[:-1]
-    assert len(lines) == len(everything)
-    for (name, _, want, want_status), line in zip(everything, lines):
-        assert line == "%d %d" % (want_status, fnv(want)), name
+
+def test_layouts_interleaved_in_one_run_of_the_host_program(cases, tmp_path):
+    """records of this fixture and of the subsampled one, alternating, in a single run of the same program: no state
+    of one layout leaks into the next record"""
+    import jpeg_subsampled_checks as S
+    sub = S.fixture_cases(os.path.join(ROOT, "tests", "golden", "mjpeg_subsampled_v1.npz"))[0]
+    plain = _with_cuts((cases["a"] + cases["b"])[::9] + cases["c"], cases["a"][5:6], D.decode)
+    sampled = _with_cuts(sub["a"][::8] + sub["b"], [c for c in sub["a"] if c[0] == "420_q85_17x33_rows"], S.decode)
+    mixed = [x for pair in zip(plain, sampled) for x in pair]
+    layouts = [(x[4]["c"],) + tuple(x[4]["sampling"]) for x in mixed]
+    assert set(layouts) == {(1, 1, 1), (3, 1, 1), (3, 2, 1), (3, 2, 2)} and len(mixed) >= 100
+    assert all(a != b for a, b in zip(layouts, layouts[1:]))
+    _check_shim(D.build_shim(ROOT, tmp_path), mixed)
 
 
 def test_product_does_not_import_the_restatement():

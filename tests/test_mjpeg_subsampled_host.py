@@ -1,14 +1,12 @@
 """CPU: the decoder of 4:2:0 and 4:2:2 files ("Subsampled Motion-JPEG decoding") and its host layer.
 
-The restatement tests/jpeg_subsampled_checks.py against the fixture tests/golden/mjpeg_subsampled_v1.npz and against
-the ideal decode within the derived bounds, the upsampling's edge rules on hand-made planes, the header parser of
-video.ops with sampling="any" on the accepted and the refused streams and with its default on all of them, the
-grouping of layouts, the restated encoder, the C ABI's declarations and refusals, and va_jpeg_decode_math.h compiled
-into a stand-alone program under sanitizers."""
+The restatement (tests/jpeg_decode_checks.py with sampling="any", and tests/jpeg_subsampled_checks.py for what only
+these layouts need) against the fixture tests/golden/mjpeg_subsampled_v1.npz and against the ideal decode within the
+derived bounds, the upsampling's edge rules on hand-made planes, the header parser of video.ops with sampling="any"
+on the accepted and the refused streams and with its default on all of them, the grouping of layouts, the restated
+encoder, the C ABI's declarations and refusals, and va_jpeg_decode_math.h compiled into a stand-alone program under
+sanitizers (tests/jpeg_decode_shim.cpp, the one shim of every layout)."""
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -41,7 +39,7 @@ def test_restatement_still_decodes_to_the_fixture(cases):
             assert status == want_status and got.dtype == np.uint8 and np.array_equal(got, want), name
             bits |= status
     assert bits == D.BAD_CODE | D.OVERRUN | D.TRUNCATED | D.MARKER
-    layouts = {S.parse_header(data)["sampling"] for _, data, _, _ in cases["a"]}
+    layouts = {D.parse_header(data, sampling="any")["sampling"] for _, data, _, _ in cases["a"]}
     assert layouts == {(2, 1), (2, 2)}
 
 
@@ -52,8 +50,8 @@ def test_accuracy_condition(golden):
     distances to Pillow's decode are measurements: every component sample within 1, RGB within 3."""
     cases, z = golden
     for name, data, want, _ in cases["a"]:
-        head = S.parse_header(data)
-        coefs, status = S.decode_coefficients(data, head)
+        head = D.parse_header(data, sampling="any")
+        coefs, status = D.decode_coefficients(data, head)
         planes, clamped = S.integer_planes(coefs, head["qtables"])
         ideal, _ = S.float_planes(coefs, head["qtables"])
         assert status == 0 and not clamped, name
@@ -68,7 +66,7 @@ def test_variants_of_a_picture_decode_to_the_same_pixels(cases):
     by_name = {name: want for name, _, want, _ in cases["a"]}
     for name, want in by_name.items():
         assert np.array_equal(want, by_name[name.rsplit("_", 1)[0] + "_plain"]), name
-    heads = {name: S.parse_header(data) for name, data, _, _ in cases["a"] if "q85_37x53" in name and "smooth" not in name}
+    heads = {name: D.parse_header(data, sampling="any") for name, data, _, _ in cases["a"] if "q85_37x53" in name and "smooth" not in name}
     assert (heads["420_q85_37x53_plain"]["ri"], heads["420_q85_37x53_plain"]["nseg"]) == (12, 1)
     assert (heads["420_q85_37x53_rows"]["ri"], heads["420_q85_37x53_rows"]["nseg"]) == (4, 3)
     assert (heads["420_q85_37x53_blocks3"]["ri"], heads["420_q85_37x53_blocks3"]["nseg"]) == (3, 4)
@@ -109,9 +107,9 @@ def test_upsampling_on_hand_made_planes():
 def test_an_error_inside_an_mcu_keeps_its_earlier_blocks(cases):
     shown = []
     for name, data, want, want_status in cases["b"]:
-        head = S.parse_header(data)
+        head = D.parse_header(data, sampling="any")
         hh, vv, my, mx, _, _ = S.geometry(head)
-        coefs, status, report = S.decode_coefficients(data, head, ret_segments=True)
+        coefs, status, report = D.decode_coefficients(data, head, ret_segments=True)
         walk = S.mcu_blocks((hh, vv))
         for j, seg in enumerate(report):
             if not seg or not seg[0]:
@@ -137,7 +135,7 @@ def test_restated_encoder_writes_what_pillow_and_the_restatement_read():
             first = None
             for ri in (None, 0, 3):
                 data = S.encode_frame(frame, 90, hv, ri)
-                head = S.parse_header(data)
+                head = D.parse_header(data, sampling="any")
                 hh, vv, my, mx, _, _ = S.geometry(head)
                 assert head["sampling"] == hv and (b"\xff\xdd" in data[:head["scan_begin"]]) == (ri != 0)
                 assert head["ri"] == (mx if ri is None else ri or my * mx)
@@ -159,15 +157,15 @@ def test_restated_encoder_writes_what_pillow_and_the_restatement_read():
 def test_both_parsers_agree(cases):
     from video import ops
     for name, data, want, _ in cases["a"] + cases["b"]:
-        head, mine = S.parse_header(data), ops.jpeg_parse_header(data, sampling="any")
-        assert S.header_key(head) == S.header_key(mine) and head["scan_begin"] == mine["scan_begin"], name
+        head, mine = D.parse_header(data, sampling="any"), ops.jpeg_parse_header(data, sampling="any")
+        assert D.header_key(head) == D.header_key(mine) and head["scan_begin"] == mine["scan_begin"], name
         assert mine["sampling"] == head["sampling"] == ((2, 2) if name.startswith("420") else (2, 1)), name
         assert (mine["h"], mine["w"], mine["c"]) == want.shape and mine["nseg"] == head["nseg"], name
         hh, vv, my, mx, _, _ = S.geometry(mine)
         assert mine["nseg"] == -(-(my * mx) // mine["ri"])
     for name, data, word in cases["c"]:
-        for parse in (lambda d: ops.jpeg_parse_header(d, sampling="any"), S.parse_header, ops.jpeg_parse_header,
-                      D.parse_header):
+        for parse in (lambda d: ops.jpeg_parse_header(d, sampling="any"), lambda d: D.parse_header(d, sampling="any"),
+                      ops.jpeg_parse_header, D.parse_header):
             with pytest.raises(ValueError) as err:
                 parse(data)
             assert word in str(err.value), (name, err.value)
@@ -179,7 +177,7 @@ def test_the_default_parse_still_refuses_every_subsampled_stream(cases):
     from video import ops
     for name, data, _, _ in cases["a"]:
         for parse in (ops.jpeg_parse_header, lambda d: ops.jpeg_parse_header(d, sampling="1x1"),
-                      lambda d: S.parse_header(d, sampling="1x1")):
+                      lambda d: D.parse_header(d, sampling="1x1")):
             with pytest.raises(ValueError) as err:
                 parse(data)
             assert "sampling" in str(err.value), name
@@ -197,13 +195,14 @@ def test_one_component_and_1x1_files_parse_as_before(cases):
         plain, any_ = ops.jpeg_parse_header(data), ops.jpeg_parse_header(data, sampling="any")
         assert plain["sampling"] == any_["sampling"] == (1, 1)
         assert ops._jpeg_header_key(plain) == ops._jpeg_header_key(any_) and plain["nseg"] == any_["nseg"]
-        assert S.header_key(S.parse_header(data)) == S.header_key(any_)
+        assert D.header_key(D.parse_header(data, sampling="any")) == D.header_key(any_)
     # a 1-component frame takes any factors and is decoded as 1 x 1
     grey = dec["b_bytes_L_q85_37x53_rows"].tobytes()
     sof = grey.index(b"\xff\xc0\x00\x0b\x08")
     odd = bytearray(grey)
     odd[sof + 11] = 0x22
-    for parse in (ops.jpeg_parse_header, lambda d: ops.jpeg_parse_header(d, sampling="any"), S.parse_header):
+    for parse in (ops.jpeg_parse_header, lambda d: ops.jpeg_parse_header(d, sampling="any"), D.parse_header,
+                  lambda d: D.parse_header(d, sampling="any")):
         head = parse(bytes(odd))
         assert head["sampling"] == (1, 1) and (head["ri"], head["nseg"]) == (7, 5)
 
@@ -218,7 +217,7 @@ def test_layouts_of_one_shape_fall_into_different_groups(cases):
     assert [hd["sampling"] for hd in heads] == [(2, 2), (2, 2), (1, 1), (1, 1), (2, 1), (2, 2)]
     assert len({(hd["h"], hd["w"], hd["c"], hd["ri"]) for hd in heads}) == 1           # only the sampling differs
     assert ops.jpeg_decode_groups(heads) == [(0, 2), (2, 4), (4, 5), (5, 6)]
-    assert len({S.header_key(hd) for hd in heads}) == 3
+    assert len({D.header_key(hd) for hd in heads}) == 3
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
@@ -282,43 +281,20 @@ def test_subsampled_math_on_the_host_under_sanitizers(cases, tmp_path):
     size; its status words and the hash of its pixels are the restatement's.  The program aborts where the
     upsampling asks for a sample that is not a real one."""
     from video import ops
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "llvm", "bin", "clang++")
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or (
-        rocm_clang if os.path.exists(rocm_clang) else None)
-    assert cxx is not None, "no host C++ compiler: neither g++, c++ or clang++ on the PATH nor %s" % rocm_clang
-    exe = str(tmp_path / "jpeg_subsampled_shim")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "video-analysis_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "jpeg_subsampled_shim.cpp"), "-o", exe])
-
-    def fnv(pixels):
-        h = 1469598103934665603
-        for v in pixels.tobytes():
-            h = ((h ^ v) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return h
-
-    def record(data, head):
-        tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
-        return (struct.pack("<7i", head["h"], head["w"], head["ri"], head["scan_begin"], len(data), *head["sampling"])
-                + head["qtables"].tobytes() + tables + data)
-    everything = [c for c in cases["a"] + cases["b"]]
-    text = [record(data, ops.jpeg_parse_header(data, sampling="any")) for _, data, _, _ in everything]
+    everything = [c + (ops.jpeg_parse_header(c[1], sampling="any"),) for c in cases["a"] + cases["b"]]
     # hand-made: files that are their header alone, and ones that end with FF
     for name in ("420_q85_17x33_rows", "422_q100_37x53_plain"):
         data = [c[1] for c in cases["a"] if c[0] == name][0]
         head = ops.jpeg_parse_header(data, sampling="any")
         for cut in (data[:head["scan_begin"]], data[:head["scan_begin"] + 1] + b"\xff"):
-            text.append(record(cut, head))
-            pixels, status = S.decode(cut, S.parse_header(data))
+            pixels, status = S.decode(cut, D.parse_header(data, sampling="any"))
             assert status & D.MARKER
-            everything = everything + [(name + " cut", cut, pixels, status)]
-    run = subprocess.run([exe], input=b"".join(text), capture_output=True)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    lines = run.stdout.decode().split("\n")[:-1]
+            everything.append((name + " cut", cut, pixels, status, head))
+    records = [D.shim_record(data, head, ops._jpeg_decode_table) for _, data, _, _, head in everything]
+    lines = D.run_shim(D.build_shim(ROOT, tmp_path), records)
     assert len(lines) == len(everything) == 234
-    for (name, _, want, want_status), line in zip(everything, lines):
-        assert line == "%d %d" % (want_status, fnv(want)), name
+    for (name, _, want, want_status, _), line in zip(everything, lines):
+        assert line == D.shim_line(want, want_status), name
 
 
 def test_product_does_not_import_the_restatement():

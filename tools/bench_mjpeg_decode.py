@@ -137,15 +137,15 @@ def main():
                 meta = torch.from_numpy(np.concatenate([offsets, scans])).to(dev)
                 room = int(L.va_jpeg_decode_sampled_workspace_bytes(N, H, W, 3, ri, lh, lv))
                 ws = torch.empty(room, dtype=torch.uint8, device=dev)
-                front = (src.data_ptr(), meta.data_ptr(), meta.data_ptr() + 8 * (N + 1), N, H, W, 3, ri)
-                back = (consts.data_ptr(), consts.data_ptr() + 192, len(tables), out.data_ptr(), status.data_ptr(),
-                        ws.data_ptr(), room, S)
+                # as ops.jpeg_decode chooses: the plain entry for 1 x 1, the _sampled one with (luma_h, luma_v) else
+                entry, luma = ((L.va_jpeg_decode_u8, ()) if (lh, lv) == (1, 1) else
+                               (L.va_jpeg_decode_sampled_u8, (lh, lv)))
+                call = ((src.data_ptr(), meta.data_ptr(), meta.data_ptr() + 8 * (N + 1), N, H, W, 3, ri) + luma
+                        + (consts.data_ptr(), consts.data_ptr() + 192, len(tables), out.data_ptr(), status.data_ptr(),
+                           ws.data_ptr(), room, S))
 
                 def decode():
-                    if (lh, lv) == (1, 1):
-                        check(L.va_jpeg_decode_u8(*(front + back)))
-                    else:
-                        check(L.va_jpeg_decode_sampled_u8(*(front + (lh, lv) + back)))
+                    check(entry(*call))
                 reps, args.reps = args.reps, args.reps if restarts != "none" else min(args.reps, 3)
                 try:
                     best, med = events(decode)

@@ -5,28 +5,31 @@
 // host tests compile.
 //
 // Every restart interval of every frame is an independent entropy segment, and everything behind the entropy decode
-// is per block, so a chunk of frames takes three launches on one stream:
+// is per block.  One flow serves the four layouts (monochrome; 3 components with luma 1 x 1, 2 x 1 (4:2:2) or 2 x 2
+// (4:2:0) and chroma 1 x 1; DESIGN.md §9, "Subsampled Motion-JPEG decoding"): the MCU grid of a frame is worked out
+// once (JpegGrid), and a chunk of frames takes these launches on one stream:
 //   locate       one workgroup per frame walks the frame's entropy bytes in tiles of 2048, 8 bytes a lane: the
 //                markers FF xx (xx not 00, FF) get their rank in the frame from ballots' popcounts scanned over the
 //                workgroup; the k-th one ends segment k and, while it is RST(k mod 8), begins segment k + 1.  The
 //                first other marker ends the scan.  Fills the chunk's table of nseg (begin, end) byte ranges (-1: a
 //                missing segment) and stores the frame's status word, the marker-sequence bit or 0.
-//   entropy      one lane per segment: va_jpeg::decode_block over the segment's MCUs with a 64-bit bit buffer and the
-//                tables in LDS; the coefficients go to the workspace as int16 in natural order, [frame][component]
-//                [block row][block column][64], a zeroed block (16-byte stores) and then its non-zero entries.  An
-//                error zeroes its block and the rest of the segment and is ORed into the frame's status word.
+//   entropy      one lane per segment, one kernel instantiated per layout: va_jpeg::decode_block over the segment's
+//                MCUs with a 64-bit bit buffer and the tables in LDS; the coefficients go to the workspace as int16 in
+//                natural order where va_jpeg::mcu_block_at puts the block, [frame][Y: by V x bx H blocks | Cb: by x bx
+//                | Cr: by x bx][64] (for 1 x 1 that is [frame][component][block row][block column][64]), a zeroed
+//                block (16-byte stores) and then its non-zero entries.  An error zeroes its block and the rest of the
+//                segment and is ORed into the frame's status word.
+// and then, for a monochrome or 1 x 1 file, one more:
 //   reconstruct  one lane per MCU: dequantise, both inverse passes and the colour conversion in registers; the lanes
 //                of a wave hold neighbouring MCUs of a block row, so each of the 8 pixel rows goes out as 8 (or 24)
 //                contiguous bytes a lane, 512 (1536) bytes a wave, where the row is complete and aligned, and
-//                bytewise at the frame's edges.
-// A 4:2:0 or 4:2:2 file ("Subsampled Motion-JPEG decoding": luma 2 x 2 or 2 x 1, an MCU of 6 or 4
-// blocks) takes four: locate as it is, entropy with the MCU walk of va_jpeg_decode_math.h into
-// [frame][Y: my V x mx H blocks | Cb: my x mx | Cr: my x mx][64], and the reconstruction in two, because the triangle
-// filter reads chroma samples of neighbouring MCUs:
-//   chroma planes  one lane per chroma block: its 64 samples as eight 8-byte rows of [frame][2][my 8][mx 8] bytes
+//                bytewise at the frame's edges (store_row).
+// or, for a 4:2:2 or 4:2:0 file, two, because the triangle filter reads chroma samples of neighbouring MCUs:
+//   chroma planes  one lane per chroma block: its 64 samples as eight 8-byte rows of [frame][2][by 8][bx 8] bytes
 //   pixels         one lane per luma block, the lanes of a wave along a block row: the Y block's samples, the 6 x 6
 //                  (4:2:0) or 8 x 6 (4:2:2) chroma samples around its quarter or half of the chroma block, clamped to
-//                  the real samples, the upsampling and the colour conversion; the pixel rows go out as in reconstruct
+//                  the real samples, the upsampling and the colour conversion; the pixel rows go out through the same
+//                  store_row
 // The only atomic is the OR into the status word, whose result does not depend on the order; every output byte
 // depends on its frame alone.  Loops over stream bytes end at the segment's end, loops over blocks at the segment's
 // MCU range.
@@ -194,9 +197,14 @@ __device__ __forceinline__ void stage_tables(va_jpeg::HuffDecode *tabs, const va
     __syncthreads();
 }
 
-template <int C>
+// C components, luma LH x LV, chroma 1 x 1; a.bx, a.by count MCUs of 8 LH x 8 LV pixels, and a monochrome MCU is its
+// one block.  An error zeroes its block and every later block of the segment; the MCU's earlier blocks keep their
+// coefficients.
+template <int C, int LH, int LV>
 __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
 {
+    static_assert(C == 3 || (C == 1 && LH == 1 && LV == 1), "one component has no sampling");
+    constexpr int kBlocks = C == 1 ? 1 : va_jpeg::mcu_blocks(LH, LV);
     __shared__ va_jpeg::HuffDecode tabs[2 * C];
     stage_tables<C>(tabs, a.huff);
     const int64_t s = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
@@ -214,52 +222,6 @@ __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
 #pragma unroll
     for (int ch = 0; ch < C; ch++)
         pred[ch] = 0;
-    for (int64_t m = m0; m < m1; m++) {
-        const int64_t row = m / a.bx, col = m % a.bx;
-#pragma unroll
-        for (int ch = 0; ch < C; ch++) {
-            int16_t *blk = a.coef + ((((f * C + ch) * a.by + row) * a.bx + col) << 6);
-            uint4 *blk16 = reinterpret_cast<uint4 *>(blk);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                blk16[i] = make_uint4(0, 0, 0, 0);
-            if (dead)
-                continue;
-            const int32_t e = va_jpeg::decode_block(r, tabs[2 * ch], tabs[2 * ch + 1], pred[ch],
-                                                    [&](int i, int v) { blk[i] = (int16_t)v; });
-            if (e) {
-                st = e;
-                dead = true;
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    blk16[i] = make_uint4(0, 0, 0, 0);
-            }
-        }
-    }
-    if (st)
-        atomicOr(&a.status[f], st);
-}
-
-// luma LH x LV, chroma 1 x 1; a.bx, a.by count MCUs of 8 LH x 8 LV pixels.  An error zeroes its block and every later
-// block of the segment; the MCU's earlier blocks keep their coefficients.
-template <int LH, int LV>
-__global__ void __launch_bounds__(kEntBlock) jpeg_entropy_sampled_kernel(EntropyArgs a)
-{
-    constexpr int kBlocks = va_jpeg::mcu_blocks(LH, LV);
-    __shared__ va_jpeg::HuffDecode tabs[6];
-    stage_tables<3>(tabs, a.huff);
-    const int64_t s = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
-    if (s >= a.nsegs)
-        return;
-    const int64_t f = s / a.nseg;
-    const int j = (int)(s % a.nseg);
-    const int64_t begin = a.table[2 * s], end = a.table[2 * s + 1];
-    const int64_t mcus = (int64_t)a.bx * a.by;
-    const int64_t m0 = (int64_t)j * a.ri, m1 = m0 + a.ri < mcus ? m0 + a.ri : mcus;
-    bool dead = begin < 0 || end < begin;
-    int32_t st = 0;
-    va_jpeg::BitReader r = va_jpeg::open_bits(a.bytes, dead ? 0 : begin, dead ? 0 : end);
-    int pred[3] = {0, 0, 0};
     int16_t *frame = a.coef + ((f * kBlocks * mcus) << 6);
     for (int64_t m = m0; m < m1; m++) {
         const int64_t row = m / a.bx, col = m % a.bx;
@@ -267,6 +229,11 @@ __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_sampled_kernel(Entropy
         for (int k = 0; k < kBlocks; k++) {
             int comp = 0;
             int16_t *blk = frame + (va_jpeg::mcu_block_at(k, LH, LV, a.by, a.bx, row, col, comp) << 6);
+            // 1 x 1: the same address as [frame][component][by][bx][64] spells it.  From the line above the compiler
+            // makes other code for these two instantiations (no division in the monochrome one), which measured 0.1
+            // to 0.4 % slower where the entropy launch decides the time
+            if constexpr (LH * LV == 1)
+                blk = a.coef + ((((f * C + k) * a.by + row) * a.bx + col) << 6);
             uint4 *blk16 = reinterpret_cast<uint4 *>(blk);
 #pragma unroll
             for (int i = 0; i < 8; i++)
@@ -326,6 +293,38 @@ __device__ __noinline__ BlockBytes block_samples(const int16_t *__restrict__ coe
     return out;
 }
 
+// a row of 8 pixels of C bytes each, as words
+template <int C>
+struct RowWords {
+    uint32_t w[2 * C];
+};
+
+// pixel x of a row of RGB pixels that started as zeros
+__device__ __forceinline__ void pack_rgb(RowWords<3> &o, int x, int r, int g, int b)
+{
+    o.w[(3 * x) / 4] |= (uint32_t)r << (8 * ((3 * x) % 4));
+    o.w[(3 * x + 1) / 4] |= (uint32_t)g << (8 * ((3 * x + 1) % 4));
+    o.w[(3 * x + 2) / 4] |= (uint32_t)b << (8 * ((3 * x + 2) % 4));
+}
+
+// the row o to dst, the pixel of column x0 of a row of w pixels: as 8-byte stores where the row holds all 8 pixels and
+// dst is 8-byte aligned, bytewise up to the row's end otherwise.  o comes by value: behind a reference the compiler
+// keeps an array of jpeg_pixels_kernel<2> in memory (12 KB of LDS a workgroup) that otherwise lives in registers
+template <int C>
+__device__ __forceinline__ void store_row(uint8_t *dst, const RowWords<C> o, int x0, int w)
+{
+    if (x0 + 8 <= w && ((uintptr_t)dst & 7) == 0) {
+#pragma unroll
+        for (int i = 0; i < C; i++)
+            reinterpret_cast<uint2 *>(dst)[i] = make_uint2(o.w[2 * i], o.w[2 * i + 1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8 * C; i++)
+            if (x0 + i / C < w)
+                dst[i] = (uint8_t)(o.w[i / 4] >> (8 * (i % 4)));
+    }
+}
+
 template <int C>
 __global__ void __launch_bounds__(kRecBlock) jpeg_reconstruct_kernel(ReconArgs a)
 {
@@ -350,42 +349,26 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_reconstruct_kernel(ReconArgs a
     }
 
     const int x0 = col * 8;
-    const bool complete = x0 + 8 <= a.w;
 #pragma unroll
     for (int y = 0; y < 8; y++) {
         const int gy = row * 8 + y;
         if (gy >= a.h)
             break;
-        uint8_t *dst = a.out + ((f * a.h + gy) * a.w + x0) * C;
-        uint32_t o[2 * C];
+        RowWords<C> o = {};
         if constexpr (C == 1) {
-            o[0] = px[0][2 * y];
-            o[1] = px[0][2 * y + 1];
+            o.w[0] = px[0][2 * y];
+            o.w[1] = px[0][2 * y + 1];
         } else {
-#pragma unroll
-            for (int i = 0; i < 2 * C; i++)
-                o[i] = 0;
 #pragma unroll
             for (int x = 0; x < 8; x++) {
                 const int sh = 8 * (x & 3), wi = 2 * y + (x >> 2);
                 int r, g, b;
                 va_jpeg::rgb_of((int)(px[0][wi] >> sh & 255u), (int)(px[1][wi] >> sh & 255u),
                                 (int)(px[2][wi] >> sh & 255u), r, g, b);
-                o[(3 * x) / 4] |= (uint32_t)r << (8 * ((3 * x) % 4));
-                o[(3 * x + 1) / 4] |= (uint32_t)g << (8 * ((3 * x + 1) % 4));
-                o[(3 * x + 2) / 4] |= (uint32_t)b << (8 * ((3 * x + 2) % 4));
+                pack_rgb(o, x, r, g, b);
             }
         }
-        if (complete && ((uintptr_t)dst & 7) == 0) {
-#pragma unroll
-            for (int i = 0; i < C; i++)
-                reinterpret_cast<uint2 *>(dst)[i] = make_uint2(o[2 * i], o[2 * i + 1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8 * C; i++)
-                if (x0 + i / C < a.w)
-                    dst[i] = (uint8_t)(o[i / 4] >> (8 * (i % 4)));
-        }
+        store_row<C>(a.out + ((f * a.h + gy) * a.w + x0) * C, o, x0, a.w);
     }
 }
 
@@ -475,7 +458,6 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_pixels_kernel(PixelArgs a)
     }
 
     const int x0 = col * 8;
-    const bool complete = x0 + 8 <= a.w;
 #pragma unroll
     for (int y = 0; y < 8; y++) {
         const int gy = row * 8 + y;
@@ -494,8 +476,7 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_pixels_kernel(PixelArgs a)
                 s[comp][i] = LV == 2 ? va_jpeg::upsample_rows(v, (int)((i < 4 ? blo : bhi) >> sh & 255u)) : v;
             }
         }
-        uint8_t *dst = a.out + ((f * a.h + gy) * a.w + x0) * 3;
-        uint32_t o[6] = {0, 0, 0, 0, 0, 0};
+        RowWords<3> o = {};
 #pragma unroll
         for (int x = 0; x < 8; x++) {
             const int mine = 1 + (x >> 1), next = va_jpeg::blend_sample(x + 2, 6, true);
@@ -503,21 +484,31 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_pixels_kernel(PixelArgs a)
             const int cr = va_jpeg::upsample_columns(s[1][mine], tri ? s[1][next] : s[1][mine], x, LV);
             int r, g, b;
             va_jpeg::rgb_of((int)(luma.w[2 * y + (x >> 2)] >> (8 * (x & 3)) & 255u), cb, cr, r, g, b);
-            o[(3 * x) / 4] |= (uint32_t)r << (8 * ((3 * x) % 4));
-            o[(3 * x + 1) / 4] |= (uint32_t)g << (8 * ((3 * x + 1) % 4));
-            o[(3 * x + 2) / 4] |= (uint32_t)b << (8 * ((3 * x + 2) % 4));
+            pack_rgb(o, x, r, g, b);
         }
-        if (complete && ((uintptr_t)dst & 7) == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                reinterpret_cast<uint2 *>(dst)[i] = make_uint2(o[2 * i], o[2 * i + 1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 24; i++)
-                if (x0 + i / 3 < a.w)
-                    dst[i] = (uint8_t)(o[i / 4] >> (8 * (i % 4)));
-        }
+        store_row<3>(a.out + ((f * a.h + gy) * a.w + x0) * 3, o, x0, a.w);
     }
+}
+
+
+// the MCU grid of a frame: by x bx MCUs of 8 lh x 8 lv pixels in nseg restart intervals; an MCU holds `blocks`
+// blocks, the first `luma` of them Y (a monochrome MCU is one block)
+struct JpegGrid {
+    int by, bx;
+    int64_t mcus;
+    int nseg, blocks, luma;
+};
+
+JpegGrid jpeg_grid(int h, int w, int c, int ri, int lh, int lv)
+{
+    JpegGrid g;
+    g.by = (h + 8 * lv - 1) / (8 * lv);
+    g.bx = (w + 8 * lh - 1) / (8 * lh);
+    g.mcus = (int64_t)g.by * g.bx;
+    g.nseg = (int)((g.mcus + ri - 1) / ri);
+    g.luma = lh * lv;
+    g.blocks = c == 1 ? 1 : va_jpeg::mcu_blocks(lh, lv);
+    return g;
 }
 
 // [segment table | coefficients | chroma planes (subsampled files only)]
@@ -525,119 +516,91 @@ struct DecodeLayout {
     size_t table, coef, planes, total;
 };
 
-DecodeLayout decode_layout(int64_t n, int h, int w, int c, int ri, int lh, int lv)
+DecodeLayout decode_layout(int64_t n, const JpegGrid &g)
 {
-    const int64_t mcus = (int64_t)((h + 8 * lv - 1) / (8 * lv)) * ((w + 8 * lh - 1) / (8 * lh));
-    const int64_t nseg = (mcus + ri - 1) / ri, blocks = c == 1 ? 1 : lh * lv + 2;
     Carve carve;
     DecodeLayout l;
-    l.table = carve.take((size_t)n * nseg * 2 * sizeof(int64_t));
-    l.coef = carve.take((size_t)n * blocks * mcus * 64 * sizeof(int16_t));
+    l.table = carve.take((size_t)n * g.nseg * 2 * sizeof(int64_t));
+    l.coef = carve.take((size_t)n * g.blocks * g.mcus * 64 * sizeof(int16_t));
     l.planes = carve.total;
-    if (lh * lv > 1)
-        l.planes = carve.take((size_t)n * 2 * mcus * 64);
+    if (g.luma > 1)
+        l.planes = carve.take((size_t)n * 2 * g.mcus * 64);
     l.total = carve.total;
     return l;
+}
+
+// the frames of one chunk: as many as the workspace holds, and no more than one launch's grid takes (the largest
+// grid has one lane per 8 x 8 block of the frame)
+int64_t jpeg_decode_chunk(int n, const JpegGrid &g, size_t workspace_bytes)
+{
+    const int64_t grid_cap = (((int64_t)1 << 31) - kRecBlock) / (g.mcus * g.luma);
+    const int64_t most = n < grid_cap ? n : grid_cap;
+    if (most < 1 || decode_layout(most, g).total <= workspace_bytes)
+        return most;
+    // k frames need at most k times one frame's regions, and a little less: each region rounds up once
+    const size_t one = decode_layout(1, g).total;
+    int64_t k = (int64_t)(workspace_bytes / one);
+    k = k < most ? k : most;
+    while (k < most && decode_layout(k + 1, g).total <= workspace_bytes)
+        k++;
+    return k;
 }
 
 }  // namespace
 
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv)
 {
-    return decode_layout(n, h, w, c, ri, lh, lv).total;
+    return decode_layout(n, jpeg_grid(h, w, c, ri, lh, lv)).total;
 }
 
-// the frames of one chunk: as many as the workspace holds, and no more than one launch's grid takes (the largest
-// grid has one lane per 8 x 8 block of the frame)
 int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, size_t workspace_bytes)
 {
-    const int64_t mcus = (int64_t)((h + 8 * lv - 1) / (8 * lv)) * ((w + 8 * lh - 1) / (8 * lh));
-    const int64_t grid_cap = (((int64_t)1 << 31) - kRecBlock) / (mcus * lh * lv);
-    const int64_t most = n < grid_cap ? n : grid_cap;
-    if (most < 1 || decode_layout(most, h, w, c, ri, lh, lv).total <= workspace_bytes)
-        return most;
-    // k frames need at most k times one frame's regions, and a little less: each region rounds up once
-    const size_t one = decode_layout(1, h, w, c, ri, lh, lv).total;
-    int64_t k = (int64_t)(workspace_bytes / one);
-    k = k < most ? k : most;
-    while (k < most && decode_layout(k + 1, h, w, c, ri, lh, lv).total <= workspace_bytes)
-        k++;
-    return k;
+    return jpeg_decode_chunk(n, jpeg_grid(h, w, c, ri, lh, lv), workspace_bytes);
 }
-
-namespace {
-
-// a chunk of 4:2:0 or 4:2:2 frames behind its locate launch
-int launch_sampled_chunk(const uint8_t *bytes, const int64_t *table, int64_t k, int h, int w, int ri, int lv,
-                         const uint8_t *qtables, const void *huff, int16_t *coef, uint8_t *planes, uint8_t *out,
-                         int32_t *status, hipStream_t st)
-{
-    const int my = (h + 8 * lv - 1) / (8 * lv), mx = (w + 15) / 16;
-    const int64_t mcus = (int64_t)my * mx;
-    const int nseg = (int)((mcus + ri - 1) / ri);
-    const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status, k * nseg, nseg, ri,
-                        mx, my};
-    const dim3 egrid((unsigned)((k * nseg + kEntBlock - 1) / kEntBlock));
-    if (lv == 2)
-        hipLaunchKernelGGL((jpeg_entropy_sampled_kernel<2, 2>), egrid, dim3(kEntBlock), 0, st, e);
-    else
-        hipLaunchKernelGGL((jpeg_entropy_sampled_kernel<2, 1>), egrid, dim3(kEntBlock), 0, st, e);
-    VA_LAUNCH_CHECK("jpeg_entropy_sampled_kernel");
-    const PlaneArgs c{coef, qtables, planes, k * 2 * mcus, mx, my, 2 * lv};
-    hipLaunchKernelGGL(jpeg_chroma_planes_kernel, dim3((unsigned)((c.nblocks + kRecBlock - 1) / kRecBlock)),
-                       dim3(kRecBlock), 0, st, c);
-    VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
-    const PixelArgs p{coef, qtables, planes, out, k * mcus * 2 * lv, h, w, mx, my};
-    const dim3 pgrid((unsigned)((p.nblocks + kRecBlock - 1) / kRecBlock));
-    if (lv == 2)
-        hipLaunchKernelGGL(jpeg_pixels_kernel<2>, pgrid, dim3(kRecBlock), 0, st, p);
-    else
-        hipLaunchKernelGGL(jpeg_pixels_kernel<1>, pgrid, dim3(kRecBlock), 0, st, p);
-    VA_LAUNCH_CHECK("jpeg_pixels_kernel");
-    return VA_OK;
-}
-
-}  // namespace
 
 int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
                        int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
                        int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st)
 {
-    const int by = (h + 8 * lv - 1) / (8 * lv), bx = (w + 8 * lh - 1) / (8 * lh);
-    const int64_t mcus = (int64_t)by * bx;
-    const int nseg = (int)((mcus + ri - 1) / ri);
-    const int64_t chunk = jpeg_decode_chunk(n, h, w, c, ri, lh, lv, workspace_bytes);
-    const DecodeLayout l = decode_layout(chunk, h, w, c, ri, lh, lv);
+    const JpegGrid g = jpeg_grid(h, w, c, ri, lh, lv);
+    const int64_t chunk = jpeg_decode_chunk(n, g, workspace_bytes);
+    const DecodeLayout l = decode_layout(chunk, g);
     int64_t *table = at<int64_t>(ws, l.table);
     int16_t *coef = at<int16_t>(ws, l.coef);
+    uint8_t *planes = at<uint8_t>(ws, l.planes);
+    void (*const entropy)(EntropyArgs) = c == 1    ? jpeg_entropy_kernel<1, 1, 1>
+                                         : lv == 2 ? jpeg_entropy_kernel<3, 2, 2>
+                                         : lh == 2 ? jpeg_entropy_kernel<3, 2, 1>
+                                                   : jpeg_entropy_kernel<3, 1, 1>;
+    const auto blocks_of = [](int64_t lanes) { return dim3((unsigned)((lanes + kRecBlock - 1) / kRecBlock)); };
     for (int64_t f0 = 0; f0 < n; f0 += chunk) {
         const int64_t k = chunk < n - f0 ? chunk : n - f0;
+        uint8_t *frames = out + (size_t)f0 * h * w * c;
         hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
-                           scan_begin + f0, nseg, table, status + f0);
+                           scan_begin + f0, g.nseg, table, status + f0);
         VA_LAUNCH_CHECK("jpeg_locate_kernel");
-        if (lh * lv > 1) {
-            const int rc = launch_sampled_chunk(bytes, table, k, h, w, ri, lv, qtables, huff, coef,
-                                                at<uint8_t>(ws, l.planes), out + (size_t)f0 * h * w * 3, status + f0,
-                                                st);
-            if (rc)
-                return rc;
+        const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
+                            k * g.nseg, g.nseg, ri, g.bx, g.by};
+        hipLaunchKernelGGL(entropy, dim3((unsigned)((e.nsegs + kEntBlock - 1) / kEntBlock)), dim3(kEntBlock), 0, st, e);
+        VA_LAUNCH_CHECK("jpeg_entropy_kernel");
+        if (g.luma == 1) {
+            const ReconArgs r{coef, qtables, frames, k * g.mcus, h, w, g.bx, g.by};
+            if (c == 1)
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            else
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
             continue;
         }
-        const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
-                            k * nseg, nseg, ri, bx, by};
-        const dim3 egrid((unsigned)((k * nseg + kEntBlock - 1) / kEntBlock));
-        if (c == 1)
-            hipLaunchKernelGGL(jpeg_entropy_kernel<1>, egrid, dim3(kEntBlock), 0, st, e);
+        const PlaneArgs cp{coef, qtables, planes, k * 2 * g.mcus, g.bx, g.by, g.luma};
+        hipLaunchKernelGGL(jpeg_chroma_planes_kernel, blocks_of(cp.nblocks), dim3(kRecBlock), 0, st, cp);
+        VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
+        const PixelArgs p{coef, qtables, planes, frames, k * g.mcus * g.luma, h, w, g.bx, g.by};
+        if (lv == 2)
+            hipLaunchKernelGGL(jpeg_pixels_kernel<2>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
         else
-            hipLaunchKernelGGL(jpeg_entropy_kernel<3>, egrid, dim3(kEntBlock), 0, st, e);
-        VA_LAUNCH_CHECK("jpeg_entropy_kernel");
-        const ReconArgs r{coef, qtables, out + (size_t)f0 * h * w * c, k * mcus, h, w, bx, by};
-        const dim3 rgrid((unsigned)((k * mcus + kRecBlock - 1) / kRecBlock));
-        if (c == 1)
-            hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, rgrid, dim3(kRecBlock), 0, st, r);
-        else
-            hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, rgrid, dim3(kRecBlock), 0, st, r);
-        VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
+            hipLaunchKernelGGL(jpeg_pixels_kernel<1>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
+        VA_LAUNCH_CHECK("jpeg_pixels_kernel");
     }
     return VA_OK;
 }

@@ -1,9 +1,11 @@
 // va_jpeg_decode_math.h -- the serial pieces of the baseline JPEG decoder ("Motion-JPEG decoding") as
 // plain inline C++ that compiles for the host and for the device: the bit reader with the stuffing removed, the
 // Huffman step, the decode of one block with its status, the dequantiser, the 8-point inverse pass, the colour
-// conversion, and for 4:2:0 and 4:2:2 files the MCU walk and the chroma upsampling.  va_jpeg_decode.hip runs the entropy decode with one lane per segment and the reconstruction with one
-// lane per MCU; tests/jpeg_decode_shim.cpp compiles the same text with the host compiler (under sanitizers) into a
-// serial decoder whose pixels and status words are the NumPy restatement's (tests/jpeg_decode_checks.py).
+// conversion, the MCU walk of every sampling layout, and for 4:2:0 and 4:2:2 files the chroma upsampling.
+// va_jpeg_decode.hip runs the entropy decode with one lane per segment and the reconstruction with one lane per MCU
+// or per luma block; tests/jpeg_decode_shim.cpp, the one host shim of all layouts, compiles the same text with the
+// host compiler (under sanitizers) into a serial decoder whose pixels and status words are the NumPy restatement's
+// (tests/jpeg_decode_checks.py, tests/jpeg_subsampled_checks.py).
 //
 // Integers only.  F = clamp(coef * Q, -2048, 2047); T = rint(2^13 A) is the encoder's matrix (va_jpeg_math.h).  The
 // column pass keeps (sum_v T[v][y] F[v][k] + 2^8) >> 9, sixteen times the half-transformed value; the row pass's

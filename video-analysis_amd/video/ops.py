@@ -2598,24 +2598,18 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
                 mb = d.upload(meta)
                 tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
                 cb = d.upload(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8))
+                # the plain entry for monochrome and 1 x 1 files, the _sampled one with (luma_h, luma_v) for the rest
                 luma = tuple(head["sampling"])
                 if luma == (1, 1):
-                    one = int(L.va_jpeg_decode_workspace_bytes(1, h, w, c, head["ri"]))
-                    need = int(L.va_jpeg_decode_workspace_bytes(k, h, w, c, head["ri"]))
+                    decode, size, luma = L.va_jpeg_decode_u8, L.va_jpeg_decode_workspace_bytes, ()
                 else:
-                    one = int(L.va_jpeg_decode_sampled_workspace_bytes(1, h, w, c, head["ri"], *luma))
-                    need = int(L.va_jpeg_decode_sampled_workspace_bytes(k, h, w, c, head["ri"], *luma))
+                    decode, size = L.va_jpeg_decode_sampled_u8, L.va_jpeg_decode_sampled_workspace_bytes
+                one, need = (int(size(frames, h, w, c, head["ri"], *luma)) for frames in (1, k))
                 room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
                 ws = d.take(room)
-                if luma == (1, 1):
-                    check(L.va_jpeg_decode_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], cb.ptr,
-                                              cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes,
-                                              status_buf.ptr + 4 * first, ws.ptr, room, stream))
-                else:
-                    check(L.va_jpeg_decode_sampled_u8(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"],
-                                                      luma[0], luma[1], cb.ptr, cb.ptr + 64 * c, len(tables),
-                                                      out.ptr + first * frame_bytes, status_buf.ptr + 4 * first,
-                                                      ws.ptr, room, stream))
+                check(decode(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], *luma, cb.ptr,
+                             cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes, status_buf.ptr + 4 * first,
+                             ws.ptr, room, stream))
             status = status_buf.download((n,), np.int32, stream)
             if status.any() and not ret_status:
                 bad = int(np.flatnonzero(status)[0])
