@@ -711,6 +711,44 @@ int va_curves_equidistant(const double *points_dev, const int64_t *point_off_dev
                           int64_t *totals_dev, double *out_points_dev, int64_t cap_points, double *out_length_dev,
                           void *stream);
 
+/* ------------------------------------------------------------------ A23 simplification
+ * replaces  simplify_curve, video/analysis/curves.py:22 (the rdp of external/simplify_polygon_rdp.py), once per
+ *           curve, and simplify_contour, video/analysis/regions.py:307-325 (simplify_ring and simplify_line of
+ *           external/simplify_polygon_visvalingam.py), once per ring
+ * The two definitions are pinned in DESIGN.md §9, "Simplification".  Curves: m of them in one packed buffer, laid
+ * out as for va_curves_equidistant: points_dev[npoints][2] float64 (x, y); curve k owns points point_off_dev[k] ..
+ * point_off_dev[k + 1] - 1 (int64, m + 1 entries, ascending).  One tolerance per curve (float64).  Both calls write
+ *   keep_dev[npoints]  (uint8)  1 for a point that is kept, 0 for one that is dropped; the simplified curve k is its
+ *                      points with flag 1, in order.  Only the slots of the m curves are written.
+ *   out_count_dev[k]   (int32)  the number of points kept; 0 for a ring that vanishes
+ *   status_dev[k]      (int32)  VA_OK, or VA_ERR_RANGE for a curve that is not run: offsets out of order or outside
+ *                      0 .. npoints, a NaN tolerance, or more than VA_SIMPLIFY_MAX_POINTS points.  Such a curve has
+ *                      the count 0 and, where its offsets lie inside the buffer, all its flags 0.
+ *
+ * va_simplify_rdp: Ramer-Douglas-Peucker on open curves, one wave per curve (in launches of 65535 curves).  Points
+ * 0 and n - 1 are kept.  A span (i0, i1) with i1 - i0 >= 2 measures every point strictly between its ends against
+ * its chord: |x0.x - x1.x| when both ends have the same x, else |a x b| / |a| with a = x2 - x1, b = x1 - x0, every
+ * operation rounded on its own; the first point of largest distance is kept and splits the span when that
+ * distance exceeds max(eps_dev[k], 0).  A curve of fewer than 3 points keeps all its points.
+ *
+ * va_simplify_visvalingam: the reference's heap procedure, one lane per curve.  closed = 1: every curve is a ring
+ * without a closing duplicate; points go while more than 2 are left and the smallest triangle area is below
+ * thr_dev[k]; a ring that ends with fewer than 3 points, or has fewer than 3, keeps none (count 0: the reference's
+ * None).  closed = 0: open lines, both ends fixed; a line of fewer than 3 points keeps all its points.
+ * workspace_dev: va_simplify_visvalingam_workspace_bytes(npoints) bytes, 12 per point (heap, prev, next, int32);
+ * what it holds before the call does not matter.
+ *
+ * Two runs write identical bytes.  m == 0 enqueues nothing; a NULL pointer with m > 0, a negative count, a
+ * misaligned pointer, closed other than 0 or 1 and a workspace that is too small are VA_ERR_INVALID. */
+#define VA_SIMPLIFY_MAX_POINTS (1 << 24)
+int va_simplify_rdp(const double *points_dev, const int64_t *point_off_dev, int64_t npoints, int m,
+                    const double *eps_dev, uint8_t *keep_dev, int32_t *out_count_dev, int32_t *status_dev,
+                    void *stream);
+size_t va_simplify_visvalingam_workspace_bytes(int64_t npoints);
+int va_simplify_visvalingam(const double *points_dev, const int64_t *point_off_dev, int64_t npoints, int m,
+                            const double *thr_dev, int closed, uint8_t *keep_dev, int32_t *out_count_dev,
+                            int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A19 composer
  * replaces  VideoComposer, video/io/composer.py: set_frame's copy of a monochrome frame into a colour video
  *           (:103-105, :119-123), highlight_mask (:131-154), add_image (:168-186), blend_image (:190-210) by

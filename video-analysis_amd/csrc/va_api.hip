@@ -1072,6 +1072,55 @@ int va_curves_equidistant(const double *points, const int64_t *point_off, int64_
                                      in_length, status, totals, out_points, cap_points, out_length, as_stream(stream));
 }
 
+// ------------------------------------------------------------------------------ simplification
+// the arguments the two simplifiers share; m == 0 is the caller's
+static int simplify_check(const char *name, const double *points, const int64_t *point_off, int64_t npoints, int m,
+                          const double *tol, const uint8_t *keep, const int32_t *out_count, const int32_t *status)
+{
+    VA_REQUIRE(npoints >= 0 && m >= 0, "%s: negative count (npoints %lld, m %d)", name, (long long)npoints, m);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(points && point_off && tol && keep && out_count && status, "%s: NULL argument", name);
+    VA_REQUIRE(aligned(points, 8) && aligned(point_off, 8) && aligned(tol, 8) && aligned(out_count, 4) &&
+                   aligned(status, 4),
+               "%s: float64 and int64 buffers must be 8-byte aligned, int32 buffers 4-byte aligned", name);
+    return VA_OK;
+}
+
+int va_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
+                    uint8_t *keep, int32_t *out_count, int32_t *status, void *stream)
+{
+    VA_ENTER();
+    const int rc = simplify_check("va_simplify_rdp", points, point_off, npoints, m, eps, keep, out_count, status);
+    if (rc || m == 0)
+        return rc;
+    return launch_simplify_rdp(points, point_off, npoints, m, eps, keep, out_count, status, as_stream(stream));
+}
+
+size_t va_simplify_visvalingam_workspace_bytes(int64_t npoints)
+{
+    return npoints < 0 ? 256 : simplify_layout(npoints).total;
+}
+
+int va_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *thr,
+                            int closed, uint8_t *keep, int32_t *out_count, int32_t *status, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(closed == 0 || closed == 1, "va_simplify_visvalingam: closed is 0 (lines) or 1 (rings), got %d", closed);
+    const int rc = simplify_check("va_simplify_visvalingam", points, point_off, npoints, m, thr, keep, out_count,
+                                  status);
+    if (rc || m == 0)
+        return rc;
+    VA_REQUIRE(workspace, "va_simplify_visvalingam: NULL argument");
+    VA_REQUIRE(aligned(workspace, 8), "va_simplify_visvalingam: the workspace must be 8-byte aligned");
+    VA_REQUIRE(workspace_bytes >= va_simplify_visvalingam_workspace_bytes(npoints),
+               "va_simplify_visvalingam: workspace of %zu bytes < required %zu", workspace_bytes,
+               va_simplify_visvalingam_workspace_bytes(npoints));
+    return launch_simplify_visvalingam(points, point_off, npoints, m, thr, closed, keep, out_count, status, workspace,
+                                       as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ composer
 int va_compose_layers_u8(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
                          const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,

@@ -460,6 +460,15 @@ int launch_curves_equidistant(const double *points, const int64_t *point_off, in
                               int32_t *out_count, int64_t *out_off, double *in_length, int32_t *status,
                               int64_t *totals, double *out_points, int64_t cap_points, double *out_length,
                               hipStream_t st);
+// simplification (va_simplify.hip): the kept flags and counts of m packed curves, Ramer-Douglas-Peucker with one
+// wave per curve, Visvalingam with one lane per curve; the workspace holds the heap and the two link tables
+struct SimplifyLayout { size_t heap, prev, next, total; };
+SimplifyLayout simplify_layout(int64_t npoints);
+int launch_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
+                        uint8_t *keep, int32_t *out_count, int32_t *status, hipStream_t st);
+int launch_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m,
+                                const double *thr, int closed, uint8_t *keep, int32_t *out_count, int32_t *status,
+                                void *ws, hipStream_t st);
 // composer (va_compose.hip): the pixel layers of a stack in one pass; the drawing commands, one workgroup per frame
 int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
                           const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,

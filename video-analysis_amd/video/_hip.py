@@ -143,6 +143,9 @@ SIGNATURES = {
     "va_ray_hits": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "va_points_in_outlines": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _vp]),
     "va_curves_equidistant": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "va_simplify_rdp": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "va_simplify_visvalingam_workspace_bytes": (_sz, [_i64]),
+    "va_simplify_visvalingam": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "va_compose_layers_u8": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "va_draw_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "va_jpeg_encode_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),

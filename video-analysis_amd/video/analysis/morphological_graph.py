@@ -194,11 +194,19 @@ class MorphologicalGraph(nx.MultiGraph):
                 return node
         return None
 
-    def simplify(self, epsilon=0):
+    def simplify(self, epsilon=0, simplify_curves=None):
         """removes every node that a curve merely passes through (degree 2, two distinct neighbours), merging its
         two edges into one, one node at a time from the front of the node list; a node with a loop, or with two
         edges to one neighbour, stays.  With epsilon > 0 every curve is then thinned by curves.simplify_curve and
-        measured again"""
+        measured again.  simplify_curves: None, or a function (list of curves, epsilon) -> list of thinned curves
+        that takes the place of the per-curve calls, e.g. curves.simplify_curves (one device call, the pinned
+        form: see its docstring for where that differs from simplify_curve); the default path needs no GPU."""
+        self.merge_pass_through_nodes()
+        if epsilon > 0:
+            self.set_curves(self.thinned_curves(epsilon, simplify_curves))
+
+    def merge_pass_through_nodes(self):
+        """the first step of simplify: the merges alone"""
         node = self._first_pass_through_node()
         while node is not None:
             left, right = self[node]
@@ -207,10 +215,19 @@ class MorphologicalGraph(nx.MultiGraph):
             self.remove_node(node)
             self.add_edge_line(left, right, merged)
             node = self._first_pass_through_node()
-        if epsilon > 0:
-            for _, _, data in self.edges(data=True):
-                data['curve'] = curves.simplify_curve(data['curve'], epsilon)
-                data['length'] = curves.curve_length(data['curve'])
+
+    def thinned_curves(self, epsilon, simplify_curves=None):
+        """the curves of all edges, in edge order, thinned with epsilon"""
+        given = [data['curve'] for _, _, data in self.edges(data=True)]
+        if simplify_curves is None:
+            return [curves.simplify_curve(c, epsilon) for c in given]
+        return simplify_curves(given, epsilon)
+
+    def set_curves(self, thinned):
+        """the second step of simplify: every edge, in edge order, gets its thinned curve and is measured again"""
+        for (_, _, data), curve in zip(self.edges(data=True), thinned):
+            data['curve'] = curve
+            data['length'] = curves.curve_length(curve)
 
     def post_process(self):
         """the clean-up from_skeleton applies by default: remove_short_edges(4), then simplify()"""

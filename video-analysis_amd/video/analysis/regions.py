@@ -6,7 +6,7 @@ expand_rectangle :153-155, get_largest_region :159-174, triangle_area :430-451,
 make_distance_map :455-509, shortest_path_in_distance_map :513-565, get_farthest_points :568-611,
 get_external_contour :201-232 (and every cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) list: find_contours),
 get_ray_hitpoint :353-391, get_ray_intersections :395-405, get_farthest_ray_intersection :409-426 (GPU; batched:
-ray_hits, ray_fans).
+ray_hits, ray_fans), simplify_contour :307-325 (GPU; batched: simplify_contours).
 """
 import numpy as np
 
@@ -141,6 +141,69 @@ def find_contours(mask):
     :575-576; video/io/composer.py:228).  A stack (n, h, w) gives one list per frame, from one call."""
     from .. import ops
     return ops.find_contours(mask)
+
+
+def _contour_points(contour, closed, what):
+    """the (n, 2) points of one contour: an (n, 2) array-like or an (n, 1, 2) array as find_contours gives; a ring's
+    closing duplicate is dropped.  A shapely geometry is a TypeError"""
+    if any(hasattr(contour, name) for name in ("coords", "exterior", "geom_type")):
+        raise TypeError("%s takes the coordinates of a contour as an (n, 2) array, not a %s: pass "
+                        "np.asarray(geometry.coords) (for a polygon, of its exterior)" % (what, type(contour).__name__))
+    a = np.asarray(contour)
+    if a.ndim == 3 and a.shape[1] == 1:
+        a = a[:, 0, :]
+    if a.size == 0:
+        a = a.reshape(0, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("%s: a contour is an (n, 2) array, got shape %r" % (what, a.shape))
+    if closed and len(a) >= 2 and a[0, 0] == a[-1, 0] and a[0, 1] == a[-1, 1]:
+        a = a[:-1]
+    return a
+
+
+def _is_frame_list(entry):
+    """whether an entry of simplify_contours' argument is one frame's list of contours, as find_contours returns
+    for a stack, and not a contour"""
+    return isinstance(entry, (list, tuple)) and all(isinstance(c, np.ndarray) and c.ndim >= 2 for c in entry)
+
+
+def simplify_contours(contours, threshold, closed=True):
+    """simplify_contour for every contour of a list in one device call (ops.simplify_curves, Visvalingam, DESIGN.md
+    §9, "Simplification").  contours: what find_contours returns, as it is -- a list of (N, 1, 2) contours, or for a
+    stack one such list per frame -- or any list of (n, 2) array-likes.  threshold: one number or one per contour
+    (for a stack: one number).  closed=True takes each contour as a ring, a closing duplicate point dropped first;
+    closed=False as an open line whose ends stay.  Returns, in the layout of the argument, the kept (K, 2) points
+    of every contour in its dtype; None for a ring that vanishes (fewer than 3 points are left, or were given)."""
+    from .. import ops
+    what = "simplify_contours"
+    contours = list(contours)
+    if contours and all(_is_frame_list(entry) for entry in contours):
+        if np.ndim(threshold) != 0:
+            raise ValueError("%s: one threshold for the contours of a stack" % what)
+        flat = simplify_contours([c for frame in contours for c in frame], threshold, closed)
+        out, at = [], 0
+        for frame in contours:
+            out.append(flat[at:at + len(frame)])
+            at += len(frame)
+        return out
+    rings = [_contour_points(c, closed, what) for c in contours]
+    return ops.simplify_curves(rings, threshold, method="visvalingam", closed=closed)
+
+
+def simplify_contour(contour, threshold):
+    """simplifies a contour based on its area: single points are removed while the area change of the resulting
+    polygon is smaller than `threshold` (Visvalingam; reference: video/analysis/regions.py:307-325 over
+    external/simplify_polygon_visvalingam.py).  contour: the coordinates of a linear ring, an (n, 2) array-like; a
+    closing duplicate point is dropped first.  Returns the kept points, a (K, 2) array of the input's dtype, or None
+    when fewer than 3 would be left.  Deviations: the reference returns the coordinates of a shapely ring, which
+    shapely has closed again and the reference then cut by one point, so a result whose last kept point equals its
+    first loses that point there and keeps it here; the shapely forms of the argument (LineString, LinearRing,
+    Polygon) are a TypeError that names the array form.  Fewer than 3 points are a ValueError, as they are for
+    shapely's LinearRing."""
+    ring = _contour_points(contour, True, "simplify_contour")
+    if len(ring) < 3:
+        raise ValueError("simplify_contour: a linear ring needs at least 3 points, got %d" % len(ring))
+    return simplify_contours([ring], threshold)[0]
 
 
 def external_contour_resolution(points):

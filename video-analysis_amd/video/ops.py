@@ -1911,6 +1911,203 @@ def curves_equidistant(curves, spacing=None, count=None, offsets=None, ret_lengt
     return (results, lengths) if ret_lengths else results
 
 
+# ------------------------------------------------------------------------------------------ simplification
+SIMPLIFY_MAX_POINTS = 1 << 24    # VA_SIMPLIFY_MAX_POINTS, include/videoanalysis_hip.h
+SIMPLIFY_METHODS = ("rdp", "visvalingam")
+# simplify_curves goes to the device from this many curves on; below it the pinned definition in Python is quicker
+# than a device round trip ("Simplification": the crossover)
+SIMPLIFY_DEVICE_MIN_BATCH = 4
+
+
+def _rdp_keep_host(P, eps):
+    """the pinned Ramer-Douglas-Peucker ("Simplification") on one (n, 2) float64 curve, a span at a
+    time in NumPy: every product, difference, root and quotient is rounded on its own, as on the device.  Returns
+    the kept flags (bool, one per point)"""
+    n = len(P)
+    keep = np.zeros(n, bool)
+    if n < 3:
+        keep[:] = True
+        return keep
+    keep[0] = keep[-1] = True
+    tol = eps if eps > 0 else 0.0
+    x, y = P[:, 0], P[:, 1]
+    todo = [(0, n - 1)]
+    with np.errstate(all="ignore"):
+        while todo:
+            i0, i1 = todo.pop()
+            if i1 - i0 < 2:
+                continue
+            if x[i0] == x[i1]:
+                d = np.abs(x[i0 + 1:i1] - x[i0])
+            else:
+                ax, ay = x[i1] - x[i0], y[i1] - y[i0]
+                bx, by = x[i0] - x[i0 + 1:i1], y[i0] - y[i0 + 1:i1]
+                d = np.abs(ax * by - ay * bx) / np.sqrt(ax * ax + ay * ay)
+            d = np.where(d > 0, d, 0.0)                # (a NaN distance is never the largest)
+            k = int(np.argmax(d))                      # the first of the largest
+            if d[k] > tol:
+                keep[i0 + 1 + k] = True
+                todo.append((i0, i0 + 1 + k))
+                todo.append((i0 + 1 + k, i1))
+    return keep
+
+
+def _visvalingam_keep_host(P, thr, closed):
+    """the pinned Visvalingam procedure ("Simplification") on one (n, 2) float64 ring (closed, no
+    closing duplicate) or open line, with Python floats: a heap of point indices, prev / next links and heapq's two
+    sift procedures, the areas measured afresh at every comparison.  Returns the kept flags (bool); a ring of fewer
+    than 3 points, or left with fewer than 3, keeps none"""
+    n = len(P)
+    keep = np.zeros(n, bool)
+    if n < 3:
+        keep[:] = not closed
+        return keep
+    xs, ys = P[:, 0].tolist(), P[:, 1].tolist()
+    prev = [i - 1 if i > 0 else (n - 1 if closed else 0) for i in range(n)]
+    nxt = [i + 1 if i + 1 < n else (0 if closed else n - 1) for i in range(n)]
+    heap = list(range(n)) if closed else list(range(1, n - 1))
+
+    def area(i):
+        b, a = prev[i], nxt[i]
+        return abs(xs[i] * (ys[b] - ys[a]) + xs[b] * (ys[a] - ys[i]) + xs[a] * (ys[i] - ys[b])) / 2.0
+
+    def siftdown(startpos, pos):
+        item = heap[pos]
+        while pos > startpos:
+            parentpos = (pos - 1) >> 1
+            parent = heap[parentpos]
+            if not area(item) < area(parent):
+                break
+            heap[pos] = parent
+            pos = parentpos
+        heap[pos] = item
+
+    def siftup(pos):
+        end, startpos, item = len(heap), pos, heap[pos]
+        childpos = 2 * pos + 1
+        while childpos < end:
+            rightpos = childpos + 1
+            if rightpos < end and not area(heap[childpos]) < area(heap[rightpos]):
+                childpos = rightpos
+            heap[pos] = heap[childpos]
+            pos = childpos
+            childpos = 2 * pos + 1
+        heap[pos] = item
+        siftdown(startpos, pos)
+
+    for i in reversed(range(len(heap) // 2)):
+        siftup(i)
+    floor = 2 if closed else 0
+    while len(heap) > floor:
+        top = heap[0]
+        if area(top) >= thr:
+            break
+        b, a = prev[top], nxt[top]
+        nxt[b] = a
+        prev[a] = b
+        last = heap.pop()
+        if heap:
+            heap[0] = last
+            siftup(0)
+    if closed and len(heap) < 3:
+        return keep
+    keep[heap] = True
+    if not closed:
+        keep[0] = keep[-1] = True
+    return keep
+
+
+def _simplify_on_host(points, tolerance, method, closed):
+    """the kept flags of one curve by the pinned definition in Python"""
+    P = np.asarray(points, np.float64).reshape(-1, 2)
+    if method == "rdp":
+        return _rdp_keep_host(P, float(tolerance))
+    return _visvalingam_keep_host(P, float(tolerance), closed)
+
+
+def simplify_curves(curves, tolerance, method="rdp", closed=False, stream=None):
+    """Simplifies every curve of a list in one device call ("Simplification").  method "rdp":
+    Ramer-Douglas-Peucker on open curves (curves.simplify_curve's algorithm with the pinned distance,
+    va_simplify_rdp), tolerance the largest distance a dropped point may have from its chord.  method
+    "visvalingam": the reference's heap procedure (regions.simplify_contour, va_simplify_visvalingam), tolerance the
+    triangle area below which a point goes; closed=True takes every curve as a ring without a closing duplicate,
+    closed=False as an open line with fixed ends.  curves: m (n, 2) array-likes of any lengths; tolerance: one number
+    or one per curve.  One packed upload, one call, one download of the flags and counts.
+    Returns a list with, per curve, the kept rows of the array as it was given, so its dtype survives; a ring that
+    vanishes (fewer than 3 points are left, or were given) is None.
+    Curves with a non-finite coordinate or an integer of 2^53 and beyond, of a dtype that is neither integer nor
+    float, curves the device refuses (a NaN tolerance, more than SIMPLIFY_MAX_POINTS points), empty curves and every
+    curve of a batch below SIMPLIFY_DEVICE_MIN_BATCH go through the same definition in Python
+    (_simplify_on_host, not curves.simplify_curve), which gives the same flags.  A curve of
+    another shape than (n, 2), an unknown method and closed=True with "rdp" are a ValueError."""
+    what = "simplify_curves"
+    if method not in SIMPLIFY_METHODS:
+        raise ValueError("%s: method is one of %s, got %r" % (what, SIMPLIFY_METHODS, method))
+    if closed and method == "rdp":
+        raise ValueError("%s: Ramer-Douglas-Peucker takes open curves (closed=False)" % what)
+    curves = list(curves)
+    m = len(curves)
+    tolerances = _per_curve(tolerance, m, what, "tolerance")
+    if any(t is None for t in tolerances):
+        raise ValueError("%s: a tolerance is a number, got None" % what)
+    given, flags = [], [None] * m
+    dev, arrs = [], []
+    for k in range(m):
+        a = np.asarray(curves[k])
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s: curve %d has shape %r, expected (n, 2)" % (what, k, a.shape))
+        given.append(a)
+        kind = a.dtype.kind
+        if not 0 < len(a) <= SIMPLIFY_MAX_POINTS or tolerances[k] != tolerances[k] or kind not in "iuf":
+            continue
+        if kind != "f" and a.dtype.itemsize > 4 and int(np.abs(a).max()) >= 2 ** 53:
+            continue
+        if kind == "f" and not np.isfinite(a).all():
+            continue
+        dev.append(k)
+        arrs.append(a)
+    if len(dev) >= max(SIMPLIFY_DEVICE_MIN_BATCH, 1):
+        md = len(dev)
+        if len({a.dtype for a in arrs}) > 1:           # (each converted on its own: no promotion among them)
+            arrs = [a.astype(np.float64) for a in arrs]
+        flat, shapes, offsets, sizes, total = _pack_ragged(arrs)
+        flat = flat.astype(np.float64, copy=False)
+        npoints = total // 2
+        first = np.append(offsets, total) // 2
+        tol = np.array([float(tolerances[k]) for k in dev], np.float64)
+        # one packed upload: [point offsets | tolerances | points]; one output buffer: [counts | status | flags]
+        packed = np.concatenate([first.astype(np.int64).view(np.uint8), tol.view(np.uint8), flat.view(np.uint8)])
+        at_tol, at_pts = 8 * (md + 1), 8 * (md + 1) + 8 * md
+        o_st, o_keep = 4 * md, 8 * md
+        L = _hip.lib()
+        with _Lease.on(stream) as d:
+            src = d.upload(packed)
+            out = d.take(o_keep + npoints)
+            if method == "rdp":
+                check(L.va_simplify_rdp(src.ptr + at_pts, src.ptr, npoints, md, src.ptr + at_tol, out.ptr + o_keep,
+                                        out.ptr, out.ptr + o_st, stream))
+            else:
+                need = L.va_simplify_visvalingam_workspace_bytes(npoints)
+                ws = d.take(need)
+                check(L.va_simplify_visvalingam(src.ptr + at_pts, src.ptr, npoints, md, src.ptr + at_tol,
+                                                1 if closed else 0, out.ptr + o_keep, out.ptr, out.ptr + o_st,
+                                                ws.ptr, need, stream))
+            raw = out.download((o_keep + npoints,), np.uint8, stream)
+        status = raw[o_st:o_keep].view(np.int32)
+        keep = raw[o_keep:] != 0
+        run, bounds = (status == 0).tolist(), first.tolist()
+        for j, k in enumerate(dev):
+            if run[j]:
+                flags[k] = keep[bounds[j]:bounds[j + 1]]
+    results = []
+    for k in range(m):
+        kept = flags[k] if flags[k] is not None else _simplify_on_host(given[k], tolerances[k], method, closed)
+        results.append(None if closed and not kept.any() else given[k][kept])
+    return results
+
+
 # ------------------------------------------------------------------------------------------------ composer
 COMPOSE_CHANNELS = {0: 0, "r": 0, "red": 0, 1: 1, "g": 1, "green": 1, 2: 2, "b": 2, "blue": 2}   # composer.py:43-45
 COMPOSE_LAYER_DTYPE = np.dtype([("kind", np.int32), ("image_channels", np.int32), ("channel", np.int32),
