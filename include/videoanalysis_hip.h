@@ -909,6 +909,36 @@ int va_jpeg_decode_sampled_u8(const uint8_t *bytes_dev, const int64_t *offsets_d
                               const void *huff_dev, int huff_bytes, uint8_t *frames_out_dev, int32_t *status_out_dev,
                               void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ A24 Motion-JPEG decoding, frames without restart markers
+ * replaces  the same cv2.VideoCapture.read of VideoOpenCV.get_frame, video/io/backend_opencv.py, behind
+ *           load_any_video, video/io/file.py:37-46, for the files that cameras, libjpeg and Pillow write by default: no
+ *           DRI, so a frame is one entropy segment, which the entries above decode with one lane
+ * The arguments and the contract of va_jpeg_decode_sampled_u8 without ri (a frame is one segment; a restart marker in
+ * it is a marker-sequence error as there), and behind workspace_bytes ("Split Motion-JPEG decoding"):
+ *   sub_bytes        the raw bytes of a subsequence, a multiple of 16 in 16 .. 65536: a frame's segment is decoded by
+ *                    one lane per subsequence, which find the serial decoder's states by self-synchronisation
+ *   max_rounds       0 or more rounds of the scan; a frame that has not converged behind them falls back to the one
+ *                    lane of the entries above (0: every frame)
+ *   max_scan_bytes   sizes the scan's grid: ceil(max_scan_bytes / sub_bytes) lanes a frame; a frame with more entropy
+ *                    bytes falls back
+ *   rounds_out_dev   int32 (n) or NULL: the last round in which a lane of the frame ran, -1 where the frame fell back
+ *   workspace_dev    va_jpeg_decode_split_workspace_bytes(n, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes) holds
+ *                    the whole batch: as above, and 88 bytes per lane more; with less the call runs in chunks
+ * Every output byte and status word is the one va_jpeg_decode_sampled_u8 writes for the same file with ri = its MCUs.
+ * Per chunk: locate, max_rounds scan launches, check, a memset of the coefficients, write, seal, the fallback, and the
+ * reconstruction launches; no host synchronisation.  Nothing is read outside a file's bytes or written outside its
+ * pixels whatever the bytes are; a hostile stream costs at most what it costs the entries above plus max_rounds
+ * rounds; two runs write identical bytes.  VA_ERR_INVALID in the order of va_jpeg_decode_sampled_u8 (rounds_out_dev
+ * not 4-byte aligned with the other alignments), then sub_bytes, a negative max_rounds, max_scan_bytes outside
+ * 0 .. 2^40; then VA_ERR_RANGE for a workspace that does not hold one frame. */
+size_t va_jpeg_decode_split_workspace_bytes(int n, int h, int w, int c, int luma_h, int luma_v, int sub_bytes,
+                                            int64_t max_scan_bytes);
+int va_jpeg_decode_split_u8(const uint8_t *bytes_dev, const int64_t *offsets_dev, const int64_t *scan_begin_dev, int n,
+                            int h, int w, int c, int luma_h, int luma_v, const uint8_t *qtables_dev,
+                            const void *huff_dev, int huff_bytes, uint8_t *frames_out_dev, int32_t *status_out_dev,
+                            void *workspace_dev, int64_t workspace_bytes, int sub_bytes, int max_rounds,
+                            int64_t max_scan_bytes, int32_t *rounds_out_dev, void *stream);
+
 /* ------------------------------------------------------------------ A9 contour moments
  * replaces  cv2.moments(contour), regionprops(contour=...), video/analysis/image.py:355, and
  *           cv2.moments(np.asarray(self.contour, np.float32)), Polygon.moments,

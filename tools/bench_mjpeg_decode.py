@@ -18,6 +18,13 @@
             through va_jpeg_decode_u8, each with one restart interval per MCU row and with none (a frame is then one
             segment, one lane), by HIP events in the same run; the launches one by one come from the same
             rocprofv3 run as above with --legs subsampled.  Skipped with a message where Pillow is missing
+  split     the Pillow-written pictures of the subsampled leg without restart markers (what cameras write), 4:4:4,
+            4:2:2 and 4:2:0, at batches of 32 and --frames: the one-lane entries (ops.jpeg_decode(split=False), the
+            only path before the split decoder existed) against va_jpeg_decode_split_u8 with ops' defaults, with the
+            rounds its frames took; at --frames a sweep of sub_bytes over 128, 256, 512, 1024 and of max_rounds; the
+            same pictures with a restart interval per MCU row next to them; and the routing crossover: both paths on
+            batches of 32 square frames of 64 .. 512 pixels (entropy bytes per frame against time).  --split-brief
+            runs only the default call (for a rocprofv3 --kernel-trace --stats run that lists its launches)
 Times are the median of the repetitions.  One JSON line per leg, appended to profiles/mjpeg_decode_bench.jsonl (or
 --out); a leg that did not run is written "not measured".
 Run on an MI355X:
@@ -43,7 +50,8 @@ ap.add_argument("--quality", type=int, default=90)
 ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow leg (0: not measured)")
 ap.add_argument("--video-frames", type=int, default=64, help="frames of the VideoMJPEG leg")
 ap.add_argument("--distinct", type=int, default=16, help="pictures of the subsampled leg, repeated to --frames")
-ap.add_argument("--legs", default="kernels,batch32,ops,pillow,video,subsampled")
+ap.add_argument("--legs", default="kernels,batch32,ops,pillow,video,subsampled,split")
+ap.add_argument("--split-brief", action="store_true", help="the split leg: only the default call at --frames")
 ap.add_argument("--modes", default="mono,rgb")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mjpeg_decode_bench.jsonl"))
 args = ap.parse_args()
@@ -161,6 +169,111 @@ def main():
                       "note": "Pillow-written; locate + entropy + %s, one chunk"
                               % ("reconstruct" if (lh, lv) == (1, 1) else "chroma planes + pixels")})
                 del src, ws
+    def split():
+        try:
+            from PIL import Image
+        except ImportError:
+            print("the split leg needs Pillow to write its streams: skipped", flush=True)
+            emit({"leg": "split", "ms_per_call_median": "not measured", "note": "Pillow is not installed"})
+            return
+
+        def prepare(pictures, n, sub, rows):
+            """n Pillow-written files of one header, resident on the device, and what both entries need"""
+            files = []
+            for picture in pictures:
+                buf = io.BytesIO()
+                Image.fromarray(picture).save(buf, "JPEG", quality=Q, subsampling=sub,
+                                              **({"restart_marker_rows": 1} if rows else {}))
+                files.append(buf.getvalue())
+            files = [files[k % len(files)] for k in range(n)]
+            heads = [ops.jpeg_parse_header(f, sampling="any") for f in files[:len(pictures)]]
+            assert len(ops.jpeg_decode_groups(heads)) == 1 and (rows or heads[0]["nseg"] == 1)
+            head = heads[0]
+            tables = b"".join(ops._jpeg_decode_table(*dc) + ops._jpeg_decode_table(*ac) for dc, ac in head["huff"])
+            offsets = np.concatenate([[0], np.cumsum([len(f) for f in files])]).astype(np.int64)
+            scans = np.array([heads[k % len(heads)]["scan_begin"] for k in range(n)], np.int64)
+            return dict(head=head, tables=tables, n=n, offsets=offsets, scan_bytes=np.diff(offsets) - scans,
+                        consts=torch.from_numpy(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8).copy()).to(dev),
+                        src=torch.from_numpy(np.frombuffer(b"".join(files), np.uint8).copy()).to(dev),
+                        meta=torch.from_numpy(np.concatenate([offsets, scans])).to(dev))
+
+        def timed(w, n, h, wd, sub_bytes=None, max_rounds=None, reps=None):
+            """(min, median, rounds or None) of one call on the first n frames: the one-lane entry for sub_bytes None"""
+            head = w["head"]
+            lh, lv = head["sampling"]
+            out = torch.empty(n * h * wd * 3, dtype=torch.uint8, device=dev)
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+            rounds = torch.zeros(n, dtype=torch.int32, device=dev)
+            front = (w["src"].data_ptr(), w["meta"].data_ptr(), w["meta"].data_ptr() + 8 * (w["n"] + 1), n, h, wd, 3)
+            mid = (w["consts"].data_ptr(), w["consts"].data_ptr() + 192, len(w["tables"]), out.data_ptr(), status.data_ptr())
+            if sub_bytes is None:
+                room = int(L.va_jpeg_decode_sampled_workspace_bytes(n, h, wd, 3, head["ri"], lh, lv))
+                ws = torch.empty(room, dtype=torch.uint8, device=dev)
+                call = lambda: check(L.va_jpeg_decode_sampled_u8(*(front + (head["ri"], lh, lv) + mid
+                                                                  + (ws.data_ptr(), room, S))))
+            else:
+                most = int(w["scan_bytes"][:n].max())
+                room = int(L.va_jpeg_decode_split_workspace_bytes(n, h, wd, 3, lh, lv, sub_bytes, most))
+                ws = torch.empty(room, dtype=torch.uint8, device=dev)
+                call = lambda: check(L.va_jpeg_decode_split_u8(*(front + (lh, lv) + mid + (
+                    ws.data_ptr(), room, sub_bytes, max_rounds, most, rounds.data_ptr(), S))))
+            keep, args.reps = args.reps, reps or args.reps
+            try:
+                best, med = events(call)
+            finally:
+                args.reps = keep
+            assert not bool(status.any())
+            return round(best, 4), round(med, 4), (None if sub_bytes is None else rounds.cpu().numpy())
+
+        def rounds_row(r):
+            return {"rounds_max": int(r.max()), "rounds_mean": round(float(r[r >= 0].mean()), 2) if (r >= 0).any() else None,
+                    "frames_fallen_back": int((r < 0).sum())}
+        pictures = scene(min(args.distinct, N), H, W, 3, np.random.default_rng(44), False)
+        sub0, rounds0 = ops.JPEG_SPLIT_SUB_BYTES, ops.JPEG_SPLIT_MAX_ROUNDS
+        for layout, sub in (("444", 0), ("422", 1), ("420", 2)):
+            w = prepare(pictures, N, sub, False)
+            base = {"frames": N, "h": H, "w": W, "quality": Q, "entropy_bytes_per_frame": int(w["scan_bytes"].mean())}
+            if args.split_brief:
+                timed(w, N, H, W, sub0, rounds0, reps=2)
+                continue
+            for n in sorted({min(32, N), N}):
+                _, one_lane, _ = timed(w, n, H, W, reps=3)
+                best, med, r = timed(w, n, H, W, sub0, rounds0)
+                row = dict(base, leg="split/%s/none" % layout, frames=n, one_lane_ms_median=one_lane,
+                           split_ms_min=best, split_ms_median=med, speedup=round(one_lane / med, 1),
+                           frames_per_s=round(n / med * 1e3, 1), sub_bytes=sub0, max_rounds=rounds0,
+                           note="Pillow-written, no restart markers; one_lane is va_jpeg_decode_sampled_u8, the only "
+                                "path before the split entry, in the same run")
+                row.update(rounds_row(r))
+                emit(row)
+            for sub_bytes in (128, 256, 512, 1024):
+                best, med, r = timed(w, N, H, W, sub_bytes, 16)
+                emit(dict(base, leg="split_sweep/%s" % layout, sub_bytes=sub_bytes, max_rounds=16, split_ms_min=best,
+                          split_ms_median=med, **rounds_row(r)))
+            for most in (1, 2, 4, 8, 16):
+                best, med, r = timed(w, N, H, W, sub0, most, reps=3)
+                emit(dict(base, leg="split_rounds/%s" % layout, sub_bytes=sub0, max_rounds=most, split_ms_min=best,
+                          split_ms_median=med, **rounds_row(r)))
+            del w
+            rows_w = prepare(pictures, N, sub, True)
+            best, med, _ = timed(rows_w, N, H, W)
+            emit(dict(base, leg="split/%s/mcu_rows" % layout, ms_per_call_min=best, ms_per_call_median=med,
+                      note="the same pictures with a restart interval per MCU row, va_jpeg_decode_sampled_u8"))
+            del rows_w
+        if args.split_brief:
+            return
+        for side in (64, 128, 256, 512):
+            small = scene(8, side, side, 3, np.random.default_rng(45), False)
+            w = prepare(small, 32, 2, False)
+            _, one_lane, _ = timed(w, 32, side, side)
+            _, med, r = timed(w, 32, side, side, sub0, rounds0)
+            emit(dict(leg="split_crossover/420", frames=32, h=side, w=side, quality=Q,
+                      entropy_bytes_per_frame=int(w["scan_bytes"].mean()), one_lane_ms_median=one_lane,
+                      split_ms_median=med, sub_bytes=sub0, max_rounds=rounds0, **rounds_row(r)))
+            del w
+    if "split" in LEGS:
+        split()
+        ops.pool_clear()
     if "subsampled" in LEGS:
         subsampled()
         ops.pool_clear()

@@ -1268,6 +1268,61 @@ int va_jpeg_decode_sampled_u8(const uint8_t *bytes, const int64_t *offsets, cons
                              qtables, huff, huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
 }
 
+namespace {
+constexpr int64_t kJpegSplitMaxScanBytes = (int64_t)1 << 40;
+bool jpeg_split_sub_taken(int sub) { return sub >= 16 && sub <= 65536 && sub % 16 == 0; }
+}  // namespace
+
+size_t va_jpeg_decode_split_workspace_bytes(int n, int h, int w, int c, int luma_h, int luma_v, int sub_bytes,
+                                            int64_t max_scan_bytes)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3)
+        || !jpeg_sampling_taken(c, luma_h, luma_v) || !jpeg_split_sub_taken(sub_bytes) || max_scan_bytes < 0
+        || max_scan_bytes > kJpegSplitMaxScanBytes)
+        return 0;
+    return jpeg_split_workspace_bytes(n, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes);
+}
+
+int va_jpeg_decode_split_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                            int c, int luma_h, int luma_v, const uint8_t *qtables, const void *huff, int huff_bytes,
+                            uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
+                            int sub_bytes, int max_rounds, int64_t max_scan_bytes, int32_t *rounds_out, void *stream)
+{
+    const char *what = "va_jpeg_decode_split_u8";
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && workspace_bytes >= 0,
+               "%s: negative or zero size (n %d, h %d, w %d, workspace %lld)", what, n, h, w, (long long)workspace_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
+    VA_REQUIRE(jpeg_sampling_taken(c, luma_h, luma_v),
+               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
+               what, luma_h, luma_v, c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
+               "%s: NULL argument", what);
+    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
+                   && aligned(workspace, 16) && aligned(rounds_out, 4),
+               "%s: offsets and scan_begin must be 8-byte aligned, the tables, the status and the rounds 4-byte, "
+               "the workspace 16-byte", what);
+    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
+    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
+               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
+               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
+    VA_REQUIRE(jpeg_split_sub_taken(sub_bytes), "%s: sub_bytes must be a multiple of 16 in 16 .. 65536, got %d", what,
+               sub_bytes);
+    VA_REQUIRE(max_rounds >= 0, "%s: max_rounds must not be negative, got %d", what, max_rounds);
+    VA_REQUIRE(max_scan_bytes >= 0 && max_scan_bytes <= kJpegSplitMaxScanBytes,
+               "%s: max_scan_bytes must lie in 0 .. 2^40, got %lld", what, (long long)max_scan_bytes);
+    if (jpeg_split_chunk(n, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes, (size_t)workspace_bytes) < 1) {
+        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what, (long long)workspace_bytes,
+                  (long long)jpeg_split_workspace_bytes(1, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes));
+        return VA_ERR_RANGE;
+    }
+    return launch_jpeg_decode_split(bytes, offsets, scan_begin, n, h, w, c, luma_h, luma_v, sub_bytes, max_rounds,
+                                    max_scan_bytes, qtables, huff, frames_out, status_out, rounds_out, workspace,
+                                    (size_t)workspace_bytes, as_stream(stream));
+}
+
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited

@@ -489,6 +489,15 @@ int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, si
 int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
                        int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
                        int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st);
+// Split Motion-JPEG decoding (va_jpeg_decode.hip): frames without restart markers, one lane per `sub` raw bytes of a
+// frame's one segment (scan rounds, check, write, seal; the one-lane fallback for a frame that did not converge or is
+// longer than max_bytes); the workspace and the chunks as above with more behind
+size_t jpeg_split_workspace_bytes(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes);
+int64_t jpeg_split_chunk(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes, size_t workspace_bytes);
+int launch_jpeg_decode_split(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                             int c, int lh, int lv, int sub, int max_rounds, int64_t max_bytes, const uint8_t *qtables,
+                             const void *huff, uint8_t *out, int32_t *status, int32_t *rounds_out, void *ws,
+                             size_t workspace_bytes, hipStream_t st);
 // cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
 int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
                            int is_float, double *out, hipStream_t st);

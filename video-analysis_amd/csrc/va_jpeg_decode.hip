@@ -32,7 +32,8 @@
 //                  store_row
 // The only atomic is the OR into the status word, whose result does not depend on the order; every output byte
 // depends on its frame alone.  Loops over stream bytes end at the segment's end, loops over blocks at the segment's
-// MCU range.
+// MCU range.  A frame without restart markers is one segment and one lane here; launch_jpeg_decode_split further
+// down gives it one lane per subsequence of its bytes ("split segments").
 #include <limits.h>
 
 #include "va_common.h"
@@ -182,6 +183,7 @@ struct EntropyArgs {
     int32_t *status;
     int64_t nsegs;                       // segments of the chunk
     int nseg, ri, bx, by;
+    const int32_t *skip;                 // kSkip: per frame, not 0 where the frame is already decoded
 };
 
 // the 2 * C tables into LDS, by the whole workgroup
@@ -200,7 +202,7 @@ __device__ __forceinline__ void stage_tables(va_jpeg::HuffDecode *tabs, const va
 // C components, luma LH x LV, chroma 1 x 1; a.bx, a.by count MCUs of 8 LH x 8 LV pixels, and a monochrome MCU is its
 // one block.  An error zeroes its block and every later block of the segment; the MCU's earlier blocks keep their
 // coefficients.
-template <int C, int LH, int LV>
+template <int C, int LH, int LV, bool kSkip = false>
 __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
 {
     static_assert(C == 3 || (C == 1 && LH == 1 && LV == 1), "one component has no sampling");
@@ -211,6 +213,9 @@ __global__ void __launch_bounds__(kEntBlock) jpeg_entropy_kernel(EntropyArgs a)
     if (s >= a.nsegs)
         return;
     const int64_t f = s / a.nseg;
+    if constexpr (kSkip)
+        if (a.skip[f])
+            return;
     const int j = (int)(s % a.nseg);
     const int64_t begin = a.table[2 * s], end = a.table[2 * s + 1];
     const int64_t mcus = (int64_t)a.bx * a.by;
@@ -546,7 +551,380 @@ int64_t jpeg_decode_chunk(int n, const JpegGrid &g, size_t workspace_bytes)
     return k;
 }
 
+// ------------------------------------------------------------------------------------------------ split segments
+// DESIGN.md §9, "Split Motion-JPEG decoding": a frame without restart markers is one segment; its raw bytes are cut
+// into subsequences of `sub` bytes and every subsequence gets a lane.  Per chunk, behind locate (nseg = 1):
+//   scan         max_rounds launches of one lane per subsequence (va_jpeg::scan_lane): round 1 from the truth (lane
+//                0) or a guess, round r + 1 from the predecessor's exit of round r (the exits are double-buffered,
+//                so the rounds are Jacobi iterations and their number does not depend on the schedule).  A lane
+//                whose entry did not change copies its exit on and returns; a workgroup of such lanes does not even
+//                stage the tables.
+//   check        one workgroup per frame: converged iff every entry is the predecessor's last exit; the exclusive
+//                scans over the frame's lanes of the blocks begun and of the DC sums per component; the frame's
+//                rounds; the error word reset.
+//   (memset)     the chunk's coefficients to zero: a block that straddles two lanes has two writers
+//   write        one lane per subsequence of a converged frame: va_jpeg::write_lane from its entry, its block index
+//                and its predictors into the coefficients' usual places; an error goes as atomicMin of (block in
+//                decode order, status bit) into the frame's 64-bit error word and ends the lane
+//   seal         zeroes every block from the error's block on (16-byte stores, through mcu_block_at) and ORs the
+//                error's one status bit into the frame's word
+//   fallback     jpeg_entropy_kernel with the per-frame skip flag: one lane for each frame that did not converge or
+//                is longer than max_bytes
+// and then the reconstruction launches as above.  Besides the OR, the atomics are the minimum of the error word and
+// a maximum in LDS; both results do not depend on the order.
+struct SplitArgs {
+    const uint8_t *bytes;
+    const int64_t *table;
+    const va_jpeg::HuffDecode *huff;
+    va_jpeg::ScanState *entry, *exits;   // [frame][lane]; exits: two of them, of the odd and of the even rounds
+    int32_t *begun, *last;               // blocks begun in the lane; the last round in which the lane ran
+    uint32_t *dc, *pred;                 // [..][3]: the lane's DC sums; the sums in front of the lane
+    int64_t *start;                      // blocks begun in front of the lane
+    int32_t *converged;                  // per frame
+    unsigned long long *err;             // per frame: va_jpeg::error_word
+    int32_t *rounds_out;                 // may be NULL
+    int16_t *coef;
+    int32_t *status;
+    int64_t lanes, per, max_bytes;       // lanes of the chunk, of a frame; a longer frame has none
+    int sub, round, max_rounds, bx, by;
+};
+
+// the segment of frame f and the number of its lanes (0: not scanned)
+__device__ __forceinline__ int64_t split_span(const SplitArgs &a, int64_t f, int64_t &b, int64_t &e)
+{
+    b = a.table[2 * f];
+    e = a.table[2 * f + 1];
+    if (b < 0 || e < b)
+        b = e = 0;
+    return e - b > a.max_bytes ? 0 : va_jpeg::subsequences(e - b, a.sub);
+}
+
+template <int C, int LH, int LV>
+__global__ void __launch_bounds__(kEntBlock) jpeg_split_scan_kernel(SplitArgs a)
+{
+    constexpr int kBlocks = C == 1 ? 1 : va_jpeg::mcu_blocks(LH, LV);
+    __shared__ va_jpeg::HuffDecode tabs[2 * C];
+    const int64_t g = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
+    bool run = false;
+    int64_t b = 0, e = 0, stop = 0;
+    va_jpeg::ScanState entry = va_jpeg::scan_end();
+    va_jpeg::ScanState *now = a.exits + (a.round & 1) * a.lanes, *before = a.exits + ((a.round - 1) & 1) * a.lanes;
+    if (g < a.lanes) {
+        const int64_t i = g % a.per, count = split_span(a, g / a.per, b, e);
+        if (i < count) {
+            stop = i + 1 == count ? e : b + (i + 1) * a.sub;
+            entry = i == 0         ? va_jpeg::scan_state(b, 0, 0, 0)
+                    : a.round == 1 ? va_jpeg::scan_guess(a.bytes, b, b + i * a.sub)
+                                   : before[g - 1];
+            run = a.round == 1 || !va_jpeg::same_state(entry, a.entry[g]);
+            if (!run)
+                now[g] = before[g];
+        }
+    }
+    if (!__syncthreads_or(run))
+        return;
+    stage_tables<C>(tabs, a.huff);
+    if (!run)
+        return;
+    const va_jpeg::ScanLane r = va_jpeg::scan_lane(a.bytes, e, entry, stop, tabs, kBlocks, LH * LV);
+    a.entry[g] = entry;
+    now[g] = r.exit;
+    a.begun[g] = r.begun;
+    a.last[g] = a.round;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++)
+        a.dc[3 * g + ch] = r.dc[ch];
+}
+
+template <class T>
+__device__ __forceinline__ T wave_inclusive(T v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const T u = __shfl_up(v, d, kWave);
+        if (lane >= d)
+            v += u;
+    }
+    return v;
+}
+
+// the exclusive scan of v over the workgroup's kRecBlock lanes; total: the sum.  `part` holds a value per wave.
+template <class T>
+__device__ __forceinline__ T block_exclusive(T v, T *part, T &total)
+{
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const T incl = wave_inclusive(v, lane);
+    __syncthreads();                                     // the last use of `part`
+    if (lane == kWave - 1)
+        part[wave] = incl;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < kRecBlock / kWave; k++) {
+        before += k < wave ? part[k] : (T)0;
+        total += part[k];
+    }
+    return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kRecBlock) jpeg_split_check_kernel(SplitArgs a)
+{
+    __shared__ long long part64[kRecBlock / kWave];
+    __shared__ uint32_t part32[kRecBlock / kWave];
+    __shared__ int32_t rounds;
+    const int64_t f = blockIdx.x;
+    int64_t b, e;
+    const int64_t count = a.max_rounds > 0 ? split_span(a, f, b, e) : 0;
+    if (threadIdx.x == 0)
+        rounds = 0;
+    __syncthreads();
+    const va_jpeg::ScanState *exits = a.exits + (a.max_rounds & 1) * a.lanes;
+    long long carry = 0;
+    uint32_t carry_dc[3] = {0, 0, 0};
+    bool good = true;
+    int32_t mine = 0;
+    for (int64_t i0 = 0; i0 < count; i0 += kRecBlock) {
+        const int64_t i = i0 + threadIdx.x, g = f * a.per + i;
+        const bool in = i < count;
+        if (in) {
+            good = good && (i == 0 || va_jpeg::same_state(a.entry[g], exits[g - 1]));
+            mine = a.last[g] > mine ? a.last[g] : mine;
+        }
+        long long total = 0;
+        const long long at = block_exclusive<long long>(in ? a.begun[g] : 0, part64, total);
+        if (in)
+            a.start[g] = carry + at;
+        carry += total;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            uint32_t sum = 0;
+            const uint32_t front = block_exclusive<uint32_t>(in ? a.dc[3 * g + ch] : 0u, part32, sum);
+            if (in)
+                a.pred[3 * g + ch] = carry_dc[ch] + front;
+            carry_dc[ch] += sum;
+        }
+    }
+    atomicMax(&rounds, mine);
+    const bool all = __syncthreads_and(good) && count > 0;
+    if (threadIdx.x == 0) {
+        a.converged[f] = all;
+        a.err[f] = va_jpeg::kNoError;
+        if (a.rounds_out)
+            a.rounds_out[f] = all ? rounds : -1;
+    }
+}
+
+template <int C, int LH, int LV>
+__global__ void __launch_bounds__(kEntBlock) jpeg_split_write_kernel(SplitArgs a)
+{
+    constexpr int kBlocks = C == 1 ? 1 : va_jpeg::mcu_blocks(LH, LV);
+    __shared__ va_jpeg::HuffDecode tabs[2 * C];
+    const int64_t g = (int64_t)blockIdx.x * kEntBlock + threadIdx.x;
+    const int64_t f = g / a.per, i = g % a.per;
+    int64_t b = 0, e = 0, count = 0;
+    if (g < a.lanes && a.converged[f])
+        count = split_span(a, f, b, e);
+    const bool run = i < count;
+    if (!__syncthreads_or(run))
+        return;
+    stage_tables<C>(tabs, a.huff);
+    if (!run)
+        return;
+    const int64_t mcus = (int64_t)a.bx * a.by, total = mcus * kBlocks;
+    int16_t *frame = a.coef + ((f * total) << 6), *blk = nullptr;
+    int64_t at = -1, block = a.start[g];
+    uint32_t pred[3] = {a.pred[3 * g], a.pred[3 * g + 1], a.pred[3 * g + 2]};
+    const bool last = i + 1 == count;
+    const int32_t st = va_jpeg::write_lane(
+        a.bytes, e, a.entry[g], last ? e : b + (i + 1) * a.sub, last, tabs, kBlocks, LH * LV, total, block, pred,
+        [&](int64_t cur, int idx, int v) {              // cur < total
+            if (cur != at) {
+                const int64_t m = cur / kBlocks;
+                int comp = 0;
+                at = cur;
+                blk = frame + (va_jpeg::mcu_block_at((int)(cur % kBlocks), LH, LV, a.by, a.bx, m / a.bx, m % a.bx, comp) << 6);
+            }
+            blk[idx] = (int16_t)v;
+        });
+    if (st)
+        atomicMin(&a.err[f], (unsigned long long)va_jpeg::error_word(block, st));
+}
+
+// one lane per block of the chunk; a workgroup lies in one frame
+template <int C, int LH, int LV>
+__global__ void __launch_bounds__(kRecBlock) jpeg_split_seal_kernel(SplitArgs a, int64_t groups)
+{
+    constexpr int kBlocks = C == 1 ? 1 : va_jpeg::mcu_blocks(LH, LV);
+    const int64_t f = blockIdx.x / groups;
+    const unsigned long long word = a.err[f];
+    if (word == va_jpeg::kNoError)
+        return;
+    const int64_t mcus = (int64_t)a.bx * a.by, total = mcus * kBlocks;
+    const int64_t cur = (blockIdx.x % groups) * kRecBlock + threadIdx.x;
+    if (cur == 0)
+        a.status[f] |= (int32_t)(word & 15u);
+    if (cur >= total || cur < (int64_t)(word >> 4))
+        return;
+    const int64_t m = cur / kBlocks;
+    int comp = 0;
+    uint4 *blk16 = reinterpret_cast<uint4 *>(
+        a.coef + ((f * total + va_jpeg::mcu_block_at((int)(cur % kBlocks), LH, LV, a.by, a.bx, m / a.bx, m % a.bx, comp)) << 6));
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        blk16[k] = make_uint4(0, 0, 0, 0);
+}
+
+// behind decode_layout's regions (nseg = 1): [converged | error words | entries | exits | begun | last | dc | pred |
+// start], per frame `per` lanes
+struct SplitLayout {
+    DecodeLayout d;
+    size_t converged, err, entry, exits, begun, last, dc, pred, start, total;
+};
+
+SplitLayout split_layout(int64_t n, const JpegGrid &g, int64_t per)
+{
+    SplitLayout l;
+    l.d = decode_layout(n, g);
+    Carve carve;
+    carve.total = l.d.total;
+    const size_t lanes = (size_t)n * (size_t)per;
+    l.converged = carve.take((size_t)n * sizeof(int32_t));
+    l.err = carve.take((size_t)n * sizeof(unsigned long long));
+    l.entry = carve.take(lanes * sizeof(va_jpeg::ScanState));
+    l.exits = carve.take(2 * lanes * sizeof(va_jpeg::ScanState));
+    l.begun = carve.take(lanes * sizeof(int32_t));
+    l.last = carve.take(lanes * sizeof(int32_t));
+    l.dc = carve.take(3 * lanes * sizeof(uint32_t));
+    l.pred = carve.take(3 * lanes * sizeof(uint32_t));
+    l.start = carve.take(lanes * sizeof(int64_t));
+    l.total = carve.total;
+    return l;
+}
+
+int64_t split_lanes(int sub, int64_t max_bytes) { return va_jpeg::subsequences(max_bytes, sub); }
+
+// as jpeg_decode_chunk, and no more frames than the scan's and the seal's grids take
+int64_t jpeg_split_chunk(int n, const JpegGrid &g, int64_t per, size_t workspace_bytes)
+{
+    const int64_t room = ((int64_t)1 << 31) - kRecBlock;
+    const int64_t groups = (g.mcus * g.blocks + kRecBlock - 1) / kRecBlock;
+    int64_t most = room / (g.mcus * g.luma);
+    most = most < room / per ? most : room / per;
+    most = most < room / groups ? most : room / groups;
+    most = most < n ? most : n;
+    if (most < 1 || split_layout(most, g, per).total <= workspace_bytes)
+        return most;
+    const size_t one = split_layout(1, g, per).total;
+    int64_t k = (int64_t)(workspace_bytes / one);
+    k = k < most ? k : most;
+    while (k < most && split_layout(k + 1, g, per).total <= workspace_bytes)
+        k++;
+    return k;
+}
+
 }  // namespace
+
+size_t jpeg_split_workspace_bytes(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes)
+{
+    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, lh, lv);
+    return split_layout(n, g, split_lanes(sub, max_bytes)).total;
+}
+
+int64_t jpeg_split_chunk(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes, size_t workspace_bytes)
+{
+    return jpeg_split_chunk(n, jpeg_grid(h, w, c, INT_MAX, lh, lv), split_lanes(sub, max_bytes), workspace_bytes);
+}
+
+namespace {
+
+template <int C, int LH, int LV>
+int launch_split_entropy(SplitArgs a, EntropyArgs e, int64_t frames, int64_t mcus, hipStream_t st)
+{
+    constexpr int kBlocks = C == 1 ? 1 : va_jpeg::mcu_blocks(LH, LV);
+    const dim3 lanes((unsigned)((a.lanes + kEntBlock - 1) / kEntBlock));
+    for (a.round = 1; a.round <= a.max_rounds; a.round++) {
+        hipLaunchKernelGGL((jpeg_split_scan_kernel<C, LH, LV>), lanes, dim3(kEntBlock), 0, st, a);
+        VA_LAUNCH_CHECK("jpeg_split_scan_kernel");
+    }
+    hipLaunchKernelGGL(jpeg_split_check_kernel, dim3((unsigned)frames), dim3(kRecBlock), 0, st, a);
+    VA_LAUNCH_CHECK("jpeg_split_check_kernel");
+    if (a.max_rounds > 0) {
+        VA_HIP(hipMemsetAsync(a.coef, 0, (size_t)frames * kBlocks * mcus * 64 * sizeof(int16_t), st));
+        hipLaunchKernelGGL((jpeg_split_write_kernel<C, LH, LV>), lanes, dim3(kEntBlock), 0, st, a);
+        VA_LAUNCH_CHECK("jpeg_split_write_kernel");
+        const int64_t groups = (mcus * kBlocks + kRecBlock - 1) / kRecBlock;
+        hipLaunchKernelGGL((jpeg_split_seal_kernel<C, LH, LV>), dim3((unsigned)(frames * groups)), dim3(kRecBlock), 0, st,
+                           a, groups);
+        VA_LAUNCH_CHECK("jpeg_split_seal_kernel");
+    }
+    hipLaunchKernelGGL((jpeg_entropy_kernel<C, LH, LV, true>), dim3((unsigned)((frames + kEntBlock - 1) / kEntBlock)),
+                       dim3(kEntBlock), 0, st, e);
+    VA_LAUNCH_CHECK("jpeg_entropy_kernel");
+    return VA_OK;
+}
+
+}  // namespace
+
+int launch_jpeg_decode_split(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                             int c, int lh, int lv, int sub, int max_rounds, int64_t max_bytes, const uint8_t *qtables,
+                             const void *huff, uint8_t *out, int32_t *status, int32_t *rounds_out, void *ws,
+                             size_t workspace_bytes, hipStream_t st)
+{
+    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, lh, lv);              // one segment a frame
+    const int64_t per = split_lanes(sub, max_bytes);
+    const int64_t chunk = jpeg_split_chunk(n, g, per, workspace_bytes);
+    const SplitLayout l = split_layout(chunk, g, per);
+    int64_t *table = at<int64_t>(ws, l.d.table);
+    int16_t *coef = at<int16_t>(ws, l.d.coef);
+    uint8_t *planes = at<uint8_t>(ws, l.d.planes);
+    const auto blocks_of = [](int64_t lanes) { return dim3((unsigned)((lanes + kRecBlock - 1) / kRecBlock)); };
+    for (int64_t f0 = 0; f0 < n; f0 += chunk) {
+        const int64_t k = chunk < n - f0 ? chunk : n - f0;
+        uint8_t *frames = out + (size_t)f0 * h * w * c;
+        hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
+                           scan_begin + f0, 1, table, status + f0);
+        VA_LAUNCH_CHECK("jpeg_locate_kernel");
+        const va_jpeg::HuffDecode *tabs = static_cast<const va_jpeg::HuffDecode *>(huff);
+        SplitArgs a{};
+        a.bytes = bytes, a.table = table, a.huff = tabs;
+        a.entry = at<va_jpeg::ScanState>(ws, l.entry), a.exits = at<va_jpeg::ScanState>(ws, l.exits);
+        a.begun = at<int32_t>(ws, l.begun), a.last = at<int32_t>(ws, l.last);
+        a.dc = at<uint32_t>(ws, l.dc), a.pred = at<uint32_t>(ws, l.pred), a.start = at<int64_t>(ws, l.start);
+        a.converged = at<int32_t>(ws, l.converged), a.err = at<unsigned long long>(ws, l.err);
+        a.rounds_out = rounds_out ? rounds_out + f0 : nullptr;
+        a.coef = coef, a.status = status + f0;
+        a.lanes = k * per, a.per = per, a.max_bytes = max_bytes;
+        a.sub = sub, a.round = 0, a.max_rounds = max_rounds, a.bx = g.bx, a.by = g.by;
+        const EntropyArgs e{bytes, table, tabs, coef, status + f0, k, 1, (int)(g.mcus < INT_MAX ? g.mcus : INT_MAX),
+                            g.bx, g.by, a.converged};
+        const int rc = c == 1    ? launch_split_entropy<1, 1, 1>(a, e, k, g.mcus, st)
+                       : lv == 2 ? launch_split_entropy<3, 2, 2>(a, e, k, g.mcus, st)
+                       : lh == 2 ? launch_split_entropy<3, 2, 1>(a, e, k, g.mcus, st)
+                                 : launch_split_entropy<3, 1, 1>(a, e, k, g.mcus, st);
+        if (rc)
+            return rc;
+        if (g.luma == 1) {
+            const ReconArgs r{coef, qtables, frames, k * g.mcus, h, w, g.bx, g.by};
+            if (c == 1)
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            else
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
+            continue;
+        }
+        const PlaneArgs cp{coef, qtables, planes, k * 2 * g.mcus, g.bx, g.by, g.luma};
+        hipLaunchKernelGGL(jpeg_chroma_planes_kernel, blocks_of(cp.nblocks), dim3(kRecBlock), 0, st, cp);
+        VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
+        const PixelArgs p{coef, qtables, planes, frames, k * g.mcus * g.luma, h, w, g.bx, g.by};
+        if (lv == 2)
+            hipLaunchKernelGGL(jpeg_pixels_kernel<2>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
+        else
+            hipLaunchKernelGGL(jpeg_pixels_kernel<1>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
+        VA_LAUNCH_CHECK("jpeg_pixels_kernel");
+    }
+    return VA_OK;
+}
 
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv)
 {
@@ -580,7 +958,7 @@ int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64
                            scan_begin + f0, g.nseg, table, status + f0);
         VA_LAUNCH_CHECK("jpeg_locate_kernel");
         const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
-                            k * g.nseg, g.nseg, ri, g.bx, g.by};
+                            k * g.nseg, g.nseg, ri, g.bx, g.by, nullptr};
         hipLaunchKernelGGL(entropy, dim3((unsigned)((e.nsegs + kEntBlock - 1) / kEntBlock)), dim3(kEntBlock), 0, st, e);
         VA_LAUNCH_CHECK("jpeg_entropy_kernel");
         if (g.luma == 1) {

@@ -164,6 +164,209 @@ VA_JPEG_FN int32_t decode_block(BitReader &r, const HuffDecode &dc, const HuffDe
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ split segments
+// DESIGN.md §9, "Split Motion-JPEG decoding": one entropy segment, the raw bytes [b, e), decoded by one lane per
+// subsequence of S raw bytes.  A state is where the serial decoder stands in front of a symbol; the scan carries
+// states from lane to lane until they are the serial decoder's, the write pass decodes from them.
+//
+// q: the raw offset of the byte that holds the next unread bit, never a stuffing byte (a 00 behind an FF, as refill
+// skips it), or e where the segment is used up; -1 is END.  w = bit | k << 3 | z << 6: the bit 0 .. 7 (0 is the
+// byte's highest), the block's index k in the MCU, z = 0 in front of a DC symbol or the zigzag index 1 .. 63 of the
+// next AC symbol.
+struct ScanState {
+    int64_t q;
+    int32_t w, unused;
+};
+
+VA_JPEG_FN ScanState scan_state(int64_t q, int bit, int k, int z) { return ScanState{q, bit | k << 3 | z << 6, 0}; }
+VA_JPEG_FN ScanState scan_end() { return ScanState{-1, 0, 0}; }
+VA_JPEG_FN bool same_state(const ScanState &a, const ScanState &b) { return a.q == b.q && a.w == b.w; }
+VA_JPEG_FN int state_bit(const ScanState &s) { return s.w & 7; }
+VA_JPEG_FN int state_k(const ScanState &s) { return s.w >> 3 & 7; }
+VA_JPEG_FN int state_z(const ScanState &s) { return s.w >> 6 & 63; }
+
+// the subsequences of a segment of len raw bytes: at least one, the last one ends with the segment
+VA_JPEG_FN int64_t subsequences(int64_t len, int sub) { return len > sub ? (len + sub - 1) / sub : 1; }
+
+// what lane i > 0 enters with before it has heard of its predecessor: the first non-stuffing byte of its subsequence
+VA_JPEG_FN ScanState scan_guess(const uint8_t *p, int64_t b, int64_t at)
+{
+    return scan_state(at > b && p[at] == 0 && p[at - 1] == 0xFFu ? at + 1 : at, 0, 0, 0);
+}
+
+// a bit reader that knows where it stands: (q, bit) follow from the bits consumed, not from how far `r` has read ahead
+struct SpanReader {
+    BitReader r;
+    int64_t q;
+    int bit;
+};
+
+VA_JPEG_FN SpanReader open_span(const uint8_t *p, int64_t e, int64_t q, int bit)
+{
+    q = q < 0 ? e : q < e ? q : e;
+    SpanReader s{open_bits(p, q, e), q, q < e ? bit : 0};
+    refill(s.r);
+    skip_bits(s.r, s.bit);                  // q < e: the reader holds at least this byte
+    return s;
+}
+
+// n bits (at most cnt) have left the reader
+VA_JPEG_FN void span_moved(SpanReader &s, int n)
+{
+    s.bit += n;
+    while (s.bit >= 8) {
+        s.bit -= 8;
+        s.q++;
+        if (s.q < s.r.end && s.r.p[s.q] == 0 && s.r.p[s.q - 1] == 0xFFu)
+            s.q++;
+    }
+}
+
+// One symbol, the code and its magnitude bits: a DC symbol for z == 0, the AC symbol in front of zigzag index z else.
+// The checks are decode_block's in its order (Huffman step, symbol, index, magnitude bits); the DC range is the
+// caller's.  A failed symbol consumes nothing.
+struct Symbol {
+    int32_t status;     // 0 or the status bit
+    int next;           // the zigzag index behind the symbol; 64: the block is complete
+    int index;          // the zigzag index of `value`, -1 where the symbol carries none (EOB, ZRL)
+    int value;          // the DC difference or the coefficient
+};
+
+VA_JPEG_FN Symbol read_symbol(SpanReader &s, const HuffDecode &dc, const HuffDecode &ac, int z)
+{
+    int sym = 0, len = 0;
+    const int32_t st = next_symbol(s.r, z ? ac : dc, sym, len);
+    if (st)
+        return Symbol{st, z, -1, 0};
+    int size = sym, next = 1, index = 0;
+    if (z) {
+        const int run = sym >> 4;
+        size = sym & 15;
+        if (size == 0) {
+            if (run != 0 && run != 15)
+                return Symbol{kStatusBadCode, z, -1, 0};
+            if (run == 15 && z + 16 > 64)
+                return Symbol{kStatusOverrun, z, -1, 0};
+            skip_bits(s.r, len);
+            span_moved(s, len);
+            return Symbol{0, run ? z + 16 : 64, -1, 0};
+        }
+        if (size > 10)
+            return Symbol{kStatusBadCode, z, -1, 0};
+        index = z + run;
+        if (index > 63)
+            return Symbol{kStatusOverrun, z, -1, 0};
+        next = index + 1;
+    } else if (sym > 11) {
+        return Symbol{kStatusBadCode, z, -1, 0};
+    }
+    if (len + size > s.r.cnt)
+        return Symbol{kStatusTruncated, z, -1, 0};
+    skip_bits(s.r, len);
+    const int value = receive_extend(s.r, size);
+    span_moved(s, len + size);
+    return Symbol{0, next, index, value};
+}
+
+// the component of block k of an MCU of `blocks` blocks, the first `luma` of them Y
+VA_JPEG_FN int mcu_component(int k, int blocks, int luma) { return blocks == 1 || k < luma ? 0 : k - luma + 1; }
+
+// What a lane of the scan learns from its subsequence [.., stop): where the decoder stands behind it, how many
+// blocks begin in it, and the sum of their DC differences per component (uint32: behind an error the sums mean
+// nothing and may wrap).
+struct ScanLane {
+    ScanState exit;
+    int32_t begun;
+    uint32_t dc[3];
+};
+
+// The scan step, from `entry` while the state lies in front of `stop` (at most e).  A symbol that needs bits beyond
+// e ends the scan (END).  Every other failure moves one bit on, to a DC symbol of the same block: the recovery rule,
+// without which a lane that was guessed wrong would never meet the right chain.  tabs: [component][DC, AC].
+VA_JPEG_FN ScanLane scan_lane(const uint8_t *p, int64_t e, ScanState entry, int64_t stop, const HuffDecode *tabs,
+                              int blocks, int luma)
+{
+    ScanLane out{entry, 0, {0, 0, 0}};
+    if (entry.q < 0)
+        return out;
+    SpanReader s = open_span(p, e, entry.q, state_bit(entry));
+    int k = state_k(entry) % blocks, z = state_z(entry);
+    while (s.q < stop) {
+        const int comp = mcu_component(k, blocks, luma);
+        const Symbol sym = read_symbol(s, tabs[2 * comp], tabs[2 * comp + 1], z);
+        out.begun += z == 0;
+        if (sym.status == kStatusTruncated) {
+            out.exit = scan_end();
+            return out;
+        }
+        if (sym.status) {
+            skip_bits(s.r, 1);
+            span_moved(s, 1);
+            z = 0;
+            continue;
+        }
+        if (z == 0)
+            out.dc[comp] += (uint32_t)sym.value;
+        z = sym.next;
+        if (z == 64) {
+            z = 0;
+            k = k + 1 == blocks ? 0 : k + 1;
+        }
+    }
+    out.exit = scan_state(s.q, s.bit, k, z);
+    return out;
+}
+
+// The write pass of one lane: the real decode from the lane's entry state while the state lies in front of `stop`
+// (the last lane: no stop, it goes on while blocks remain, so that a stream which ends early is reported where the
+// serial decoder reports it) and blocks remain.  `block` comes in as the number of blocks begun in front of the
+// entry, pred as the sums of the DC differences in front of it; store(block in decode order, natural index,
+// value).  Returns 0, or the status bit of the first error with its block in `block`; the checks are decode_block's
+// in its order.
+template <class Store>
+VA_JPEG_FN int32_t write_lane(const uint8_t *p, int64_t e, ScanState entry, int64_t stop, bool last,
+                              const HuffDecode *tabs, int blocks, int luma, int64_t total, int64_t &block,
+                              uint32_t *pred, Store store)
+{
+    if (entry.q < 0)
+        return 0;
+    SpanReader s = open_span(p, e, entry.q, state_bit(entry));
+    int z = state_z(entry);
+    int64_t cur = z ? block - 1 : block;
+    if (cur < 0)
+        return 0;
+    while (cur < total && (last || s.q < stop)) {
+        const int comp = mcu_component((int)(cur % blocks), blocks, luma);
+        const Symbol sym = read_symbol(s, tabs[2 * comp], tabs[2 * comp + 1], z);
+        if (sym.status) {
+            block = cur;
+            return sym.status;
+        }
+        if (z == 0) {
+            pred[comp] += (uint32_t)sym.value;
+            const int32_t v = (int32_t)pred[comp];
+            if (v < -2048 || v > 2047) {
+                block = cur;
+                return kStatusBadCode;
+            }
+            store(cur, 0, (int)v);
+        } else if (sym.index >= 0) {
+            store(cur, zigzag_at(sym.index), sym.value);
+        }
+        z = sym.next;
+        if (z == 64) {
+            z = 0;
+            cur++;
+        }
+    }
+    return 0;
+}
+
+// an error as one word whose minimum over a frame is the serial decoder's error: the block in decode order above
+// the status bit
+VA_JPEG_FN uint64_t error_word(int64_t block, int32_t status) { return (uint64_t)block << 4 | (uint64_t)status; }
+constexpr uint64_t kNoError = ~(uint64_t)0;
+
 // ------------------------------------------------------------------------------------------------ reconstruction
 VA_JPEG_FN int dequantise(int coef, int q)
 {

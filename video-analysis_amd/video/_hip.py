@@ -154,6 +154,9 @@ SIGNATURES = {
     "va_jpeg_decode_sampled_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "va_jpeg_decode_sampled_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64,
                                        _vp]),
+    "va_jpeg_decode_split_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i64]),
+    "va_jpeg_decode_split_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _i,
+                                     _i64, _vp, _vp]),
     "va_pipeline_create": (_i, [C.POINTER(va_config), C.POINTER(_vp)]),
     "va_pipeline_destroy": (_i, [_vp]),
     "va_pipeline_run": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

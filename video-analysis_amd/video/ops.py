@@ -2731,7 +2731,15 @@ def jpeg_status_text(status):
     return " | ".join(name for bit, name in _JPEG_STATUS_NAMES if status & bit) or "ok"
 
 
-def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
+# the split decoder ("Split Motion-JPEG decoding", with the measurements behind these three)
+JPEG_SPLIT_SUB_BYTES = 256                     # raw bytes of a lane: 128 .. 512 measure within 10 % of each other
+JPEG_SPLIT_MAX_ROUNDS = 16                     # rounds of the scan: an unused round costs 5 us, a frame that needs more
+                                               # takes the one-lane path, 40 times the time
+JPEG_SPLIT_MIN_BYTES = 2048                    # split=None: the mean entropy bytes a frame from which a group is split
+                                               # (32 frames: one lane wins at 1.1 KB a frame, the split at 3.2 KB)
+
+
+def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False, split=None, ret_rounds=False):
     """the frames of a batch of stored baseline JPEG files ("Motion-JPEG decoding" and "Subsampled
     Motion-JPEG decoding"); the pixels are pinned and equal the restatement's.  Decoded are monochrome files, 4:4:4
     files, and 4:2:2 and 4:2:0 files (luma 2 x 1 or 2 x 2, Cb and Cr 1 x 1: what cameras, libjpeg and Pillow write by
@@ -2744,8 +2752,19 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
     Returns the uint8 array (n, h, w) or (n, h, w, 3) RGB; keep=True: a DeviceFrames that is the caller's (nothing but
     the status words is downloaded).  A frame whose status word is not 0 raises a ValueError that names the first
     such frame and its bits; ret_status=True returns (frames, int32 status (n,)) in place of raising: blocks at and
-    behind an error in their segment decode as sample 128."""
+    behind an error in their segment decode as sample 128.
+    split: how a group of frames without restart markers (one entropy segment a frame, one lane a frame on the path
+    above) is decoded.  True, or the bytes of a subsequence (a multiple of 16 in 16 .. 65536): by
+    va_jpeg_decode_split_u8, one lane per subsequence (DESIGN.md §9, "Split Motion-JPEG decoding"); False: as above;
+    None: split where the group's mean entropy bytes a frame reach JPEG_SPLIT_MIN_BYTES.  Groups with restart markers
+    always take the path above; pixels and status words are the same on both.  ret_rounds=True appends the int32
+    array (n,) of the rounds the split decoder's scan took: 0 for a frame of the path above, -1 for one that did not
+    converge in JPEG_SPLIT_MAX_ROUNDS and was decoded by one lane."""
     what = "jpeg_decode"
+    if not (split is None or isinstance(split, (bool, np.bool_))):
+        if int(split) != split or not 16 <= split <= 65536 or split % 16:
+            raise ValueError("%s: split is None, a bool or a multiple of 16 in 16 .. 65536, got %r" % (what, split))
+    sub_bytes = JPEG_SPLIT_SUB_BYTES if split is None or isinstance(split, (bool, np.bool_)) else int(split)
     if (isinstance(streams, tuple) and len(streams) == 2 and isinstance(streams[0], np.ndarray)
             and streams[0].dtype == np.uint8):
         blob = np.ascontiguousarray(streams[0]).ravel()
@@ -2772,7 +2791,8 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
         frames = np.zeros((0, 0, 0), np.uint8)
         if keep:
             frames = DeviceFrames(_take(1), 0, 0, 0, 1)
-        return (frames, np.zeros(0, np.int32)) if ret_status else frames
+        extra = ((np.zeros(0, np.int32),) if ret_status else ()) + ((np.zeros(0, np.int32),) if ret_rounds else ())
+        return (frames,) + extra if extra else frames
     h, w, c = heads[0]["h"], heads[0]["w"], heads[0]["c"]
     for k, head in enumerate(heads):
         if (head["h"], head["w"], head["c"]) != (h, w, c):
@@ -2786,6 +2806,7 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
     try:
         with _Lease.on(stream) as d:
             status_buf = d.take(4 * n)
+            rounds_buf, split_groups = d.take(4 * n), []
             for first, stop in jpeg_decode_groups(heads):
                 k, head = stop - first, heads[first]
                 base = int(offsets[first])
@@ -2795,8 +2816,23 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
                 mb = d.upload(meta)
                 tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
                 cb = d.upload(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8))
-                # the plain entry for monochrome and 1 x 1 files, the _sampled one with (luma_h, luma_v) for the rest
                 luma = tuple(head["sampling"])
+                scan_bytes = (np.diff(offsets[first:stop + 1])
+                              - np.array([hd["scan_begin"] for hd in heads[first:stop]], np.int64)).clip(0)
+                if head["nseg"] == 1 and split is not False and (
+                        split is not None or scan_bytes.mean() >= JPEG_SPLIT_MIN_BYTES):
+                    # one segment a frame: one lane per sub_bytes of it
+                    size, most = L.va_jpeg_decode_split_workspace_bytes, int(scan_bytes.max())
+                    one, need = (int(size(frames, h, w, c, luma[0], luma[1], sub_bytes, most)) for frames in (1, k))
+                    room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
+                    ws = d.take(room)
+                    check(L.va_jpeg_decode_split_u8(
+                        src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, luma[0], luma[1], cb.ptr, cb.ptr + 64 * c,
+                        len(tables), out.ptr + first * frame_bytes, status_buf.ptr + 4 * first, ws.ptr, room, sub_bytes,
+                        JPEG_SPLIT_MAX_ROUNDS, most, rounds_buf.ptr + 4 * first, stream))
+                    split_groups.append((first, stop))
+                    continue
+                # the plain entry for monochrome and 1 x 1 files, the _sampled one with (luma_h, luma_v) for the rest
                 if luma == (1, 1):
                     decode, size, luma = L.va_jpeg_decode_u8, L.va_jpeg_decode_workspace_bytes, ()
                 else:
@@ -2808,6 +2844,11 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
                              cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes, status_buf.ptr + 4 * first,
                              ws.ptr, room, stream))
             status = status_buf.download((n,), np.int32, stream)
+            rounds = np.zeros(n, np.int32)
+            if ret_rounds and split_groups:
+                got = rounds_buf.download((n,), np.int32, stream)
+                for first, stop in split_groups:
+                    rounds[first:stop] = got[first:stop]
             if status.any() and not ret_status:
                 bad = int(np.flatnonzero(status)[0])
                 raise ValueError("%s: frame %d does not decode: %s (status %d); %d of %d frames have errors"
@@ -2820,4 +2861,5 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False):
         raise
     if not keep:
         _give(out)
-    return (frames, status) if ret_status else frames
+    extra = ((status,) if ret_status else ()) + ((rounds,) if ret_rounds else ())
+    return (frames,) + extra if extra else frames
