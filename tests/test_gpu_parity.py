@@ -964,7 +964,7 @@ def test_rccl_gather_counts_single_rank():
 
 def test_two_streams_do_not_share_scratch(oracle):
     """the stand-alone entry points lease their device scratch per call on the call's own stream
-    (va_api.hip ScratchLease): interleaved calls of different sizes on two streams -- the
+    (va_scratch.hip ScratchLease): interleaved calls of different sizes on two streams -- the
     reference's VideoPreprocessor worker threads, video/io/parallel.py:398-400 -- must not see
     each other's intermediates (the generic Gaussian keeps its u16 row pass there; the bit-packed
     morphology both of its masks)"""

@@ -1,8 +1,11 @@
-// va_api.hip -- the extern "C" surface of libvideoanalysis_hip.so (include/videoanalysis_hip.h)
+// va_api.hip -- the runtime plumbing of libvideoanalysis_hip.so and the entry points that sequence launchers of
+// more than one file (include/videoanalysis_hip.h)
 //
-// Host-side plumbing only: argument checks, workspace layouts, kernel sequencing for the
-// fused pipeline, lazy RCCL binding.  No exception crosses the ABI; every failure sets the
-// thread-local message returned by va_last_error().
+// Host code only: the error message, the device and the entry prologue; memory, streams and events; the tap
+// tables; the entries of the Gaussian, background, pointwise, morphology, stencil and labelling launchers that
+// the pipeline shares; the contour and geodesic entries, whose workspaces hold labelling rows; the fused
+// pipeline; the lazy RCCL binding.  A stand-alone op's entry points are in the file of its kernels.  No exception
+// crosses the ABI; every failure sets the thread-local message returned by va_last_error().
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -38,12 +41,6 @@ int enter_device()
     }
     return VA_OK;
 }
-#define VA_ENTER()                   \
-    do {                             \
-        int _rc = va::enter_device(); \
-        if (_rc)                     \
-            return _rc;              \
-    } while (0)
 
 }  // namespace va
 
@@ -86,32 +83,6 @@ struct va_pipeline {
     char desc[160];
     StageProfiler *prof;
 };
-
-// cv2.resize entry points (uint8 / float32 share everything but the kernels)
-template <class T>
-static int resize_any(const T *src, T *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
-                      int interpolation, void *stream, const char *who)
-{
-    VA_ENTER();
-    VA_REQUIRE(src && dst && src != dst, "%s: src/dst must be distinct non-NULL", who);
-    VA_REQUIRE(n >= 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && c >= 1 && c <= 4,
-               "%s: bad shape (%d,%d,%d,%d) -> (%d,%d)", who, n, src_h, src_w, c, dst_h, dst_w);
-    VA_REQUIRE((size_t)src_h * src_w < kMaxFramePixels && (size_t)dst_h * dst_w < kMaxFramePixels,
-               "%s: frames above 2^29 pixels are not supported", who);
-    VA_REQUIRE(interpolation >= VA_INTER_NEAREST && interpolation <= VA_INTER_LANCZOS4,
-               "%s: interpolation %d not supported (0 nearest, 1 linear, 2 cubic, 3 area, 4 lanczos4)", who,
-               interpolation);
-    ScratchLease scratch;
-    int rc = scratch.acquire(resize_scratch_bytes(src_h, src_w, dst_h, dst_w), as_stream(stream));
-    if (rc)
-        return rc;
-    if constexpr (sizeof(T) == 1)
-        return launch_resize_u8(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, scratch.ptr,
-                                as_stream(stream));
-    else
-        return launch_resize_f32(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, scratch.ptr,
-                                 as_stream(stream));
-}
 
 extern "C" {
 
@@ -726,101 +697,6 @@ int va_mask_thinning_u8(uint8_t *img, uint8_t *scratch, uint8_t *skel, int h, in
     return VA_OK;
 }
 
-int va_guo_hall_thinning_batch(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
-                               int m, int max_words, uint8_t *out, int32_t *iterations_out, int32_t *status,
-                               void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m >= 0 && total >= 0, "va_guo_hall_thinning_batch: negative count (m %d, total %lld)", m,
-               (long long)total);
-    VA_REQUIRE(max_words >= 0 && max_words <= kThinResidentMaxWords,
-               "va_guo_hall_thinning_batch: max_words %d outside 0 .. %d", max_words, kThinResidentMaxWords);
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(masks && shapes && offsets && out && iterations_out && status,
-               "va_guo_hall_thinning_batch: NULL argument");
-    return launch_guo_hall_resident(masks, shapes, offsets, total, m, max_words, out, iterations_out, status,
-                                    as_stream(stream));
-}
-
-size_t va_guo_hall_thinning_scratch_bytes(int n, int h, int w)
-{
-    if (n <= 0 || h <= 0 || w <= 0 || n > 65535 || h > VA_THIN_MAX_ROWS || (size_t)h * (size_t)w >= kMaxFramePixels ||
-        (size_t)n * h * words_per_row(w) >= ((size_t)1 << 31))
-        return 0;
-    return guo_hall_tiled_scratch_bytes(n, h, w);
-}
-
-int va_guo_hall_thinning_u8(const uint8_t *src, void *scratch, size_t scratch_bytes, uint8_t *dst, int n, int h,
-                            int w, int sub_iterations, int poll_period, int32_t *iterations_out,
-                            int32_t *stats_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_guo_hall_thinning_u8: bad shape (%d, %d, %d)", n, h, w);
-    VA_REQUIRE(n <= kMaxGridYZ, "va_guo_hall_thinning_u8: %d frames, at most 65535 frames in one call are supported",
-               n);
-    VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels,
-               "va_guo_hall_thinning_u8: frames above 2^29 pixels are not supported");
-    // grid.y = ceil(h / (64 - 2 K)) <= 65535 for every K, and the pack / unpack grids count words in 32 bits
-    VA_REQUIRE(h <= VA_THIN_MAX_ROWS, "va_guo_hall_thinning_u8: %d rows, at most %d are supported", h,
-               VA_THIN_MAX_ROWS);
-    VA_REQUIRE((size_t)n * h * words_per_row(w) < ((size_t)1 << 31),
-               "va_guo_hall_thinning_u8: a stack of 2^31 or more packed words is not supported");
-    const int K = sub_iterations ? sub_iterations : 16, poll = poll_period ? poll_period : 2;
-    VA_REQUIRE(K >= 2 && K <= kThinMaxK && K % 2 == 0,
-               "va_guo_hall_thinning_u8: sub_iterations %d is not an even number in 2 .. %d", K, kThinMaxK);
-    VA_REQUIRE(poll >= 1 && poll <= kThinMaxPoll, "va_guo_hall_thinning_u8: poll_period %d outside 1 .. %d", poll,
-               kThinMaxPoll);
-    if (stats_out)
-        stats_out[0] = stats_out[1] = 0;
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(src && scratch && dst, "va_guo_hall_thinning_u8: NULL argument");
-    VA_REQUIRE(scratch_bytes >= guo_hall_tiled_scratch_bytes(n, h, w),
-               "va_guo_hall_thinning_u8: scratch of %zu bytes, %zu needed", scratch_bytes,
-               guo_hall_tiled_scratch_bytes(n, h, w));
-    return run_guo_hall_tiled(src, dst, scratch, n, h, w, K, poll, iterations_out, stats_out, as_stream(stream));
-}
-
-// the arguments the two warp calls share; m == 0 is checked by the caller after this
-static int warp_check(const char *name, int n, int h, int w, int m, int total_items, int64_t total_out)
-{
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: bad shape (%d, %d, %d)", name, n, h, w);
-    VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels, "%s: frames above 2^29 pixels are not supported", name);
-    VA_REQUIRE(m >= 0 && total_out >= 0, "%s: negative count (m %d, total_out %lld)", name, m, (long long)total_out);
-    VA_REQUIRE(total_items >= m, "%s: %d work items for %d items (every item has at least one)", name, total_items,
-               m);
-    return VA_OK;
-}
-
-int va_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx, const double *mats,
-                    const int32_t *shapes, const int64_t *out_off, const int32_t *prefix, int total_chunks,
-                    int64_t total_out, int32_t *sums, int32_t *status, void *stream)
-{
-    VA_ENTER();
-    int rc = warp_check("va_line_scan_u8", n, h, w, m, total_chunks, total_out);
-    if (rc || m == 0)
-        return rc;
-    VA_REQUIRE(frames && frame_idx && mats && shapes && out_off && prefix && sums && status,
-               "va_line_scan_u8: NULL argument");
-    return launch_line_scan_u8(frames, n, h, w, m, frame_idx, mats, shapes, out_off, prefix, total_chunks, total_out,
-                               sums, status, as_stream(stream));
-}
-
-int va_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx, const double *mats,
-                      const int32_t *shapes, const int32_t *flags, const int64_t *out_off, const int32_t *prefix,
-                      int total_tiles, int64_t total_out, uint8_t *out, int32_t *status, void *stream)
-{
-    VA_ENTER();
-    int rc = warp_check("va_warp_affine_u8", n, h, w, m, total_tiles, total_out);
-    if (rc || m == 0)
-        return rc;
-    VA_REQUIRE(frames && frame_idx && mats && shapes && flags && out_off && prefix && out && status,
-               "va_warp_affine_u8: NULL argument");
-    return launch_warp_affine_u8(frames, n, h, w, m, frame_idx, mats, shapes, flags, out_off, prefix, total_tiles,
-                                 total_out, out, status, as_stream(stream));
-}
-
 int va_image_statistics_u8(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
                            int w, int kernel, int ksize, double prior, int exclude_center,
                            void *stream)
@@ -976,353 +852,6 @@ int va_find_contours(const uint8_t *mask, int n, int h, int w, int32_t *ncontour
                                 cap_points, st);
 }
 
-// ------------------------------------------------------------------------------ skeleton graphs
-size_t va_skeleton_graph_workspace_bytes(int64_t total, int m)
-{
-    if (total < 0 || m < 0)
-        return 256;
-    return skeleton_layout(total, m).total;
-}
-
-int va_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
-                      int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
-                      va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
-                      int64_t cap_points, void *workspace, size_t workspace_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m >= 0 && total >= 0, "va_skeleton_graph: negative count (m %d, total %lld)", m, (long long)total);
-    VA_REQUIRE(total < ((int64_t)1 << 31) - 2, "va_skeleton_graph: 2^31 - 2 or more packed elements are not supported");
-    VA_REQUIRE(masks && shapes && offsets && counts && totals && nodes && edges && point_off && points && workspace,
-               "va_skeleton_graph: NULL argument");
-    VA_REQUIRE(cap_nodes >= 0 && cap_edges >= 0 && cap_points >= 0,
-               "va_skeleton_graph: negative capacity (%lld nodes, %lld edges, %lld points)", (long long)cap_nodes,
-               (long long)cap_edges, (long long)cap_points);
-    VA_REQUIRE(aligned(points, 8) && aligned(nodes, 4) && aligned(edges, 8) && aligned(point_off, 8) &&
-                   aligned(totals, 8) && aligned(counts, 4) && aligned(workspace, 8),
-               "va_skeleton_graph: points, edge records, offsets, totals and workspace must be 8-byte aligned");
-    VA_REQUIRE(workspace_bytes >= va_skeleton_graph_workspace_bytes(total, m),
-               "va_skeleton_graph: workspace of %zu bytes < required %zu", workspace_bytes,
-               va_skeleton_graph_workspace_bytes(total, m));
-    return launch_skeleton_graph(masks, shapes, offsets, total, m, counts, totals, nodes, cap_nodes, edges, point_off,
-                                 cap_edges, points, cap_points, workspace, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ outline queries
-// the arguments the two outline calls share; `lanes` comes back as 8 or 64.  q == 0 and m == 0 are the caller's
-static int outline_check(const char *name, int64_t npoints, int m, int64_t q, int &lanes)
-{
-    VA_REQUIRE(npoints >= 0 && m >= 0 && q >= 0, "%s: negative count (npoints %lld, m %d, q %lld)", name,
-               (long long)npoints, m, (long long)q);
-    VA_REQUIRE(lanes == 0 || lanes == 8 || lanes == 64, "%s: lanes is 0 (the library's choice), 8 or 64, got %d", name,
-               lanes);
-    if (lanes == 0)
-        lanes = m > 0 && npoints / m >= VA_OUTLINE_WIDE_MIN_POINTS ? 64 : 8;
-    VA_REQUIRE(q <= (int64_t)0x7FFFFFFF * (256 / lanes), "%s: %lld queries are more than one launch of %d lanes takes",
-               name, (long long)q, lanes);
-    return VA_OK;
-}
-
-int va_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
-                const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes, double *t_out,
-                double *hits_out, int32_t *edge_out, int32_t *count_out, void *stream)
-{
-    VA_ENTER();
-    int rc = outline_check("va_ray_hits", npoints, m, q, lanes);
-    if (rc || q == 0 || m == 0)
-        return rc;
-    VA_REQUIRE(points && point_off && closed && anchors && fars && index && t_out && hits_out && edge_out && count_out,
-               "va_ray_hits: NULL argument");
-    return launch_ray_hits(points, point_off, closed, npoints, m, anchors, fars, index, q, lanes, t_out, hits_out,
-                           edge_out, count_out, as_stream(stream));
-}
-
-int va_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *query,
-                          const int32_t *index, int64_t q, int lanes, uint8_t *inside_out, void *stream)
-{
-    VA_ENTER();
-    int rc = outline_check("va_points_in_outlines", npoints, m, q, lanes);
-    if (rc || q == 0 || m == 0)
-        return rc;
-    VA_REQUIRE(points && point_off && query && index && inside_out, "va_points_in_outlines: NULL argument");
-    return launch_points_in_outlines(points, point_off, npoints, m, query, index, q, lanes, inside_out,
-                                     as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ equidistant curves
-int va_curves_equidistant(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *spacing,
-                          const int32_t *count, const double *translate, int32_t *out_count, int64_t *out_off,
-                          double *in_length, int32_t *status, int64_t *totals, double *out_points, int64_t cap_points,
-                          double *out_length, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(npoints >= 0 && m >= 0 && cap_points >= 0,
-               "va_curves_equidistant: negative count (npoints %lld, m %d, cap_points %lld)", (long long)npoints, m,
-               (long long)cap_points);
-    if (m == 0)
-        return VA_OK;
-    // (count may be NULL: a curve in count mode then reads none and is refused by the kernel's own test below)
-    VA_REQUIRE(points && point_off && spacing && out_count && out_off && in_length && status && totals && out_points &&
-                   out_length,
-               "va_curves_equidistant: NULL argument");
-    VA_REQUIRE(aligned(points, 8) && aligned(point_off, 8) && aligned(spacing, 8) && aligned(count, 4) &&
-                   aligned(translate, 8) && aligned(out_count, 4) && aligned(out_off, 8) && aligned(in_length, 8) &&
-                   aligned(status, 4) && aligned(totals, 8) && aligned(out_points, 8) && aligned(out_length, 8),
-               "va_curves_equidistant: float64 and int64 buffers must be 8-byte aligned, int32 buffers 4-byte aligned");
-    return launch_curves_equidistant(points, point_off, npoints, m, spacing, count, translate, out_count, out_off,
-                                     in_length, status, totals, out_points, cap_points, out_length, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ simplification
-// the arguments the two simplifiers share; m == 0 is the caller's
-static int simplify_check(const char *name, const double *points, const int64_t *point_off, int64_t npoints, int m,
-                          const double *tol, const uint8_t *keep, const int32_t *out_count, const int32_t *status)
-{
-    VA_REQUIRE(npoints >= 0 && m >= 0, "%s: negative count (npoints %lld, m %d)", name, (long long)npoints, m);
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(points && point_off && tol && keep && out_count && status, "%s: NULL argument", name);
-    VA_REQUIRE(aligned(points, 8) && aligned(point_off, 8) && aligned(tol, 8) && aligned(out_count, 4) &&
-                   aligned(status, 4),
-               "%s: float64 and int64 buffers must be 8-byte aligned, int32 buffers 4-byte aligned", name);
-    return VA_OK;
-}
-
-int va_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
-                    uint8_t *keep, int32_t *out_count, int32_t *status, void *stream)
-{
-    VA_ENTER();
-    const int rc = simplify_check("va_simplify_rdp", points, point_off, npoints, m, eps, keep, out_count, status);
-    if (rc || m == 0)
-        return rc;
-    return launch_simplify_rdp(points, point_off, npoints, m, eps, keep, out_count, status, as_stream(stream));
-}
-
-size_t va_simplify_visvalingam_workspace_bytes(int64_t npoints)
-{
-    return npoints < 0 ? 256 : simplify_layout(npoints).total;
-}
-
-int va_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *thr,
-                            int closed, uint8_t *keep, int32_t *out_count, int32_t *status, void *workspace,
-                            size_t workspace_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(closed == 0 || closed == 1, "va_simplify_visvalingam: closed is 0 (lines) or 1 (rings), got %d", closed);
-    const int rc = simplify_check("va_simplify_visvalingam", points, point_off, npoints, m, thr, keep, out_count,
-                                  status);
-    if (rc || m == 0)
-        return rc;
-    VA_REQUIRE(workspace, "va_simplify_visvalingam: NULL argument");
-    VA_REQUIRE(aligned(workspace, 8), "va_simplify_visvalingam: the workspace must be 8-byte aligned");
-    VA_REQUIRE(workspace_bytes >= va_simplify_visvalingam_workspace_bytes(npoints),
-               "va_simplify_visvalingam: workspace of %zu bytes < required %zu", workspace_bytes,
-               va_simplify_visvalingam_workspace_bytes(npoints));
-    return launch_simplify_visvalingam(points, point_off, npoints, m, thr, closed, keep, out_count, status, workspace,
-                                       as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ composer
-int va_compose_layers_u8(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
-                         const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,
-                         const uint8_t *images, int64_t images_bytes, const uint8_t *masks, int64_t masks_bytes,
-                         void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h >= 0 && w >= 0 && nlayers >= 0 && images_bytes >= 0 && masks_bytes >= 0,
-               "va_compose_layers_u8: negative count (n %d, h %d, w %d, nlayers %lld, images %lld, masks %lld)", n, h,
-               w, (long long)nlayers, (long long)images_bytes, (long long)masks_bytes);
-    VA_REQUIRE((c_src == 1 || c_src == 3) && (c == 1 || c == 3) && c_src <= c,
-               "va_compose_layers_u8: channels must be 1 or 3 with c_src <= c, got %d -> %d", c_src, c);
-    VA_REQUIRE((size_t)h * w < kMaxFramePixels, "va_compose_layers_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src != dst || c_src == c || !src,
-               "va_compose_layers_u8: src and dst must be distinct when c_src != c");
-    if (n == 0 || h == 0 || w == 0 || (nlayers == 0 && src == dst && src))
-        return VA_OK;
-    VA_REQUIRE(src && dst && layer_off && (layers || nlayers == 0) && (images || images_bytes == 0) &&
-                   (masks || masks_bytes == 0),
-               "va_compose_layers_u8: NULL argument");
-    VA_REQUIRE(aligned(layers, 8) && aligned(layer_off, 8),
-               "va_compose_layers_u8: the layer tables must be 8-byte aligned");
-    VA_REQUIRE(((int64_t)n * h * ((w + 15) / 16) + 255) / 256 < ((int64_t)1 << 31),
-               "va_compose_layers_u8: the stack is too large for one launch");
-    return launch_compose_layers(src, c_src, dst, n, h, w, c, layers, layer_off, nlayers, images, images_bytes, masks,
-                                 masks_bytes, as_stream(stream));
-}
-
-int va_draw_u8(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
-               int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h >= 0 && w >= 0 && ncmds >= 0 && npoints >= 0,
-               "va_draw_u8: negative count (n %d, h %d, w %d, ncmds %lld, npoints %lld)", n, h, w, (long long)ncmds,
-               (long long)npoints);
-    VA_REQUIRE(c == 1 || c == 3, "va_draw_u8: channels must be 1 or 3, got %d", c);
-    VA_REQUIRE((size_t)h * w < kMaxFramePixels, "va_draw_u8: frames above 2^29 pixels are not supported");
-    if (n == 0 || ncmds == 0)
-        return VA_OK;
-    VA_REQUIRE((frames || h == 0 || w == 0) && cmds && cmd_off && status && (points || npoints == 0),
-               "va_draw_u8: NULL argument");
-    VA_REQUIRE(aligned(cmds, 8) && aligned(cmd_off, 8) && aligned(points, 4) && aligned(status, 4),
-               "va_draw_u8: the command tables must be 8-byte aligned, points and status 4-byte aligned");
-    return launch_draw(frames, n, h, w, c, cmds, cmd_off, ncmds, points, npoints, status, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ Motion-JPEG
-int va_jpeg_encode_u8(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
-                      int header_bytes, int64_t *sizes_out, int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out,
-                      int64_t cap_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
-               "va_jpeg_encode_u8: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", n, h, w,
-               header_bytes, (long long)cap_bytes);
-    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_encode_u8: channels must be 1 or 3, got %d", c);
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
-               "va_jpeg_encode_u8: NULL argument");
-    VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
-               "va_jpeg_encode_u8: the int64 buffers must be 8-byte aligned");
-    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_encode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
-    VA_REQUIRE((int64_t)n * ((h + 7) / 8) < ((int64_t)1 << 31),
-               "va_jpeg_encode_u8: the stack has too many MCU rows for one launch");
-    ScratchLease scratch;
-    int rc = scratch.acquire(jpeg_workspace_bytes(n, h), as_stream(stream));
-    if (rc)
-        return rc;
-    return launch_jpeg_encode(frames, n, h, w, c, qtables, header, header_bytes, sizes_out, offsets_out, totals,
-                              bytes_out, cap_bytes, scratch.ptr, as_stream(stream));
-}
-
-size_t va_jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri)
-{
-    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0)
-        return 0;
-    return jpeg_decode_workspace_bytes(n, h, w, c, ri, 1, 1);
-}
-
-namespace {
-bool jpeg_sampling_taken(int c, int lh, int lv)
-{
-    return (lh == 1 && lv == 1) || (c == 3 && lh == 2 && (lv == 1 || lv == 2));
-}
-
-// both decode entries: `what` names the one that was called
-int jpeg_decode_entry(const char *what, const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n,
-                      int h, int w, int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff,
-                      int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
-                      void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ri > 0 && workspace_bytes >= 0,
-               "%s: negative or zero size (n %d, h %d, w %d, ri %d, workspace %lld)", what, n, h, w, ri,
-               (long long)workspace_bytes);
-    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
-    VA_REQUIRE(jpeg_sampling_taken(c, lh, lv),
-               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
-               what, lh, lv, c);
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
-               "%s: NULL argument", what);
-    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
-                   && aligned(workspace, 16),
-               "%s: offsets and scan_begin must be 8-byte aligned, the tables and the status 4-byte, "
-               "the workspace 16-byte", what);
-    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
-    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
-               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
-               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
-    if (jpeg_decode_chunk(n, h, w, c, ri, lh, lv, (size_t)workspace_bytes) < 1) {
-        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what,
-                  (long long)workspace_bytes, (long long)jpeg_decode_workspace_bytes(1, h, w, c, ri, lh, lv));
-        return VA_ERR_RANGE;
-    }
-    return launch_jpeg_decode(bytes, offsets, scan_begin, n, h, w, c, ri, lh, lv, qtables, huff, frames_out,
-                              status_out, workspace, (size_t)workspace_bytes, as_stream(stream));
-}
-}  // namespace
-
-int va_jpeg_decode_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w, int c,
-                      int ri, const uint8_t *qtables, const void *huff, int huff_bytes, uint8_t *frames_out,
-                      int32_t *status_out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return jpeg_decode_entry("va_jpeg_decode_u8", bytes, offsets, scan_begin, n, h, w, c, ri, 1, 1, qtables, huff,
-                             huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
-}
-
-size_t va_jpeg_decode_sampled_workspace_bytes(int n, int h, int w, int c, int ri, int luma_h, int luma_v)
-{
-    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0
-        || !jpeg_sampling_taken(c, luma_h, luma_v))
-        return 0;
-    return jpeg_decode_workspace_bytes(n, h, w, c, ri, luma_h, luma_v);
-}
-
-int va_jpeg_decode_sampled_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h,
-                              int w, int c, int ri, int luma_h, int luma_v, const uint8_t *qtables, const void *huff,
-                              int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace,
-                              int64_t workspace_bytes, void *stream)
-{
-    return jpeg_decode_entry("va_jpeg_decode_sampled_u8", bytes, offsets, scan_begin, n, h, w, c, ri, luma_h, luma_v,
-                             qtables, huff, huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
-}
-
-namespace {
-constexpr int64_t kJpegSplitMaxScanBytes = (int64_t)1 << 40;
-bool jpeg_split_sub_taken(int sub) { return sub >= 16 && sub <= 65536 && sub % 16 == 0; }
-}  // namespace
-
-size_t va_jpeg_decode_split_workspace_bytes(int n, int h, int w, int c, int luma_h, int luma_v, int sub_bytes,
-                                            int64_t max_scan_bytes)
-{
-    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3)
-        || !jpeg_sampling_taken(c, luma_h, luma_v) || !jpeg_split_sub_taken(sub_bytes) || max_scan_bytes < 0
-        || max_scan_bytes > kJpegSplitMaxScanBytes)
-        return 0;
-    return jpeg_split_workspace_bytes(n, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes);
-}
-
-int va_jpeg_decode_split_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                            int c, int luma_h, int luma_v, const uint8_t *qtables, const void *huff, int huff_bytes,
-                            uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
-                            int sub_bytes, int max_rounds, int64_t max_scan_bytes, int32_t *rounds_out, void *stream)
-{
-    const char *what = "va_jpeg_decode_split_u8";
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && workspace_bytes >= 0,
-               "%s: negative or zero size (n %d, h %d, w %d, workspace %lld)", what, n, h, w, (long long)workspace_bytes);
-    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
-    VA_REQUIRE(jpeg_sampling_taken(c, luma_h, luma_v),
-               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
-               what, luma_h, luma_v, c);
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
-               "%s: NULL argument", what);
-    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
-                   && aligned(workspace, 16) && aligned(rounds_out, 4),
-               "%s: offsets and scan_begin must be 8-byte aligned, the tables, the status and the rounds 4-byte, "
-               "the workspace 16-byte", what);
-    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
-    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
-               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
-               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
-    VA_REQUIRE(jpeg_split_sub_taken(sub_bytes), "%s: sub_bytes must be a multiple of 16 in 16 .. 65536, got %d", what,
-               sub_bytes);
-    VA_REQUIRE(max_rounds >= 0, "%s: max_rounds must not be negative, got %d", what, max_rounds);
-    VA_REQUIRE(max_scan_bytes >= 0 && max_scan_bytes <= kJpegSplitMaxScanBytes,
-               "%s: max_scan_bytes must lie in 0 .. 2^40, got %lld", what, (long long)max_scan_bytes);
-    if (jpeg_split_chunk(n, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes, (size_t)workspace_bytes) < 1) {
-        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what, (long long)workspace_bytes,
-                  (long long)jpeg_split_workspace_bytes(1, h, w, c, luma_h, luma_v, sub_bytes, max_scan_bytes));
-        return VA_ERR_RANGE;
-    }
-    return launch_jpeg_decode_split(bytes, offsets, scan_begin, n, h, w, c, luma_h, luma_v, sub_bytes, max_rounds,
-                                    max_scan_bytes, qtables, huff, frames_out, status_out, rounds_out, workspace,
-                                    (size_t)workspace_bytes, as_stream(stream));
-}
-
 // ------------------------------------------------------------------------------ geodesic
 // [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
 // start is chosen the pairs hold the 8-connected forest and the background labels, the visited
@@ -1431,193 +960,6 @@ int va_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *
     }
     return launch_farthest_points(mask, n, h, w, p1, p1_out, p2_out, dist_out, rounds_out, path_out, max_points,
                                   npath_out, pairs, visited, default_start, st);
-}
-
-int va_farneback_poly_consts(int poly_n, double poly_sigma, float *g, float *xg, float *xxg, double *ig)
-{
-    VA_REQUIRE(g && xg && xxg && ig, "va_farneback_poly_consts: NULL argument");
-    return farneback_poly_consts(poly_n, poly_sigma, g, xg, xxg, ig);
-}
-
-size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels, int winsize, int iterations,
-                                    int poly_n)
-{
-    if (farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, 0))
-        return 0;
-    return farneback_workspace_bytes(n, h, w, pyr_scale, levels);
-}
-
-int va_optical_flow_farneback(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
-                              int winsize, int iterations, int poly_n, double poly_sigma, int flags, float *flow_out,
-                              float *mag_out, void *ws, size_t ws_bytes, void *stream)
-{
-    VA_ENTER();
-    int rc = farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, flags);
-    if (rc)
-        return rc;
-    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "optical flow: frames must be VA_U8 or VA_F32 (got dtype %d)", dtype);
-    VA_REQUIRE(frames, "optical flow: NULL frames");
-    VA_REQUIRE(flow_out || mag_out, "optical flow: flow_out and mag_out are both NULL");
-    return launch_optical_flow(frames, dtype, n, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
-                               flow_out, mag_out, ws, ws_bytes, as_stream(stream));
-}
-
-int va_sobel5_f64(const void *src, int dtype, double *fx_out, double *fy_out, int n, int h, int w, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "va_sobel5_f64: frames must be VA_U8 or VA_F32 (got dtype %d)",
-               dtype);
-    VA_REQUIRE(src && (fx_out || fy_out), "va_sobel5_f64: NULL frames, or fx_out and fy_out both NULL");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && (size_t)h * w < kMaxFramePixels, "va_sobel5_f64: bad shape (%d, %d, %d)",
-               n, h, w);
-    if (n == 0)
-        return VA_OK;
-    return launch_sobel5_f64(src, dtype, fx_out, fy_out, n, h, w, as_stream(stream));
-}
-
-int va_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
-                      const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_offset,
-                      int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
-                      double tol_gamma, int max_iterations, double *pts_inout, int32_t *iterations_out,
-                      double *total_variation_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n > 0 && h >= 2 && w >= 2 && (size_t)h * w < kMaxFramePixels,
-               "va_active_contour: bad gradient shape (%d, %d, %d): frames need h, w >= 2", n, h, w);
-    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
-               "va_active_contour: bad contour table (%d contours of up to %d points; at most %d points)", m,
-               max_points, kSnakeMaxN);
-    VA_REQUIRE(max_iterations >= 1, "va_active_contour: max_iterations must be >= 1 (got %d)", max_iterations);
-    VA_REQUIRE(mats_count >= 0, "va_active_contour: negative matrix table size");
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(fx && fy && npts && frame && mats && mat_offset && pts_inout && iterations_out && total_variation_out,
-               "va_active_contour: NULL argument");
-    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour: anchor flags without anchor values");
-    return launch_active_contour(fx, fy, nullptr, nullptr, 0, n, h, w, m, max_points, npts, frame, mats, mat_offset,
-                                 mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts_inout,
-                                 iterations_out, total_variation_out, as_stream(stream));
-}
-
-int va_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
-                                  int64_t total, int m, int max_pixels, double sigma, double *fx_out, double *fy_out,
-                                  int32_t *status, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32,
-               "va_potential_gradients_ragged: items must be VA_U8 or VA_F32 (got dtype %d)", dtype);
-    VA_REQUIRE(sigma >= 0 && sigma == sigma, "va_potential_gradients_ragged: sigma must be >= 0 (got %g)", sigma);
-    VA_REQUIRE(dtype == VA_F32 || sigma == 0,
-               "va_potential_gradients_ragged: VA_U8 items take sigma == 0 only (the 8-bit blur is fixed-point)");
-    VA_REQUIRE(m >= 0 && total >= 0, "va_potential_gradients_ragged: negative count (m %d, total %lld)", m,
-               (long long)total);
-    VA_REQUIRE(max_pixels >= 0 && max_pixels <= kGradResidentMaxPixels,
-               "va_potential_gradients_ragged: max_pixels %d outside 0 .. %d", max_pixels, kGradResidentMaxPixels);
-    TapsF32 taps;
-    taps.ksize = 0;
-    if (sigma > 0) {
-        int rc = gauss_taps_f32(sigma, &taps.ksize, taps.t, kMaxTaps);
-        if (rc)
-            return rc;
-    }
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(shapes && offsets && status && ((src && fx_out && fy_out) || total == 0),
-               "va_potential_gradients_ragged: NULL argument");
-    return launch_potential_gradients_ragged(src, dtype, shapes, offsets, total, m, max_pixels, taps, fx_out, fy_out,
-                                             status, as_stream(stream));
-}
-
-int va_active_contour_ragged(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
-                             int64_t total, int n_items, int m, int max_points, const int32_t *npts,
-                             const int32_t *item, const double *mats, const int64_t *mat_offset, int64_t mats_count,
-                             const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
-                             int max_iterations, double *pts_inout, int32_t *iterations_out,
-                             double *total_variation_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n_items >= 0 && total >= 0, "va_active_contour_ragged: negative count (n_items %d, total %lld)",
-               n_items, (long long)total);
-    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
-               "va_active_contour_ragged: bad contour table (%d contours of up to %d points; at most %d points)", m,
-               max_points, kSnakeMaxN);
-    VA_REQUIRE(max_iterations >= 1, "va_active_contour_ragged: max_iterations must be >= 1 (got %d)", max_iterations);
-    VA_REQUIRE(mats_count >= 0, "va_active_contour_ragged: negative matrix table size");
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(fx && fy && shapes && offsets && npts && item && mats && mat_offset && pts_inout && iterations_out &&
-                   total_variation_out,
-               "va_active_contour_ragged: NULL argument");
-    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour_ragged: anchor flags without anchor values");
-    return launch_active_contour(fx, fy, shapes, offsets, total, n_items, 0, 0, m, max_points, npts, item, mats,
-                                 mat_offset, mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations,
-                                 pts_inout, iterations_out, total_variation_out, as_stream(stream));
-}
-
-int va_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
-                 const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
-                 void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m >= 0 && nverts >= 0 && out_elems >= 0, "va_fill_poly: negative count (m %d, nverts %lld, out %lld)",
-               m, (long long)nverts, (long long)out_elems);
-    VA_REQUIRE(elem_size == 1 || elem_size == 4, "va_fill_poly: elem_size must be 1 (uint8) or 4 (int32), got %d",
-               elem_size);
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(vert_off && boxes && out_off && status && (verts || nverts == 0) && (out || out_elems == 0),
-               "va_fill_poly: NULL argument");
-    return launch_fill_poly(verts, vert_off, nverts, boxes, out_off, out_elems, m, elem_size, out, status,
-                            as_stream(stream));
-}
-
-int va_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
-                               int m, int max_w, float *out, int32_t *status, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m >= 0 && total >= 0, "va_distance_transform_l2_5: negative count (m %d, total %lld)", m,
-               (long long)total);
-    VA_REQUIRE(max_w >= 0 && max_w <= kDtMaxWidth, "va_distance_transform_l2_5: max_w %d outside 0 .. %d", max_w,
-               kDtMaxWidth);
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(shapes && offsets && status && ((masks && out) || total == 0),
-               "va_distance_transform_l2_5: NULL argument");
-    return launch_distance_transform_l2_5(masks, shapes, offsets, total, m, max_w, out, status, as_stream(stream));
-}
-
-int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
-                 int interpolation, void *stream)
-{
-    return resize_any<uint8_t>(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, stream, "va_resize_u8");
-}
-
-int va_resize_f32(const float *src, float *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
-                  int interpolation, void *stream)
-{
-    return resize_any<float>(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, stream, "va_resize_f32");
-}
-
-int va_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
-                       int is_float, double *moments_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(points && moments_out, "va_contour_moments: NULL argument");
-    VA_REQUIRE(n >= 0 && max_points > 0, "va_contour_moments: bad shape (%d contours, %d points)", n,
-               max_points);
-    return launch_contour_moments(points, npoints, n, max_points, is_float, moments_out,
-                                  as_stream(stream));
-}
-
-int va_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float,
-                              double *moments_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m >= 0, "va_contour_moments_ragged: negative count (%lld contours)", (long long)m);
-    if (m == 0)
-        return VA_OK;
-    VA_REQUIRE(points && point_off && moments_out, "va_contour_moments_ragged: NULL argument");
-    return launch_contour_moments_ragged(points, point_off, m, is_float, moments_out, as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------ pipeline

@@ -2139,7 +2139,9 @@ static int frame_rows_per_wave(int h, int w32)
     return span_chunks(w32, 8) <= 2 && frame_layout(h, w32, 8).lds_runs >= kMinLdsRuns ? 8 : 0;
 }
 
-bool ccl_frame_kernel_used(int n, int h, int w)
+// true: launch_ccl labels with one workgroup per frame (forest in LDS); false: chip-wide
+// multi-pass path (large frames, small batches, or the test hook)
+static bool ccl_frame_kernel_used(int n, int h, int w)
 {
     if (g_ccl_path == 1)
         return false;

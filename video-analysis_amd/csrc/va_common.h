@@ -15,6 +15,15 @@ const char *get_error();
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// the prologue of every entry point that allocates or launches: selects va_init's device for the calling thread
+int enter_device();
+#define VA_ENTER()                    \
+    do {                              \
+        int _rc = va::enter_device(); \
+        if (_rc)                      \
+            return _rc;               \
+    } while (0)
+
 #define VA_HIP(call)                                                                        \
     do {                                                                                    \
         hipError_t _e = (call);                                                             \
@@ -136,6 +145,9 @@ int gauss_taps_f32(double sigma, int *ksize, float *taps, int cap);
 void gauss_taps_f64(double sigma, int n, double *out);
 
 // ---- launchers (each enqueues on `stream`, returns VA_OK or an error) -------------------
+// Only what has callers in more than one file is declared here: the launchers the pipeline and the entries of
+// va_api.hip sequence, and what one op's file borrows from another's.  The launchers, workspace layouts and limits
+// of a stand-alone op are private to the file of its kernels, which also holds its extern "C" entry points.
 constexpr int kMaxTaps = 255;  // by-value tap tables in the kernel arguments
 struct TapsQ8 {
     int ksize;
@@ -146,12 +158,6 @@ struct TapsF32 {
     float t[kMaxTaps + 1];
 };
 
-// generic (any radius / channel count) two-pass Gaussian through a u16 / f32 scratch in HBM
-// (16-bit row sums while the tap sum allows)
-int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h,
-                            int w, int c, const TapsQ8 &taps, hipStream_t st);
-int launch_gauss_generic_f32(const float *src, float *dst, float *scratch, int n, int h, int w,
-                             int c, const TapsF32 &taps, hipStream_t st);
 // fast float32 path: LDS-staged row pass + register-window column pass (1 or 3 channels)
 bool gauss_f32_fast_supported(int w, int c, const TapsF32 &taps);
 int launch_gauss_f32_fast(const float *src, float *dst, float *scratch, int n, int h, int w, int c,
@@ -290,9 +296,6 @@ int launch_morph_fused(const uint32_t *src, uint32_t *dst, int n, int h,
 // workspace of the entry points that label a u8 mask: its packed bits, then launch_ccl's workspace
 struct CclLayout { size_t bits, rows, rows_bytes, total; };
 CclLayout ccl_layout(int n, int h, int w);
-// true: launch_ccl labels with one workgroup per frame (forest in LDS); false: chip-wide
-// multi-pass path (large frames, small batches, or the test hook)
-bool ccl_frame_kernel_used(int n, int h, int w);
 void ccl_test_hook(int path, int lds_runs);   // see va_test_hook_labelling
 size_t ccl_rows_workspace_bytes(int n, int h);   // launch_ccl's workspace (the caller owns the bit mask)
 int launch_ccl(const uint32_t *bits, int32_t *labels, int32_t *counts, int n, int h, int w,
@@ -367,143 +370,17 @@ int launch_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int sr
                       double tmin, hipStream_t st);
 int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
                           uint64_t first_index, hipStream_t st);
-// cv2.resize for uint8 / float32 frames (va_resize.hip); mode 0 nearest, 1 linear, 2 cubic, 3 area, 4 lanczos4
+// cv2.resize for float32 frames (va_resize.hip), as the optical flow's pyramid calls it; mode 0 nearest, 1 linear,
+// 2 cubic, 3 area, 4 lanczos4; scratch: resize_scratch_bytes
 size_t resize_scratch_bytes(int sh, int sw, int dh, int dw);
-int launch_resize_u8(const uint8_t *src, uint8_t *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
-                     void *scratch, hipStream_t st);
-// stage (float32): Upload puts the tables into scratch with a blocking copy and enqueues nothing; Launch then
-// enqueues the kernel on them without copying -- a caller that runs several geometries on one stream uploads
-// every table first, into disjoint scratch, so that no copy can overtake a kernel still reading its tables
+// stage: Upload puts the tables into scratch with a blocking copy and enqueues nothing; Launch then enqueues the
+// kernel on them without copying -- a caller that runs several geometries on one stream uploads every table first,
+// into disjoint scratch, so that no copy can overtake a kernel still reading its tables
 enum class ResizeStage { Both, Upload, Launch };
 int launch_resize_f32(const float *src, float *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
                       void *scratch, hipStream_t st, ResizeStage stage = ResizeStage::Both);
-// cv2.calcOpticalFlowFarneback (flags 0) over n frames = n - 1 pairs (va_optflow.hip); g, xg, xxg: 2 poly_n + 1
-// floats (offsets -poly_n..poly_n), ig: ig11, ig03, ig33, ig55.  farneback_check: the argument rules (VA_OK or
-// VA_ERR_INVALID with a message)
-int farneback_poly_consts(int poly_n, double poly_sigma, float *g, float *xg, float *xxg, double ig[4]);
-int farneback_check(int n, int h, int w, double pyr_scale, int levels, int winsize, int iterations, int poly_n,
-                    int flags);
-size_t farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels);
-int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
-                        int winsize, int iterations, int poly_n, double poly_sigma, float *flow_out,
-                        float *mag_out, void *ws, size_t ws_bytes, hipStream_t st);
-// ActiveContour (va_snake.hip): both 5-tap Sobel planes in float64, and every iteration of m snakes in one
-// launch.  Contours of up to kSnakeLdsMaxN points keep their matrix in LDS, longer ones read it from global
-// memory; kSnakeMaxN is the longest contour a call takes
-constexpr int kSnakeLdsMaxN = 128;
-constexpr int kSnakeMaxN = 1024;
-int launch_sobel5_f64(const void *src, int dtype, double *fx, double *fy, int n, int h, int w, hipStream_t st);
-// shapes, offsets, total: the planes are the items of a ragged buffer (n of them; h, w unused), null for a stack
-int launch_active_contour(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
-                          int64_t total, int n, int h, int w, int m, int max_points, const int32_t *npts,
-                          const int32_t *frame, const double *mats, const int64_t *mat_off, int64_t mats_count,
-                          const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
-                          int max_iterations, double *pts, int32_t *iterations, double *total_variation,
-                          hipStream_t st);
-// blur + Sobel of the items of a ragged buffer, one workgroup per item with the item in LDS (va_gradients.hip);
-// taps.ksize == 0: no blur
-constexpr int kGradResidentMaxPixels = VA_GRAD_RESIDENT_MAX_PIXELS;
-int launch_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
-                                      int64_t total, int m, int max_pixels, const TapsF32 &taps, double *fx,
-                                      double *fy, int32_t *status, hipStream_t st);
-// Polygons (va_polygon.hip): batched cv2.fillPoly and cv2.distanceTransform(DIST_L2, 5), one workgroup per item
-constexpr int kFillMaxVerts = VA_FILL_MAX_VERTS;
-constexpr int kPolyMaxSide = VA_FILL_MAX_SIDE;
+// the largest coordinate the rasterisers of va_polygon.hip and va_compose.hip take
 constexpr int64_t kPolyMaxCoord = VA_FILL_MAX_COORD;
-constexpr int kDtMaxWidth = VA_DT_MAX_WIDTH;
-constexpr int kDtMaxHeight = VA_DT_MAX_HEIGHT;
-int launch_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
-                     const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
-                     hipStream_t st);
-int launch_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets,
-                                   int64_t total, int m, int max_w, float *out, int32_t *status, hipStream_t st);
-// Guo-Hall thinning (va_thinning.hip): one workgroup per mask in LDS, or K sub-iterations per launch on tiles
-// of bit planes in HBM (scratch: guo_hall_tiled_scratch_bytes; iterations_out / stats_out are host pointers)
-constexpr int kThinResidentMaxWords = VA_THIN_RESIDENT_MAX_WORDS;
-constexpr int kThinMaxK = VA_THIN_MAX_SUB_ITERATIONS;
-constexpr int kThinMaxPoll = VA_THIN_MAX_POLL;
-int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const int64_t *offsets, int64_t total,
-                             int m, int max_words, uint8_t *dst, int32_t *iterations, int32_t *status,
-                             hipStream_t st);
-size_t guo_hall_tiled_scratch_bytes(int n, int h, int w);
-int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
-                       int32_t *iterations_out, int32_t *stats_out, hipStream_t st);
-// skeleton graphs (va_skeleton.hip): va_skeleton_graph's outputs from eleven chip-wide launches over the packed
-// pixels; the workspace holds per pixel the forest, the anchor key and the tally of its node (zeroed per call),
-// the adjacency and ownership masks, the point counts and the point offsets, then the scan's block sums
-struct SkeletonLayout { size_t zeroed, anchor, tally, zeroed_bytes, forest, adj, owned, npts, point_base, sums,
-                        first_node, total; };
-SkeletonLayout skeleton_layout(int64_t total, int m);
-int launch_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
-                          int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
-                          va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
-                          int64_t cap_points, void *ws, hipStream_t st);
-// 8-bit affine warps (va_warp.hip): m line scans as int32 column sums, or m warped uint8 destinations, one launch
-int launch_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
-                        const double *mats, const int32_t *shapes, const int64_t *out_off, const int32_t *prefix,
-                        int total_chunks, int64_t total_out, int32_t *sums, int32_t *status, hipStream_t st);
-int launch_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
-                          const double *mats, const int32_t *shapes, const int32_t *flags, const int64_t *out_off,
-                          const int32_t *prefix, int total_tiles, int64_t total_out, uint8_t *out, int32_t *status,
-                          hipStream_t st);
-// outline queries (va_outline.hip): q rays, or q points, each against one of m packed float64 outlines, a group of
-// `lanes` (8 or 64) lanes per query; one launch, no workspace
-int launch_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
-                    const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes,
-                    double *t_out, double *hits_out, int32_t *edge_out, int32_t *count_out, hipStream_t st);
-int launch_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                              const double *query, const int32_t *index, int64_t q, int lanes, uint8_t *inside_out,
-                              hipStream_t st);
-// equidistant curves (va_curves.hip): va_curves_equidistant's outputs from three launches, one lane per curve
-int launch_curves_equidistant(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                              const double *spacing, const int32_t *count, const double *translate,
-                              int32_t *out_count, int64_t *out_off, double *in_length, int32_t *status,
-                              int64_t *totals, double *out_points, int64_t cap_points, double *out_length,
-                              hipStream_t st);
-// simplification (va_simplify.hip): the kept flags and counts of m packed curves, Ramer-Douglas-Peucker with one
-// wave per curve, Visvalingam with one lane per curve; the workspace holds the heap and the two link tables
-struct SimplifyLayout { size_t heap, prev, next, total; };
-SimplifyLayout simplify_layout(int64_t npoints);
-int launch_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
-                        uint8_t *keep, int32_t *out_count, int32_t *status, hipStream_t st);
-int launch_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                                const double *thr, int closed, uint8_t *keep, int32_t *out_count, int32_t *status,
-                                void *ws, hipStream_t st);
-// composer (va_compose.hip): the pixel layers of a stack in one pass; the drawing commands, one workgroup per frame
-int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
-                          const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,
-                          const uint8_t *images, int64_t images_bytes, const uint8_t *masks, int64_t masks_bytes,
-                          hipStream_t st);
-int launch_draw(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
-                int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, hipStream_t st);
-// Motion-JPEG (va_jpeg.hip): one baseline JFIF file per frame from three launches; ws: jpeg_workspace_bytes
-size_t jpeg_workspace_bytes(int n, int h);
-int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
-                       int header_bytes, int64_t *sizes, int64_t *offsets, int64_t *totals, uint8_t *out, int64_t cap,
-                       void *ws, hipStream_t st);
-// Motion-JPEG decoding (va_jpeg_decode.hip): locate, entropy and reconstruct per chunk of frames; the chunk is what
-// the workspace holds (jpeg_decode_chunk: 0 when it does not hold one frame).  lh x lv is the sampling of the luma
-// component, 1 x 1, 2 x 1 or 2 x 2; behind a subsampled file the reconstruction is two launches (chroma planes, pixels)
-size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv);
-int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, size_t workspace_bytes);
-int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                       int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
-                       int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st);
-// Split Motion-JPEG decoding (va_jpeg_decode.hip): frames without restart markers, one lane per `sub` raw bytes of a
-// frame's one segment (scan rounds, check, write, seal; the one-lane fallback for a frame that did not converge or is
-// longer than max_bytes); the workspace and the chunks as above with more behind
-size_t jpeg_split_workspace_bytes(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes);
-int64_t jpeg_split_chunk(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes, size_t workspace_bytes);
-int launch_jpeg_decode_split(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                             int c, int lh, int lv, int sub, int max_rounds, int64_t max_bytes, const uint8_t *qtables,
-                             const void *huff, uint8_t *out, int32_t *status, int32_t *rounds_out, void *ws,
-                             size_t workspace_bytes, hipStream_t st);
-// cv2.moments(contour): ten spatial moments (float64) per contour, points int32 or float32 (x, y)
-int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
-                           int is_float, double *out, hipStream_t st);
-// the same over a ragged list: contour i = points point_off[i] .. point_off[i + 1]
-int launch_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float, double *out,
-                                  hipStream_t st);
 int launch_stats_from_labels(const int32_t *labels, int n, int h, int w, int max_labels,
                              int64_t *stats, hipStream_t st);
 int launch_largest_region(const int32_t *labels, const int32_t *counts, const int64_t *stats,

@@ -311,11 +311,36 @@ __global__ void __launch_bounds__(kDrawBlock) draw_kernel(DrawArgs a)
 
 }  // namespace
 
-int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
-                          const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,
-                          const uint8_t *images, int64_t images_bytes, const uint8_t *masks, int64_t masks_bytes,
-                          hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_compose_layers_u8(const uint8_t *src, int c_src, uint8_t *dst, int n, int h, int w, int c,
+                         const va_compose_layer *layers, const int64_t *layer_off, int64_t nlayers,
+                         const uint8_t *images, int64_t images_bytes, const uint8_t *masks, int64_t masks_bytes,
+                         void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h >= 0 && w >= 0 && nlayers >= 0 && images_bytes >= 0 && masks_bytes >= 0,
+               "va_compose_layers_u8: negative count (n %d, h %d, w %d, nlayers %lld, images %lld, masks %lld)", n, h,
+               w, (long long)nlayers, (long long)images_bytes, (long long)masks_bytes);
+    VA_REQUIRE((c_src == 1 || c_src == 3) && (c == 1 || c == 3) && c_src <= c,
+               "va_compose_layers_u8: channels must be 1 or 3 with c_src <= c, got %d -> %d", c_src, c);
+    VA_REQUIRE((size_t)h * w < kMaxFramePixels, "va_compose_layers_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src != dst || c_src == c || !src,
+               "va_compose_layers_u8: src and dst must be distinct when c_src != c");
+    if (n == 0 || h == 0 || w == 0 || (nlayers == 0 && src == dst && src))
+        return VA_OK;
+    VA_REQUIRE(src && dst && layer_off && (layers || nlayers == 0) && (images || images_bytes == 0) &&
+                   (masks || masks_bytes == 0),
+               "va_compose_layers_u8: NULL argument");
+    VA_REQUIRE(aligned(layers, 8) && aligned(layer_off, 8),
+               "va_compose_layers_u8: the layer tables must be 8-byte aligned");
+    VA_REQUIRE(((int64_t)n * h * ((w + 15) / 16) + 255) / 256 < ((int64_t)1 << 31),
+               "va_compose_layers_u8: the stack is too large for one launch");
+    hipStream_t st = as_stream(stream);
     ComposeArgs a{src, dst, n, h, w, c_src, layers, layer_off, nlayers, images, images_bytes, masks, masks_bytes, 0, 0};
     a.chunks = (w + kLanePixels - 1) / kLanePixels;
     a.lanes = (int64_t)n * h * a.chunks;
@@ -328,9 +353,22 @@ int launch_compose_layers(const uint8_t *src, int c_src, uint8_t *dst, int n, in
     return VA_OK;
 }
 
-int launch_draw(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
-                int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, hipStream_t st)
+int va_draw_u8(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *cmds, const int64_t *cmd_off,
+               int64_t ncmds, const int32_t *points, int64_t npoints, int32_t *status, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h >= 0 && w >= 0 && ncmds >= 0 && npoints >= 0,
+               "va_draw_u8: negative count (n %d, h %d, w %d, ncmds %lld, npoints %lld)", n, h, w, (long long)ncmds,
+               (long long)npoints);
+    VA_REQUIRE(c == 1 || c == 3, "va_draw_u8: channels must be 1 or 3, got %d", c);
+    VA_REQUIRE((size_t)h * w < kMaxFramePixels, "va_draw_u8: frames above 2^29 pixels are not supported");
+    if (n == 0 || ncmds == 0)
+        return VA_OK;
+    VA_REQUIRE((frames || h == 0 || w == 0) && cmds && cmd_off && status && (points || npoints == 0),
+               "va_draw_u8: NULL argument");
+    VA_REQUIRE(aligned(cmds, 8) && aligned(cmd_off, 8) && aligned(points, 4) && aligned(status, 4),
+               "va_draw_u8: the command tables must be 8-byte aligned, points and status 4-byte aligned");
+    hipStream_t st = as_stream(stream);
     const DrawArgs a{frames, n, h, w, cmds, cmd_off, ncmds, points, npoints, status};
     if (c == 1)
         hipLaunchKernelGGL(draw_kernel<1>, dim3(n), dim3(kDrawBlock), 0, st, a);
@@ -340,4 +378,4 @@ int launch_draw(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -164,12 +164,32 @@ curves_fill_kernel(const double *__restrict__ points, const int64_t *__restrict_
 
 }  // namespace
 
-int launch_curves_equidistant(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                              const double *spacing, const int32_t *count, const double *translate,
-                              int32_t *out_count, int64_t *out_off, double *in_length, int32_t *status,
-                              int64_t *totals, double *out_points, int64_t cap_points, double *out_length,
-                              hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_curves_equidistant(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *spacing,
+                          const int32_t *count, const double *translate, int32_t *out_count, int64_t *out_off,
+                          double *in_length, int32_t *status, int64_t *totals, double *out_points, int64_t cap_points,
+                          double *out_length, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(npoints >= 0 && m >= 0 && cap_points >= 0,
+               "va_curves_equidistant: negative count (npoints %lld, m %d, cap_points %lld)", (long long)npoints, m,
+               (long long)cap_points);
+    if (m == 0)
+        return VA_OK;
+    // (count may be NULL: a curve in count mode then reads none and is refused by the kernel's own test below)
+    VA_REQUIRE(points && point_off && spacing && out_count && out_off && in_length && status && totals && out_points &&
+                   out_length,
+               "va_curves_equidistant: NULL argument");
+    VA_REQUIRE(aligned(points, 8) && aligned(point_off, 8) && aligned(spacing, 8) && aligned(count, 4) &&
+                   aligned(translate, 8) && aligned(out_count, 4) && aligned(out_off, 8) && aligned(in_length, 8) &&
+                   aligned(status, 4) && aligned(totals, 8) && aligned(out_points, 8) && aligned(out_length, 8),
+               "va_curves_equidistant: float64 and int64 buffers must be 8-byte aligned, int32 buffers 4-byte aligned");
+    hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)cdiv(m, kCurvesBlock)), block(kCurvesBlock);
     hipLaunchKernelGGL(curves_count_kernel, grid, block, 0, st, points, point_off, npoints, m, spacing, count,
                        out_count, in_length, status);
@@ -182,4 +202,4 @@ int launch_curves_equidistant(const double *points, const int64_t *point_off, in
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -207,8 +207,10 @@ static int taps_sum(const TapsQ8 &taps)
     return sum;
 }
 
-int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h,
-                            int w, int c, const TapsQ8 &taps, hipStream_t st)
+// generic (any radius / channel count) two-pass Gaussian through a u16 / f32 scratch in HBM
+// (16-bit row sums while the tap sum allows)
+static int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h,
+                                   int w, int c, const TapsQ8 &taps, hipStream_t st)
 {
     size_t total = (size_t)n * h * w * c;
     if (total == 0)
@@ -227,8 +229,8 @@ int launch_gauss_generic_u8(const uint8_t *src, uint8_t *dst, void *scratch, int
     return VA_OK;
 }
 
-int launch_gauss_generic_f32(const float *src, float *dst, float *scratch, int n, int h, int w,
-                             int c, const TapsF32 &taps, hipStream_t st)
+static int launch_gauss_generic_f32(const float *src, float *dst, float *scratch, int n, int h, int w,
+                                    int c, const TapsF32 &taps, hipStream_t st)
 {
     size_t total = (size_t)n * h * w * c;
     if (total == 0)

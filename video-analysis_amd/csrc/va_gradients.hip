@@ -25,6 +25,7 @@ namespace va {
 namespace {
 
 constexpr int kGradBlock = 256;
+constexpr int kGradResidentMaxPixels = VA_GRAD_RESIDENT_MAX_PIXELS;
 
 // both Sobel values of pixel (y, x) of the h x w plane A
 __device__ __forceinline__ void sobel_at(const float *A, int h, int w, int y, int x, double *gx, double *gy)
@@ -177,23 +178,49 @@ grad_ragged_kernel(const T *__restrict__ src, const int32_t *__restrict__ shapes
 
 }  // namespace
 
-int launch_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
-                                      int64_t total, int m, int max_pixels, const TapsF32 &taps, double *fx,
-                                      double *fy, int32_t *status, hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_potential_gradients_ragged(const void *src, int dtype, const int32_t *shapes, const int64_t *offsets,
+                                  int64_t total, int m, int max_pixels, double sigma, double *fx_out, double *fy_out,
+                                  int32_t *status, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32,
+               "va_potential_gradients_ragged: items must be VA_U8 or VA_F32 (got dtype %d)", dtype);
+    VA_REQUIRE(sigma >= 0 && sigma == sigma, "va_potential_gradients_ragged: sigma must be >= 0 (got %g)", sigma);
+    VA_REQUIRE(dtype == VA_F32 || sigma == 0,
+               "va_potential_gradients_ragged: VA_U8 items take sigma == 0 only (the 8-bit blur is fixed-point)");
+    VA_REQUIRE(m >= 0 && total >= 0, "va_potential_gradients_ragged: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_pixels >= 0 && max_pixels <= kGradResidentMaxPixels,
+               "va_potential_gradients_ragged: max_pixels %d outside 0 .. %d", max_pixels, kGradResidentMaxPixels);
+    TapsF32 taps;                                    // ksize == 0: no blur
+    taps.ksize = 0;
+    if (sigma > 0) {
+        int rc = gauss_taps_f32(sigma, &taps.ksize, taps.t, kMaxTaps);
+        if (rc)
+            return rc;
+    }
     if (m == 0)
         return VA_OK;
-    const int vec2 = ((uintptr_t)fx % 16 == 0) && ((uintptr_t)fy % 16 == 0);
+    VA_REQUIRE(shapes && offsets && status && ((src && fx_out && fy_out) || total == 0),
+               "va_potential_gradients_ragged: NULL argument");
+    hipStream_t st = as_stream(stream);
+    const int vec2 = ((uintptr_t)fx_out % 16 == 0) && ((uintptr_t)fy_out % 16 == 0);
     const size_t lds = (size_t)(max_pixels > 0 ? max_pixels : 1) * 2 * sizeof(float);
     const dim3 grid(m), block(kGradBlock);
     if (dtype == VA_U8)
         hipLaunchKernelGGL(grad_ragged_kernel<uint8_t>, grid, block, lds, st, static_cast<const uint8_t *>(src), shapes,
-                           offsets, total, max_pixels, taps, fx, fy, vec2, status);
+                           offsets, total, max_pixels, taps, fx_out, fy_out, vec2, status);
     else
         hipLaunchKernelGGL(grad_ragged_kernel<float>, grid, block, lds, st, static_cast<const float *>(src), shapes,
-                           offsets, total, max_pixels, taps, fx, fy, vec2, status);
+                           offsets, total, max_pixels, taps, fx_out, fy_out, vec2, status);
     VA_LAUNCH_CHECK("grad_ragged_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -383,21 +383,44 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
 
 }  // namespace
 
-size_t jpeg_workspace_bytes(int n, int h)
-{
-    const size_t nsegs = (size_t)n * ((h + 7) / 8);
-    return Carve::up(nsegs * sizeof(int32_t)) + Carve::up((nsegs + 1) * sizeof(int64_t));
-}
+}  // namespace va
 
-int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
-                       int header_bytes, int64_t *sizes, int64_t *offsets, int64_t *totals, uint8_t *out, int64_t cap,
-                       void *ws, hipStream_t st)
+using namespace va;
+
+extern "C" {
+
+int va_jpeg_encode_u8(const uint8_t *frames, int n, int h, int w, int c, const uint8_t *qtables, const uint8_t *header,
+                      int header_bytes, int64_t *sizes_out, int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out,
+                      int64_t cap_bytes, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
+               "va_jpeg_encode_u8: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", n, h, w,
+               header_bytes, (long long)cap_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_encode_u8: channels must be 1 or 3, got %d", c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
+               "va_jpeg_encode_u8: NULL argument");
+    VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
+               "va_jpeg_encode_u8: the int64 buffers must be 8-byte aligned");
+    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_encode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
+    VA_REQUIRE((int64_t)n * ((h + 7) / 8) < ((int64_t)1 << 31),
+               "va_jpeg_encode_u8: the stack has too many MCU rows for one launch");
+    hipStream_t st = as_stream(stream);
     const int nseg = (h + 7) / 8;
     const int64_t nsegs = (int64_t)n * nseg;
-    int32_t *seg_len = at<int32_t>(ws, 0);
-    int64_t *seg_start = at<int64_t>(ws, Carve::up((size_t)nsegs * sizeof(int32_t)));
-    const JpegArgs a{frames, n, h, w, nseg, (w + 7) / 8, qtables, header, header_bytes, seg_len, seg_start, totals, out, cap};
+    Carve ws;                                        // [seg_len | seg_start]
+    const size_t o_len = ws.take((size_t)nsegs * sizeof(int32_t));
+    const size_t o_start = ws.take(((size_t)nsegs + 1) * sizeof(int64_t));
+    ScratchLease scratch;
+    int rc = scratch.acquire(ws.total, st);
+    if (rc)
+        return rc;
+    int32_t *seg_len = at<int32_t>(scratch.ptr, o_len);
+    int64_t *seg_start = at<int64_t>(scratch.ptr, o_start);
+    const JpegArgs a{frames, n, h, w, nseg, (w + 7) / 8, qtables, header, header_bytes, seg_len, seg_start, totals,
+                     bytes_out, cap_bytes};
     const dim3 grid((unsigned)nsegs), block(kJpegBlock);
     if (c == 1)
         hipLaunchKernelGGL((jpeg_segment_kernel<1, false>), grid, block, 0, st, a);
@@ -405,7 +428,7 @@ int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const 
         hipLaunchKernelGGL((jpeg_segment_kernel<3, false>), grid, block, 0, st, a);
     VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, header_bytes,
-                       seg_start, offsets, sizes, totals);
+                       seg_start, offsets_out, sizes_out, totals);
     VA_LAUNCH_CHECK("jpeg_scan_kernel");
     if (c == 1)
         hipLaunchKernelGGL((jpeg_segment_kernel<1, true>), grid, block, 0, st, a);
@@ -415,4 +438,4 @@ int launch_jpeg_encode(const uint8_t *frames, int n, int h, int w, int c, const 
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -823,21 +823,6 @@ int64_t jpeg_split_chunk(int n, const JpegGrid &g, int64_t per, size_t workspace
     return k;
 }
 
-}  // namespace
-
-size_t jpeg_split_workspace_bytes(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes)
-{
-    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, lh, lv);
-    return split_layout(n, g, split_lanes(sub, max_bytes)).total;
-}
-
-int64_t jpeg_split_chunk(int n, int h, int w, int c, int lh, int lv, int sub, int64_t max_bytes, size_t workspace_bytes)
-{
-    return jpeg_split_chunk(n, jpeg_grid(h, w, c, INT_MAX, lh, lv), split_lanes(sub, max_bytes), workspace_bytes);
-}
-
-namespace {
-
 template <int C, int LH, int LV>
 int launch_split_entropy(SplitArgs a, EntropyArgs e, int64_t frames, int64_t mcus, hipStream_t st)
 {
@@ -864,88 +849,52 @@ int launch_split_entropy(SplitArgs a, EntropyArgs e, int64_t frames, int64_t mcu
     return VA_OK;
 }
 
-}  // namespace
-
-int launch_jpeg_decode_split(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                             int c, int lh, int lv, int sub, int max_rounds, int64_t max_bytes, const uint8_t *qtables,
-                             const void *huff, uint8_t *out, int32_t *status, int32_t *rounds_out, void *ws,
-                             size_t workspace_bytes, hipStream_t st)
+bool jpeg_sampling_taken(int c, int lh, int lv)
 {
-    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, lh, lv);              // one segment a frame
-    const int64_t per = split_lanes(sub, max_bytes);
-    const int64_t chunk = jpeg_split_chunk(n, g, per, workspace_bytes);
-    const SplitLayout l = split_layout(chunk, g, per);
-    int64_t *table = at<int64_t>(ws, l.d.table);
-    int16_t *coef = at<int16_t>(ws, l.d.coef);
-    uint8_t *planes = at<uint8_t>(ws, l.d.planes);
-    const auto blocks_of = [](int64_t lanes) { return dim3((unsigned)((lanes + kRecBlock - 1) / kRecBlock)); };
-    for (int64_t f0 = 0; f0 < n; f0 += chunk) {
-        const int64_t k = chunk < n - f0 ? chunk : n - f0;
-        uint8_t *frames = out + (size_t)f0 * h * w * c;
-        hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
-                           scan_begin + f0, 1, table, status + f0);
-        VA_LAUNCH_CHECK("jpeg_locate_kernel");
-        const va_jpeg::HuffDecode *tabs = static_cast<const va_jpeg::HuffDecode *>(huff);
-        SplitArgs a{};
-        a.bytes = bytes, a.table = table, a.huff = tabs;
-        a.entry = at<va_jpeg::ScanState>(ws, l.entry), a.exits = at<va_jpeg::ScanState>(ws, l.exits);
-        a.begun = at<int32_t>(ws, l.begun), a.last = at<int32_t>(ws, l.last);
-        a.dc = at<uint32_t>(ws, l.dc), a.pred = at<uint32_t>(ws, l.pred), a.start = at<int64_t>(ws, l.start);
-        a.converged = at<int32_t>(ws, l.converged), a.err = at<unsigned long long>(ws, l.err);
-        a.rounds_out = rounds_out ? rounds_out + f0 : nullptr;
-        a.coef = coef, a.status = status + f0;
-        a.lanes = k * per, a.per = per, a.max_bytes = max_bytes;
-        a.sub = sub, a.round = 0, a.max_rounds = max_rounds, a.bx = g.bx, a.by = g.by;
-        const EntropyArgs e{bytes, table, tabs, coef, status + f0, k, 1, (int)(g.mcus < INT_MAX ? g.mcus : INT_MAX),
-                            g.bx, g.by, a.converged};
-        const int rc = c == 1    ? launch_split_entropy<1, 1, 1>(a, e, k, g.mcus, st)
-                       : lv == 2 ? launch_split_entropy<3, 2, 2>(a, e, k, g.mcus, st)
-                       : lh == 2 ? launch_split_entropy<3, 2, 1>(a, e, k, g.mcus, st)
-                                 : launch_split_entropy<3, 1, 1>(a, e, k, g.mcus, st);
-        if (rc)
-            return rc;
-        if (g.luma == 1) {
-            const ReconArgs r{coef, qtables, frames, k * g.mcus, h, w, g.bx, g.by};
-            if (c == 1)
-                hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
-            else
-                hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
-            VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
-            continue;
-        }
-        const PlaneArgs cp{coef, qtables, planes, k * 2 * g.mcus, g.bx, g.by, g.luma};
-        hipLaunchKernelGGL(jpeg_chroma_planes_kernel, blocks_of(cp.nblocks), dim3(kRecBlock), 0, st, cp);
-        VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
-        const PixelArgs p{coef, qtables, planes, frames, k * g.mcus * g.luma, h, w, g.bx, g.by};
-        if (lv == 2)
-            hipLaunchKernelGGL(jpeg_pixels_kernel<2>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
-        else
-            hipLaunchKernelGGL(jpeg_pixels_kernel<1>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
-        VA_LAUNCH_CHECK("jpeg_pixels_kernel");
-    }
-    return VA_OK;
+    return (lh == 1 && lv == 1) || (c == 3 && lh == 2 && (lv == 1 || lv == 2));
 }
 
-size_t jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri, int lh, int lv)
-{
-    return decode_layout(n, jpeg_grid(h, w, c, ri, lh, lv)).total;
-}
+constexpr int64_t kJpegSplitMaxScanBytes = (int64_t)1 << 40;
+bool jpeg_split_sub_taken(int sub) { return sub >= 16 && sub <= 65536 && sub % 16 == 0; }
 
-int64_t jpeg_decode_chunk(int n, int h, int w, int c, int ri, int lh, int lv, size_t workspace_bytes)
+// both decode entries: `what` names the one that was called
+int jpeg_decode_entry(const char *what, const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n,
+                      int h, int w, int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff,
+                      int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
+                      void *stream)
 {
-    return jpeg_decode_chunk(n, jpeg_grid(h, w, c, ri, lh, lv), workspace_bytes);
-}
-
-int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
-                       int c, int ri, int lh, int lv, const uint8_t *qtables, const void *huff, uint8_t *out,
-                       int32_t *status, void *ws, size_t workspace_bytes, hipStream_t st)
-{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ri > 0 && workspace_bytes >= 0,
+               "%s: negative or zero size (n %d, h %d, w %d, ri %d, workspace %lld)", what, n, h, w, ri,
+               (long long)workspace_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
+    VA_REQUIRE(jpeg_sampling_taken(c, lh, lv),
+               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
+               what, lh, lv, c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
+               "%s: NULL argument", what);
+    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
+                   && aligned(workspace, 16),
+               "%s: offsets and scan_begin must be 8-byte aligned, the tables and the status 4-byte, "
+               "the workspace 16-byte", what);
+    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
+    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
+               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
+               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
     const JpegGrid g = jpeg_grid(h, w, c, ri, lh, lv);
-    const int64_t chunk = jpeg_decode_chunk(n, g, workspace_bytes);
+    const int64_t chunk = jpeg_decode_chunk(n, g, (size_t)workspace_bytes);
+    if (chunk < 1) {
+        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what,
+                  (long long)workspace_bytes, (long long)decode_layout(1, g).total);
+        return VA_ERR_RANGE;
+    }
+    hipStream_t st = as_stream(stream);
     const DecodeLayout l = decode_layout(chunk, g);
-    int64_t *table = at<int64_t>(ws, l.table);
-    int16_t *coef = at<int16_t>(ws, l.coef);
-    uint8_t *planes = at<uint8_t>(ws, l.planes);
+    int64_t *table = at<int64_t>(workspace, l.table);
+    int16_t *coef = at<int16_t>(workspace, l.coef);
+    uint8_t *planes = at<uint8_t>(workspace, l.planes);
     void (*const entropy)(EntropyArgs) = c == 1    ? jpeg_entropy_kernel<1, 1, 1>
                                          : lv == 2 ? jpeg_entropy_kernel<3, 2, 2>
                                          : lh == 2 ? jpeg_entropy_kernel<3, 2, 1>
@@ -953,11 +902,11 @@ int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64
     const auto blocks_of = [](int64_t lanes) { return dim3((unsigned)((lanes + kRecBlock - 1) / kRecBlock)); };
     for (int64_t f0 = 0; f0 < n; f0 += chunk) {
         const int64_t k = chunk < n - f0 ? chunk : n - f0;
-        uint8_t *frames = out + (size_t)f0 * h * w * c;
+        uint8_t *frames = frames_out + (size_t)f0 * h * w * c;
         hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
-                           scan_begin + f0, g.nseg, table, status + f0);
+                           scan_begin + f0, g.nseg, table, status_out + f0);
         VA_LAUNCH_CHECK("jpeg_locate_kernel");
-        const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status + f0,
+        const EntropyArgs e{bytes, table, static_cast<const va_jpeg::HuffDecode *>(huff), coef, status_out + f0,
                             k * g.nseg, g.nseg, ri, g.bx, g.by, nullptr};
         hipLaunchKernelGGL(entropy, dim3((unsigned)((e.nsegs + kEntBlock - 1) / kEntBlock)), dim3(kEntBlock), 0, st, e);
         VA_LAUNCH_CHECK("jpeg_entropy_kernel");
@@ -983,4 +932,147 @@ int launch_jpeg_decode(const uint8_t *bytes, const int64_t *offsets, const int64
     return VA_OK;
 }
 
+}  // namespace
+
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+size_t va_jpeg_decode_workspace_bytes(int n, int h, int w, int c, int ri)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0)
+        return 0;
+    return decode_layout(n, jpeg_grid(h, w, c, ri, 1, 1)).total;
+}
+
+int va_jpeg_decode_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w, int c,
+                      int ri, const uint8_t *qtables, const void *huff, int huff_bytes, uint8_t *frames_out,
+                      int32_t *status_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return jpeg_decode_entry("va_jpeg_decode_u8", bytes, offsets, scan_begin, n, h, w, c, ri, 1, 1, qtables, huff,
+                             huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
+}
+
+size_t va_jpeg_decode_sampled_workspace_bytes(int n, int h, int w, int c, int ri, int luma_h, int luma_v)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3) || ri <= 0
+        || !jpeg_sampling_taken(c, luma_h, luma_v))
+        return 0;
+    return decode_layout(n, jpeg_grid(h, w, c, ri, luma_h, luma_v)).total;
+}
+
+int va_jpeg_decode_sampled_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h,
+                              int w, int c, int ri, int luma_h, int luma_v, const uint8_t *qtables, const void *huff,
+                              int huff_bytes, uint8_t *frames_out, int32_t *status_out, void *workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    return jpeg_decode_entry("va_jpeg_decode_sampled_u8", bytes, offsets, scan_begin, n, h, w, c, ri, luma_h, luma_v,
+                             qtables, huff, huff_bytes, frames_out, status_out, workspace, workspace_bytes, stream);
+}
+
+size_t va_jpeg_decode_split_workspace_bytes(int n, int h, int w, int c, int luma_h, int luma_v, int sub_bytes,
+                                            int64_t max_scan_bytes)
+{
+    if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || (c != 1 && c != 3)
+        || !jpeg_sampling_taken(c, luma_h, luma_v) || !jpeg_split_sub_taken(sub_bytes) || max_scan_bytes < 0
+        || max_scan_bytes > kJpegSplitMaxScanBytes)
+        return 0;
+    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, luma_h, luma_v);
+    return split_layout(n, g, split_lanes(sub_bytes, max_scan_bytes)).total;
+}
+
+int va_jpeg_decode_split_u8(const uint8_t *bytes, const int64_t *offsets, const int64_t *scan_begin, int n, int h, int w,
+                            int c, int luma_h, int luma_v, const uint8_t *qtables, const void *huff, int huff_bytes,
+                            uint8_t *frames_out, int32_t *status_out, void *workspace, int64_t workspace_bytes,
+                            int sub_bytes, int max_rounds, int64_t max_scan_bytes, int32_t *rounds_out, void *stream)
+{
+    const char *what = "va_jpeg_decode_split_u8";
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && workspace_bytes >= 0,
+               "%s: negative or zero size (n %d, h %d, w %d, workspace %lld)", what, n, h, w, (long long)workspace_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
+    VA_REQUIRE(jpeg_sampling_taken(c, luma_h, luma_v),
+               "%s: luma sampling %d x %d with %d channel(s); 1 x 1, and with 3 channels 2 x 1 and 2 x 2, are decoded",
+               what, luma_h, luma_v, c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(bytes && offsets && scan_begin && qtables && huff && frames_out && status_out && workspace,
+               "%s: NULL argument", what);
+    VA_REQUIRE(aligned(offsets, 8) && aligned(scan_begin, 8) && aligned(huff, 4) && aligned(status_out, 4)
+                   && aligned(workspace, 16) && aligned(rounds_out, 4),
+               "%s: offsets and scan_begin must be 8-byte aligned, the tables, the status and the rounds 4-byte, "
+               "the workspace 16-byte", what);
+    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
+    VA_REQUIRE(huff_bytes == 2 * c * VA_JPEG_HUFF_DECODE_BYTES,
+               "%s: the Huffman tables of %d component(s) are %d bytes, got %d", what, c,
+               2 * c * VA_JPEG_HUFF_DECODE_BYTES, huff_bytes);
+    VA_REQUIRE(jpeg_split_sub_taken(sub_bytes), "%s: sub_bytes must be a multiple of 16 in 16 .. 65536, got %d", what,
+               sub_bytes);
+    VA_REQUIRE(max_rounds >= 0, "%s: max_rounds must not be negative, got %d", what, max_rounds);
+    VA_REQUIRE(max_scan_bytes >= 0 && max_scan_bytes <= kJpegSplitMaxScanBytes,
+               "%s: max_scan_bytes must lie in 0 .. 2^40, got %lld", what, (long long)max_scan_bytes);
+    const JpegGrid g = jpeg_grid(h, w, c, INT_MAX, luma_h, luma_v);              // one segment a frame
+    const int64_t per = split_lanes(sub_bytes, max_scan_bytes);
+    const int64_t chunk = jpeg_split_chunk(n, g, per, (size_t)workspace_bytes);
+    if (chunk < 1) {
+        set_error("%s: a workspace of %lld bytes does not hold one frame (%lld bytes)", what, (long long)workspace_bytes,
+                  (long long)split_layout(1, g, per).total);
+        return VA_ERR_RANGE;
+    }
+    hipStream_t st = as_stream(stream);
+    const SplitLayout l = split_layout(chunk, g, per);
+    int64_t *table = at<int64_t>(workspace, l.d.table);
+    int16_t *coef = at<int16_t>(workspace, l.d.coef);
+    uint8_t *planes = at<uint8_t>(workspace, l.d.planes);
+    const auto blocks_of = [](int64_t lanes) { return dim3((unsigned)((lanes + kRecBlock - 1) / kRecBlock)); };
+    for (int64_t f0 = 0; f0 < n; f0 += chunk) {
+        const int64_t k = chunk < n - f0 ? chunk : n - f0;
+        uint8_t *frames = frames_out + (size_t)f0 * h * w * c;
+        hipLaunchKernelGGL(jpeg_locate_kernel, dim3((unsigned)k), dim3(kLocBlock), 0, st, bytes, offsets + f0,
+                           scan_begin + f0, 1, table, status_out + f0);
+        VA_LAUNCH_CHECK("jpeg_locate_kernel");
+        const va_jpeg::HuffDecode *tabs = static_cast<const va_jpeg::HuffDecode *>(huff);
+        SplitArgs a{};
+        a.bytes = bytes, a.table = table, a.huff = tabs;
+        a.entry = at<va_jpeg::ScanState>(workspace, l.entry), a.exits = at<va_jpeg::ScanState>(workspace, l.exits);
+        a.begun = at<int32_t>(workspace, l.begun), a.last = at<int32_t>(workspace, l.last);
+        a.dc = at<uint32_t>(workspace, l.dc), a.pred = at<uint32_t>(workspace, l.pred);
+        a.start = at<int64_t>(workspace, l.start);
+        a.converged = at<int32_t>(workspace, l.converged), a.err = at<unsigned long long>(workspace, l.err);
+        a.rounds_out = rounds_out ? rounds_out + f0 : nullptr;
+        a.coef = coef, a.status = status_out + f0;
+        a.lanes = k * per, a.per = per, a.max_bytes = max_scan_bytes;
+        a.sub = sub_bytes, a.round = 0, a.max_rounds = max_rounds, a.bx = g.bx, a.by = g.by;
+        const EntropyArgs e{bytes, table, tabs, coef, status_out + f0, k, 1,
+                            (int)(g.mcus < INT_MAX ? g.mcus : INT_MAX), g.bx, g.by, a.converged};
+        const int rc = c == 1        ? launch_split_entropy<1, 1, 1>(a, e, k, g.mcus, st)
+                       : luma_v == 2 ? launch_split_entropy<3, 2, 2>(a, e, k, g.mcus, st)
+                       : luma_h == 2 ? launch_split_entropy<3, 2, 1>(a, e, k, g.mcus, st)
+                                     : launch_split_entropy<3, 1, 1>(a, e, k, g.mcus, st);
+        if (rc)
+            return rc;
+        if (g.luma == 1) {
+            const ReconArgs r{coef, qtables, frames, k * g.mcus, h, w, g.bx, g.by};
+            if (c == 1)
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<1>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            else
+                hipLaunchKernelGGL(jpeg_reconstruct_kernel<3>, blocks_of(r.nmcus), dim3(kRecBlock), 0, st, r);
+            VA_LAUNCH_CHECK("jpeg_reconstruct_kernel");
+            continue;
+        }
+        const PlaneArgs cp{coef, qtables, planes, k * 2 * g.mcus, g.bx, g.by, g.luma};
+        hipLaunchKernelGGL(jpeg_chroma_planes_kernel, blocks_of(cp.nblocks), dim3(kRecBlock), 0, st, cp);
+        VA_LAUNCH_CHECK("jpeg_chroma_planes_kernel");
+        const PixelArgs p{coef, qtables, planes, frames, k * g.mcus * g.luma, h, w, g.bx, g.by};
+        if (luma_v == 2)
+            hipLaunchKernelGGL(jpeg_pixels_kernel<2>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
+        else
+            hipLaunchKernelGGL(jpeg_pixels_kernel<1>, blocks_of(p.nblocks), dim3(kRecBlock), 0, st, p);
+        VA_LAUNCH_CHECK("jpeg_pixels_kernel");
+    }
+    return VA_OK;
+}
+
+}  // extern "C"

@@ -96,33 +96,46 @@ __global__ __launch_bounds__(64) void contour_moments_ragged_kernel(const void *
 
 }  // namespace
 
-int launch_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
-                           int is_float, double *out, hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_contour_moments(const void *points, const int32_t *npoints, int n, int max_points,
+                       int is_float, double *moments_out, void *stream)
 {
-    VA_REQUIRE(points && out && n >= 0 && max_points > 0, "contour_moments: bad argument");
+    VA_ENTER();
+    VA_REQUIRE(points && moments_out, "va_contour_moments: NULL argument");
+    VA_REQUIRE(n >= 0 && max_points > 0, "va_contour_moments: bad shape (%d contours, %d points)", n,
+               max_points);
     if (n == 0)
         return VA_OK;
+    hipStream_t st = as_stream(stream);
     if (is_float)
-        contour_moments_kernel<true><<<n, 64, 0, st>>>(points, npoints, max_points, out);
+        contour_moments_kernel<true><<<n, 64, 0, st>>>(points, npoints, max_points, moments_out);
     else
-        contour_moments_kernel<false><<<n, 64, 0, st>>>(points, npoints, max_points, out);
+        contour_moments_kernel<false><<<n, 64, 0, st>>>(points, npoints, max_points, moments_out);
     VA_LAUNCH_CHECK("contour_moments_kernel");
     return VA_OK;
 }
 
-int launch_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float, double *out,
-                                  hipStream_t st)
+int va_contour_moments_ragged(const void *points, const int64_t *point_off, int64_t m, int is_float,
+                              double *moments_out, void *stream)
 {
-    VA_REQUIRE(points && point_off && out && m >= 0, "contour_moments_ragged: bad argument");
+    VA_ENTER();
+    VA_REQUIRE(m >= 0, "va_contour_moments_ragged: negative count (%lld contours)", (long long)m);
     if (m == 0)
         return VA_OK;
+    VA_REQUIRE(points && point_off && moments_out, "va_contour_moments_ragged: NULL argument");
+    hipStream_t st = as_stream(stream);
     const int grid = (int)(m < (1 << 20) ? m : (1 << 20));
     if (is_float)
-        contour_moments_ragged_kernel<true><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, out);
+        contour_moments_ragged_kernel<true><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, moments_out);
     else
-        contour_moments_ragged_kernel<false><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, out);
+        contour_moments_ragged_kernel<false><<<grid, 64, 0, st>>>(points, (const long long *)point_off, m, moments_out);
     VA_LAUNCH_CHECK("contour_moments_ragged_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -378,8 +378,7 @@ OfLayout of_layout(int n, int h, int w, const std::vector<OfLevel> &lv)
     return L;
 }
 
-}  // namespace
-
+// g, xg, xxg: 2 poly_n + 1 floats (offsets -poly_n..poly_n), ig: ig11, ig03, ig33, ig55
 int farneback_poly_consts(int n, double sigma, float *g, float *xg, float *xxg, double ig[4])
 {
     VA_REQUIRE(n == 5 || n == 7, "optical flow: poly_n must be 5 or 7 (got %d)", n);
@@ -472,15 +471,40 @@ int farneback_check(int n, int h, int w, double pyr_scale, int levels, int winsi
     return VA_OK;
 }
 
-size_t farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels)
+}  // namespace
+
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_farneback_poly_consts(int poly_n, double poly_sigma, float *g, float *xg, float *xxg, double *ig)
 {
+    VA_REQUIRE(g && xg && xxg && ig, "va_farneback_poly_consts: NULL argument");
+    return farneback_poly_consts(poly_n, poly_sigma, g, xg, xxg, ig);
+}
+
+size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int levels, int winsize, int iterations,
+                                    int poly_n)
+{
+    if (farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, 0))
+        return 0;
     return of_layout(n, h, w, of_levels(h, w, pyr_scale, levels)).total;
 }
 
-int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
-                        int winsize, int iterations, int poly_n, double poly_sigma, float *flow_out,
-                        float *mag_out, void *ws, size_t ws_bytes, hipStream_t st)
+int va_optical_flow_farneback(const void *frames, int dtype, int n, int h, int w, double pyr_scale, int levels,
+                              int winsize, int iterations, int poly_n, double poly_sigma, int flags, float *flow_out,
+                              float *mag_out, void *ws, size_t ws_bytes, void *stream)
 {
+    VA_ENTER();
+    int rc = farneback_check(n, h, w, pyr_scale, levels, winsize, iterations, poly_n, flags);
+    if (rc)
+        return rc;
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "optical flow: frames must be VA_U8 or VA_F32 (got dtype %d)", dtype);
+    VA_REQUIRE(frames, "optical flow: NULL frames");
+    VA_REQUIRE(flow_out || mag_out, "optical flow: flow_out and mag_out are both NULL");
+    hipStream_t st = as_stream(stream);
     const std::vector<OfLevel> lv = of_levels(h, w, pyr_scale, levels);
     const OfLayout L = of_layout(n, h, w, lv);
     if (!ws || ws_bytes < L.total) {
@@ -491,7 +515,7 @@ int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, doub
     {
         float g[2 * kMaxPolyN + 1], xg[2 * kMaxPolyN + 1], xxg[2 * kMaxPolyN + 1];
         double ig[4];
-        int rc = farneback_poly_consts(poly_n, poly_sigma, g, xg, xxg, ig);
+        rc = farneback_poly_consts(poly_n, poly_sigma, g, xg, xxg, ig);
         if (rc)
             return rc;
         for (int k = 0; k <= poly_n; k++) {
@@ -528,7 +552,6 @@ int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, doub
     // stream has drained: the blocking copies are not ordered with a non-blocking stream, so neither an earlier
     // call's kernels nor this call's may still read a table region while it is written.
     VA_HIP(hipStreamSynchronize(st));
-    int rc;
     for (size_t i = 0; i < lv.size(); i++) {
         const OfLevel &l = lv[i];
         if (L.tab_img[i] != SIZE_MAX &&
@@ -597,4 +620,4 @@ int launch_optical_flow(const void *frames, int dtype, int n, int h, int w, doub
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -169,12 +169,39 @@ points_in_outlines_kernel(const double *__restrict__ points, const int64_t *__re
 template <int L>
 unsigned query_blocks(int64_t q) { return (unsigned)((q + kOutlineBlock / L - 1) / (kOutlineBlock / L)); }
 
+// the arguments the two outline calls share; `lanes` comes back as 8 or 64.  q == 0 and m == 0 are the caller's
+int outline_check(const char *name, int64_t npoints, int m, int64_t q, int &lanes)
+{
+    VA_REQUIRE(npoints >= 0 && m >= 0 && q >= 0, "%s: negative count (npoints %lld, m %d, q %lld)", name,
+               (long long)npoints, m, (long long)q);
+    VA_REQUIRE(lanes == 0 || lanes == 8 || lanes == 64, "%s: lanes is 0 (the library's choice), 8 or 64, got %d", name,
+               lanes);
+    if (lanes == 0)
+        lanes = m > 0 && npoints / m >= VA_OUTLINE_WIDE_MIN_POINTS ? 64 : 8;
+    VA_REQUIRE(q <= (int64_t)0x7FFFFFFF * (256 / lanes), "%s: %lld queries are more than one launch of %d lanes takes",
+               name, (long long)q, lanes);
+    return VA_OK;
+}
+
 }  // namespace
 
-int launch_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
-                    const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes,
-                    double *t_out, double *hits_out, int32_t *edge_out, int32_t *count_out, hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_ray_hits(const double *points, const int64_t *point_off, const uint8_t *closed, int64_t npoints, int m,
+                const double *anchors, const double *fars, const int32_t *index, int64_t q, int lanes, double *t_out,
+                double *hits_out, int32_t *edge_out, int32_t *count_out, void *stream)
 {
+    VA_ENTER();
+    int rc = outline_check("va_ray_hits", npoints, m, q, lanes);
+    if (rc || q == 0 || m == 0)
+        return rc;
+    VA_REQUIRE(points && point_off && closed && anchors && fars && index && t_out && hits_out && edge_out && count_out,
+               "va_ray_hits: NULL argument");
+    hipStream_t st = as_stream(stream);
     const dim3 block(kOutlineBlock);
     if (lanes == 8)
         hipLaunchKernelGGL(ray_hits_kernel<8>, dim3(query_blocks<8>(q)), block, 0, st, points, point_off, closed,
@@ -186,10 +213,15 @@ int launch_ray_hits(const double *points, const int64_t *point_off, const uint8_
     return VA_OK;
 }
 
-int launch_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                              const double *query, const int32_t *index, int64_t q, int lanes, uint8_t *inside_out,
-                              hipStream_t st)
+int va_points_in_outlines(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *query,
+                          const int32_t *index, int64_t q, int lanes, uint8_t *inside_out, void *stream)
 {
+    VA_ENTER();
+    int rc = outline_check("va_points_in_outlines", npoints, m, q, lanes);
+    if (rc || q == 0 || m == 0)
+        return rc;
+    VA_REQUIRE(points && point_off && query && index && inside_out, "va_points_in_outlines: NULL argument");
+    hipStream_t st = as_stream(stream);
     const dim3 block(kOutlineBlock);
     if (lanes == 8)
         hipLaunchKernelGGL(points_in_outlines_kernel<8>, dim3(query_blocks<8>(q)), block, 0, st, points, point_off,
@@ -201,4 +233,4 @@ int launch_points_in_outlines(const double *points, const int64_t *point_off, in
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -21,6 +21,10 @@ namespace va {
 
 namespace {
 
+constexpr int kFillMaxVerts = VA_FILL_MAX_VERTS;
+constexpr int kPolyMaxSide = VA_FILL_MAX_SIDE;
+constexpr int kDtMaxWidth = VA_DT_MAX_WIDTH;
+constexpr int kDtMaxHeight = VA_DT_MAX_HEIGHT;
 constexpr int kPolyBlock = 256;
 constexpr int kPolyWaves = kPolyBlock / kWave;
 constexpr int kDtBlock = 256;
@@ -287,29 +291,53 @@ dt_l2_5_kernel(const uint8_t *__restrict__ masks, const int32_t *__restrict__ sh
 
 }  // namespace
 
-int launch_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
-                     const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
-                     hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_fill_poly(const int32_t *verts, const int64_t *vert_off, int64_t nverts, const int32_t *boxes,
+                 const int64_t *out_off, int64_t out_elems, int m, int elem_size, void *out, int32_t *status,
+                 void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && nverts >= 0 && out_elems >= 0, "va_fill_poly: negative count (m %d, nverts %lld, out %lld)",
+               m, (long long)nverts, (long long)out_elems);
+    VA_REQUIRE(elem_size == 1 || elem_size == 4, "va_fill_poly: elem_size must be 1 (uint8) or 4 (int32), got %d",
+               elem_size);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(vert_off && boxes && out_off && status && (verts || nverts == 0) && (out || out_elems == 0),
+               "va_fill_poly: NULL argument");
     FillArgs a{verts, vert_off, nverts, boxes, out_off, out_elems, status};
     if (elem_size == 1)
-        hipLaunchKernelGGL(fill_poly_kernel<uint8_t>, dim3(m), dim3(kPolyBlock), 0, st, a,
+        hipLaunchKernelGGL(fill_poly_kernel<uint8_t>, dim3(m), dim3(kPolyBlock), 0, as_stream(stream), a,
                            static_cast<uint8_t *>(out));
     else
-        hipLaunchKernelGGL(fill_poly_kernel<int32_t>, dim3(m), dim3(kPolyBlock), 0, st, a,
+        hipLaunchKernelGGL(fill_poly_kernel<int32_t>, dim3(m), dim3(kPolyBlock), 0, as_stream(stream), a,
                            static_cast<int32_t *>(out));
     VA_LAUNCH_CHECK("fill_poly_kernel");
     return VA_OK;
 }
 
-int launch_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets,
-                                   int64_t total, int m, int max_w, float *out, int32_t *status, hipStream_t st)
+int va_distance_transform_l2_5(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
+                               int m, int max_w, float *out, int32_t *status, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_distance_transform_l2_5: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_w >= 0 && max_w <= kDtMaxWidth, "va_distance_transform_l2_5: max_w %d outside 0 .. %d", max_w,
+               kDtMaxWidth);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(shapes && offsets && status && ((masks && out) || total == 0),
+               "va_distance_transform_l2_5: NULL argument");
     const size_t lds = (size_t)3 * (max_w + 4) * sizeof(uint32_t);
-    hipLaunchKernelGGL(dt_l2_5_kernel, dim3(m), dim3(kDtBlock), lds, st, masks, shapes, offsets, total, max_w,
-                       out, status);
+    hipLaunchKernelGGL(dt_l2_5_kernel, dim3(m), dim3(kDtBlock), lds, as_stream(stream), masks, shapes, offsets, total,
+                       max_w, out, status);
     VA_LAUNCH_CHECK("dt_l2_5_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -397,7 +397,7 @@ void taps_tab(int ssize, int dsize, int ksize, bool area_mode, bool clamp_linear
 
 }  // namespace
 
-// scratch_bytes: size of the device buffer launch_resize_u8 needs for its tables
+// scratch_bytes: size of the device buffer launch_resize needs for its tables
 size_t resize_scratch_bytes(int sh, int sw, int dh, int dw)
 {
     const size_t ints = (size_t)dw + dh + 4 + (size_t)dw + dh + 4;
@@ -572,16 +572,49 @@ static int launch_resize(const T *src, T *dst, int n, int sh, int sw, int c, int
     return VA_OK;
 }
 
-int launch_resize_u8(const uint8_t *src, uint8_t *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
-                     void *scratch, hipStream_t st)
-{
-    return launch_resize<uint8_t>(src, dst, n, sh, sw, c, dh, dw, mode, scratch, st);
-}
-
 int launch_resize_f32(const float *src, float *dst, int n, int sh, int sw, int c, int dh, int dw, int mode,
                       void *scratch, hipStream_t st, ResizeStage stage)
 {
     return launch_resize<float>(src, dst, n, sh, sw, c, dh, dw, mode, scratch, st, stage);
 }
 
+// cv2.resize entry points (uint8 / float32 share everything but the kernels)
+template <class T>
+static int resize_any(const T *src, T *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
+                      int interpolation, void *stream, const char *who)
+{
+    VA_ENTER();
+    VA_REQUIRE(src && dst && src != dst, "%s: src/dst must be distinct non-NULL", who);
+    VA_REQUIRE(n >= 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && c >= 1 && c <= 4,
+               "%s: bad shape (%d,%d,%d,%d) -> (%d,%d)", who, n, src_h, src_w, c, dst_h, dst_w);
+    VA_REQUIRE((size_t)src_h * src_w < kMaxFramePixels && (size_t)dst_h * dst_w < kMaxFramePixels,
+               "%s: frames above 2^29 pixels are not supported", who);
+    VA_REQUIRE(interpolation >= VA_INTER_NEAREST && interpolation <= VA_INTER_LANCZOS4,
+               "%s: interpolation %d not supported (0 nearest, 1 linear, 2 cubic, 3 area, 4 lanczos4)", who,
+               interpolation);
+    ScratchLease scratch;
+    int rc = scratch.acquire(resize_scratch_bytes(src_h, src_w, dst_h, dst_w), as_stream(stream));
+    if (rc)
+        return rc;
+    return launch_resize<T>(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, scratch.ptr, as_stream(stream));
+}
+
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_resize_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
+                 int interpolation, void *stream)
+{
+    return resize_any<uint8_t>(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, stream, "va_resize_u8");
+}
+
+int va_resize_f32(const float *src, float *dst, int n, int src_h, int src_w, int c, int dst_h, int dst_w,
+                  int interpolation, void *stream)
+{
+    return resize_any<float>(src, dst, n, src_h, src_w, c, dst_h, dst_w, interpolation, stream, "va_resize_f32");
+}
+
+}  // extern "C"

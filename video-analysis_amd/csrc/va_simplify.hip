@@ -143,8 +143,8 @@ simplify_visvalingam_kernel(const double *__restrict__ points, const int64_t *__
     status[k] = st;
 }
 
-}  // namespace
-
+// Visvalingam's workspace: the heap and the two link tables
+struct SimplifyLayout { size_t heap, prev, next, total; };
 SimplifyLayout simplify_layout(int64_t npoints)
 {
     Carve c;
@@ -152,28 +152,71 @@ SimplifyLayout simplify_layout(int64_t npoints)
     return {c.take(table), c.take(table), c.take(table), c.total};
 }
 
-int launch_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
-                        uint8_t *keep, int32_t *out_count, int32_t *status, hipStream_t st)
+// the arguments the two simplifiers share; m == 0 is the caller's
+int simplify_check(const char *name, const double *points, const int64_t *point_off, int64_t npoints, int m,
+                   const double *tol, const uint8_t *keep, const int32_t *out_count, const int32_t *status)
 {
+    VA_REQUIRE(npoints >= 0 && m >= 0, "%s: negative count (npoints %lld, m %d)", name, (long long)npoints, m);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(points && point_off && tol && keep && out_count && status, "%s: NULL argument", name);
+    VA_REQUIRE(aligned(points, 8) && aligned(point_off, 8) && aligned(tol, 8) && aligned(out_count, 4) &&
+                   aligned(status, 4),
+               "%s: float64 and int64 buffers must be 8-byte aligned, int32 buffers 4-byte aligned", name);
+    return VA_OK;
+}
+
+}  // namespace
+
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_simplify_rdp(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *eps,
+                    uint8_t *keep, int32_t *out_count, int32_t *status, void *stream)
+{
+    VA_ENTER();
+    const int rc = simplify_check("va_simplify_rdp", points, point_off, npoints, m, eps, keep, out_count, status);
+    if (rc || m == 0)
+        return rc;
     for (int64_t first = 0; first < m; first += kRdpMaxGrid) {
         const unsigned blocks = (unsigned)(m - first < kRdpMaxGrid ? m - first : kRdpMaxGrid);
-        hipLaunchKernelGGL(simplify_rdp_kernel, dim3(blocks), dim3(kWave), 0, st, points, point_off, npoints, first,
-                           eps, keep, out_count, status);
+        hipLaunchKernelGGL(simplify_rdp_kernel, dim3(blocks), dim3(kWave), 0, as_stream(stream), points, point_off,
+                           npoints, first, eps, keep, out_count, status);
         VA_LAUNCH_CHECK("simplify_rdp_kernel");
     }
     return VA_OK;
 }
 
-int launch_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m,
-                                const double *thr, int closed, uint8_t *keep, int32_t *out_count, int32_t *status,
-                                void *ws, hipStream_t st)
+size_t va_simplify_visvalingam_workspace_bytes(int64_t npoints)
 {
+    return npoints < 0 ? 256 : simplify_layout(npoints).total;
+}
+
+int va_simplify_visvalingam(const double *points, const int64_t *point_off, int64_t npoints, int m, const double *thr,
+                            int closed, uint8_t *keep, int32_t *out_count, int32_t *status, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(closed == 0 || closed == 1, "va_simplify_visvalingam: closed is 0 (lines) or 1 (rings), got %d", closed);
+    const int rc = simplify_check("va_simplify_visvalingam", points, point_off, npoints, m, thr, keep, out_count,
+                                  status);
+    if (rc || m == 0)
+        return rc;
+    VA_REQUIRE(workspace, "va_simplify_visvalingam: NULL argument");
+    VA_REQUIRE(aligned(workspace, 8), "va_simplify_visvalingam: the workspace must be 8-byte aligned");
+    VA_REQUIRE(workspace_bytes >= va_simplify_visvalingam_workspace_bytes(npoints),
+               "va_simplify_visvalingam: workspace of %zu bytes < required %zu", workspace_bytes,
+               va_simplify_visvalingam_workspace_bytes(npoints));
     const SimplifyLayout lay = simplify_layout(npoints);
-    hipLaunchKernelGGL(simplify_visvalingam_kernel, dim3((unsigned)cdiv(m, kWave)), dim3(kWave), 0, st, points,
-                       point_off, npoints, m, thr, closed, keep, out_count, status, at<int32_t>(ws, lay.heap),
-                       at<int32_t>(ws, lay.prev), at<int32_t>(ws, lay.next));
+    hipLaunchKernelGGL(simplify_visvalingam_kernel, dim3((unsigned)cdiv(m, kWave)), dim3(kWave), 0, as_stream(stream),
+                       points, point_off, npoints, m, thr, closed, keep, out_count, status,
+                       at<int32_t>(workspace, lay.heap), at<int32_t>(workspace, lay.prev),
+                       at<int32_t>(workspace, lay.next));
     VA_LAUNCH_CHECK("simplify_visvalingam_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

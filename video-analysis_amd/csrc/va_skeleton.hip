@@ -535,8 +535,10 @@ __global__ void __launch_bounds__(kBlock) skel_walk_write(const uint8_t *adj, It
     }
 }
 
-}  // namespace
-
+// the workspace holds per pixel the forest, the anchor key and the tally of its node (zeroed per call), the adjacency
+// and ownership masks, the point counts and the point offsets, then the scan's block sums
+struct SkeletonLayout { size_t zeroed, anchor, tally, zeroed_bytes, forest, adj, owned, npts, point_base, sums,
+                        first_node, total; };
 SkeletonLayout skeleton_layout(int64_t total, int m)
 {
     const size_t px = (size_t)(total > 0 ? total : 1);
@@ -558,19 +560,49 @@ SkeletonLayout skeleton_layout(int64_t total, int m)
     return L;
 }
 
-int launch_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
-                          int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
-                          va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
-                          int64_t cap_points, void *ws, hipStream_t st)
+}  // namespace
+
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+size_t va_skeleton_graph_workspace_bytes(int64_t total, int m)
 {
+    if (total < 0 || m < 0)
+        return 256;
+    return skeleton_layout(total, m).total;
+}
+
+int va_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total, int m,
+                      int32_t *counts, int64_t *totals, va_skeleton_node *nodes, int64_t cap_nodes,
+                      va_skeleton_edge *edges, int64_t *point_off, int64_t cap_edges, int32_t *points,
+                      int64_t cap_points, void *workspace, size_t workspace_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_skeleton_graph: negative count (m %d, total %lld)", m, (long long)total);
+    VA_REQUIRE(total < ((int64_t)1 << 31) - 2, "va_skeleton_graph: 2^31 - 2 or more packed elements are not supported");
+    VA_REQUIRE(masks && shapes && offsets && counts && totals && nodes && edges && point_off && points && workspace,
+               "va_skeleton_graph: NULL argument");
+    VA_REQUIRE(cap_nodes >= 0 && cap_edges >= 0 && cap_points >= 0,
+               "va_skeleton_graph: negative capacity (%lld nodes, %lld edges, %lld points)", (long long)cap_nodes,
+               (long long)cap_edges, (long long)cap_points);
+    VA_REQUIRE(aligned(points, 8) && aligned(nodes, 4) && aligned(edges, 8) && aligned(point_off, 8) &&
+                   aligned(totals, 8) && aligned(counts, 4) && aligned(workspace, 8),
+               "va_skeleton_graph: points, edge records, offsets, totals and workspace must be 8-byte aligned");
+    VA_REQUIRE(workspace_bytes >= va_skeleton_graph_workspace_bytes(total, m),
+               "va_skeleton_graph: workspace of %zu bytes < required %zu", workspace_bytes,
+               va_skeleton_graph_workspace_bytes(total, m));
+    hipStream_t st = as_stream(stream);
     const SkeletonLayout L = skeleton_layout(total, m);
     const Items it{shapes, offsets, total, m};
-    uint32_t *P = at<uint32_t>(ws, L.forest), *anchor = at<uint32_t>(ws, L.anchor);
-    unsigned long long *tally = at<unsigned long long>(ws, L.tally);
-    uint8_t *adj = at<uint8_t>(ws, L.adj), *owned = at<uint8_t>(ws, L.owned);
-    int32_t *npts = at<int32_t>(ws, L.npts);
-    long long *point_base = at<long long>(ws, L.point_base), *sums = at<long long>(ws, L.sums);
-    long long *first_node = at<long long>(ws, L.first_node);
+    uint32_t *P = at<uint32_t>(workspace, L.forest), *anchor = at<uint32_t>(workspace, L.anchor);
+    unsigned long long *tally = at<unsigned long long>(workspace, L.tally);
+    uint8_t *adj = at<uint8_t>(workspace, L.adj), *owned = at<uint8_t>(workspace, L.owned);
+    int32_t *npts = at<int32_t>(workspace, L.npts);
+    long long *point_base = at<long long>(workspace, L.point_base), *sums = at<long long>(workspace, L.sums);
+    long long *first_node = at<long long>(workspace, L.first_node);
 
     if (m > 0)
         VA_HIP(hipMemsetAsync(counts, 0, (size_t)m * 2 * sizeof(int32_t), st));
@@ -579,7 +611,7 @@ int launch_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int
         VA_HIP(hipMemsetAsync(point_off, 0, sizeof(int64_t), st));
         return VA_OK;
     }
-    VA_HIP(hipMemsetAsync(at(ws, L.zeroed), 0, L.zeroed_bytes, st));
+    VA_HIP(hipMemsetAsync(at(workspace, L.zeroed), 0, L.zeroed_bytes, st));
     const int grid = cdiv(total, kBlock), sgrid = cdiv(total, kScanBlock);
     skel_classify<<<grid, kBlock, 0, st>>>(masks, it, adj, P);
     VA_LAUNCH_CHECK("skel_classify");
@@ -607,4 +639,4 @@ int launch_skeleton_graph(const uint8_t *masks, const int32_t *shapes, const int
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -124,6 +124,10 @@ sobel5_f64_kernel(const T *__restrict__ src, double *__restrict__ fx, double *__
 
 // ------------------------------------------------------------------------------------------- snake
 constexpr int kSnakeBlock = 256;
+// contours of up to kSnakeLdsMaxN points keep their matrix in LDS, longer ones read it from global memory;
+// kSnakeMaxN is the longest contour a call takes
+constexpr int kSnakeLdsMaxN = 128;
+constexpr int kSnakeMaxN = 1024;
 
 struct SnakeArgs {
     const double *fx, *fy;
@@ -308,27 +312,7 @@ snake_kernel(SnakeArgs a)
     }
 }
 
-}  // namespace
-
-int launch_sobel5_f64(const void *src, int dtype, double *fx, double *fy, int n, int h, int w, hipStream_t st)
-{
-    const int vec2 = (w % 2 == 0) && ((uintptr_t)fx % 16 == 0) && ((uintptr_t)fy % 16 == 0);
-    for (int f0 = 0; f0 < n; f0 += 65535) {
-        const int k = n - f0 < 65535 ? n - f0 : 65535;
-        const size_t o = (size_t)f0 * h * w;
-        dim3 grid(cdiv(w, kSobTW), cdiv(h, kSobTH), k);
-        double *ox = fx ? fx + o : nullptr, *oy = fy ? fy + o : nullptr;
-        if (dtype == VA_U8)
-            hipLaunchKernelGGL(sobel5_f64_kernel<uint8_t>, grid, dim3(kSobBlock), 0, st,
-                               static_cast<const uint8_t *>(src) + o, ox, oy, h, w, vec2);
-        else
-            hipLaunchKernelGGL(sobel5_f64_kernel<float>, grid, dim3(kSobBlock), 0, st,
-                               static_cast<const float *>(src) + o, ox, oy, h, w, vec2);
-        VA_LAUNCH_CHECK("sobel5_f64_kernel");
-    }
-    return VA_OK;
-}
-
+// shapes, offsets, total: the planes are the items of a ragged buffer (n of them; h, w unused), null for a stack
 int launch_active_contour(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
                           int64_t total, int n, int h, int w, int m, int max_points, const int32_t *npts,
                           const int32_t *frame, const double *mats, const int64_t *mat_off, int64_t mats_count,
@@ -351,4 +335,90 @@ int launch_active_contour(const double *fx, const double *fy, const int32_t *sha
     return VA_OK;
 }
 
+}  // namespace
+
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_sobel5_f64(const void *src, int dtype, double *fx_out, double *fy_out, int n, int h, int w, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32, "va_sobel5_f64: frames must be VA_U8 or VA_F32 (got dtype %d)",
+               dtype);
+    VA_REQUIRE(src && (fx_out || fy_out), "va_sobel5_f64: NULL frames, or fx_out and fy_out both NULL");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && (size_t)h * w < kMaxFramePixels, "va_sobel5_f64: bad shape (%d, %d, %d)",
+               n, h, w);
+    if (n == 0)
+        return VA_OK;
+    hipStream_t st = as_stream(stream);
+    const int vec2 = (w % 2 == 0) && ((uintptr_t)fx_out % 16 == 0) && ((uintptr_t)fy_out % 16 == 0);
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int k = n - f0 < 65535 ? n - f0 : 65535;
+        const size_t o = (size_t)f0 * h * w;
+        dim3 grid(cdiv(w, kSobTW), cdiv(h, kSobTH), k);
+        double *ox = fx_out ? fx_out + o : nullptr, *oy = fy_out ? fy_out + o : nullptr;
+        if (dtype == VA_U8)
+            hipLaunchKernelGGL(sobel5_f64_kernel<uint8_t>, grid, dim3(kSobBlock), 0, st,
+                               static_cast<const uint8_t *>(src) + o, ox, oy, h, w, vec2);
+        else
+            hipLaunchKernelGGL(sobel5_f64_kernel<float>, grid, dim3(kSobBlock), 0, st,
+                               static_cast<const float *>(src) + o, ox, oy, h, w, vec2);
+        VA_LAUNCH_CHECK("sobel5_f64_kernel");
+    }
+    return VA_OK;
+}
+
+int va_active_contour(const double *fx, const double *fy, int n, int h, int w, int m, int max_points,
+                      const int32_t *npts, const int32_t *frame, const double *mats, const int64_t *mat_offset,
+                      int64_t mats_count, const uint8_t *anchor_flags, const double *anchor_vals, double gamma,
+                      double tol_gamma, int max_iterations, double *pts_inout, int32_t *iterations_out,
+                      double *total_variation_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n > 0 && h >= 2 && w >= 2 && (size_t)h * w < kMaxFramePixels,
+               "va_active_contour: bad gradient shape (%d, %d, %d): frames need h, w >= 2", n, h, w);
+    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
+               "va_active_contour: bad contour table (%d contours of up to %d points; at most %d points)", m,
+               max_points, kSnakeMaxN);
+    VA_REQUIRE(max_iterations >= 1, "va_active_contour: max_iterations must be >= 1 (got %d)", max_iterations);
+    VA_REQUIRE(mats_count >= 0, "va_active_contour: negative matrix table size");
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(fx && fy && npts && frame && mats && mat_offset && pts_inout && iterations_out && total_variation_out,
+               "va_active_contour: NULL argument");
+    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour: anchor flags without anchor values");
+    return launch_active_contour(fx, fy, nullptr, nullptr, 0, n, h, w, m, max_points, npts, frame, mats, mat_offset,
+                                 mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations, pts_inout,
+                                 iterations_out, total_variation_out, as_stream(stream));
+}
+
+int va_active_contour_ragged(const double *fx, const double *fy, const int32_t *shapes, const int64_t *offsets,
+                             int64_t total, int n_items, int m, int max_points, const int32_t *npts,
+                             const int32_t *item, const double *mats, const int64_t *mat_offset, int64_t mats_count,
+                             const uint8_t *anchor_flags, const double *anchor_vals, double gamma, double tol_gamma,
+                             int max_iterations, double *pts_inout, int32_t *iterations_out,
+                             double *total_variation_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n_items >= 0 && total >= 0, "va_active_contour_ragged: negative count (n_items %d, total %lld)",
+               n_items, (long long)total);
+    VA_REQUIRE(m >= 0 && max_points >= 1 && max_points <= kSnakeMaxN,
+               "va_active_contour_ragged: bad contour table (%d contours of up to %d points; at most %d points)", m,
+               max_points, kSnakeMaxN);
+    VA_REQUIRE(max_iterations >= 1, "va_active_contour_ragged: max_iterations must be >= 1 (got %d)", max_iterations);
+    VA_REQUIRE(mats_count >= 0, "va_active_contour_ragged: negative matrix table size");
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(fx && fy && shapes && offsets && npts && item && mats && mat_offset && pts_inout && iterations_out &&
+                   total_variation_out,
+               "va_active_contour_ragged: NULL argument");
+    VA_REQUIRE(!anchor_flags || anchor_vals, "va_active_contour_ragged: anchor flags without anchor values");
+    return launch_active_contour(fx, fy, shapes, offsets, total, n_items, 0, 0, m, max_points, npts, item, mats,
+                                 mat_offset, mats_count, anchor_flags, anchor_vals, gamma, tol_gamma, max_iterations,
+                                 pts_inout, iterations_out, total_variation_out, as_stream(stream));
+}
+
+}  // extern "C"

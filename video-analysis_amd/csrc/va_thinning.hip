@@ -28,6 +28,9 @@ namespace va {
 
 namespace {
 
+constexpr int kThinResidentMaxWords = VA_THIN_RESIDENT_MAX_WORDS;
+constexpr int kThinMaxK = VA_THIN_MAX_SUB_ITERATIONS;
+constexpr int kThinMaxPoll = VA_THIN_MAX_POLL;
 constexpr int kThinBlock = 256;
 constexpr int kThinWaves = kThinBlock / kWave;
 constexpr int kTileRows = 64, kTileWordsX = 16;                 // the LDS window of the tiled path
@@ -272,36 +275,80 @@ TiledLayout tiled_layout(int n, int h, int w)
 
 }  // namespace
 
-int launch_guo_hall_resident(const uint8_t *src, const int32_t *shapes, const int64_t *offsets, int64_t total,
-                             int m, int max_words, uint8_t *dst, int32_t *iterations, int32_t *status,
-                             hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_guo_hall_thinning_batch(const uint8_t *masks, const int32_t *shapes, const int64_t *offsets, int64_t total,
+                               int m, int max_words, uint8_t *out, int32_t *iterations_out, int32_t *status,
+                               void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(m >= 0 && total >= 0, "va_guo_hall_thinning_batch: negative count (m %d, total %lld)", m,
+               (long long)total);
+    VA_REQUIRE(max_words >= 0 && max_words <= kThinResidentMaxWords,
+               "va_guo_hall_thinning_batch: max_words %d outside 0 .. %d", max_words, kThinResidentMaxWords);
+    if (m == 0)
+        return VA_OK;
+    VA_REQUIRE(masks && shapes && offsets && out && iterations_out && status,
+               "va_guo_hall_thinning_batch: NULL argument");
+    hipStream_t st = as_stream(stream);
     const size_t lds = ((size_t)max_words + 2) * sizeof(uint32_t);
     const dim3 grid(m), block(kThinBlock);
     if (max_words <= 4 * kThinBlock)
-        hipLaunchKernelGGL(gh_resident_kernel<4>, grid, block, lds, st, src, shapes, offsets, total, max_words, dst,
-                           iterations, status);
+        hipLaunchKernelGGL(gh_resident_kernel<4>, grid, block, lds, st, masks, shapes, offsets, total, max_words, out,
+                           iterations_out, status);
     else if (max_words <= 16 * kThinBlock)
-        hipLaunchKernelGGL(gh_resident_kernel<16>, grid, block, lds, st, src, shapes, offsets, total, max_words, dst,
-                           iterations, status);
+        hipLaunchKernelGGL(gh_resident_kernel<16>, grid, block, lds, st, masks, shapes, offsets, total, max_words, out,
+                           iterations_out, status);
     else
-        hipLaunchKernelGGL(gh_resident_kernel<kThinResidentMaxWords / kThinBlock>, grid, block, lds, st, src, shapes,
-                           offsets, total, max_words, dst, iterations, status);
+        hipLaunchKernelGGL(gh_resident_kernel<kThinResidentMaxWords / kThinBlock>, grid, block, lds, st, masks, shapes,
+                           offsets, total, max_words, out, iterations_out, status);
     VA_LAUNCH_CHECK("gh_resident_kernel");
     return VA_OK;
 }
 
-size_t guo_hall_tiled_scratch_bytes(int n, int h, int w)
+size_t va_guo_hall_thinning_scratch_bytes(int n, int h, int w)
 {
+    if (n <= 0 || h <= 0 || w <= 0 || n > 65535 || h > VA_THIN_MAX_ROWS || (size_t)h * (size_t)w >= kMaxFramePixels ||
+        (size_t)n * h * words_per_row(w) >= ((size_t)1 << 31))
+        return 0;
     return tiled_layout(n, h, w).total;
 }
 
-int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, int h, int w, int K, int poll,
-                       int32_t *iterations_out, int32_t *stats_out, hipStream_t st)
+int va_guo_hall_thinning_u8(const uint8_t *src, void *scratch, size_t scratch_bytes, uint8_t *dst, int n, int h,
+                            int w, int sub_iterations, int poll_period, int32_t *iterations_out,
+                            int32_t *stats_out, void *stream)
 {
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_guo_hall_thinning_u8: bad shape (%d, %d, %d)", n, h, w);
+    VA_REQUIRE(n <= kMaxGridYZ, "va_guo_hall_thinning_u8: %d frames, at most 65535 frames in one call are supported",
+               n);
+    VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels,
+               "va_guo_hall_thinning_u8: frames above 2^29 pixels are not supported");
+    // grid.y = ceil(h / (64 - 2 K)) <= 65535 for every K, and the pack / unpack grids count words in 32 bits
+    VA_REQUIRE(h <= VA_THIN_MAX_ROWS, "va_guo_hall_thinning_u8: %d rows, at most %d are supported", h,
+               VA_THIN_MAX_ROWS);
+    VA_REQUIRE((size_t)n * h * words_per_row(w) < ((size_t)1 << 31),
+               "va_guo_hall_thinning_u8: a stack of 2^31 or more packed words is not supported");
+    const int K = sub_iterations ? sub_iterations : 16, poll = poll_period ? poll_period : 2;
+    VA_REQUIRE(K >= 2 && K <= kThinMaxK && K % 2 == 0,
+               "va_guo_hall_thinning_u8: sub_iterations %d is not an even number in 2 .. %d", K, kThinMaxK);
+    VA_REQUIRE(poll >= 1 && poll <= kThinMaxPoll, "va_guo_hall_thinning_u8: poll_period %d outside 1 .. %d", poll,
+               kThinMaxPoll);
+    if (stats_out)
+        stats_out[0] = stats_out[1] = 0;
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(src && scratch && dst, "va_guo_hall_thinning_u8: NULL argument");
+    const TiledLayout L = tiled_layout(n, h, w);
+    VA_REQUIRE(scratch_bytes >= L.total, "va_guo_hall_thinning_u8: scratch of %zu bytes, %zu needed", scratch_bytes,
+               L.total);
+    hipStream_t st = as_stream(stream);
     const int wpr = words_per_row(w), per_launch = K / 2, per_poll = poll * per_launch;
     const int64_t rows = (int64_t)n * h;
-    const TiledLayout L = tiled_layout(n, h, w);
     uint32_t *cur = at<uint32_t>(scratch, L.cur), *nxt = at<uint32_t>(scratch, L.nxt);
     uint32_t *flags = at<uint32_t>(scratch, L.flags);
     const bool fast = (w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0;
@@ -358,4 +405,4 @@ int run_guo_hall_tiled(const uint8_t *src, uint8_t *dst, void *scratch, int n, i
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

@@ -167,29 +167,57 @@ warp_affine_kernel(const uint8_t *__restrict__ frames, int n, int h, int w, int 
     }
 }
 
+// the arguments the two warp calls share; m == 0 is checked by the caller after this
+int warp_check(const char *name, int n, int h, int w, int m, int total_items, int64_t total_out)
+{
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: bad shape (%d, %d, %d)", name, n, h, w);
+    VA_REQUIRE((size_t)h * (size_t)w < kMaxFramePixels, "%s: frames above 2^29 pixels are not supported", name);
+    VA_REQUIRE(m >= 0 && total_out >= 0, "%s: negative count (m %d, total_out %lld)", name, m, (long long)total_out);
+    VA_REQUIRE(total_items >= m, "%s: %d work items for %d items (every item has at least one)", name, total_items,
+               m);
+    return VA_OK;
+}
+
 }  // namespace
 
-int launch_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
-                        const double *mats, const int32_t *shapes, const int64_t *out_off, const int32_t *prefix,
-                        int total_chunks, int64_t total_out, int32_t *sums, int32_t *status, hipStream_t st)
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_line_scan_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx, const double *mats,
+                    const int32_t *shapes, const int64_t *out_off, const int32_t *prefix, int total_chunks,
+                    int64_t total_out, int32_t *sums, int32_t *status, void *stream)
 {
+    VA_ENTER();
+    int rc = warp_check("va_line_scan_u8", n, h, w, m, total_chunks, total_out);
+    if (rc || m == 0)
+        return rc;
+    VA_REQUIRE(frames && frame_idx && mats && shapes && out_off && prefix && sums && status,
+               "va_line_scan_u8: NULL argument");
     const dim3 grid((unsigned)cdiv(total_chunks, kWarpWaves)), block(kWarpBlock);
-    hipLaunchKernelGGL(line_scan_kernel, grid, block, 0, st, frames, n, h, w, m, frame_idx, mats, shapes, out_off,
-                       prefix, total_chunks, total_out, sums, status);
+    hipLaunchKernelGGL(line_scan_kernel, grid, block, 0, as_stream(stream), frames, n, h, w, m, frame_idx, mats, shapes,
+                       out_off, prefix, total_chunks, total_out, sums, status);
     VA_LAUNCH_CHECK("line_scan_kernel");
     return VA_OK;
 }
 
-int launch_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx,
-                          const double *mats, const int32_t *shapes, const int32_t *flags, const int64_t *out_off,
-                          const int32_t *prefix, int total_tiles, int64_t total_out, uint8_t *out, int32_t *status,
-                          hipStream_t st)
+int va_warp_affine_u8(const uint8_t *frames, int n, int h, int w, int m, const int32_t *frame_idx, const double *mats,
+                      const int32_t *shapes, const int32_t *flags, const int64_t *out_off, const int32_t *prefix,
+                      int total_tiles, int64_t total_out, uint8_t *out, int32_t *status, void *stream)
 {
+    VA_ENTER();
+    int rc = warp_check("va_warp_affine_u8", n, h, w, m, total_tiles, total_out);
+    if (rc || m == 0)
+        return rc;
+    VA_REQUIRE(frames && frame_idx && mats && shapes && flags && out_off && prefix && out && status,
+               "va_warp_affine_u8: NULL argument");
     const dim3 grid((unsigned)total_tiles), block(kWarpBlock);
-    hipLaunchKernelGGL(warp_affine_kernel, grid, block, 0, st, frames, n, h, w, m, frame_idx, mats, shapes, flags,
-                       out_off, prefix, total_out, out, status);
+    hipLaunchKernelGGL(warp_affine_kernel, grid, block, 0, as_stream(stream), frames, n, h, w, m, frame_idx, mats,
+                       shapes, flags, out_off, prefix, total_out, out, status);
     VA_LAUNCH_CHECK("warp_affine_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"
