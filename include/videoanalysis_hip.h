@@ -845,6 +845,15 @@ int va_draw_u8(uint8_t *frames_dev, int n, int h, int w, int c, const va_draw_cm
 int va_jpeg_encode_u8(const uint8_t *frames_dev, int n, int h, int w, int c, const uint8_t *qtables_dev,
                       const uint8_t *header_dev, int header_bytes, int64_t *sizes_out_dev, int64_t *offsets_out_dev,
                       int64_t *totals_dev, uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
+/* The same with a luma sampling of luma_h x luma_v ("Subsampled Motion-JPEG encoding"): 1 x 1 writes
+ * the bytes of va_jpeg_encode_u8; 2 x 1 (4:2:2) and 2 x 2 (4:2:0) take c == 3 and write MCUs of luma_h luma_v luma
+ * blocks, Cb and Cr, whose chroma is the rounded box average, one restart interval and one workgroup per MCU row of
+ * 8 luma_v pixel rows.  header_dev is video.ops.jpeg_header(h, w, 3, quality, (luma_h, luma_v)).  VA_ERR_INVALID as
+ * above and in that order, then: a sampling other than 1 x 1, 2 x 1 and 2 x 2; a subsampled layout with c == 1. */
+int va_jpeg_encode_sampled_u8(const uint8_t *frames_dev, int n, int h, int w, int c, int luma_h, int luma_v,
+                              const uint8_t *qtables_dev, const uint8_t *header_dev, int header_bytes,
+                              int64_t *sizes_out_dev, int64_t *offsets_out_dev, int64_t *totals_dev,
+                              uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
 
 /* ------------------------------------------------------------------ A21 Motion-JPEG decoding
  * replaces  the frame-by-frame cv2.VideoCapture.read of VideoOpenCV.get_frame, video/io/backend_opencv.py, behind

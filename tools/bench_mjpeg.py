@@ -9,10 +9,13 @@
   composer  VideoComposer end to end into an AVI file (a tracker's calls, as tools/bench_composer.py makes them),
             next to the same calls with sink=None, which downloads every frame uncompressed; same process, same clip
   pillow    Pillow's encoder (libjpeg) on one core, a few frames, where Pillow exists
+  sampling  (--sampling: this leg alone) the RGB clips in 4:4:4, 4:2:2 and 4:2:0 (va_jpeg_encode_sampled_u8) in one
+            run: the three launches by HIP events on resident data, the device copy, the bytes per frame, and
+            ops.jpeg_encode with its download for each layout
 Times are the median of the repetitions.  One JSON line per leg, appended to profiles/mjpeg_bench.jsonl (or --out);
 a leg that did not run is written "not measured".
 Run on an MI355X:
-    python tools/bench_mjpeg.py [--reps 15] [--frames 256]"""
+    python tools/bench_mjpeg.py [--reps 15] [--frames 256] [--sampling]"""
 import argparse
 import io
 import json
@@ -33,9 +36,10 @@ ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--quality", type=int, default=90)
 ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow leg (0: not measured)")
 ap.add_argument("--legs", default="kernels,encode,composer,pillow")
+ap.add_argument("--sampling", action="store_true", help="run the sampling leg, and nothing else")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mjpeg_bench.jsonl"))
 args = ap.parse_args()
-LEGS = set(args.legs.split(","))
+LEGS = {"sampling"} if args.sampling else set(args.legs.split(","))
 N, H, W, Q = args.frames, args.height, args.width, args.quality
 
 
@@ -152,6 +156,43 @@ def main():
                             "bytes_out_per_frame": size // args.cpu_frames, "note": "libjpeg through Pillow, one core, 4:4:4"})
             emit(row)
     clips.clear()
+    if "sampling" in LEGS:
+        for noise in (False, True):
+            clip = scene(N, H, W, 3, rng, noise)
+            raw = clip.nbytes
+            frames = torch.from_numpy(clip).to(dev)
+            twin = torch.empty_like(frames)
+            _, copy_med = events(lambda: twin.copy_(frames))
+            del twin
+            info = torch.zeros(2 * N + 2, dtype=torch.int64, device=dev)
+            cap = raw + N * 4096
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            stack = ops.DeviceFrames.upload(clip)
+            base = None
+            for layout, (hh, vv) in ops.JPEG_SAMPLINGS.items():
+                head = np.frombuffer(ops.jpeg_header(H, W, 3, Q, (hh, vv)), np.uint8)
+                consts = torch.from_numpy(np.concatenate(ops.jpeg_tables(Q) + (head,))).to(dev)
+                tail = (consts.data_ptr(), consts.data_ptr() + 128, len(head), info.data_ptr() + 16 + 8 * N,
+                        info.data_ptr() + 8, info.data_ptr(), out.data_ptr(), cap, S)
+                if (hh, vv) == (1, 1):
+                    run = lambda: check(L.va_jpeg_encode_u8(frames.data_ptr(), N, H, W, 3, *tail))
+                else:
+                    run = lambda: check(L.va_jpeg_encode_sampled_u8(frames.data_ptr(), N, H, W, 3, hh, vv, *tail))
+                best, med = events(run)
+                total = int(info[0])
+                assert total <= cap
+                base = med if base is None else base
+                enc = wall(lambda: ops.jpeg_encode(stack, Q, ret_packed=True, sampling=(hh, vv)), args.reps)
+                emit({"leg": "sampling/rgb/%s/%s" % ("noise" if noise else "smooth", layout), "frames": N, "h": H, "w": W,
+                      "quality": Q, "ms_per_call_min": round(best, 4), "ms_per_call_median": round(med, 4),
+                      "of_the_444_time": round(med / base, 3), "frames_per_s": round(N / med * 1e3, 1),
+                      "bytes_out_per_frame": total // N, "raw_bytes_per_frame": raw // N,
+                      "memcpy_same_input_ms_median": round(copy_med, 4), "times_the_memcpy": round(med / copy_med, 2),
+                      "jpeg_encode_with_downloads_ms_median": round(enc, 2),
+                      "note": "count + scan + write launches by HIP events on resident frames; 4:4:4, the copy and the "
+                              "other layouts in one run; jpeg_encode: wall clock on a resident stack"})
+            stack.release()
+            del frames, out
     if "composer" in LEGS:
         rng = np.random.default_rng(41)
         for noise in (False, True):

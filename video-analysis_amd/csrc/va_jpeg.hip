@@ -15,7 +15,11 @@
 //
 // A segment is walked in chunks of 32 MCUs, so its length is not bounded by LDS.  Per chunk:
 //   A   each wave loads 8 MCUs, 8 (or 24) bytes of a pixel row per lane, converts colour and transforms block after
-//       block with one lane per sample: the row and column sums and the zigzag order are lane exchanges
+//       block with one lane per sample: the row and column sums and the zigzag order are lane exchanges.  In a
+//       subsampled layout (va_jpeg_encode_sampled_u8; DESIGN.md §9, "Subsampled Motion-JPEG encoding") a segment is
+//       8 V pixel rows and a chunk 24 (4:2:2) or 16 (4:2:0) MCUs of 16 pixels' width; a wave loads 8 V rows of 64 / V
+//       pixels, 4 / V MCUs, at a time, box-averages Cb and Cr in the lane and, for 4:2:0, with the lane of the
+//       neighbouring row, and gathers the samples of every block of the MCU from the lanes that hold them
 //   B1  one lane per coefficient: the length of its bit string (va_jpeg::coefficient_bits), summed per block
 //   --  a scan of the blocks' bit counts gives every block its bit position behind the chunk's carry
 //   B2  the same strings again, ORed into the chunk's bit buffer in LDS at block position + lane prefix
@@ -34,12 +38,16 @@ namespace {
 constexpr int kJpegBlock = 256;
 constexpr int kJpegWaves = kJpegBlock / kWave;
 constexpr int kGroupMcus = 8;                          // MCUs a wave loads at once
-constexpr int kChunkMcus = kGroupMcus * kJpegWaves;    // MCUs of a chunk
+constexpr int kChunkMcus = kGroupMcus * kJpegWaves;    // MCUs of a chunk of 1 x 1 sampling
+// MCUs of a chunk: at most 128 blocks, two entries a lane of the block-position scan; the subsampled layouts keep the
+// 96 blocks of 4:4:4, and with them its LDS
+constexpr int chunk_mcus(int hs, int vs) { return hs == 1 ? kChunkMcus : vs == 1 ? 24 : 16; }
+constexpr int mcu_blocks(int c, int hs, int vs) { return c == 1 ? 1 : hs * vs + 2; }
 // a block has at most 22 + 63 * 26 bits: a DC string of 11 + 11, and an AC coefficient behind a run r adds at most
 // 11 (r / 16) + 26 bits over its r + 1 lanes
 constexpr int kMaxBlockBits = 22 + 63 * 26;
 // words of a chunk's bit buffer: its blocks, the carry, the padding, and put_bits' reach
-constexpr int bit_words(int c) { return (kChunkMcus * c * kMaxBlockBits + 31 + 7) / 32 + 3; }
+constexpr int bit_words(int blocks) { return (blocks * kMaxBlockBits + 31 + 7) / 32 + 3; }
 constexpr int kScanBlock = 256;
 constexpr int kScanPerThread = 4;
 
@@ -102,15 +110,38 @@ __device__ __forceinline__ void load_pixels(const uint8_t *row, int x0, int w, u
     }
 }
 
-template <int C, bool WRITE>
+// one block, lane = 8 y + x holding its sample minus 128: the lane's coefficient in zigzag order, quantised by q[]
+__device__ __forceinline__ int16_t transform_block(int sample, const int (&t_row)[8], const int (&t_col)[8],
+                                                   const uint8_t *q, int zz_from, int lane)
+{
+    int sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        sum += t_row[i] * __shfl(sample, (lane & ~7) | i, kWave);
+    const int rows = va_jpeg::row_round(sum);            // lane = 8 y + k
+    sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        sum += t_col[i] * __shfl(rows, 8 * i + (lane & 7), kWave);
+    const int v = va_jpeg::quantise(sum, q[lane]);       // lane = 8 v + k
+    return (int16_t)__shfl(v, zz_from, kWave);
+}
+
+// C components with luma sampling HS x VS: <1, 1, 1> monochrome, <3, 1, 1> 4:4:4, <3, 2, 1> 4:2:2, <3, 2, 2> 4:2:0
+template <int C, int HS, int VS, bool WRITE>
 __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
 {
-    constexpr int kBitWords = bit_words(C);
-    __shared__ int16_t coef[kChunkMcus * C][64];
+    static_assert(C == 3 ? (HS == 1 || HS == 2) && (VS == 1 || VS == HS) : C == 1 && HS == 1 && VS == 1, "layout");
+    constexpr int HV = HS * VS, BPM = mcu_blocks(C, HS, VS);         // luma blocks and all blocks of an MCU
+    constexpr int kMcus = chunk_mcus(HS, VS), kBlocks = kMcus * BPM;
+    static_assert(kBlocks <= 2 * kWave, "the block-position scan takes two entries a lane");
+    constexpr int kBitWords = bit_words(kBlocks);
+    constexpr int CG = 8 / VS;           // 8-pixel column groups a wave loads at once: lane = CG * row + group
+    __shared__ int16_t coef[kBlocks][64];
     __shared__ uint32_t bitbuf[kBitWords];
     __shared__ uint32_t huff_dc[2][16], huff_ac[2][256];
     __shared__ uint8_t qt[2][64];
-    __shared__ int32_t block_bits[kChunkMcus * C];
+    __shared__ int32_t block_bits[kBlocks];
     __shared__ int32_t wave_total[kJpegWaves];
     __shared__ int32_t pred[3];
     __shared__ uint32_t chunk_end;
@@ -160,19 +191,77 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
         t_col[i] = va_jpeg::dct_at(lane >> 3, i);
     }
     const int zz_from = va_jpeg::zigzag_at(lane);
-    const int y_load = min(j * 8 + (lane >> 3), a.h - 1);
+    const int y_load = min(j * 8 * VS + lane / CG, a.h - 1);
     const uint8_t *row = a.frames + ((int64_t)frame * a.h + y_load) * a.w * C;
 
     uint32_t carry_bits = 0;             // bits of bitbuf[0] that belong to the previous chunk
     int64_t emitted = 0;                 // bytes of the segment so far
     __syncthreads();
 
-    for (int m0 = 0; m0 < a.mcus; m0 += kChunkMcus) {
-        const int cm = min(kChunkMcus, a.mcus - m0), nblk = cm * C;
-        const bool last = m0 + kChunkMcus >= a.mcus;
+    for (int m0 = 0; m0 < a.mcus; m0 += kMcus) {
+        const int cm = min(kMcus, a.mcus - m0), nblk = cm * BPM;
+        const bool last = m0 + kMcus >= a.mcus;
         // ---------------------------------------------------------------- A: transform
-        const int g = wave * kGroupMcus;
-        if (g < cm) {
+        if constexpr (HV > 1) {
+            constexpr int MW = CG / 2;   // MCUs a wave loads at once
+            const int cg = lane % CG;
+            // the real chroma rows from this segment's first on, and the real chroma columns
+            const int crows = (a.h + VS - 1) / VS - j * 8, ccols = (a.w + HS - 1) / HS;
+            for (int g = wave * MW; g < cm; g += kJpegWaves * MW) {
+                uint32_t px[6];          // the lane's 8 pixels of MCU g + cg / 2, row lane / CG, left or right half
+                const int mcu = min(m0 + g + (cg >> 1), a.mcus - 1);
+                load_pixels<3>(row, mcu * 16 + (cg & 1) * 8, a.w, px);
+                uint32_t luma[2] = {0, 0};           // the 8 Y samples as bytes
+                uint32_t sums[2][2] = {{0, 0}, {0, 0}};      // Cb, Cr: the 4 sums of horizontal pairs, 16 bits each
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int r = (px[(3 * i) / 4] >> (8 * ((3 * i) % 4))) & 255;
+                    const int gg = (px[(3 * i + 1) / 4] >> (8 * ((3 * i + 1) % 4))) & 255;
+                    const int b = (px[(3 * i + 2) / 4] >> (8 * ((3 * i + 2) % 4))) & 255;
+                    int yy, cb, cr;
+                    va_jpeg::ycbcr(r, gg, b, yy, cb, cr);
+                    luma[i / 4] |= (uint32_t)yy << (8 * (i % 4));
+                    sums[0][i / 4] += (uint32_t)cb << (16 * ((i / 2) % 2));
+                    sums[1][i / 4] += (uint32_t)cr << (16 * ((i / 2) % 2));
+                }
+                uint32_t chroma[2];                  // Cb, Cr: the 4 averages as bytes; both rows of a pair hold them
+#pragma unroll
+                for (int ch = 0; ch < 2; ch++) {
+                    chroma[ch] = 0;
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        uint32_t s = sums[ch][i];
+                        if constexpr (VS == 2)
+                            s += __shfl_xor(s, CG, kWave);           // the row below or above: no field overflows
+                        chroma[ch] |= (uint32_t)va_jpeg::box_average((int)(s & 0xFFFFu), HV) << (16 * i);
+                        chroma[ch] |= (uint32_t)va_jpeg::box_average((int)(s >> 16), HV) << (16 * i + 8);
+                    }
+                }
+                const int here = min(MW, cm - g);
+                const int crow = va_jpeg::edge_index(lane >> 3, crows);
+                for (int mi = 0; mi < here; mi++) {
+                    const int c0 = (m0 + g + mi) * 8;                // (c0 < ccols: the MCU exists)
+                    const int ccol = va_jpeg::edge_index(c0 + (lane & 7), ccols) - c0;
+#pragma unroll
+                    for (int k = 0; k < BPM; k++) {
+                        // lane = 8 y + x of the block
+                        int sample;
+                        if (k < HV) {
+                            const int src = ((k / HS) * 8 + (lane >> 3)) * CG + 2 * mi + k % HS;
+                            const uint32_t lo = __shfl(luma[0], src, kWave), hi = __shfl(luma[1], src, kWave);
+                            const int x = lane & 7;
+                            sample = (int)(((x < 4 ? lo : hi) >> (8 * (x & 3))) & 255u) - 128;
+                        } else {
+                            const int src = crow * VS * CG + 2 * mi + (ccol >> 2);
+                            const uint32_t v = __shfl(chroma[k - HV], src, kWave);
+                            sample = (int)((v >> (8 * (ccol & 3))) & 255u) - 128;
+                        }
+                        coef[(g + mi) * BPM + k][lane] =
+                            transform_block(sample, t_row, t_col, qt[k < HV ? 0 : 1], zz_from, lane);
+                    }
+                }
+            }
+        } else if (const int g = wave * kGroupMcus; g < cm) {
             uint32_t px[2 * C];          // the lane's 8 pixels of MCU g + (lane & 7), row lane >> 3
             const int mcu = min(m0 + g + (lane & 7), a.mcus - 1);
             load_pixels<C>(row, mcu * 8, a.w, px);
@@ -204,26 +293,17 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
                     const uint32_t lo = __shfl(comp[ch][0], src, kWave), hi = __shfl(comp[ch][1], src, kWave);
                     const int x = lane & 7;
                     const int sample = (int)(((x < 4 ? lo : hi) >> (8 * (x & 3))) & 255u) - 128;
-                    int sum = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++)
-                        sum += t_row[i] * __shfl(sample, (lane & ~7) | i, kWave);
-                    const int rows = va_jpeg::row_round(sum);            // lane = 8 y + k
-                    sum = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++)
-                        sum += t_col[i] * __shfl(rows, 8 * i + (lane & 7), kWave);
-                    const int q = va_jpeg::quantise(sum, qt[ch ? 1 : 0][lane]);   // lane = 8 v + k
-                    coef[(g + jj) * C + ch][lane] = (int16_t)__shfl(q, zz_from, kWave);
+                    coef[(g + jj) * C + ch][lane] = transform_block(sample, t_row, t_col, qt[ch ? 1 : 0], zz_from, lane);
                 }
             }
         }
         __syncthreads();
         // ---------------------------------------------------------------- B1: bits of every block
         for (int q = wave; q < nblk; q += kJpegWaves) {
-            const int ch = q % C, tab = ch ? 1 : 0;
+            const int k = q % BPM, ch = va_jpeg::block_component(k, HV), tab = ch ? 1 : 0;
+            const int back = va_jpeg::predictor_back(k, HV, BPM);
             const int v = coef[q][lane];
-            const int p = q >= C ? coef[q - C][0] : pred[ch];
+            const int p = q >= back ? coef[q - back][0] : pred[ch];
             const uint64_t nonzero = __ballot(v != 0);
             const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
             const int total = wave_sum(b.len);
@@ -245,13 +325,14 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
         }
         int next_pred = 0;
         if (tid < C)
-            next_pred = coef[(cm - 1) * C + tid][0];
+            next_pred = coef[(cm - 1) * BPM + HV - 1 + tid][0];      // the chunk's last block of component tid
         __syncthreads();
         // ---------------------------------------------------------------- B2: the strings into the bit buffer
         for (int q = wave; q < nblk; q += kJpegWaves) {
-            const int ch = q % C, tab = ch ? 1 : 0;
+            const int k = q % BPM, ch = va_jpeg::block_component(k, HV), tab = ch ? 1 : 0;
+            const int back = va_jpeg::predictor_back(k, HV, BPM);
             const int v = coef[q][lane];
-            const int p = q >= C ? coef[q - C][0] : pred[ch];
+            const int p = q >= back ? coef[q - back][0] : pred[ch];
             const uint64_t nonzero = __ballot(v != 0);
             const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
             const uint32_t pos = (uint32_t)(block_bits[q] + wave_inclusive(b.len, lane) - b.len);
@@ -381,6 +462,68 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
         sizes[f] = offsets[f + 1] - offsets[f];
 }
 
+template <bool WRITE>
+void launch_segments(int c, int hs, int vs, int64_t nsegs, hipStream_t st, const JpegArgs &a)
+{
+    const dim3 grid((unsigned)nsegs), block(kJpegBlock);
+    if (c == 1)
+        hipLaunchKernelGGL((jpeg_segment_kernel<1, 1, 1, WRITE>), grid, block, 0, st, a);
+    else if (hs == 1)
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 1, 1, WRITE>), grid, block, 0, st, a);
+    else if (vs == 1)
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 1, WRITE>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 2, WRITE>), grid, block, 0, st, a);
+}
+
+// both entry points; `sampled`: the luma sampling is an argument and checked
+int jpeg_encode(const char *what, bool sampled, const uint8_t *frames, int n, int h, int w, int c, int hs, int vs,
+                const uint8_t *qtables, const uint8_t *header, int header_bytes, int64_t *sizes_out,
+                int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out, int64_t cap_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
+               "%s: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", what, n, h, w, header_bytes,
+               (long long)cap_bytes);
+    VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
+    if (n == 0)
+        return VA_OK;
+    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
+               "%s: NULL argument", what);
+    VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
+               "%s: the int64 buffers must be 8-byte aligned", what);
+    VA_REQUIRE(h <= 65535 && w <= 65535, "%s: SOF0 holds 16-bit sizes, got %d x %d", what, w, h);
+    VA_REQUIRE((int64_t)n * ((h + 7) / 8) < ((int64_t)1 << 31), "%s: the stack has too many MCU rows for one launch",
+               what);
+    if (sampled) {
+        VA_REQUIRE((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)),
+                   "%s: the luma sampling is 1 x 1, 2 x 1 or 2 x 2, got %d x %d", what, hs, vs);
+        VA_REQUIRE(c == 3 || hs * vs == 1, "%s: luma sampling %d x %d needs 3 channels", what, hs, vs);
+    }
+    hipStream_t st = as_stream(stream);
+    const int nseg = (h + 8 * vs - 1) / (8 * vs);
+    const int64_t nsegs = (int64_t)n * nseg;
+    Carve ws;                                        // [seg_len | seg_start]
+    const size_t o_len = ws.take((size_t)nsegs * sizeof(int32_t));
+    const size_t o_start = ws.take(((size_t)nsegs + 1) * sizeof(int64_t));
+    ScratchLease scratch;
+    int rc = scratch.acquire(ws.total, st);
+    if (rc)
+        return rc;
+    int32_t *seg_len = at<int32_t>(scratch.ptr, o_len);
+    int64_t *seg_start = at<int64_t>(scratch.ptr, o_start);
+    const JpegArgs a{frames, n, h, w, nseg, (w + 8 * hs - 1) / (8 * hs), qtables, header, header_bytes, seg_len,
+                     seg_start, totals, bytes_out, cap_bytes};
+    launch_segments<false>(c, hs, vs, nsegs, st, a);
+    VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, header_bytes,
+                       seg_start, offsets_out, sizes_out, totals);
+    VA_LAUNCH_CHECK("jpeg_scan_kernel");
+    launch_segments<true>(c, hs, vs, nsegs, st, a);
+    VA_LAUNCH_CHECK("jpeg_segment_kernel (write)");
+    return VA_OK;
+}
+
 }  // namespace
 
 }  // namespace va
@@ -393,49 +536,18 @@ int va_jpeg_encode_u8(const uint8_t *frames, int n, int h, int w, int c, const u
                       int header_bytes, int64_t *sizes_out, int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out,
                       int64_t cap_bytes, void *stream)
 {
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
-               "va_jpeg_encode_u8: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", n, h, w,
-               header_bytes, (long long)cap_bytes);
-    VA_REQUIRE(c == 1 || c == 3, "va_jpeg_encode_u8: channels must be 1 or 3, got %d", c);
-    if (n == 0)
-        return VA_OK;
-    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
-               "va_jpeg_encode_u8: NULL argument");
-    VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
-               "va_jpeg_encode_u8: the int64 buffers must be 8-byte aligned");
-    VA_REQUIRE(h <= 65535 && w <= 65535, "va_jpeg_encode_u8: SOF0 holds 16-bit sizes, got %d x %d", w, h);
-    VA_REQUIRE((int64_t)n * ((h + 7) / 8) < ((int64_t)1 << 31),
-               "va_jpeg_encode_u8: the stack has too many MCU rows for one launch");
-    hipStream_t st = as_stream(stream);
-    const int nseg = (h + 7) / 8;
-    const int64_t nsegs = (int64_t)n * nseg;
-    Carve ws;                                        // [seg_len | seg_start]
-    const size_t o_len = ws.take((size_t)nsegs * sizeof(int32_t));
-    const size_t o_start = ws.take(((size_t)nsegs + 1) * sizeof(int64_t));
-    ScratchLease scratch;
-    int rc = scratch.acquire(ws.total, st);
-    if (rc)
-        return rc;
-    int32_t *seg_len = at<int32_t>(scratch.ptr, o_len);
-    int64_t *seg_start = at<int64_t>(scratch.ptr, o_start);
-    const JpegArgs a{frames, n, h, w, nseg, (w + 7) / 8, qtables, header, header_bytes, seg_len, seg_start, totals,
-                     bytes_out, cap_bytes};
-    const dim3 grid((unsigned)nsegs), block(kJpegBlock);
-    if (c == 1)
-        hipLaunchKernelGGL((jpeg_segment_kernel<1, false>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((jpeg_segment_kernel<3, false>), grid, block, 0, st, a);
-    VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, header_bytes,
-                       seg_start, offsets_out, sizes_out, totals);
-    VA_LAUNCH_CHECK("jpeg_scan_kernel");
-    if (c == 1)
-        hipLaunchKernelGGL((jpeg_segment_kernel<1, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((jpeg_segment_kernel<3, true>), grid, block, 0, st, a);
-    VA_LAUNCH_CHECK("jpeg_segment_kernel (write)");
-    return VA_OK;
+    return jpeg_encode("va_jpeg_encode_u8", false, frames, n, h, w, c, 1, 1, qtables, header, header_bytes, sizes_out,
+                       offsets_out, totals, bytes_out, cap_bytes, stream);
+}
+
+int va_jpeg_encode_sampled_u8(const uint8_t *frames, int n, int h, int w, int c, int luma_h, int luma_v,
+                              const uint8_t *qtables, const uint8_t *header, int header_bytes, int64_t *sizes_out,
+                              int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out, int64_t cap_bytes,
+                              void *stream)
+{
+    return jpeg_encode("va_jpeg_encode_sampled_u8", true, frames, n, h, w, c, luma_h, luma_v, qtables, header,
+                       header_bytes, sizes_out, offsets_out, totals, bytes_out, cap_bytes, stream);
 }
 
 }  // extern "C"
+

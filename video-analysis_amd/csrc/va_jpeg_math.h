@@ -1,8 +1,10 @@
 // va_jpeg_math.h -- the per-block arithmetic of the baseline JPEG encoder ("Motion-JPEG") as plain
 // inline C++ that compiles for the host and for the device: colour conversion, the integer DCT, the quantiser, the
-// Huffman strings of one coefficient, the bit writer and the byte stuffing.  va_jpeg.hip runs it with one lane per
-// coefficient of a block; tests/jpeg_shim.cpp compiles it with the host compiler (under sanitizers) into a serial
-// encoder whose bytes are the NumPy restatement's (tests/jpeg_checks.py).
+// Huffman strings of one coefficient, the bit writer and the byte stuffing, and what the subsampled layouts add: the box
+// average, the edge rule and the maps from a block's place in its MCU to its component and DC predictor.  va_jpeg.hip
+// runs it with one lane per coefficient of a block; tests/jpeg_shim.cpp and tests/jpeg_sampled_shim.cpp compile it with
+// the host compiler (under sanitizers) into serial encoders whose bytes are the NumPy restatements'
+// (tests/jpeg_checks.py, tests/jpeg_subsampled_checks.py: encode_frame).
 //
 // Integers only.  A block is 64 samples minus 128; T[k][n] = rint(2^13 A[k][n]) with A the orthonormal 8-point
 // DCT-II matrix.  The row pass keeps (sum + 1024) >> 11, four times the row coefficient; the column pass's sum is the
@@ -50,6 +52,24 @@ VA_JPEG_FN void ycbcr(int r, int g, int b, int &y, int &cb, int &cr)
     cb = (-11059 * r - 21709 * g + 32768 * b + 8421375) >> 16;
     cr = (32768 * r - 27439 * g - 5329 * b + 8421375) >> 16;
 }
+
+// ------------------------------------------------------------------------------------------------ sampling layouts
+// ("Subsampled Motion-JPEG encoding").  An MCU holds hv = H V luma blocks, then Cb, then Cr (one block,
+// hv = 1, in a monochrome file); k is a block's position in its MCU, bpm the blocks of an MCU.
+
+// a chroma sample of the H x V box: the sum of its hv pixels, rounded half up
+VA_JPEG_FN int box_average(int sum, int hv) { return (int)(((uint32_t)sum + (uint32_t)hv / 2) / (uint32_t)hv); }
+
+// index i of a plane padded by repeating the last of its `real` rows or columns
+VA_JPEG_FN int edge_index(int i, int real) { return i < real ? i : real - 1; }
+
+// the component of the block at position k: 0 luma, 1 Cb, 2 Cr
+VA_JPEG_FN int block_component(int k, int hv) { return k < hv ? 0 : k - hv + 1; }
+
+// how many blocks back in coding order the block lies whose DC predicts the block at position k: the luma block
+// before it, for the first luma block of an MCU the last one of the MCU before, for Cb and Cr the same component one
+// MCU back
+VA_JPEG_FN int predictor_back(int k, int hv, int bpm) { return k == 0 ? bpm - hv + 1 : k < hv ? 1 : bpm; }
 
 VA_JPEG_FN int row_round(int sum) { return (sum + 1024) >> 11; }
 

@@ -61,12 +61,15 @@ def _avi_header(size, fps, frames, movi_bytes, idx_bytes, largest):
 class VideoWriterMJPEG(object):
     """writes uint8 frames into a Motion-JPEG AVI file, `batch` frames per encoder call"""
 
-    def __init__(self, filename, size, fps, is_color=True, quality=90, batch=32, **kwargs):
-        """`size` = (width, height); `quality` 1 .. 100 (the IJG scale); further keyword arguments -- the codec
-        and bitrate of the reference's writers -- have no meaning here and are refused"""
+    def __init__(self, filename, size, fps, is_color=True, quality=90, batch=32, sampling=(1, 1), **kwargs):
+        """`size` = (width, height); `quality` 1 .. 100 (the IJG scale); `sampling` of a colour video: (1, 1) /
+        "4:4:4", (2, 1) / "4:2:2" or (2, 2) / "4:2:0" ("Subsampled Motion-JPEG encoding"); further
+        keyword arguments -- the codec and bitrate of the reference's writers -- have no meaning here and are
+        refused"""
         if kwargs:
-            raise TypeError("VideoWriterMJPEG: unknown arguments %s (the codec is MJPG; quality and batch are "
-                            "what can be set)" % ", ".join(sorted(kwargs)))
+            raise TypeError("VideoWriterMJPEG: unknown arguments %s (the codec is MJPG; quality, batch and sampling "
+                            "are what can be set)" % ", ".join(sorted(kwargs)))
+        self.sampling = ops.jpeg_sampling(sampling, 3 if is_color else 1, "VideoWriterMJPEG")
         if batch < 1:
             raise ValueError("batch must be positive")
         self.filename = os.fspath(filename)
@@ -132,7 +135,9 @@ class VideoWriterMJPEG(object):
             self._encode(stack)
 
     def _encode(self, stack):
-        blob, offsets = ops.jpeg_encode(stack, quality=self.quality, color=self.is_color, ret_packed=True)
+        layout = {} if self.sampling == (1, 1) else {"sampling": self.sampling}        # (1, 1): the call as it was
+        blob, offsets = ops.jpeg_encode(stack, quality=self.quality, color=self.is_color, ret_packed=True,
+                                        **layout)
         blob = np.asarray(blob, np.uint8)
         for k in range(len(offsets) - 1):
             data = blob[offsets[k]:offsets[k + 1]]

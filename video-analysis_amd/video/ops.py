@@ -2467,15 +2467,35 @@ def _jpeg_segment(marker, payload):
     return bytes([0xFF, marker, (len(payload) + 2) >> 8, (len(payload) + 2) & 255]) + bytes(payload)
 
 
-def jpeg_header(h, w, c, quality):
+JPEG_SAMPLINGS = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}      # the luma sampling (H, V) of a layout
+
+
+def jpeg_sampling(sampling, c=3, what="jpeg_sampling"):
+    """the luma sampling (H, V) of `sampling`: (1, 1), (2, 1), (2, 2) or "4:4:4", "4:2:2", "4:2:0"; a ValueError for
+    anything else and for a subsampled layout of c = 1 component (host only)"""
+    hv = JPEG_SAMPLINGS.get(sampling) if isinstance(sampling, str) else None
+    if hv is None and isinstance(sampling, (tuple, list)) and len(sampling) == 2:
+        if all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in sampling):
+            hv = (int(sampling[0]), int(sampling[1]))
+    if hv not in JPEG_SAMPLINGS.values():
+        raise ValueError("%s: the sampling is (1, 1), (2, 1), (2, 2), '4:4:4', '4:2:2' or '4:2:0', got %r"
+                         % (what, sampling))
+    if c == 1 and hv != (1, 1):
+        raise ValueError("%s: monochrome frames have no chroma to subsample (sampling %r)" % (what, sampling))
+    return hv
+
+
+def jpeg_header(h, w, c, quality, sampling=(1, 1)):
     """the bytes SOI .. SOS every frame's file starts with ("Motion-JPEG"): APP0 JFIF 1.01, one DQT per
-    table, SOF0 with 1 x 1 sampling, one DHT per Annex K table (DC0, AC0 and, in colour, DC1, AC1), DRI =
-    ceil(w / 8), SOS (host only)"""
+    table, SOF0 with luma sampling `sampling` (Cb and Cr 1 x 1), one DHT per Annex K table (DC0, AC0 and, in colour,
+    DC1, AC1), DRI = the MCUs of a row, ceil(w / 8 H), SOS (host only)"""
     h, w, c = int(h), int(w), int(c)
+    hh, vv = jpeg_sampling(sampling, what="jpeg_header")
     if not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
         raise ValueError("jpeg_header: sides are 1 .. %d, got %d x %d" % (JPEG_MAX_SIDE, w, h))
     if c not in (1, 3):
         raise ValueError("jpeg_header: 1 or 3 components, got %d" % c)
+    jpeg_sampling(sampling, c, "jpeg_header")
     tables = jpeg_tables(quality)
     zz = list(_JPEG_ZIGZAG)
     comps = [(1, 0)] if c == 1 else [(1, 0), (2, 1), (3, 1)]
@@ -2483,21 +2503,22 @@ def jpeg_header(h, w, c, quality):
     for t in range(1 if c == 1 else 2):
         out += _jpeg_segment(0xDB, bytes([t]) + tables[t][zz].tobytes())
     out += _jpeg_segment(0xC0, bytes([8, h >> 8, h & 255, w >> 8, w & 255, len(comps)])
-                         + b"".join(bytes([i, 0x11, t]) for i, t in comps))
+                         + b"".join(bytes([i, hh << 4 | vv if i == 1 else 0x11, t]) for i, t in comps))
     for key in (0x00, 0x10) + ((0x01, 0x11) if c == 3 else ()):
         bits, vals = JPEG_DHT[key]
         out += _jpeg_segment(0xC4, bytes((key,) + bits + vals))
-    ri = (w + 7) // 8
+    ri = -(-w // (8 * hh))
     out += _jpeg_segment(0xDD, bytes([ri >> 8, ri & 255]))
     out += _jpeg_segment(0xDA, bytes([len(comps)]) + b"".join(bytes([i, 0x11 * t]) for i, t in comps)
                          + bytes([0, 63, 0]))
     return out
 
 
-def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
+def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, sampling=(1, 1)):
     """one baseline JFIF file per frame of a stack in one va_jpeg_encode_u8 call ("Motion-JPEG"): 4:4:4
     or monochrome, the Annex K Huffman tables, one restart interval per MCU row; the bytes are pinned and equal the
-    restatement's.  frames: uint8 (n, h, w) or (n, h, w, 3) RGB, or a DeviceFrames (it stays the caller's; nothing
+    restatement's.  sampling: (2, 1) / "4:2:2" or (2, 2) / "4:2:0" write colour frames with box-averaged chroma in
+    one va_jpeg_encode_sampled_u8 call ("Subsampled Motion-JPEG encoding"), as pinned.  frames: uint8 (n, h, w) or (n, h, w, 3) RGB, or a DeviceFrames (it stays the caller's; nothing
     is uploaded then).  color: None takes the channels from the shape; True / False say what a 3-dimensional array
     is, one colour frame (h, w, 3) or a monochrome stack, and must agree with a 4-dimensional one.
     One upload of the frames and one of [tables | header], one call, and the downloads of the sizes and of the used
@@ -2506,6 +2527,7 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
     Returns the list of n `bytes`; ret_packed: (uint8 blob, int64 offsets of n + 1 entries), frame k being
     blob[offsets[k]:offsets[k + 1]]."""
     what = "jpeg_encode"
+    hh, vv = jpeg_sampling(sampling, what=what)
     dev = frames if isinstance(frames, DeviceFrames) else None
     if dev is None:
         arr = np.asarray(frames)
@@ -2518,14 +2540,15 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
         n, h, w, c = dev.n, dev.h, dev.w, dev.c
     if color is not None and (c == 3) != bool(color):
         raise ValueError("%s: color=%r with frames of %d channel(s)" % (what, color, c))
+    jpeg_sampling(sampling, c, what)
     if n and not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
         raise ValueError("%s: sides are 1 .. %d, got %d x %d" % (what, JPEG_MAX_SIDE, w, h))
     tables = jpeg_tables(quality)
     if n == 0:
         return (np.zeros(0, np.uint8), np.zeros(1, np.int64)) if ret_packed else []
-    head = np.frombuffer(jpeg_header(h, w, c, quality), np.uint8)
+    head = np.frombuffer(jpeg_header(h, w, c, quality, (hh, vv)), np.uint8)
     consts = np.concatenate([tables[0], tables[1], head])
-    nseg = (h + 7) // 8
+    nseg = -(-h // (8 * vv))
     room = n * (len(head) + 2 * nseg) + (n * h * w * c) // JPEG_ROOM_DIVISOR
     L = _hip.lib()
     with _Lease.on(stream) as d:
@@ -2535,8 +2558,12 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False):
 
         def run(cap):
             out = d.take(max(cap, 1))
-            check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, cb.ptr, cb.ptr + 128, len(head), info.ptr + 16 + 8 * n,
-                                      info.ptr + 8, info.ptr, out.ptr, cap, stream))
+            outs = (cb.ptr, cb.ptr + 128, len(head), info.ptr + 16 + 8 * n, info.ptr + 8, info.ptr, out.ptr, cap,
+                    stream)
+            if (hh, vv) == (1, 1):
+                check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, *outs))
+            else:
+                check(L.va_jpeg_encode_sampled_u8(src.ptr, n, h, w, c, hh, vv, *outs))
             meta = info.download((2 * n + 2,), np.int64, stream)
             return out, meta
         out, meta = run(room)
