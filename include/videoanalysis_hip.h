@@ -1097,6 +1097,8 @@ int va_morph_bits_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int
  * 3 = the library's choice, but the per-frame kernel hands its labels to the paint pass as sparse words in the
  * label image (round 1's convention) instead of compact run tables; 4 = the per-frame kernel (as 2),
  * staging the mask rows in LDS even where it could read its spans straight from global memory;
+ * 5 = the per-frame kernel (as 2), linking rows with the dense sweep over every span even where it would
+ * walk its list of non-empty spans (16-byte aligned rows; frames up to 2048 pixels wide, wider ones up to 685 rows);
  * lds_runs > 0 caps the per-frame kernel's run table (frames above it take its large-frame mode) */
 int va_test_hook_labelling(int path, int lds_runs);
 /* force_valu != 0: pipelines created from now on run their 8-bit Gaussian in the LDS/VALU (dot4/dot2)

@@ -2,7 +2,8 @@ import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "video-analysis_amd"))
 from video import _hip
-_hip.LIB_PATH = os.path.join(ROOT, "video-analysis_amd/csrc/build/dbg/libva_dbg.so")
+# the -DVA_CCL_STAMPS build: build/dbg/libva_dbg.so, or the library under build/dbg named on the command line
+_hip.LIB_PATH = os.path.join(ROOT, "video-analysis_amd/csrc/build/dbg", sys.argv[1] if len(sys.argv) > 1 else "libva_dbg.so")
 import torch
 from bench import synth_batch
 from video.engine import FrameEngine
@@ -26,4 +27,5 @@ for rep in range(12):
     print("frame WGs 0..7 on XCC", list(xb[0:8]), " paint blocks 0..7 on XCC", list(xb[16:24]),
           " paint %.4f ms" % (stt["ccl_paint"][0] / stt["ccl_paint"][1]))
     L.va_debug_ccl_stamps.argtypes = [C.c_void_p]
-    print(L.va_debug_ccl_stamps(buf), [ (buf[i+1]-buf[i])/100.0 for i in range(6)], "| link:", [buf[i]/100.0 for i in range(8,12)], int(counts.sum()))
+    print(L.va_debug_ccl_stamps(buf), [ (buf[i+1]-buf[i])/100.0 for i in range(6)], "| link:", [buf[i]/100.0 for i in range(8,12)],
+          "| span list of frame 0:", int(buf[12]), "(-1: dense sweep)", int(counts.sum()))

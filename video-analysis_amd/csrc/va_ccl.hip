@@ -516,6 +516,10 @@ ccl_rank_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels,
 //     unions serialise: a wave runs the longest lane's chain at every word);
 //     unions are ds_min atomics towards the smaller id, so the root is again the component's
 //     first run in raster order and label = 1 + number of roots with a smaller id;
+//   * frames whose rows are 16-byte aligned and fit one 8-word span per lane skip the stage (the direct
+//     form): lanes load their spans straight from global memory; where the stages' LDS holds both tables
+//     (1080p does, 4K does not) the first sweep keeps the spans' prefixes and lists the spans that hold
+//     foreground, and the link phase visits the listed spans only;
 //   * the only global traffic is the bit mask (read three times, L2-resident after the first)
 //     and one sparse write per run: -(label) at the run's first pixel (bit 30 set for runs that
 //     are not their component's first), which is what ccl_paint_kernel / the contour tracer read.
@@ -531,6 +535,21 @@ constexpr int kMinLdsRuns = 4096;                                 // else: chip-
 constexpr int kMaxFrameWords = 320 * 1024;                        // mask words per frame (1080p: 64.8 k, 4K: 259 k)
 constexpr int kWantLdsRuns = 16384;                               // below: try 4 rows per wave (smaller stages)
 constexpr int kNonRootBit = 1 << 30;
+// The direct form links through its span list (ccl_frame_kernel) while the list holds at most this share of the
+// frame's h * G spans, and sweeps every span otherwise.  Measured (tools/span_list_crossover.py, va_label_i32 on
+// 64 x 1080p, list / dense sweep, us): one pixel in 10 / 25 / 50 / 75 / 100 % of the spans 123 / 131, 127 / 130,
+// 131 / 134, 136 / 139, 143 / 143; all foreground 163 / 174.  The list is never the slower one, and
+// level with the sweep where every span is listed: no crossover below 100 %.  The sweep stays for frames whose
+// list does not fit the row stages and for the test hook.
+#ifndef VA_CCL_LIST_PERCENT
+#define VA_CCL_LIST_PERCENT 100
+#endif
+constexpr int kListPercent = VA_CCL_LIST_PERCENT;
+#ifdef VA_CCL_LIST_DIRECT_UNIONS
+constexpr bool kListQueued = false;
+#else
+constexpr bool kListQueued = true;
+#endif
 
 constexpr int kChunk = 8;                                         // words per lane and chunk
 constexpr int kStagePad = 4;                                      // zero words left of a staged row
@@ -734,6 +753,7 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
     __shared__ __attribute__((aligned(16))) int s_mem[kFrameLdsWords];
     __shared__ int s_part[kFrameWaves];
     __shared__ int s_total;
+    __shared__ int s_nlist;                                   // entries of the span list (direct form, below)
 
     const int f = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, lane = tid & (kWave - 1);
 #ifdef VA_CCL_STAMPS
@@ -819,6 +839,10 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
                 sp.b = *reinterpret_cast<const v4i *>(src + 4);
         }
     };
+    auto any_set = [](const v4i &v) { return v.x | v.y | v.z | v.w; };
+    auto lanes_below = [](unsigned long long m) {    // set bits of m below this lane
+        return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    };
     auto expand = [&](const SpanRegs &sp, uint32_t (&m)[NCH][kChunk + 2]) {
         m[0][1] = sp.a.x, m[0][2] = sp.a.y, m[0][3] = sp.a.z, m[0][4] = sp.a.w;
         m[0][5] = sp.b.x, m[0][6] = sp.b.y, m[0][7] = sp.b.z, m[0][8] = sp.b.w;
@@ -827,11 +851,19 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
         m[0][0] = dg > 0 ? left : 0u;
         m[0][9] = dg < G - 1 ? right : 0u;
     };
-    // the row stages are unused in this form: where they are large enough they keep every span's
-    // prefix (run starts of its row to the left) from the first sweep for the second
-    int *pref = s_mem;
-    const bool keep_pref = h * G <= lay.queue_off;
+    // the row stages are unused in this form: where they are large enough they keep, as 16-bit entries
+    // (a row of <= 4096 pixels has <= 2048 runs, and h * G <= queue_off < 2^16), every span's prefix (run
+    // starts of its row to the left) from the first sweep for the second, and behind them the SPAN LIST: the
+    // index y * G + dg of every span of a row y > 0 that holds a foreground pixel, in no particular order.
+    // Every contact between rows y and y - 1 is attributed to a pixel of row y inside the span (both
+    // diagonal kinds included), so the link phase needs to visit the listed spans only.
+    unsigned short *pref = reinterpret_cast<unsigned short *>(s_mem);
+    const bool keep_pref = h * G <= lay.queue_off;           // two 16-bit tables of h * G entries
+    unsigned short *span_list = pref + h * G;
     if (spans_direct) {
+        if (tid == 0)
+            s_nlist = 0;
+        __syncthreads();
         SpanRegs pre;
         load_direct(wv * RPW + dr, pre);
         for (int it = 0; it < sweeps; it++) {      // (deeper prefetch changes nothing: the sweep is issue-bound)
@@ -845,7 +877,20 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
             if (dg == G - 1 && y < h)
                 rowbase[y] = n;
             if (keep_pref && y < h)
-                pref[y * G + dg] = n - own;
+                pref[y * G + dg] = (unsigned short)(n - own);
+            if (keep_pref) {
+                // one LDS add per wave hands out the slots (ballot + mbcnt); rows past the frame load as zeros
+                const bool listed = y > 0 && (any_set(cur.a) | any_set(cur.b)) != 0;
+                const unsigned long long bal = __ballot(listed);
+                if (bal) {                                     // wave-uniform
+                    int base = 0;
+                    if (lane == 0)
+                        base = atomicAdd(&s_nlist, __popcll(bal));
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    if (listed)
+                        span_list[base + lanes_below(bal)] = (unsigned short)(y * G + dg);
+                }
+            }
         }
     } else {
     RowRegs rr1;
@@ -929,11 +974,12 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
 #endif
     // contacts of one sweep step: mw / uw = this lane's span of row y and of row y - 1, cc / cu = runs of
     // those rows that start left of the span
+    // (`queued` == false, an ablation of the list walk: every contact is united where it is found)
     auto link_rows = [&](bool act, int y, const uint32_t (&mw)[NCH][kChunk + 2],
-                         const uint32_t (&uw)[NCH][kChunk + 2], int cc, int cu) {
+                         const uint32_t (&uw)[NCH][kChunk + 2], int cc, int cu, bool queued) {
         // contacts of this lane's span (the same bit tricks as below, counted)
         int ncontacts = 0;
-        if (act) {
+        if (act && queued) {
 #pragma unroll
             for (int j = 0; j < NCH; j++)
 #pragma unroll
@@ -949,11 +995,13 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
                     }
                 }
         }
-        int nq_total;
-        int slot = wave_prefix(ncontacts, &nq_total);
-        CCL_ACC(a_count, a_t0);
-        if (nq_total == 0)                 // wave-uniform: nothing touches the rows above in this step
-            return;
+        int nq_total = 0, slot = kQueue;
+        if (queued) {
+            slot = wave_prefix(ncontacts, &nq_total);
+            CCL_ACC(a_count, a_t0);
+            if (nq_total == 0)             // wave-uniform: nothing touches the rows above in this step
+                return;
+        }
         if (act) {
             cc += rowbase[y] - 1;        // id of the run that holds pixel x = cc + starts in the
             cu += rowbase[y - 1] - 1;    // span at or left of x (same for the row above)
@@ -1003,6 +1051,8 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
                 }
             }
         }
+        if (!queued)
+            return;
         // drain: every lane takes queued contacts, so the wave runs one union chain deep
         wave_sync();
         CCL_ACC(a_pairs, a_t0);
@@ -1011,7 +1061,66 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
             lds_unite(parent, queue[2 * i], queue[2 * i + 1]);
     };
     CCL_STAMP(3);
-    if (spans_direct) {
+    // The span list against the dense sweep, per frame (workgroup-uniform): the list where it is short
+    // enough to pay for its scattered loads (kListPercent, above); `direct` == 2 (test hook) forces the sweep.
+    const int nlist = spans_direct && keep_pref ? s_nlist : 0;
+    const bool use_list = spans_direct && keep_pref && direct == 1 && nlist * 100 <= h * G * kListPercent;
+    if (use_list) {
+        // lane i of the workgroup takes entries i, i + 1024, ...: both rows of the span and the words next to
+        // it straight from global memory (L2-resident since the first sweep), the next entry's loads in flight
+        // while this one is processed.  Contacts are queued per wave and drained as in the dense sweep, counted
+        // over listed spans only.
+        struct EntryRegs {
+            SpanRegs c, u;               // the span of row y and of row y - 1
+            uint32_t cl, ul, cr, ur;     // the words left and right of them
+            int e;
+        };
+        auto load_entry = [&](int i, EntryRegs &r) {
+            r.c.a = r.c.b = r.u.a = r.u.b = v4i{0, 0, 0, 0};
+            r.cl = r.ul = r.cr = r.ur = 0u;
+            r.e = G;                                           // (row 1: its prefix reads stay in range)
+            if (i < nlist) {
+                r.e = span_list[i];
+                const int g = r.e % G;
+                const uint32_t *src = fbits + (size_t)(r.e / G) * w32 + 8 * g;    // row >= 1, 8 * g + 4 <= w32
+                if (8 * g + 4 <= w32) {
+                    r.c.a = *reinterpret_cast<const v4i *>(src);
+                    r.u.a = *reinterpret_cast<const v4i *>(src - w32);
+                }
+                if (8 * g + 8 <= w32) {
+                    r.c.b = *reinterpret_cast<const v4i *>(src + 4);
+                    r.u.b = *reinterpret_cast<const v4i *>(src + 4 - w32);
+                }
+                if (g > 0) {
+                    r.cl = src[-1];
+                    r.ul = src[-1 - w32];
+                }
+                if (CONN8 && 8 * g + 8 < w32) {
+                    r.cr = src[8];
+                    r.ur = src[8 - w32];
+                }
+            }
+        };
+        auto expand_entry = [&](const SpanRegs &sp, uint32_t left, uint32_t right, uint32_t (&m)[NCH][kChunk + 2]) {
+            m[0][0] = left;
+            m[0][1] = sp.a.x, m[0][2] = sp.a.y, m[0][3] = sp.a.z, m[0][4] = sp.a.w;
+            m[0][5] = sp.b.x, m[0][6] = sp.b.y, m[0][7] = sp.b.z, m[0][8] = sp.b.w;
+            m[0][9] = right;
+        };
+        EntryRegs nx;
+        load_entry(tid, nx);
+        for (int i = tid; i - tid < nlist; i += kFrameThreads) {      // (uniform trip count: link_rows is wave-wide)
+            const EntryRegs cur = nx;
+            load_entry(i + kFrameThreads, nx);
+            const bool act = i < nlist;
+            uint32_t mw[NCH][kChunk + 2], uw[NCH][kChunk + 2];
+            expand_entry(cur.c, cur.cl, cur.cr, mw);
+            expand_entry(cur.u, cur.ul, cur.ur, uw);
+            const int cc = pref[cur.e], cu = pref[cur.e - G];
+            link_rows(act, cur.e / G, mw, uw, cc, cu, kListQueued);
+            CCL_ACC(a_drain, a_t0);
+        }
+    } else if (spans_direct) {
         SpanRegs pre, pre_up;
         load_direct(wv * RPW + dr, pre);
         load_direct(wv * RPW + dr - 1, pre_up);
@@ -1036,7 +1145,7 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
                 cc = seg_inclusive<G>(nc, dg) - nc;
                 cu = seg_inclusive<G>(nu, dg) - nu;
             }
-            link_rows(act, y, mw, uw, cc, cu);
+            link_rows(act, y, mw, uw, cc, cu, true);
         }
     } else {
     RowRegs rr3;
@@ -1055,13 +1164,14 @@ ccl_frame_kernel(const uint32_t *__restrict__ bits, int32_t *__restrict__ labels
         const int nu = act ? count_starts<NCH>(uw) : 0;
         // runs of the row that start left of this lane's span
         int cc = row_prefix<RPW>(nc, lane), cu = row_prefix<RPW>(nu, lane);
-        link_rows(act, c.y, mw, uw, cc, cu);
+        link_rows(act, c.y, mw, uw, cc, cu, true);
         CCL_ACC(a_drain, a_t0);
     }
     }
 #ifdef VA_CCL_STAMPS
     if (blockIdx.x == 0 && tid == 0) {
         g_ccl_stamps[8] = a_commit; g_ccl_stamps[9] = a_count; g_ccl_stamps[10] = a_pairs; g_ccl_stamps[11] = a_drain;
+        g_ccl_stamps[12] = use_list ? nlist : -1;              // entries walked by the link phase, -1: dense sweep
     }
 #endif
     __syncthreads();
@@ -2118,11 +2228,14 @@ static int g_ccl_sparse = 0;   // hook path 3: the library's choice of kernel, l
                                // pass as sparse words in the label image (the round-1 convention)
 static int g_ccl_no_direct = 0; // hook path 4: the per-frame kernel (as path 2), staging its rows in LDS even
                                // where it could read its spans straight from global memory
+static int g_ccl_dense = 0;    // hook path 5: the per-frame kernel (as path 2), its direct form linking with the
+                               // dense sweep over every span whatever the length of the span list
 void ccl_test_hook(int path, int lds_runs)
 {
     g_ccl_sparse = path == 3;
     g_ccl_no_direct = path == 4;
-    g_ccl_path = path == 4 ? 2 : path == 3 ? 0 : path;
+    g_ccl_dense = path == 5;
+    g_ccl_path = path == 4 || path == 5 ? 2 : path == 3 ? 0 : path;
     g_ccl_lds_runs = lds_runs;
 }
 
@@ -2242,7 +2355,8 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
             lay.lds_runs = min(lay.lds_runs, g_ccl_lds_runs);
         const int nch = span_chunks(w32, rpw);
         // spans straight from 16-byte global loads (no LDS stage) where rows are 16-byte aligned
-        const int direct = nch == 1 && (w32 % 4 == 0) && aligned(bits, 16) && !g_ccl_no_direct;
+        // (2: the direct form with its dense link sweep forced, see the kernel)
+        const int direct = nch == 1 && (w32 % 4 == 0) && aligned(bits, 16) && !g_ccl_no_direct ? 1 + g_ccl_dense : 0;
         table_mode = paint && !g_ccl_sparse; // (the contour tracer reads roots in the label image instead)
         table_stride = lay.lds_runs;
 #define VA_FRAME_LAUNCH(C8, NCH, RPW)                                                                       \
