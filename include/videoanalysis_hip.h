@@ -822,6 +822,30 @@ int va_compose_layers_u8(const uint8_t *src_dev, int c_src, uint8_t *dst_dev, in
 int va_draw_u8(uint8_t *frames_dev, int n, int h, int w, int c, const va_draw_cmd *cmds_dev,
                const int64_t *cmd_off_dev, int64_t ncmds, const int32_t *points_dev, int64_t npoints,
                int32_t *status_dev, void *stream);
+/* replaces  the cv2.findContours -> cv2.drawContours pair of add_contour given a mask, video/io/composer.py:228-237,
+ *           without the host lists in between
+ * va_draw_contours_u8: a result of va_find_contours, as it lies in device memory, drawn into a frame stack of n_out
+ * frames: every contour a closed polyline of thickness 1, all in one colour (packed as in va_draw_cmd).  ncontours
+ * and npoints are the valid slots and points: min(total, capacity) of the va_find_contours call.
+ * Slot s owns the points v[0 .. k - 1] at point_off_dev[s] .. point_off_dev[s + 1] of points_dev; for k >= 1 its k
+ * segments v[i] -> v[(i + 1) mod k] are drawn as va_draw_u8 draws a closed VA_DRAW_POLYLINE (a contour of one point
+ * is that pixel, a slot with k == 0 draws nothing), into frame info_dev[s].frame, or, with frame_map_dev (int32,
+ * n_src entries), into frame frame_map_dev[info_dev[s].frame]; a mapped value of -1 means that the source frame is
+ * not drawn and is no error.  All stores carry one value: two calls write identical bytes.
+ * Nothing outside the buffers is read or written.  A segment is not drawn, and status_dev[0] (int32) becomes
+ * VA_ERR_RANGE, when its slot has info.frame outside 0 .. n_src - 1, a target that is neither -1 nor in
+ * 0 .. n_out - 1, or offsets that are not 0 <= point_off[s] <= point_off[s + 1] <= npoints, or when one of its two
+ * end points is beyond +-VA_FILL_MAX_COORD.  The slot of a point is found by binary search in point_off_dev; on a
+ * table that is not sorted (at least one slot is refused then) a point is drawn only with the slot the search
+ * finds for it.  Otherwise status_dev[0] is VA_OK; it is written on every call, ncontours == 0 included.
+ * One launch per 2^30 lanes, a lane per slot and a lane per point; no workspace.  c outside {1, 3}, negative counts,
+ * NULL pointers where data is required (frame_map_dev may be NULL) and frames of 2^29 pixels or more are
+ * VA_ERR_INVALID. */
+int va_draw_contours_u8(uint8_t *frames_dev, int n_out, int h, int w, int c,
+                        const va_contour_info *info_dev, const int64_t *point_off_dev, int64_t ncontours,
+                        const int32_t *points_dev, int64_t npoints,
+                        const int32_t *frame_map_dev, int n_src, uint32_t color,
+                        int32_t *status_dev, void *stream);
 
 /* ------------------------------------------------------------------ A20 Motion-JPEG
  * replaces  the frame-by-frame cv2.VideoWriter.write of VideoWriterOpenCV, video/io/backend_opencv.py:240-242, behind

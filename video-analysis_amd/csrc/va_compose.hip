@@ -12,6 +12,11 @@
 //                  segments, or the steps of a circle's recurrence, to the lanes; between two phases the
 //                  workgroup's stores are ordered by a fence and a barrier, so that the last command in list order
 //                  that covers a pixel decides it.
+// draw_contours  : a va_find_contours result as it lies in device memory, every contour a closed polyline in one
+//                  colour (composer.py:228-237, findContours -> drawContours).  The batch's totals are known on the
+//                  host, so the launch is chip-wide: one lane per slot checks the slot's table entries, one lane per
+//                  point finds its slot by binary search in the offsets and draws the segment that starts at its
+//                  point.  All stores carry one value, so no order between the lanes is needed: no LDS, no barrier.
 #include "va_common.h"
 #include "va_raster.h"
 
@@ -23,6 +28,8 @@ constexpr int kComposeBlock = 256;
 constexpr int kLanePixels = 16;
 constexpr int kDrawBlock = 256;
 constexpr int kDrawWaves = kDrawBlock / kWave;
+constexpr int kContourBlock = 256;
+constexpr int64_t kContourPieceLanes = (int64_t)1 << 30;     // lanes of one launch: 2^22 workgroups in grid x
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -309,6 +316,82 @@ __global__ void __launch_bounds__(kDrawBlock) draw_kernel(DrawArgs a)
         a.status[f] = VA_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------ contours
+struct ContourDrawArgs {
+    uint8_t *frames;
+    int n_out, h, w;
+    const va_contour_info *info;
+    const int64_t *point_off;           // ncontours + 1 entries
+    int64_t ncontours;
+    const int32_t *points;
+    int64_t npoints;
+    const int32_t *frame_map;           // n_src entries, or NULL: the identity
+    int n_src;
+    uint32_t color;
+    int32_t *status;
+    int64_t first, lanes;               // this launch: lanes first .. lanes - 1 of ncontours + npoints
+};
+
+// the checks of slot s that need no point: its offsets, its frame and the frame's target.  false: none of its
+// segments is drawn.  *target is -1 for a source frame the map leaves out (which is no error).
+__device__ __forceinline__ bool contour_slot_ok(const ContourDrawArgs &a, int64_t s, int64_t lo, int64_t hi,
+                                                int *target, bool *refused)
+{
+    *refused = true;
+    if (!(lo >= 0 && lo <= hi && hi <= a.npoints))
+        return false;
+    const int f = a.info[s].frame;
+    if (f < 0 || f >= a.n_src)
+        return false;
+    const int t = a.frame_map ? a.frame_map[f] : f;
+    if (t < (a.frame_map ? -1 : 0) || t >= a.n_out)
+        return false;
+    *refused = false;
+    *target = t;
+    return t >= 0;
+}
+
+template <int C>
+__global__ void __launch_bounds__(kContourBlock) draw_contours_kernel(ContourDrawArgs a)
+{
+    const int64_t lane = a.first + (int64_t)blockIdx.x * kContourBlock + threadIdx.x;
+    if (lane >= a.lanes)
+        return;
+    int target;
+    bool refused;
+    if (lane < a.ncontours) {           // a slot lane: it reports what is wrong with the slot and draws nothing
+        contour_slot_ok(a, lane, a.point_off[lane], a.point_off[lane + 1], &target, &refused);
+        if (refused)
+            a.status[0] = VA_ERR_RANGE;
+        return;
+    }
+    // a point lane: the slot of point p is the last one that starts at or before p (the table is sorted when every
+    // slot passes its check); only entries 1 .. ncontours - 1 are read here, s and s + 1 afterwards
+    const int64_t p = lane - a.ncontours;
+    int64_t s = 0, e = a.ncontours;
+    if (e == 0)
+        return;
+    while (e - s > 1) {
+        const int64_t mid = s + (e - s) / 2;
+        if (a.point_off[mid] <= p)
+            s = mid;
+        else
+            e = mid;
+    }
+    const int64_t lo = a.point_off[s], hi = a.point_off[s + 1];
+    if (!contour_slot_ok(a, s, lo, hi, &target, &refused) || p < lo || p >= hi)
+        return;                         // (the slot lane has reported a refused slot)
+    const int64_t q = p + 1 == hi ? lo : p + 1;
+    const int64_t x1 = a.points[2 * p], y1 = a.points[2 * p + 1], x2 = a.points[2 * q], y2 = a.points[2 * q + 1];
+    if (!(coord_ok(x1) && coord_ok(y1) && coord_ok(x2) && coord_ok(y2))) {
+        a.status[0] = VA_ERR_RANGE;
+        return;
+    }
+    const Plot<C> plot{a.frames + (int64_t)target * a.h * a.w * C, a.w, a.color};
+    line8(a.w, a.h, x1, y1, x2, y2, plot);
+}
+
 }  // namespace
 
 }  // namespace va
@@ -375,6 +458,42 @@ int va_draw_u8(uint8_t *frames, int n, int h, int w, int c, const va_draw_cmd *c
     else
         hipLaunchKernelGGL(draw_kernel<3>, dim3(n), dim3(kDrawBlock), 0, st, a);
     VA_LAUNCH_CHECK("draw_kernel");
+    return VA_OK;
+}
+
+int va_draw_contours_u8(uint8_t *frames, int n_out, int h, int w, int c, const va_contour_info *info,
+                        const int64_t *point_off, int64_t ncontours, const int32_t *points, int64_t npoints,
+                        const int32_t *frame_map, int n_src, uint32_t color, int32_t *status, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(n_out >= 0 && h >= 0 && w >= 0 && ncontours >= 0 && npoints >= 0 && n_src >= 0,
+               "va_draw_contours_u8: negative count (n_out %d, h %d, w %d, ncontours %lld, npoints %lld, n_src %d)",
+               n_out, h, w, (long long)ncontours, (long long)npoints, n_src);
+    VA_REQUIRE(c == 1 || c == 3, "va_draw_contours_u8: channels must be 1 or 3, got %d", c);
+    VA_REQUIRE((size_t)h * w < kMaxFramePixels,
+               "va_draw_contours_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(status && (frames || n_out == 0 || h == 0 || w == 0) && ((info && point_off) || ncontours == 0) &&
+                   (points || npoints == 0),
+               "va_draw_contours_u8: NULL argument");
+    VA_REQUIRE(aligned(info, 8) && aligned(point_off, 8) && aligned(points, 4) && aligned(frame_map, 4) &&
+                   aligned(status, 4),
+               "va_draw_contours_u8: the records and offsets must be 8-byte aligned, points, map and status 4-byte "
+               "aligned");
+    hipStream_t st = as_stream(stream);
+    VA_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));        // VA_OK, on every call
+    if (ncontours == 0)
+        return VA_OK;
+    ContourDrawArgs a{frames, n_out, h, w, info, point_off, ncontours, points, npoints, frame_map, n_src, color,
+                      status, 0, ncontours + npoints};
+    for (a.first = 0; a.first < a.lanes; a.first += kContourPieceLanes) {
+        const int64_t here = a.lanes - a.first < kContourPieceLanes ? a.lanes - a.first : kContourPieceLanes;
+        const unsigned blocks = (unsigned)((here + kContourBlock - 1) / kContourBlock);
+        if (c == 1)
+            hipLaunchKernelGGL(draw_contours_kernel<1>, dim3(blocks), dim3(kContourBlock), 0, st, a);
+        else
+            hipLaunchKernelGGL(draw_contours_kernel<3>, dim3(blocks), dim3(kContourBlock), 0, st, a);
+        VA_LAUNCH_CHECK("draw_contours_kernel");
+    }
     return VA_OK;
 }
 

@@ -148,6 +148,7 @@ SIGNATURES = {
     "va_simplify_visvalingam": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "va_compose_layers_u8": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "va_draw_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "va_draw_contours_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, C.c_uint32, _vp, _vp]),
     "va_jpeg_encode_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "va_jpeg_encode_sampled_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "va_jpeg_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),

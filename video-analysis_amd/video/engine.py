@@ -118,6 +118,16 @@ class FrameEngine(object):
             b = self._dev[name] = DeviceBuffer(nbytes)
         return b
 
+    def _check_keep(self, keep):
+        """the outputs that stay on the device: 'mask', and 'filtered' on a uint8 engine"""
+        keep = (keep,) if isinstance(keep, str) else tuple(keep)
+        allowed = {"mask"} | ({"filtered"} if self.dtype == np.uint8 and self.channels in (1, 3) else set())
+        unknown = sorted(set(keep) - allowed)
+        if unknown:
+            raise ValueError("outputs %r cannot be kept on the device (this engine keeps %s)"
+                             % (unknown, ", ".join(sorted(allowed))))
+        return set(keep)
+
     def _check_batch(self, shape, n, want):
         in_shape = self.prepare["src_shape"] if self.prepare else self.frame_shape
         if tuple(shape) != tuple(in_shape):
@@ -130,10 +140,13 @@ class FrameEngine(object):
             raise ValueError("unknown outputs %r" % sorted(unknown))
         return want
 
-    def _run_resident(self, raw_ptr, n, want):
+    def _run_resident(self, raw_ptr, n, want, keep=()):
         """the chain on `n` source frames at device address `raw_ptr` (raw frames where the engine has prepare
         stages: crop / monochrome / normalize run first, one device pass, no host round trip) and the downloads
-        of the outputs in `want`"""
+        of the outputs in `want`; the outputs in `keep` are not downloaded: each comes back as an ops.DeviceFrames
+        of the caller's, a device-to-device copy out of the engine's buffer into a pool buffer"""
+        keep = self._check_keep(keep)
+        want = set(want) | keep
         px = self.width * self.height
         frame_bytes = px * self.channels * self.dtype.itemsize
         src_ptr = raw_ptr
@@ -161,9 +174,22 @@ class FrameEngine(object):
         if getattr(self, "_overlap", False):
             self.fence(None)                # the downloads below read what the side stream writes
         out = {}
-        if "filtered" in want:
+        if keep:
+            from . import ops
+            for name in sorted(keep):
+                c = self.channels if name == "filtered" else 1
+                kept = ops.DeviceFrames(ops._take(max(n * px * c, 1)), n, self.height, self.width, c)
+                out[name] = kept
+                try:
+                    check(self._lib.va_memcpy_d2d(kept.buf.ptr, ptr[name].ptr, n * px * c, None))
+                    check(self._lib.va_stream_sync(None))
+                except Exception:
+                    for done in out.values():
+                        done.release()
+                    raise
+        if "filtered" in want - keep:
             out["filtered"] = ptr["filtered"].download((n,) + self.frame_shape, self.dtype)
-        if "mask" in want:
+        if "mask" in want - keep:
             out["mask"] = ptr["mask"].download((n, self.height, self.width), np.uint8)
         if "labels" in want:
             out["labels"] = ptr["labels"].download((n, self.height, self.width), np.int32)
@@ -173,23 +199,27 @@ class FrameEngine(object):
             out["stats"] = ptr["stats"].download((n, self.max_labels, _hip.STATS_STRIDE), np.int64)
         return out
 
-    def run(self, frames, want=("mask", "labels", "counts")):
+    def run(self, frames, want=("mask", "labels", "counts"), keep=()):
         """frames: (n, H, W[, C]) array; returns a dict with the requested outputs among
-        'filtered', 'mask', 'labels', 'counts', 'stats'"""
+        'filtered', 'mask', 'labels', 'counts', 'stats'.  The outputs named in `keep` ('mask', and 'filtered' on a
+        uint8 engine) are not downloaded: they come back as ops.DeviceFrames that the caller owns and releases, and
+        that the engine's next run does not change.  Any other name in `keep` is a ValueError."""
         arr = np.ascontiguousarray(frames, self.dtype)
         want = self._check_batch(arr.shape[1:], arr.shape[0], want)
+        self._check_keep(keep)
         raw = self._buf("raw" if self.prepare else "src", arr.nbytes)
         raw.upload(arr)
-        return self._run_resident(raw.ptr, arr.shape[0], want)
+        return self._run_resident(raw.ptr, arr.shape[0], want, keep)
 
-    def run_frames(self, device_frames, want=("mask", "labels", "counts")):
+    def run_frames(self, device_frames, want=("mask", "labels", "counts"), keep=()):
         """`run` on a stack that is already on the device (an `ops.DeviceFrames`, e.g. what `ops.jpeg_decode(...,
         keep=True)` or `VideoMJPEG.get_device_frames` return): the same dict of outputs, and no pixel is uploaded.
-        The stack stays the caller's."""
+        The stack stays the caller's.  `keep` as for `run`: with keep=('mask',) no pixel is downloaded either."""
         if self.dtype != np.uint8:
             raise TypeError("run_frames takes uint8 device frames, the engine works on %s" % self.dtype)
         want = self._check_batch(device_frames.shape[1:], device_frames.n, want)
-        return self._run_resident(device_frames.buf.ptr, device_frames.n, want)
+        self._check_keep(keep)
+        return self._run_resident(device_frames.buf.ptr, device_frames.n, want, keep)
 
     # ------------------------------------------------------------------ per-stage timing
     def profile(self, enable=True, every=1):

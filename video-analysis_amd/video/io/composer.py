@@ -27,9 +27,15 @@
   anti-aliased lines and no `add_text` (Hershey fonts): each raises `NotImplementedError`.  With the reference's
   defaults every call stays inside the supported set, for any zoom factor >= 1.
 
+* **Whole stacks.**  `annotate_frames` (not in the reference) composes the common annotation -- highlight the mask,
+  outline the blobs -- for a stack of frames in one call, from arrays or from stacks that are already on the device
+  (`ops.DeviceFrames` of a decoder or of `FrameEngine.run(..., keep=("mask",))`, an `ops.DeviceContours`): with a
+  `write_frames` sink nothing but what the sink makes of the frames leaves the device.
+
 The ops are looked up on `video.ops` when a flush runs (`ops.compose_layers`, `ops.draw`, `ops.resize`,
-`ops.find_contours`), so a test can put other implementations in their place with `monkeypatch.setattr(ops, ...)`.
-The pinned definitions are in DESIGN.md §9, "Composer".
+`ops.find_contours`, and for `annotate_frames` `ops.draw_contours`, `ops.DeviceFrames` and `ops.DeviceContours`), so a
+test can put other implementations in their place with `monkeypatch.setattr(ops, ...)`.
+The pinned definitions are in DESIGN.md §9, "Composer" and "Annotating on the device".
 """
 import math
 import os
@@ -225,9 +231,8 @@ class VideoComposer(object):
             raise ValueError("Cannot add a color image to a monochrome one")
         return self._capture(image)
 
-    @skip_if_no_output
-    def highlight_mask(self, mask, channel="all", strength=128):
-        """highlights the non-zero entries of a mask in the current frame"""
+    def _highlight_args(self, channel, strength):
+        """the checked (channel, strength) of a highlight: the channel's index, or None for all"""
         if channel is None or (isinstance(channel, str) and channel == "all"):
             channel = None
         elif self.is_color:
@@ -239,7 +244,13 @@ class VideoComposer(object):
             raise ValueError("Highlighting a specific channel is only supported for color videos.")
         if isinstance(strength, (bool, np.bool_)) or int(strength) != strength or not 0 <= strength <= 255:
             raise ValueError("the strength is an integer in 0 .. 255, got %r" % (strength,))
-        self._record("layer", ("highlight", self._layer_mask(mask), channel, int(strength)))
+        return channel, int(strength)
+
+    @skip_if_no_output
+    def highlight_mask(self, mask, channel="all", strength=128):
+        """highlights the non-zero entries of a mask in the current frame"""
+        channel, strength = self._highlight_args(channel, strength)
+        self._record("layer", ("highlight", self._layer_mask(mask), channel, strength))
 
     @skip_if_no_output
     def add_image(self, image, mask=None):
@@ -462,6 +473,115 @@ class VideoComposer(object):
         self._pending = pending[-1:] if keep_last else []
         for p in done:
             self._write(p.image)
+
+    # ------------------------------------------------------------------------------------------ whole stacks
+    def annotate_frames(self, frames, masks=None, channel="all", strength=128, contours=None, color="w"):
+        """A whole stack of `n` source frames at once, with the result of this loop, byte for byte:
+
+            for i in range(n):
+                composer.set_frame(frames[i])
+                if masks is not None:    composer.highlight_mask(masks[i], channel, strength)
+                if contours is not None: composer.add_contour(<the contours of frame i>, color)
+
+        frames: an (n, h, w[, 3]) uint8 array or an `ops.DeviceFrames`; masks: an (n, h, w) array or a monochrome
+        `ops.DeviceFrames`; contours: an `ops.DeviceContours` of the same `n` frames, or True for the outer contours
+        of `masks` (one `ops.find_contours(..., keep=True)`), or None.  What is handed in is not modified and stays
+        the caller's.  With stacks that are on the device, nothing crosses to the host but what the sink makes of
+        the finished frames: a sink with ``write_frames`` receives them as one `ops.DeviceFrames` (the composer's,
+        for the duration of the call); any other sink gets a download.
+
+        Pending per-frame work is flushed first, so the output order is the call order; `next_frame` advances by
+        `n`; with `output_period != 1` only the frames the loop would write are composed (gathered on the device,
+        their contours selected through a frame map).  Afterwards there is no current frame until the next
+        `set_frame`.  The checks of `set_frame`, `highlight_mask` and `get_color` apply as in the loop: none when no
+        frame of the stack is written.  `zoom_factor != 1` raises NotImplementedError."""
+        if self.zoom_factor != 1:
+            raise NotImplementedError("annotate_frames: zoom_factor %r is not supported on whole stacks, only 1 "
+                                      "(ops.resize has no device-resident form)" % (self.zoom_factor,))
+        on_device = isinstance(frames, ops.DeviceFrames)
+        if not on_device:
+            frames = np.asarray(frames)
+        if len(frames.shape) < 1:
+            raise ValueError("frames are a stack (n, h, w) or (n, h, w, 3), got shape %r" % (frames.shape,))
+        n = frames.shape[0]
+        chosen = [i for i in range(n) if (self.next_frame + 1 + i) % self.output_period == 0]
+        if not chosen:
+            self.next_frame += n
+            return
+        if not on_device and frames.dtype != np.uint8:
+            raise TypeError("frames are uint8, got %s" % frames.dtype)
+        shape = tuple(frames.shape)
+        if not self.is_color and len(shape) == 4:
+            raise ValueError("Cannot copy a color image into a monochrome video.")
+        if not (len(shape) == 3 or (len(shape) == 4 and shape[3] == 3)):
+            raise ValueError("frames are a stack (n, h, w) or (n, h, w, 3), got shape %r" % (shape,))
+        size = (self.source_size[1], self.source_size[0])
+        if shape[1:3] != size:
+            raise ValueError("frames of shape %r in a video of size %r" % (shape, self.source_size))
+        masks_on_device = isinstance(masks, ops.DeviceFrames)
+        if masks is not None:
+            if not masks_on_device:
+                masks = np.asarray(masks)
+            if tuple(masks.shape) != (n,) + size:
+                raise ValueError("masks of shape %r for %d frames in a video of size %r"
+                                 % (tuple(masks.shape), n, self.source_size))
+            channel, strength = self._highlight_args(channel, strength)
+        if contours is not None:
+            if contours is True:
+                if masks is None:
+                    raise ValueError("contours=True finds the contours of the masks: there are none")
+            elif not isinstance(contours, ops.DeviceContours):
+                raise TypeError("contours are an ops.DeviceContours, True or None, got %s" % type(contours).__name__)
+            elif (contours.n, contours.h, contours.w) != (n,) + size:
+                raise ValueError("contours of %d frames of %r for %d frames of %r"
+                                 % (contours.n, (contours.h, contours.w), n, size))
+            color = self.get_color(color)
+        self._flush(keep_last=False)
+        self.next_frame += n
+        whole = len(chosen) == n
+        own = []                                  # what this call has put on the device
+        current = None
+        try:
+            # the frames that are written, as a stack of the composer's own
+            if on_device:
+                current = frames.gather(chosen)
+            else:
+                current = ops.DeviceFrames.upload(frames if whole else frames[chosen])
+            # their masks: planes of the caller's stack, or an upload of the chosen ones' non-zero patterns
+            planes = None
+            if masks is not None:
+                if masks_on_device:
+                    mask_stack, planes = masks, chosen
+                else:
+                    picked = masks if whole else masks[chosen]
+                    bits = picked if picked.dtype == np.uint8 else (picked != 0).view(np.uint8)
+                    mask_stack, planes = ops.DeviceFrames.upload(bits), list(range(len(chosen)))
+                    own.append(mask_stack)
+            # their contours, and the map from the frames these were found in to the frames of `current`
+            frame_map = None
+            if contours is True:
+                contours = ops.find_contours(mask_stack, keep=True)
+                own.append(contours)
+                if masks_on_device and not whole:
+                    frame_map = np.full(n, -1, np.int32)
+                    frame_map[chosen] = np.arange(len(chosen), dtype=np.int32)
+            elif contours is not None and not whole:
+                frame_map = np.full(n, -1, np.int32)
+                frame_map[chosen] = np.arange(len(chosen), dtype=np.int32)
+            layers = [[("highlight", (mask_stack, k), channel, strength)] if planes is not None else []
+                      for k in (planes if planes is not None else chosen)]
+            current = ops.compose_layers(current, layers, color=self.is_color, keep=True)
+            if contours is not None:
+                current = ops.draw_contours(current, contours, color, frame_map=frame_map, keep=True)
+            if hasattr(self.sink, "write_frames"):
+                self.sink.write_frames(current)
+                self.frames_written += len(chosen)
+            else:
+                for image in current.download():
+                    self._write(image)
+        finally:
+            for held in own + ([current] if current is not None else []):
+                held.release()
 
     def close(self):
         """compose and write what is pending"""

@@ -543,7 +543,50 @@ CONTOUR_INFO_DTYPE = np.dtype([("frame", np.int32), ("npoints", np.int32), ("sta
 CONTOUR_RECORD_DTYPE = np.dtype([("area", np.float64), ("perimeter", np.float64), ("rect", np.int32, 4)])
 
 
-def find_contours(masks, ret_info=False, moments=False, stream=None):
+class DeviceContours(object):
+    """one va_find_contours result that stays on the device: the records (`info`, CONTOUR_INFO_DTYPE), the offsets
+    (`point_off`, ncontours + 1 int64) and the points (`points`, int32 (x, y)) in leased buffers, with what the host
+    knows of them: the stack's n, h, w, the contours per frame (`counts`, int32) and the totals `ncontours` and
+    `npoints`.  ops.draw_contours draws it; download() gives what find_contours returns for a stack; release()
+    hands the buffers back to the pool (the caller has synchronised by then: find_contours and download() do)."""
+
+    def __init__(self, info, point_off, points, n, h, w, counts, ncontours, npoints):
+        self.info, self.point_off, self.points = info, point_off, points
+        self.n, self.h, self.w = n, h, w
+        self.counts, self.ncontours, self.npoints = counts, int(ncontours), int(npoints)
+
+    def download(self, ret_info=False, moments=False, stream=None):
+        """the per-frame lists of (N, 1, 2) int32 contours; ret_info and moments append what find_contours appends"""
+        n, k, npts = self.n, self.ncontours, self.npoints
+        extras = bool(ret_info) + bool(moments)
+        if n == 0:
+            return ([],) * (1 + extras) if extras else []
+        offsets = self.point_off.download((k + 1,), np.int64, stream)
+        points = self.points.download((npts, 2), np.int32, stream)
+        first = np.concatenate([[0], np.cumsum(self.counts, dtype=np.int64)])
+        res = ([[points[offsets[s]:offsets[s + 1]].reshape(-1, 1, 2) for s in range(first[f], first[f + 1])]
+                for f in range(n)],)
+        if ret_info:
+            rec = self.info.download((k,), CONTOUR_INFO_DTYPE, stream)
+            out = np.empty(k, CONTOUR_RECORD_DTYPE)
+            for name in CONTOUR_RECORD_DTYPE.names:
+                out[name] = rec[name]
+            res += ([out[first[f]:first[f + 1]] for f in range(n)],)
+        if moments:
+            with _Lease.on(stream) as d:
+                mom = d.take(max(k, 1) * 80)
+                check(_hip.lib().va_contour_moments_ragged(self.points.ptr, self.point_off.ptr, k, 0, mom.ptr, stream))
+                allm = mom.download((k, 10), np.float64, stream)
+            res += ([allm[first[f]:first[f + 1]] for f in range(n)],)
+        return res if len(res) > 1 else res[0]
+
+    def release(self):
+        bufs = (self.info, self.point_off, self.points)
+        self.info = self.point_off = self.points = None
+        _give(*bufs)
+
+
+def find_contours(masks, ret_info=False, moments=False, stream=None, keep=False):
     """cv2.findContours(mask, cv2.RETR_EXTERNAL, cv2.CHAIN_APPROX_SIMPLE)[1] for one mask (h, w) or a stack
     (n, h, w), foreground = non-zero (video/analysis/regions.py:180-182, :229-231, :575-576;
     video/io/composer.py:228): the list of (N, 1, 2) int32 contours in OpenCV's order, one list per frame for a
@@ -551,51 +594,60 @@ def find_contours(masks, ret_info=False, moments=False, stream=None):
     cv2.arcLength(c, True) and cv2.boundingRect (x, y, w, h) of its contours; moments appends the (k, 10) spatial
     cv2.moments(contour) values per frame, computed from the points on the device.  The first launch has room for
     DEFAULT_CONTOUR_CAPACITY contours and DEFAULT_CONTOUR_POINT_CAPACITY points in the batch; a batch that holds
-    more runs exactly once more, with exact room."""
-    arr, n, fshape, single = _as_batch(np.asarray(masks), 2)
-    extras = bool(ret_info) + bool(moments)
-    if n == 0:
-        return ([],) * (1 + extras) if extras else []
+    more runs exactly once more, with exact room.
+    masks may be a monochrome DeviceFrames (a stack: it is not uploaded and stays the caller's).  keep=True returns a
+    DeviceContours instead (ret_info and moments are then its download()'s): 16 bytes of totals and the counts per
+    frame cross to the host, and no points."""
+    if isinstance(masks, DeviceFrames):
+        if masks.c != 1:
+            raise ValueError("find_contours: masks on the device are a monochrome stack, got %d channels" % masks.c)
+        arr, n, fshape, single = None, masks.n, (masks.h, masks.w), False
+    else:
+        arr, n, fshape, single = _as_batch(np.asarray(masks), 2)
     h, w = fshape
-    if h == 0 or w == 0:
-        raise ValueError("find_contours: frames of shape %r have no pixels" % (tuple(fshape),))
-    arr = _as_mask(arr, keep_uint8=True)
-    L = _hip.lib()
-    with _Lease.on(stream) as d:
-        ws_bytes = L.va_find_contours_workspace_bytes(n, h, w)
-        src, ws, ncb, tot = d.upload(arr), d.take(ws_bytes), d.take(n * 4), d.take(16)
+    if n == 0:
+        found = DeviceContours(None, None, None, 0, h, w, np.zeros(0, np.int32), 0, 0)
+    else:
+        if h == 0 or w == 0:
+            raise ValueError("find_contours: frames of shape %r have no pixels" % (tuple(fshape),))
+        if arr is not None:
+            arr = _as_mask(arr, keep_uint8=True)
+        L = _hip.lib()
+        held = []                           # the result's buffers: they outlive the call's lease
+        try:
+            with _Lease.on(stream) as d:
+                ws_bytes = L.va_find_contours_workspace_bytes(n, h, w)
+                src = masks.buf if arr is None else d.upload(arr)
+                ws, ncb, tot = d.take(ws_bytes), d.take(n * 4), d.take(16)
 
-        def run(capc, capp):
-            info, off, pts = d.take(max(capc, 1) * CONTOUR_INFO_DTYPE.itemsize), d.take((capc + 1) * 8), d.take(
-                max(capp, 1) * 8)
-            check(L.va_find_contours(src.ptr, n, h, w, ncb.ptr, tot.ptr, info.ptr, off.ptr, capc, pts.ptr, capp,
-                                     ws.ptr, ws_bytes, stream))
-            return info, off, pts, tot.download((2,), np.int64, stream)
-        capc, capp = DEFAULT_CONTOUR_CAPACITY, DEFAULT_CONTOUR_POINT_CAPACITY
-        info, off, pts, (k, npts) = run(capc, capp)
-        if k > capc or npts > capp:
-            info, off, pts, (k, npts) = run(int(k), int(npts))
-        k, npts = int(k), int(npts)
-        counts = ncb.download((n,), np.int32, stream)
-        offsets = off.download((k + 1,), np.int64, stream)
-        points = pts.download((npts, 2), np.int32, stream)
-        first = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
-        res = ([[points[offsets[s]:offsets[s + 1]].reshape(-1, 1, 2) for s in range(first[f], first[f + 1])]
-                for f in range(n)],)
-        if ret_info:
-            rec = info.download((k,), CONTOUR_INFO_DTYPE, stream)
-            out = np.empty(k, CONTOUR_RECORD_DTYPE)
-            for name in CONTOUR_RECORD_DTYPE.names:
-                out[name] = rec[name]
-            res += ([out[first[f]:first[f + 1]] for f in range(n)],)
-        if moments:
-            mom = d.take(max(k, 1) * 80)
-            check(L.va_contour_moments_ragged(pts.ptr, off.ptr, k, 0, mom.ptr, stream))
-            allm = mom.download((k, 10), np.float64, stream)
-            res += ([allm[first[f]:first[f + 1]] for f in range(n)],)
+                def run(capc, capp):
+                    _give(*held)
+                    held[:] = []
+                    for nbytes in (max(capc, 1) * CONTOUR_INFO_DTYPE.itemsize, (capc + 1) * 8, max(capp, 1) * 8):
+                        held.append(_take(nbytes))
+                    info, off, pts = held
+                    check(L.va_find_contours(src.ptr, n, h, w, ncb.ptr, tot.ptr, info.ptr, off.ptr, capc, pts.ptr,
+                                             capp, ws.ptr, ws_bytes, stream))
+                    return tot.download((2,), np.int64, stream)
+                capc, capp = DEFAULT_CONTOUR_CAPACITY, DEFAULT_CONTOUR_POINT_CAPACITY
+                k, npts = run(capc, capp)
+                if k > capc or npts > capp:
+                    k, npts = run(int(k), int(npts))
+                counts = ncb.download((n,), np.int32, stream)
+        except Exception:
+            _give(*held)
+            raise
+        found = DeviceContours(held[0], held[1], held[2], n, h, w, counts, k, npts)
+    if keep:
+        return found
+    try:
+        res = found.download(ret_info, moments, stream)
+    finally:
+        if n:
+            found.release()
     if single:
-        res = tuple(r[0] for r in res)
-    return res if len(res) > 1 else res[0]
+        res = tuple(r[0] for r in res) if isinstance(res, tuple) else res[0]
+    return res
 
 
 # ------------------------------------------------------------------------ geodesic distance maps
@@ -2151,6 +2203,28 @@ class DeviceFrames(object):
     def download(self, stream=None):
         return self.buf.download(self.shape, np.uint8, stream)
 
+    def gather(self, indices, stream=None):
+        """a new DeviceFrames of the frames `indices` of this one, in that order (the caller's, like an upload):
+        device-to-device copies, one per run of consecutive frames; synchronises the stream"""
+        idx = [int(i) for i in indices]
+        if any(not 0 <= i < self.n for i in idx):
+            raise IndexError("DeviceFrames.gather: frames are 0 .. %d, got %r" % (self.n - 1, idx))
+        frame = self.h * self.w * self.c
+        out = DeviceFrames(_take(max(len(idx) * frame, 1)), len(idx), self.h, self.w, self.c)
+        try:
+            L, k = _hip.lib(), 0
+            while k < len(idx) and frame:
+                run = 1
+                while k + run < len(idx) and idx[k + run] == idx[k] + run:
+                    run += 1
+                check(L.va_memcpy_d2d(out.buf.ptr + k * frame, self.buf.ptr + idx[k] * frame, run * frame, stream))
+                k += run
+            check(L.va_stream_sync(stream))
+        except Exception:
+            out.release()
+            raise
+        return out
+
     def release(self):
         buf, self.buf = self.buf, None
         if buf is not None:
@@ -2190,15 +2264,36 @@ class _BytePacker(object):
 
 def _compose_tables(layers, n, h, w, c, what):
     """the checked operands of va_compose_layers_u8: (records, layer_off, images, masks), the last two packed byte
-    arrays or None; raises as compose_layers documents"""
+    arrays or None, or the DeviceFrames whose planes the layers name as (DeviceFrames, index); raises as
+    compose_layers documents"""
     if len(layers) != n:
         raise ValueError("%s: need one layer list per frame (%d frames, %d lists)" % (what, n, len(layers)))
     images, masks, recs = _BytePacker(), _BytePacker(), []
     off = np.zeros(n + 1, np.int64)
 
+    device = {"mask": None, "image": None}       # the one DeviceFrames the call's device planes of a role come from
+
+    def device_plane(operand, role):
+        """(byte offset, channels) of the plane (DeviceFrames, index)"""
+        stack, index = operand
+        if isinstance(index, (bool, np.bool_)) or int(index) != index or not 0 <= index < stack.n:
+            raise ValueError("%s: a device %s is plane 0 .. %d of its stack, got %r" % (what, role, stack.n - 1, index))
+        if device[role] is None:
+            device[role] = stack
+        elif device[role] is not stack:
+            raise ValueError("%s: all device %ss of one call must come from one DeviceFrames" % (what, role))
+        return int(index) * h * w * stack.c, stack.c
+
+    def is_device(operand):
+        return isinstance(operand, tuple) and len(operand) == 2 and isinstance(operand[0], DeviceFrames)
+
     def mask_of(mask):
         if mask is None:
             return -1
+        if is_device(mask):
+            if (mask[0].h, mask[0].w, mask[0].c) != (h, w, 1):
+                raise ValueError("%s: a mask of shape %r on frames of %r" % (what, mask[0].shape[1:], (h, w)))
+            return device_plane(mask, "mask")[0]
         m = np.asarray(mask)
         if m.shape != (h, w):
             raise ValueError("%s: a mask of shape %r on frames of %r" % (what, m.shape, (h, w)))
@@ -2208,6 +2303,12 @@ def _compose_tables(layers, n, h, w, c, what):
         return masks.add(m, origin)
 
     def image_of(image):
+        if is_device(image):
+            if (image[0].h, image[0].w) != (h, w):
+                raise ValueError("The two images to be added must have the same size")
+            if image[0].c == 3 and c == 1:
+                raise ValueError("Cannot add a color image to a monochrome one")
+            return device_plane(image, "image")
         im = np.asarray(image)
         if im.dtype != np.uint8:
             raise TypeError("%s: images are uint8, got %s" % (what, im.dtype))
@@ -2258,7 +2359,12 @@ def _compose_tables(layers, n, h, w, c, what):
             recs.append(rec)
         off[f + 1] = len(recs)
     table = np.array(recs, COMPOSE_LAYER_DTYPE) if recs else np.zeros(0, COMPOSE_LAYER_DTYPE)
-    return table, off, images.packed(), masks.packed()
+    for role, packer in (("mask", masks), ("image", images)):
+        if device[role] is not None and packer.parts:
+            raise ValueError("%s: device and host %ss in one call (the entry point takes one %ss buffer)"
+                             % (what, role, role))
+    return (table, off, device["image"] if device["image"] is not None else images.packed(),
+            device["mask"] if device["mask"] is not None else masks.packed())
 
 
 def compose_layers(frames, layers, color=None, keep=False, stream=None):
@@ -2270,7 +2376,10 @@ def compose_layers(frames, layers, color=None, keep=False, stream=None):
         ('blend', image, weight, mask)           cv2.addWeighted(frame, 1 - weight, image, weight, 0)
     applied in order; masks (h, w), taken as non-zero; images uint8 (h, w) or (h, w, 3).  color: None keeps the
     channels of the frames, True writes a colour stack (a monochrome frame is copied into the three channels first),
-    False asks for a monochrome one.  An array that appears in several layers is uploaded once.
+    False asks for a monochrome one.  An array that appears in several layers is uploaded once.  A mask or an image
+    may be the pair (DeviceFrames, index): plane `index` of a stack that is already on the device (masks monochrome,
+    taken as non-zero) and stays the caller's.  All device masks of one call come from one DeviceFrames, and so do all
+    device images; device and host planes of the same role in one call are a ValueError.
     ValueError, before anything is launched: a size mismatch, a colour image or colour frames on a monochrome
     result, a channel on a monochrome stack, an unknown channel or layer, a strength outside 0 .. 255.
     Returns the composed stack; keep=True returns a DeviceFrames instead (a DeviceFrames handed in with the same
@@ -2295,11 +2404,11 @@ def compose_layers(frames, layers, color=None, keep=False, stream=None):
     dst = src if c == c_src else DeviceFrames(_take(n * h * w * c), n, h, w, c)
     try:
         with _Lease.on(stream) as d:
-            tb, ob, ib, mb = (d.upload(table) if len(table) else None, d.upload(off), d.upload(images),
-                              d.upload(masks))
+            tb, ob = d.upload(table) if len(table) else None, d.upload(off)
+            (ib, ibytes), (mb, mbytes) = ((x.buf, x.nbytes) if isinstance(x, DeviceFrames) else
+                                          (d.upload(x), 0 if x is None else len(x)) for x in (images, masks))
             check(L.va_compose_layers_u8(src.buf.ptr, c_src, dst.buf.ptr, n, h, w, c, _ptr(tb), ob.ptr, len(table),
-                                         _ptr(ib), 0 if images is None else len(images), _ptr(mb),
-                                         0 if masks is None else len(masks), stream))
+                                         _ptr(ib), ibytes, _ptr(mb), mbytes, stream))
             if keep:                       # the tables go back to the pool: the launch must have read them
                 check(L.va_stream_sync(stream))
                 out = dst
@@ -2401,6 +2510,67 @@ def draw(frames, commands, keep=False, stream=None):
             bad = np.flatnonzero(status != 0)
             if len(bad):
                 raise RuntimeError("%s: the device refused frame %d (status %d)" % (what, bad[0], status[bad[0]]))
+        out = src if keep else src.download(stream)
+    except Exception:
+        if dev is None:
+            src.release()
+        raise
+    if not keep:
+        src.release()
+    return out
+
+
+def _frame_map(frame_map, n_src, n_out, what):
+    """the checked int32 map of draw_contours, or None"""
+    if frame_map is None:
+        if n_src != n_out:
+            raise ValueError("%s: contours of %d frames on %d frames need a frame_map" % (what, n_src, n_out))
+        return None
+    fm = np.asarray(frame_map)
+    if fm.ndim != 1 or len(fm) != n_src:
+        raise ValueError("%s: frame_map holds one entry per source frame (%d), got shape %r" % (what, n_src, fm.shape))
+    if fm.size and not np.issubdtype(fm.dtype, np.integer):
+        raise ValueError("%s: frame_map holds integers, got %s" % (what, fm.dtype))
+    if fm.size and (fm.min() < -1 or fm.max() >= n_out):
+        raise ValueError("%s: frame_map values are -1 .. %d" % (what, n_out - 1))
+    return np.ascontiguousarray(fm, np.int32)
+
+
+def draw_contours(frames, contours, color, frame_map=None, keep=False, stream=None):
+    """every contour of a DeviceContours (find_contours(..., keep=True)) as a closed polyline of thickness 1 in one
+    colour, in one chip-wide va_draw_contours_u8 launch (video/io/composer.py:228-237; DESIGN.md §9, "Annotating on
+    the device"): the bytes of ops.draw with one closed polyline per contour, without the host lists.  frames: uint8
+    (n, h, w) or (n, h, w, 3), or a DeviceFrames; color as for ops.draw.  frame_map: None (source frame f is drawn
+    into frame f) or one integer per source frame, the frame it is drawn into or -1 for "not drawn".
+    ValueError, before anything is launched: frames of another size than the contours', a frame_map of the wrong
+    length or with a value outside -1 .. n - 1, a bad colour; RuntimeError: a non-zero device status.
+    Returns the stack; keep=True returns a DeviceFrames (the one handed in, drawn in place).  A DeviceFrames handed
+    in without keep is downloaded and released."""
+    what = "draw_contours"
+    dev = frames if isinstance(frames, DeviceFrames) else None
+    if dev is None:
+        arr, n, h, w, c = _frame_stack(frames, what)
+    else:
+        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    if not isinstance(contours, DeviceContours):
+        raise TypeError("%s: contours are a DeviceContours, got %s" % (what, type(contours).__name__))
+    if (contours.h, contours.w) != (h, w):
+        raise ValueError("%s: contours of frames of %r on frames of %r" % (what, (contours.h, contours.w), (h, w)))
+    packed = _draw_color(color, c, what)
+    fm = _frame_map(frame_map, contours.n, n, what)
+    if contours.ncontours == 0 and dev is None and not keep:
+        return arr.copy()
+    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
+    try:
+        if contours.ncontours:
+            with _Lease.on(stream) as d:
+                mb, st = d.upload(fm), d.take(4)
+                check(_hip.lib().va_draw_contours_u8(src.buf.ptr, n, h, w, c, contours.info.ptr, contours.point_off.ptr,
+                                                     contours.ncontours, contours.points.ptr, contours.npoints,
+                                                     _ptr(mb), contours.n, packed, st.ptr, stream))
+                status = int(st.download((1,), np.int32, stream)[0])
+            if status:
+                raise RuntimeError("%s: the device refused a contour (status %d)" % (what, status))
         out = src if keep else src.download(stream)
     except Exception:
         if dev is None:
