@@ -125,8 +125,14 @@ class _Lease(list):
     when the block ends: after the call's downloads, which synchronise its stream, or on an exception as it is,
     without a synchronisation of its own (none may be added to any path: the pool exists to keep them off the
     per-call ops).  The one exception is compose_layers(keep=True), which returns without a download: it
-    synchronises its stream once before its tables go back to the pool, because the launch still reads them."""
+    synchronises its stream once before its tables go back to the pool, because the launch still reads them.
+    A buffer that outlives the call is a result (result, adopt): the lease owns it until the block ends.  A clean end
+    leaves it to the caller; an exception disposes of it with the rest: into the pool, or through its own `drop`."""
     stream = None                       # the call's stream, for the ops that have one: _Lease.on(stream)
+
+    def __init__(self):
+        list.__init__(self)
+        self.results = []               # (buffer, drop)
 
     @classmethod
     def on(cls, stream):
@@ -137,8 +143,12 @@ class _Lease(list):
     def __enter__(self):
         return self
 
-    def __exit__(self, *exc):
-        _give(*self)
+    def __exit__(self, failure, *exc):
+        try:
+            if failure is not None:
+                self.recall()
+        finally:
+            _give(*self)
 
     def take(self, nbytes):
         """a buffer of at least `nbytes` bytes for an output or a workspace"""
@@ -146,9 +156,28 @@ class _Lease(list):
         self.append(buf)
         return buf
 
+    def adopt(self, buf, drop=None):
+        """`buf` becomes a result of this call; drop: how a buffer that is not the pool's is disposed of"""
+        self.results.append((buf, drop))
+        return buf
+
+    def result(self, nbytes):
+        """a pooled buffer of at least `nbytes` bytes that is a result of this call"""
+        return self.adopt(_take(nbytes))
+
+    def absorb(self, buf):
+        """the pooled buffer `buf`, a result or the caller's, is the lease's from now on: it goes back with the rest"""
+        self.results = [(b, drop) for b, drop in self.results if b is not buf]
+        self.append(buf)
+
+    def recall(self):
+        """the results so far are disposed of now: after a failure, or before a second attempt takes its own"""
+        lost, self.results = self.results, []
+        for buf, drop in lost:
+            (drop or _give)(buf)
+
     def upload(self, arr):
-        """a buffer holding the array `arr`, copied on the call's stream; None (an optional operand left out) stays
-        None"""
+        """a buffer holding `arr`, copied on the call's stream; None (an optional operand left out) stays None"""
         if arr is None:
             return None
         buf = self.take(arr.nbytes)
@@ -158,6 +187,40 @@ class _Lease(list):
 
 def _ptr(buf):
     return None if buf is None else buf.ptr
+
+
+def _rerun(run, *caps):
+    """run(*caps) launches with room for caps and returns (payload, needs), what the input needs of each.  A need beyond
+    its cap runs exactly once more, with the needs as caps; the last answer is returned, and the buffers are run's."""
+    payload, needs = run(*caps)
+    if any(int(need) > cap for need, cap in zip(needs, caps)):
+        payload, needs = run(*(int(need) for need in needs))
+    return payload, needs
+
+
+class _Layout(object):
+    """named fields back to back in one buffer of `nbytes`, in the order given and unpadded (the orders in use are
+    naturally aligned), field `name` at byte at[name].  A field is an array (an upload) or (count, dtype) (an output)."""
+
+    def __init__(self, **fields):
+        self.fields, self.at, self.nbytes = fields, {}, 0
+        for name, field in fields.items():
+            self.at[name] = self.nbytes
+            self.nbytes += field[0] * np.dtype(field[1]).itemsize if type(field) is tuple else field.nbytes
+
+    def packed(self):
+        """the uint8 array of an upload: the bytes of every field"""
+        return np.concatenate([np.frombuffer(arr, np.uint8) for arr in self.fields.values()])     # (C-contiguous arrays)
+
+    def ptr(self, buf, name):
+        """the device address of field `name` in the buffer `buf`"""
+        return buf.ptr + self.at[name]
+
+    def view(self, raw, name):
+        """field `name` of the downloaded uint8 array `raw`, in its dtype"""
+        field = self.fields[name]
+        count, dtype = field if type(field) is tuple else (field.size, field.dtype)
+        return np.frombuffer(raw, dtype, count, self.at[name])
 
 
 # the one dtype -> VA_* table (TEMPORAL_DTYPES: what the temporal statistics take, which is all of it)
@@ -494,11 +557,10 @@ def _with_room(max_points, run):
     """run(capacity) launches with room for `capacity` points per item and returns (points buffer, counts found).
     An explicit max_points truncates; otherwise a count beyond DEFAULT_POINT_CAPACITY (rare: a very long contour or
     path) runs once more with room for the largest.  Returns (points buffer, counts kept, capacity)."""
-    cap = int(max_points) if max_points else DEFAULT_POINT_CAPACITY
-    pts, counts = run(cap)
-    if not max_points and counts.max(initial=0) > cap:
-        cap = int(counts.max())
+    def once(cap):
         pts, counts = run(cap)
+        return (pts, counts, cap), (counts.max(initial=0),)
+    (pts, counts, cap), _ = once(int(max_points)) if max_points else _rerun(once, DEFAULT_POINT_CAPACITY)
     return pts, np.minimum(counts, cap), cap
 
 
@@ -613,38 +675,25 @@ def find_contours(masks, ret_info=False, moments=False, stream=None, keep=False)
         if arr is not None:
             arr = _as_mask(arr, keep_uint8=True)
         L = _hip.lib()
-        held = []                           # the result's buffers: they outlive the call's lease
-        try:
-            with _Lease.on(stream) as d:
-                ws_bytes = L.va_find_contours_workspace_bytes(n, h, w)
-                src = masks.buf if arr is None else d.upload(arr)
-                ws, ncb, tot = d.take(ws_bytes), d.take(n * 4), d.take(16)
+        with _Lease.on(stream) as d:
+            ws_bytes = L.va_find_contours_workspace_bytes(n, h, w)
+            src = masks.buf if arr is None else d.upload(arr)
+            ws, ncb, tot = d.take(ws_bytes), d.take(n * 4), d.take(16)
 
-                def run(capc, capp):
-                    _give(*held)
-                    held[:] = []
-                    for nbytes in (max(capc, 1) * CONTOUR_INFO_DTYPE.itemsize, (capc + 1) * 8, max(capp, 1) * 8):
-                        held.append(_take(nbytes))
-                    info, off, pts = held
-                    check(L.va_find_contours(src.ptr, n, h, w, ncb.ptr, tot.ptr, info.ptr, off.ptr, capc, pts.ptr,
-                                             capp, ws.ptr, ws_bytes, stream))
-                    return tot.download((2,), np.int64, stream)
-                capc, capp = DEFAULT_CONTOUR_CAPACITY, DEFAULT_CONTOUR_POINT_CAPACITY
-                k, npts = run(capc, capp)
-                if k > capc or npts > capp:
-                    k, npts = run(int(k), int(npts))
-                counts = ncb.download((n,), np.int32, stream)
-        except Exception:
-            _give(*held)
-            raise
-        found = DeviceContours(held[0], held[1], held[2], n, h, w, counts, k, npts)
+            def run(capc, capp):
+                d.recall()                  # the result's buffers outlive the lease; a first attempt's do not
+                held = [d.result(nbytes) for nbytes in (max(capc, 1) * CONTOUR_INFO_DTYPE.itemsize, (capc + 1) * 8,
+                                                        max(capp, 1) * 8)]
+                check(L.va_find_contours(src.ptr, n, h, w, ncb.ptr, tot.ptr, held[0].ptr, held[1].ptr, capc,
+                                         held[2].ptr, capp, ws.ptr, ws_bytes, stream))
+                return held, tot.download((2,), np.int64, stream)
+            held, (k, npts) = _rerun(run, DEFAULT_CONTOUR_CAPACITY, DEFAULT_CONTOUR_POINT_CAPACITY)
+            found = DeviceContours(held[0], held[1], held[2], n, h, w, ncb.download((n,), np.int32, stream), k, npts)
     if keep:
         return found
-    try:
+    with _Lease.on(stream) as d:            # the result's buffers are this lease's: they go back behind the download
+        d.extend((found.info, found.point_off, found.points))
         res = found.download(ret_info, moments, stream)
-    finally:
-        if n:
-            found.release()
     if single:
         res = tuple(r[0] for r in res) if isinstance(res, tuple) else res[0]
     return res
@@ -900,20 +949,16 @@ def potential_gradients(frames, sigma=0.0, stream=None):
     arr, dtype = _potential_stack(frames)
     n, h, w = arr.shape
     L = _hip.lib()
-    fx, fy = DeviceBuffer(arr.nbytes * (8 // arr.itemsize)), DeviceBuffer(arr.nbytes * (8 // arr.itemsize))
-    try:
-        with _Lease.on(stream) as d:
-            src, blur = d.upload(arr), None
-            if sigma > 0 and n:
-                blur = d.take(arr.nbytes)
-                fn = L.va_gaussian_u8 if dtype == _hip.VA_U8 else L.va_gaussian_f32
-                check(fn(src.ptr, blur.ptr, n, h, w, 1, float(sigma), stream))
-            check(L.va_sobel5_f64((blur or src).ptr, dtype, fx.ptr, fy.ptr, n, h, w, stream))
-            check(L.va_stream_sync(stream))
-    except Exception:                  # the caller never sees fx and fy: they are not pooled, free them here
-        fx.free()
-        fy.free()
-        raise
+    with _Lease.on(stream) as d:
+        # fx and fy are the caller's to free, not pooled: a call that fails frees them, the caller never sees them
+        fx, fy = (d.adopt(DeviceBuffer(arr.nbytes * (8 // arr.itemsize)), DeviceBuffer.free) for _ in range(2))
+        src, blur = d.upload(arr), None
+        if sigma > 0 and n:
+            blur = d.take(arr.nbytes)
+            fn = L.va_gaussian_u8 if dtype == _hip.VA_U8 else L.va_gaussian_f32
+            check(fn(src.ptr, blur.ptr, n, h, w, 1, float(sigma), stream))
+        check(L.va_sobel5_f64((blur or src).ptr, dtype, fx.ptr, fy.ptr, n, h, w, stream))
+        check(L.va_stream_sync(stream))
     return fx, fy, (n, h, w)
 
 
@@ -1172,21 +1217,16 @@ def potential_gradients_ragged(potentials, sigma=0.0, implementation=None, strea
     code = _DTYPE_CODES[arrs[0].dtype]
     resident = _grad_resident_items(sizes, code, sigma, implementation, "potential_gradients_ragged")
     L = _hip.lib()
-    fx, fy = DeviceBuffer(total * 8), DeviceBuffer(total * 8)
-    try:
-        with _Lease.on(stream) as d:
-            src, st = d.upload(flat), d.take(m * 4)
-            plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
-            _enqueue_ragged_gradients(d, plan, src, code, shapes, offsets, sizes, total, sigma, resident, fx, fy,
-                                      st.ptr, stream)
-            if resident:
-                _check_status(st.download((len(resident),), np.int32, stream), "potential_gradients_ragged")
-            else:
-                check(L.va_stream_sync(stream))
-    except Exception:                  # the caller never sees fx and fy: they are not pooled, free them here
-        fx.free()
-        fy.free()
-        raise
+    with _Lease.on(stream) as d:
+        fx, fy = (d.adopt(DeviceBuffer(total * 8), DeviceBuffer.free) for _ in range(2))
+        src, st = d.upload(flat), d.take(m * 4)
+        plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
+        _enqueue_ragged_gradients(d, plan, src, code, shapes, offsets, sizes, total, sigma, resident, fx, fy,
+                                  st.ptr, stream)
+        if resident:
+            _check_status(st.download((len(resident),), np.int32, stream), "potential_gradients_ragged")
+        else:
+            check(L.va_stream_sync(stream))
     return fx, fy, shapes, offsets
 
 
@@ -1251,27 +1291,22 @@ def centerline_gradients(contours, boxes, sigma=1.0, stream=None):
                          % (DT_MAX_HEIGHT, DT_MAX_WIDTH))
     resident = _grad_resident_items(sizes, _hip.VA_F32, sigma, None, "centerline_gradients")
     L = _hip.lib()
-    fx, fy = DeviceBuffer(total * 8), DeviceBuffer(total * 8)
-    try:
-        with _Lease.on(stream) as d:
-            vb, vob, bb, sb, ob = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)), d.upload(shapes),
-                                   d.upload(offsets))
-            mask, dist, st = d.take(max(total, 1)), d.take(max(total, 1) * 4), d.take(3 * m * 4)
-            plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
-            check(L.va_fill_poly(vb.ptr, vob.ptr, len(verts), bb.ptr, ob.ptr, total, m, 1, mask.ptr, st.ptr, stream))
-            check(L.va_distance_transform_l2_5(mask.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()), dist.ptr,
-                                               st.ptr + 4 * m, stream))
-            # a mask or a map a status refuses is not written: what the later kernels make of it is discarded below
-            _enqueue_ragged_gradients(d, plan, dist, _hip.VA_F32, shapes, offsets, sizes, total, sigma, resident, fx, fy,
-                                      st.ptr + 8 * m, stream)
-            status = st.download((2 * m + len(resident),), np.int32, stream)
-            _check_status(status[:m], "centerline_gradients (fill)")
-            _check_status(status[m:2 * m], "centerline_gradients (distance transform)")
-            _check_status(status[2 * m:], "centerline_gradients (gradients)")
-    except Exception:
-        fx.free()
-        fy.free()
-        raise
+    with _Lease.on(stream) as d:
+        fx, fy = (d.adopt(DeviceBuffer(total * 8), DeviceBuffer.free) for _ in range(2))
+        vb, vob, bb, sb, ob = (d.upload(verts), d.upload(vert_off), d.upload(bx.astype(np.int32)), d.upload(shapes),
+                               d.upload(offsets))
+        mask, dist, st = d.take(max(total, 1)), d.take(max(total, 1) * 4), d.take(3 * m * 4)
+        plan = _plan_ragged_gradients(d, shapes, offsets, sizes, resident)
+        check(L.va_fill_poly(vb.ptr, vob.ptr, len(verts), bb.ptr, ob.ptr, total, m, 1, mask.ptr, st.ptr, stream))
+        check(L.va_distance_transform_l2_5(mask.ptr, sb.ptr, ob.ptr, total, m, int(shapes[:, 1].max()), dist.ptr,
+                                           st.ptr + 4 * m, stream))
+        # a mask or a map a status refuses is not written: what the later kernels make of it is discarded below
+        _enqueue_ragged_gradients(d, plan, dist, _hip.VA_F32, shapes, offsets, sizes, total, sigma, resident, fx, fy,
+                                  st.ptr + 8 * m, stream)
+        status = st.download((2 * m + len(resident),), np.int32, stream)
+        _check_status(status[:m], "centerline_gradients (fill)")
+        _check_status(status[m:2 * m], "centerline_gradients (distance transform)")
+        _check_status(status[2 * m:], "centerline_gradients (gradients)")
     return fx, fy, shapes, offsets
 
 
@@ -1576,11 +1611,9 @@ def _skeleton_graph_run(d, src, sb, ob, total, m, stream):
                                   d.take(max(capp, 1) * 8))
         check(L.va_skeleton_graph(src.ptr, sb.ptr, ob.ptr, total, m, cnt.ptr, tot.ptr, nodes.ptr, capn, edges.ptr,
                                   off.ptr, cape, pts.ptr, capp, ws.ptr, ws_bytes, stream))
-        return nodes, edges, off, pts, tot.download((3,), np.int64, stream)
-    caps = (DEFAULT_SKELETON_NODE_CAPACITY, DEFAULT_SKELETON_EDGE_CAPACITY, DEFAULT_SKELETON_POINT_CAPACITY)
-    nodes, edges, off, pts, totals = run(*caps)
-    if any(int(t) > c for t, c in zip(totals, caps)):
-        nodes, edges, off, pts, totals = run(*(int(t) for t in totals))
+        return (nodes, edges, off, pts), tot.download((3,), np.int64, stream)
+    (nodes, edges, off, pts), totals = _rerun(run, DEFAULT_SKELETON_NODE_CAPACITY, DEFAULT_SKELETON_EDGE_CAPACITY,
+                                              DEFAULT_SKELETON_POINT_CAPACITY)
     nn, ne, npts = (int(t) for t in totals)
     counts = cnt.download((m, 2), np.int32, stream).astype(np.int64)
     node_rec = nodes.download((nn,), SKELETON_NODE_DTYPE, stream)
@@ -1925,36 +1958,31 @@ def curves_equidistant(curves, spacing=None, count=None, offsets=None, ret_lengt
                            2.0 * CURVES_MAX_STEPS)
         room = int(np.where(walked, np.maximum(np.floor(steps).astype(np.int64) + CURVES_ROOM_SLACK, npts), ct).sum())
         # one packed upload: [point offsets | spacings | translations | points | counts]
-        parts = {"off": first.astype(np.int64), "sp": sp,
-                 "tr": np.ascontiguousarray(shifts[dev]).reshape(-1) if shifts is not None else np.zeros(0),
-                 "pts": flat, "ct": np.where(walked, 0, ct).astype(np.int32)}
-        at, nbytes = {}, 0
-        for name, part in parts.items():
-            at[name], nbytes = nbytes, nbytes + part.nbytes
-        packed = np.concatenate([part.view(np.uint8) for part in parts.values()])
-        # one output buffer: [total | out offsets | in lengths | out lengths | counts | status | points]
-        o_total, o_off, o_lin, o_lout = 0, 8, 8 * md + 16, 16 * md + 16
-        o_cnt, o_st, head = 24 * md + 16, 28 * md + 16, 32 * md + 16
+        ins = _Layout(off=first.astype(np.int64), sp=sp,
+                      tr=np.ascontiguousarray(shifts[dev]) if shifts is not None else np.zeros(0),
+                      pts=flat, ct=np.where(walked, 0, ct).astype(np.int32))
         L = _hip.lib()
         with _Lease.on(stream) as d:
-            src = d.upload(packed)
+            src = d.upload(ins.packed())
 
             def run(cap):
-                out = d.take(head + 16 * max(cap, 1))
-                check(L.va_curves_equidistant(src.ptr + at["pts"], src.ptr + at["off"], total // 2, md,
-                                              src.ptr + at["sp"], src.ptr + at["ct"],
-                                              src.ptr + at["tr"] if shifts is not None else None,
-                                              out.ptr + o_cnt, out.ptr + o_off, out.ptr + o_lin, out.ptr + o_st,
-                                              out.ptr + o_total, out.ptr + head, cap, out.ptr + o_lout, stream))
-                raw = out.download((head + 16 * max(cap, 1),), np.uint8, stream)
-                return raw, int(raw[:8].view(np.int64)[0])
-            raw, found = run(room)
-            if found > room:                   # nothing was written: exactly once more, with exact room
-                raw, found = run(found)
-        out_off = raw[o_off:o_lin].view(np.int64)
-        out_len = raw[o_lout:o_cnt].view(np.float64)
-        status = raw[o_st:head].view(np.int32)
-        pts = raw[head:head + 16 * found].view(np.float64).reshape(found, 2).copy()
+                # one output buffer: [total | out offsets | in lengths | out lengths | counts | status | points]
+                outs = _Layout(total=(1, np.int64), off=(md + 1, np.int64), lin=(md, np.float64),
+                               lout=(md, np.float64), cnt=(md, np.int32), st=(md, np.int32),
+                               pts=(2 * max(cap, 1), np.float64))
+                out = d.take(outs.nbytes)
+                check(L.va_curves_equidistant(ins.ptr(src, "pts"), ins.ptr(src, "off"), total // 2, md,
+                                              ins.ptr(src, "sp"), ins.ptr(src, "ct"),
+                                              ins.ptr(src, "tr") if shifts is not None else None,
+                                              outs.ptr(out, "cnt"), outs.ptr(out, "off"), outs.ptr(out, "lin"),
+                                              outs.ptr(out, "st"), outs.ptr(out, "total"), outs.ptr(out, "pts"), cap,
+                                              outs.ptr(out, "lout"), stream))
+                raw = out.download((outs.nbytes,), np.uint8, stream)
+                return (outs, raw), outs.view(raw, "total")
+            (outs, raw), needs = _rerun(run, room)         # a need beyond the room: nothing was written
+        found = int(needs[0])
+        out_off, out_len, status = (outs.view(raw, name) for name in ("off", "lout", "st"))
+        pts = outs.view(raw, "pts")[:2 * found].reshape(found, 2).copy()
         for j, k in enumerate(dev):
             if status[j] != 0:                 # (VA_CURVES_MAX_STEPS: the reference's own walk, as slow as it is)
                 on_host(k)
@@ -2130,25 +2158,23 @@ def simplify_curves(curves, tolerance, method="rdp", closed=False, stream=None):
         first = np.append(offsets, total) // 2
         tol = np.array([float(tolerances[k]) for k in dev], np.float64)
         # one packed upload: [point offsets | tolerances | points]; one output buffer: [counts | status | flags]
-        packed = np.concatenate([first.astype(np.int64).view(np.uint8), tol.view(np.uint8), flat.view(np.uint8)])
-        at_tol, at_pts = 8 * (md + 1), 8 * (md + 1) + 8 * md
-        o_st, o_keep = 4 * md, 8 * md
+        ins = _Layout(off=first.astype(np.int64), tol=tol, pts=flat)
+        outs = _Layout(cnt=(md, np.int32), st=(md, np.int32), keep=(npoints, np.uint8))
         L = _hip.lib()
         with _Lease.on(stream) as d:
-            src = d.upload(packed)
-            out = d.take(o_keep + npoints)
+            src = d.upload(ins.packed())
+            out = d.take(outs.nbytes)
+            operands = (ins.ptr(src, "pts"), ins.ptr(src, "off"), npoints, md, ins.ptr(src, "tol"))
+            results = (outs.ptr(out, "keep"), outs.ptr(out, "cnt"), outs.ptr(out, "st"))
             if method == "rdp":
-                check(L.va_simplify_rdp(src.ptr + at_pts, src.ptr, npoints, md, src.ptr + at_tol, out.ptr + o_keep,
-                                        out.ptr, out.ptr + o_st, stream))
+                check(L.va_simplify_rdp(*operands, *results, stream))
             else:
                 need = L.va_simplify_visvalingam_workspace_bytes(npoints)
                 ws = d.take(need)
-                check(L.va_simplify_visvalingam(src.ptr + at_pts, src.ptr, npoints, md, src.ptr + at_tol,
-                                                1 if closed else 0, out.ptr + o_keep, out.ptr, out.ptr + o_st,
-                                                ws.ptr, need, stream))
-            raw = out.download((o_keep + npoints,), np.uint8, stream)
-        status = raw[o_st:o_keep].view(np.int32)
-        keep = raw[o_keep:] != 0
+                check(L.va_simplify_visvalingam(*operands, 1 if closed else 0, *results, ws.ptr, need, stream))
+            raw = out.download((outs.nbytes,), np.uint8, stream)
+        status = outs.view(raw, "st")
+        keep = outs.view(raw, "keep") != 0
         run, bounds = (status == 0).tolist(), first.tolist()
         for j, k in enumerate(dev):
             if run[j]:
@@ -2192,13 +2218,10 @@ class DeviceFrames(object):
     @classmethod
     def upload(cls, frames, stream=None):
         arr, n, h, w, c = _frame_stack(frames, "DeviceFrames.upload")
-        buf = _take(max(arr.nbytes, 1))
-        try:
+        with _Lease.on(stream) as d:
+            buf = d.result(max(arr.nbytes, 1))
             buf.upload(arr, stream)
-        except Exception:
-            _give(buf)
-            raise
-        return cls(buf, n, h, w, c)
+            return cls(buf, n, h, w, c)
 
     def download(self, stream=None):
         return self.buf.download(self.shape, np.uint8, stream)
@@ -2210,8 +2233,8 @@ class DeviceFrames(object):
         if any(not 0 <= i < self.n for i in idx):
             raise IndexError("DeviceFrames.gather: frames are 0 .. %d, got %r" % (self.n - 1, idx))
         frame = self.h * self.w * self.c
-        out = DeviceFrames(_take(max(len(idx) * frame, 1)), len(idx), self.h, self.w, self.c)
-        try:
+        with _Lease.on(stream) as d:
+            out = DeviceFrames(d.result(max(len(idx) * frame, 1)), len(idx), self.h, self.w, self.c)
             L, k = _hip.lib(), 0
             while k < len(idx) and frame:
                 run = 1
@@ -2220,15 +2243,12 @@ class DeviceFrames(object):
                 check(L.va_memcpy_d2d(out.buf.ptr + k * frame, self.buf.ptr + idx[k] * frame, run * frame, stream))
                 k += run
             check(L.va_stream_sync(stream))
-        except Exception:
-            out.release()
-            raise
-        return out
+            return out
 
-    def release(self):
+    def release(self, into=None):
         buf, self.buf = self.buf, None
         if buf is not None:
-            _give(buf)
+            (_give if into is None else into.absorb)(buf)      # into: a lease, which gives it back with its own
 
 
 def _frame_stack(frames, what):
@@ -2239,6 +2259,30 @@ def _frame_stack(frames, what):
     if not (arr.ndim == 3 or (arr.ndim == 4 and arr.shape[3] == 3)):
         raise ValueError("%s: frames are a stack (n, h, w) or (n, h, w, 3), got shape %r" % (what, arr.shape))
     return (np.ascontiguousarray(arr),) + tuple(arr.shape[:3]) + (1 if arr.ndim == 3 else 3,)
+
+
+def _frames_in(frames, what):
+    """(src, n, h, w, c, owned): the caller's DeviceFrames, or the _frame_stack array the call uploads itself (owned)"""
+    if isinstance(frames, DeviceFrames):
+        return frames, frames.n, frames.h, frames.w, frames.c, False
+    return _frame_stack(frames, what) + (True,)
+
+
+def _frames_on_device(d, src, owned):
+    """the DeviceFrames of `src` (_frames_in); one the call uploads itself is a result of the lease `d`"""
+    if owned:
+        src = DeviceFrames.upload(src, d.stream)
+        d.adopt(src.buf)
+    return src
+
+
+def _frames_out(d, stack, keep):
+    """the tail of the ops that return frames, in their lease `d`: the stack under keep, else its download and release"""
+    if keep:
+        return stack
+    out = stack.download(d.stream)
+    stack.release(into=d)
+    return out
 
 
 class _BytePacker(object):
@@ -2385,46 +2429,31 @@ def compose_layers(frames, layers, color=None, keep=False, stream=None):
     Returns the composed stack; keep=True returns a DeviceFrames instead (a DeviceFrames handed in with the same
     channels is composed in place and returned; otherwise it is released)."""
     what = "compose_layers"
-    dev = frames if isinstance(frames, DeviceFrames) else None
-    if dev is None:
-        arr, n, h, w, c_src = _frame_stack(frames, what)
-    else:
-        n, h, w, c_src = dev.n, dev.h, dev.w, dev.c
+    frames, n, h, w, c_src, owned = _frames_in(frames, what)
     c = c_src if color is None else (3 if color else 1)
     if c_src == 3 and c == 1:
         raise ValueError("Cannot copy a color image into a monochrome video.")
     table, off, images, masks = _compose_tables(list(layers), n, h, w, c, what)
     if n == 0 or h == 0 or w == 0:
         out = np.zeros((n, h, w) + ((3,) if c == 3 else ()), np.uint8)
-        if dev is not None:
-            dev.release()
+        if not owned:
+            frames.release()
         return DeviceFrames.upload(out, stream) if keep else out
     L = _hip.lib()
-    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
-    dst = src if c == c_src else DeviceFrames(_take(n * h * w * c), n, h, w, c)
-    try:
-        with _Lease.on(stream) as d:
-            tb, ob = d.upload(table) if len(table) else None, d.upload(off)
-            (ib, ibytes), (mb, mbytes) = ((x.buf, x.nbytes) if isinstance(x, DeviceFrames) else
-                                          (d.upload(x), 0 if x is None else len(x)) for x in (images, masks))
-            check(L.va_compose_layers_u8(src.buf.ptr, c_src, dst.buf.ptr, n, h, w, c, _ptr(tb), ob.ptr, len(table),
-                                         _ptr(ib), ibytes, _ptr(mb), mbytes, stream))
-            if keep:                       # the tables go back to the pool: the launch must have read them
-                check(L.va_stream_sync(stream))
-                out = dst
-            else:
-                out = dst.download(stream)
-    except Exception:
+    with _Lease.on(stream) as d:
+        src = _frames_on_device(d, frames, owned)
+        dst = src if c == c_src else DeviceFrames(d.result(n * h * w * c), n, h, w, c)
+        tb, ob = d.upload(table) if len(table) else None, d.upload(off)
+        (ib, ibytes), (mb, mbytes) = ((x.buf, x.nbytes) if isinstance(x, DeviceFrames) else
+                                      (d.upload(x), 0 if x is None else len(x)) for x in (images, masks))
+        check(L.va_compose_layers_u8(src.buf.ptr, c_src, dst.buf.ptr, n, h, w, c, _ptr(tb), ob.ptr, len(table),
+                                     _ptr(ib), ibytes, _ptr(mb), mbytes, stream))
+        if keep:                           # the tables go back to the pool: the launch must have read them
+            check(L.va_stream_sync(stream))
+        out = _frames_out(d, dst, keep)
         if dst is not src:
-            dst.release()
-        if dev is None:
-            src.release()
-        raise
-    if dst is not src:
-        src.release()
-    if not keep:
-        dst.release()
-    return out
+            src.release(into=d)
+        return out
 
 
 def _draw_color(color, c, what):
@@ -2477,6 +2506,18 @@ def _draw_tables(commands, n, c, what):
     return table, off, np.ascontiguousarray(points, np.int32)
 
 
+def _drawn(frames, owned, launch, keep, stream):
+    """the body draw and draw_contours share, for frames as _frames_in gives them: launch(lease, DeviceFrames) draws
+    in place (None: there is nothing to draw), and the stack comes back as _frames_out returns it"""
+    if launch is None and owned and not keep:
+        return frames.copy()
+    with _Lease.on(stream) as d:
+        dst = _frames_on_device(d, frames, owned)
+        if launch is not None:
+            launch(d, dst)
+        return _frames_out(d, dst, keep)
+
+
 def draw(frames, commands, keep=False, stream=None):
     """the thickness-1 drawing of VideoComposer (cv2.drawContours, polylines, rectangle, circle;
     video/io/composer.py:236, :257, :284, :298) on a whole stack in one va_draw_u8 launch, one workgroup per frame
@@ -2491,33 +2532,18 @@ def draw(frames, commands, keep=False, stream=None):
     Returns the stack; keep=True returns a DeviceFrames (the one handed in, drawn in place).  A DeviceFrames handed
     in without keep is downloaded and released."""
     what = "draw"
-    dev = frames if isinstance(frames, DeviceFrames) else None
-    if dev is None:
-        arr, n, h, w, c = _frame_stack(frames, what)
-    else:
-        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    frames, n, h, w, c, owned = _frames_in(frames, what)
     table, off, points = _draw_tables(list(commands), n, c, what)
-    if len(table) == 0 and dev is None and not keep:
-        return arr.copy()
-    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
-    try:
-        if len(table):
-            with _Lease.on(stream) as d:
-                tb, ob, pb, st = d.upload(table), d.upload(off), d.upload(points) if len(points) else None, d.take(n * 4)
-                check(_hip.lib().va_draw_u8(src.buf.ptr, n, h, w, c, tb.ptr, ob.ptr, len(table), _ptr(pb), len(points),
-                                            st.ptr, stream))
-                status = st.download((n,), np.int32, stream)
-            bad = np.flatnonzero(status != 0)
-            if len(bad):
-                raise RuntimeError("%s: the device refused frame %d (status %d)" % (what, bad[0], status[bad[0]]))
-        out = src if keep else src.download(stream)
-    except Exception:
-        if dev is None:
-            src.release()
-        raise
-    if not keep:
-        src.release()
-    return out
+
+    def launch(d, dst):
+        tb, ob, pb, st = d.upload(table), d.upload(off), d.upload(points) if len(points) else None, d.take(n * 4)
+        check(_hip.lib().va_draw_u8(dst.buf.ptr, n, h, w, c, tb.ptr, ob.ptr, len(table), _ptr(pb), len(points),
+                                    st.ptr, stream))
+        status = st.download((n,), np.int32, stream)
+        bad = np.flatnonzero(status != 0)
+        if len(bad):
+            raise RuntimeError("%s: the device refused frame %d (status %d)" % (what, bad[0], status[bad[0]]))
+    return _drawn(frames, owned, launch if len(table) else None, keep, stream)
 
 
 def _frame_map(frame_map, n_src, n_out, what):
@@ -2547,38 +2573,23 @@ def draw_contours(frames, contours, color, frame_map=None, keep=False, stream=No
     Returns the stack; keep=True returns a DeviceFrames (the one handed in, drawn in place).  A DeviceFrames handed
     in without keep is downloaded and released."""
     what = "draw_contours"
-    dev = frames if isinstance(frames, DeviceFrames) else None
-    if dev is None:
-        arr, n, h, w, c = _frame_stack(frames, what)
-    else:
-        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    frames, n, h, w, c, owned = _frames_in(frames, what)
     if not isinstance(contours, DeviceContours):
         raise TypeError("%s: contours are a DeviceContours, got %s" % (what, type(contours).__name__))
     if (contours.h, contours.w) != (h, w):
         raise ValueError("%s: contours of frames of %r on frames of %r" % (what, (contours.h, contours.w), (h, w)))
     packed = _draw_color(color, c, what)
     fm = _frame_map(frame_map, contours.n, n, what)
-    if contours.ncontours == 0 and dev is None and not keep:
-        return arr.copy()
-    src = dev if dev is not None else DeviceFrames.upload(arr, stream)
-    try:
-        if contours.ncontours:
-            with _Lease.on(stream) as d:
-                mb, st = d.upload(fm), d.take(4)
-                check(_hip.lib().va_draw_contours_u8(src.buf.ptr, n, h, w, c, contours.info.ptr, contours.point_off.ptr,
-                                                     contours.ncontours, contours.points.ptr, contours.npoints,
-                                                     _ptr(mb), contours.n, packed, st.ptr, stream))
-                status = int(st.download((1,), np.int32, stream)[0])
-            if status:
-                raise RuntimeError("%s: the device refused a contour (status %d)" % (what, status))
-        out = src if keep else src.download(stream)
-    except Exception:
-        if dev is None:
-            src.release()
-        raise
-    if not keep:
-        src.release()
-    return out
+
+    def launch(d, dst):
+        mb, st = d.upload(fm), d.take(4)
+        check(_hip.lib().va_draw_contours_u8(dst.buf.ptr, n, h, w, c, contours.info.ptr, contours.point_off.ptr,
+                                             contours.ncontours, contours.points.ptr, contours.npoints,
+                                             _ptr(mb), contours.n, packed, st.ptr, stream))
+        status = int(st.download((1,), np.int32, stream)[0])
+        if status:
+            raise RuntimeError("%s: the device refused a contour (status %d)" % (what, status))
+    return _drawn(frames, owned, launch if contours.ncontours else None, keep, stream)
 
 
 # ------------------------------------------------------------------------------------------------ Motion-JPEG
@@ -2698,16 +2709,11 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, s
     blob[offsets[k]:offsets[k + 1]]."""
     what = "jpeg_encode"
     hh, vv = jpeg_sampling(sampling, what=what)
-    dev = frames if isinstance(frames, DeviceFrames) else None
-    if dev is None:
-        arr = np.asarray(frames)
-        if arr.dtype != np.uint8:
-            raise TypeError("%s: frames are uint8, got %s" % (what, arr.dtype))
-        if color is not None and arr.ndim == (3 if color else 2):
-            arr = arr[None]
-        arr, n, h, w, c = _frame_stack(arr, what)
-    else:
-        n, h, w, c = dev.n, dev.h, dev.w, dev.c
+    if not isinstance(frames, DeviceFrames):
+        frames = np.asarray(frames)                 # (_frames_in checks the dtype and the shape)
+        if color is not None and frames.ndim == (3 if color else 2):
+            frames = frames[None]
+    frames, n, h, w, c, owned = _frames_in(frames, what)
     if color is not None and (c == 3) != bool(color):
         raise ValueError("%s: color=%r with frames of %d channel(s)" % (what, color, c))
     jpeg_sampling(sampling, c, what)
@@ -2717,30 +2723,29 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, s
     if n == 0:
         return (np.zeros(0, np.uint8), np.zeros(1, np.int64)) if ret_packed else []
     head = np.frombuffer(jpeg_header(h, w, c, quality, (hh, vv)), np.uint8)
-    consts = np.concatenate([tables[0], tables[1], head])
+    consts = _Layout(luma=tables[0], chroma=tables[1], head=head)
+    sizes = _Layout(total=(1, np.int64), offsets=(n + 1, np.int64), sizes=(n, np.int64))
     nseg = -(-h // (8 * vv))
     room = n * (len(head) + 2 * nseg) + (n * h * w * c) // JPEG_ROOM_DIVISOR
     L = _hip.lib()
     with _Lease.on(stream) as d:
-        src = dev.buf if dev is not None else d.upload(arr)
-        cb = d.upload(consts)
-        info = d.take(16 * n + 16)                  # [total | offsets (n + 1) | sizes (n)], int64
+        src = d.upload(frames) if owned else frames.buf
+        cb = d.upload(consts.packed())
+        info = d.take(sizes.nbytes)
 
         def run(cap):
             out = d.take(max(cap, 1))
-            outs = (cb.ptr, cb.ptr + 128, len(head), info.ptr + 16 + 8 * n, info.ptr + 8, info.ptr, out.ptr, cap,
-                    stream)
+            outs = (consts.ptr(cb, "luma"), consts.ptr(cb, "head"), len(head), sizes.ptr(info, "sizes"),
+                    sizes.ptr(info, "offsets"), sizes.ptr(info, "total"), out.ptr, cap, stream)
             if (hh, vv) == (1, 1):
                 check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, *outs))
             else:
                 check(L.va_jpeg_encode_sampled_u8(src.ptr, n, h, w, c, hh, vv, *outs))
-            meta = info.download((2 * n + 2,), np.int64, stream)
-            return out, meta
-        out, meta = run(room)
-        if meta[0] > room:                          # nothing was written: exactly once more, with exact room
-            out, meta = run(int(meta[0]))
-        blob = out.download((int(meta[0]),), np.uint8, stream)
-    offsets = meta[1:n + 2].copy()
+            meta = info.download((sizes.nbytes,), np.uint8, stream)
+            return (out, meta), sizes.view(meta, "total")
+        (out, meta), (total,) = _rerun(run, room)   # a total beyond the room: nothing was written
+        blob = out.download((int(total),), np.uint8, stream)
+    offsets = sizes.view(meta, "offsets").copy()
     if ret_packed:
         return blob, offsets
     raw = blob.tobytes()
@@ -2999,64 +3004,57 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False, 
         raise ValueError("%s: color=%r with files of %d component(s)" % (what, color, c))
     frame_bytes = h * w * c
     L = _hip.lib()
-    out = _take(max(n * frame_bytes, 1))
-    try:
-        with _Lease.on(stream) as d:
-            status_buf = d.take(4 * n)
-            rounds_buf, split_groups = d.take(4 * n), []
-            for first, stop in jpeg_decode_groups(heads):
-                k, head = stop - first, heads[first]
-                base = int(offsets[first])
-                src = d.upload(blob[base:max(int(offsets[stop]), base + 1)])
-                meta = np.concatenate([offsets[first:stop + 1] - base,
-                                       np.array([hd["scan_begin"] for hd in heads[first:stop]], np.int64)])
-                mb = d.upload(meta)
-                tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
-                cb = d.upload(np.frombuffer(head["qtables"].tobytes() + tables, np.uint8))
-                luma = tuple(head["sampling"])
-                scan_bytes = (np.diff(offsets[first:stop + 1])
-                              - np.array([hd["scan_begin"] for hd in heads[first:stop]], np.int64)).clip(0)
-                if head["nseg"] == 1 and split is not False and (
-                        split is not None or scan_bytes.mean() >= JPEG_SPLIT_MIN_BYTES):
-                    # one segment a frame: one lane per sub_bytes of it
-                    size, most = L.va_jpeg_decode_split_workspace_bytes, int(scan_bytes.max())
-                    one, need = (int(size(frames, h, w, c, luma[0], luma[1], sub_bytes, most)) for frames in (1, k))
-                    room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
-                    ws = d.take(room)
-                    check(L.va_jpeg_decode_split_u8(
-                        src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, luma[0], luma[1], cb.ptr, cb.ptr + 64 * c,
-                        len(tables), out.ptr + first * frame_bytes, status_buf.ptr + 4 * first, ws.ptr, room, sub_bytes,
-                        JPEG_SPLIT_MAX_ROUNDS, most, rounds_buf.ptr + 4 * first, stream))
-                    split_groups.append((first, stop))
-                    continue
-                # the plain entry for monochrome and 1 x 1 files, the _sampled one with (luma_h, luma_v) for the rest
-                if luma == (1, 1):
-                    decode, size, luma = L.va_jpeg_decode_u8, L.va_jpeg_decode_workspace_bytes, ()
-                else:
-                    decode, size = L.va_jpeg_decode_sampled_u8, L.va_jpeg_decode_sampled_workspace_bytes
-                one, need = (int(size(frames, h, w, c, head["ri"], *luma)) for frames in (1, k))
+    with _Lease.on(stream) as d:
+        out = (d.result if keep else d.take)(max(n * frame_bytes, 1))       # under keep it leaves with the caller
+        status_buf = d.take(4 * n)
+        rounds_buf, split_groups = d.take(4 * n), []
+        for first, stop in jpeg_decode_groups(heads):
+            k, head = stop - first, heads[first]
+            base = int(offsets[first])
+            src = d.upload(blob[base:max(int(offsets[stop]), base + 1)])
+            scan_begin = np.array([hd["scan_begin"] for hd in heads[first:stop]], np.int64)
+            meta = _Layout(offsets=offsets[first:stop + 1] - base, scan_begin=scan_begin)
+            mb = d.upload(meta.packed())
+            tables = b"".join(_jpeg_decode_table(*dc) + _jpeg_decode_table(*ac) for dc, ac in head["huff"])
+            consts = _Layout(qtables=head["qtables"], huff=np.frombuffer(tables, np.uint8))
+            cb = d.upload(consts.packed())
+            files = (src.ptr, meta.ptr(mb, "offsets"), meta.ptr(mb, "scan_begin"), k, h, w, c)
+            coding = (consts.ptr(cb, "qtables"), consts.ptr(cb, "huff"), len(tables), out.ptr + first * frame_bytes,
+                      status_buf.ptr + 4 * first)
+            luma = tuple(head["sampling"])
+            scan_bytes = (np.diff(offsets[first:stop + 1]) - scan_begin).clip(0)
+            if head["nseg"] == 1 and split is not False and (
+                    split is not None or scan_bytes.mean() >= JPEG_SPLIT_MIN_BYTES):
+                # one segment a frame: one lane per sub_bytes of it
+                size, most = L.va_jpeg_decode_split_workspace_bytes, int(scan_bytes.max())
+                one, need = (int(size(frames, h, w, c, luma[0], luma[1], sub_bytes, most)) for frames in (1, k))
                 room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
                 ws = d.take(room)
-                check(decode(src.ptr, mb.ptr, mb.ptr + 8 * (k + 1), k, h, w, c, head["ri"], *luma, cb.ptr,
-                             cb.ptr + 64 * c, len(tables), out.ptr + first * frame_bytes, status_buf.ptr + 4 * first,
-                             ws.ptr, room, stream))
-            status = status_buf.download((n,), np.int32, stream)
-            rounds = np.zeros(n, np.int32)
-            if ret_rounds and split_groups:
-                got = rounds_buf.download((n,), np.int32, stream)
-                for first, stop in split_groups:
-                    rounds[first:stop] = got[first:stop]
-            if status.any() and not ret_status:
-                bad = int(np.flatnonzero(status)[0])
-                raise ValueError("%s: frame %d does not decode: %s (status %d); %d of %d frames have errors"
-                                 % (what, bad, jpeg_status_text(int(status[bad])), status[bad],
-                                    int(np.count_nonzero(status)), n))
-            frames = DeviceFrames(out, n, h, w, c) if keep else out.download(
-                (n, h, w) + ((3,) if c == 3 else ()), np.uint8, stream)
-    except Exception:
-        _give(out)
-        raise
-    if not keep:
-        _give(out)
+                check(L.va_jpeg_decode_split_u8(*files, luma[0], luma[1], *coding, ws.ptr, room, sub_bytes,
+                                                JPEG_SPLIT_MAX_ROUNDS, most, rounds_buf.ptr + 4 * first, stream))
+                split_groups.append((first, stop))
+                continue
+            # the plain entry for monochrome and 1 x 1 files, the _sampled one with (luma_h, luma_v) for the rest
+            if luma == (1, 1):
+                decode, size, luma = L.va_jpeg_decode_u8, L.va_jpeg_decode_workspace_bytes, ()
+            else:
+                decode, size = L.va_jpeg_decode_sampled_u8, L.va_jpeg_decode_sampled_workspace_bytes
+            one, need = (int(size(frames, h, w, c, head["ri"], *luma)) for frames in (1, k))
+            room = min(need, max(one, JPEG_DECODE_WORKSPACE_MAX))
+            ws = d.take(room)
+            check(decode(*files, head["ri"], *luma, *coding, ws.ptr, room, stream))
+        status = status_buf.download((n,), np.int32, stream)
+        rounds = np.zeros(n, np.int32)
+        if ret_rounds and split_groups:
+            got = rounds_buf.download((n,), np.int32, stream)
+            for first, stop in split_groups:
+                rounds[first:stop] = got[first:stop]
+        if status.any() and not ret_status:
+            bad = int(np.flatnonzero(status)[0])
+            raise ValueError("%s: frame %d does not decode: %s (status %d); %d of %d frames have errors"
+                             % (what, bad, jpeg_status_text(int(status[bad])), status[bad],
+                                int(np.count_nonzero(status)), n))
+        frames = DeviceFrames(out, n, h, w, c) if keep else out.download(
+            (n, h, w) + ((3,) if c == 3 else ()), np.uint8, stream)
     extra = ((status,) if ret_status else ()) + ((rounds,) if ret_rounds else ())
     return (frames,) + extra if extra else frames
