@@ -878,6 +878,28 @@ int va_jpeg_encode_sampled_u8(const uint8_t *frames_dev, int n, int h, int w, in
                               const uint8_t *qtables_dev, const uint8_t *header_dev, int header_bytes,
                               int64_t *sizes_out_dev, int64_t *offsets_out_dev, int64_t *totals_dev,
                               uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
+/* The same with Huffman tables made for the call ("Optimised Huffman tables"): one set of tables from
+ * the symbol counts of all n frames, as libjpeg's jpeg_gen_optimal_table builds them, in the DHT segments of every
+ * frame's header and in its entropy segments; every other byte is the plain call's.  The header is given in two
+ * pieces: header_pre_dev, the pre_bytes bytes in front of the DHT segments (SOI .. SOF0), and header_post_dev, the
+ * post_bytes bytes behind them (DRI, SOS); video.ops.jpeg_header_pieces cuts them from video.ops.jpeg_header.
+ *   bits_vals_out_dev  uint8 [c == 1 ? 2 : 4][272]: per table, in the order DC0, AC0, DC1, AC1 of the header, BITS
+ *                      (16) and HUFFVAL (256, the unused entries 0)
+ * The other outputs, the capacity rule (a total above cap_bytes stores no file and reports the total) and n == 0
+ * are the plain call's.  The counts are zeroed by the call; then five launches on `stream` (histogram, tables, count,
+ * scan, write) with no host synchronisation between them; integer atomics only: two runs write identical bytes.
+ * VA_ERR_INVALID as above and in that order, pre_bytes and post_bytes below 1 among the sizes and header_post_dev
+ * and bits_vals_out_dev among the pointers. */
+int va_jpeg_encode_optimized_u8(const uint8_t *frames_dev, int n, int h, int w, int c, int luma_h, int luma_v,
+                                const uint8_t *qtables_dev, const uint8_t *header_pre_dev, int pre_bytes,
+                                const uint8_t *header_post_dev, int post_bytes, uint8_t *bits_vals_out_dev,
+                                int64_t *sizes_out_dev, int64_t *offsets_out_dev, int64_t *totals_dev,
+                                uint8_t *bytes_out_dev, int64_t cap_bytes, void *stream);
+/* The table construction alone: freq_dev int64 [t][256] symbol counts (non-negative, the sum of a table's 256 counts
+ * at most 2^63 - 1: the merges add them in 64 bits, which the call cannot check; 8-byte aligned) ->
+ * bits_vals_out_dev uint8 [t][272] as above, one wave per table.  A row of zeros gives an empty table.  t == 0
+ * enqueues nothing; VA_ERR_INVALID for a negative t, a NULL pointer, counts that are not 8-byte aligned. */
+int va_jpeg_optimal_tables(const int64_t *freq_dev, int t, uint8_t *bits_vals_out_dev, void *stream);
 
 /* ------------------------------------------------------------------ A21 Motion-JPEG decoding
  * replaces  the frame-by-frame cv2.VideoCapture.read of VideoOpenCV.get_frame, video/io/backend_opencv.py, behind

@@ -12,10 +12,16 @@
   sampling  (--sampling: this leg alone) the RGB clips in 4:4:4, 4:2:2 and 4:2:0 (va_jpeg_encode_sampled_u8) in one
             run: the three launches by HIP events on resident data, the device copy, the bytes per frame, and
             ops.jpeg_encode with its download for each layout
+  optimize  (--optimize: this leg alone) monochrome and the three colour layouts with the Annex K tables and with
+            tables made for the call (va_jpeg_encode_optimized_u8; DESIGN.md §9, "Optimised Huffman tables") in one
+            run: both calls by HIP events on resident data, the table kernel alone (va_jpeg_optimal_tables on the four
+            tables of the fixture's largest file), the bytes per frame of both, Pillow's own optimised / plain ratio
+            on frame 0 as tests/golden/mjpeg_optimized_v1.npz stores it, and ops.jpeg_encode with its download for
+            both modes
 Times are the median of the repetitions.  One JSON line per leg, appended to profiles/mjpeg_bench.jsonl (or --out);
 a leg that did not run is written "not measured".
 Run on an MI355X:
-    python tools/bench_mjpeg.py [--reps 15] [--frames 256] [--sampling]"""
+    python tools/bench_mjpeg.py [--reps 15] [--frames 256] [--sampling | --optimize]"""
 import argparse
 import io
 import json
@@ -37,9 +43,10 @@ ap.add_argument("--quality", type=int, default=90)
 ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow leg (0: not measured)")
 ap.add_argument("--legs", default="kernels,encode,composer,pillow")
 ap.add_argument("--sampling", action="store_true", help="run the sampling leg, and nothing else")
+ap.add_argument("--optimize", action="store_true", help="run the optimize leg, and nothing else")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mjpeg_bench.jsonl"))
 args = ap.parse_args()
-LEGS = {"sampling"} if args.sampling else set(args.legs.split(","))
+LEGS = {"sampling"} if args.sampling else {"optimize"} if args.optimize else set(args.legs.split(","))
 N, H, W, Q = args.frames, args.height, args.width, args.quality
 
 
@@ -193,6 +200,57 @@ def main():
                               "other layouts in one run; jpeg_encode: wall clock on a resident stack"})
             stack.release()
             del frames, out
+    if "optimize" in LEGS:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "mjpeg_optimized_v1.npz"))
+        pillow = {str(k): [int(x) for x in v] for k, v in zip(z["ratio_names"], z["ratio_bytes"])}
+        at = int(np.argmax(z["pin_counts"].reshape(-1, 256).sum(axis=1))) // 4 * 4    # (colour files come first, 4 tables each)
+        counts = torch.from_numpy(z["pin_counts"][at:at + 4].astype(np.int64)).to(dev)
+        tables = torch.zeros(4 * ops.JPEG_TABLE_BYTES, dtype=torch.uint8, device=dev)
+        _, table_med = events(lambda: check(L.va_jpeg_optimal_tables(counts.data_ptr(), 4, tables.data_ptr(), S)))
+        for noise in (False, True):
+            for c in (1, 3):
+                clip = scene(N, H, W, c, np.random.default_rng(47 + noise), noise)   # (frame 0: the fixture generator's)
+                raw = clip.nbytes
+                frames = torch.from_numpy(clip).to(dev)
+                info = torch.zeros(2 * N + 2, dtype=torch.int64, device=dev)
+                cap = raw + N * 4096
+                out = torch.empty(cap, dtype=torch.uint8, device=dev)
+                stack = ops.DeviceFrames.upload(clip)
+                for layout, (hh, vv) in ([("mono", (1, 1))] if c == 1 else
+                                         [(k.replace(":", ""), v) for k, v in ops.JPEG_SAMPLINGS.items()]):
+                    head = ops.jpeg_header(H, W, c, Q, (hh, vv))
+                    pre, post = ops.jpeg_header_pieces(head)
+                    consts = torch.from_numpy(np.concatenate(ops.jpeg_tables(Q) + tuple(
+                        np.frombuffer(b, np.uint8) for b in (head, pre, post)))).to(dev)
+                    qt, at_pre = consts.data_ptr(), consts.data_ptr() + 128 + len(head)
+                    tail = (info.data_ptr() + 16 + 8 * N, info.data_ptr() + 8, info.data_ptr(), out.data_ptr(), cap, S)
+                    plain = lambda: check(L.va_jpeg_encode_sampled_u8(frames.data_ptr(), N, H, W, c, hh, vv, qt, qt + 128,
+                                                                      len(head), *tail))
+                    optimised = lambda: check(L.va_jpeg_encode_optimized_u8(
+                        frames.data_ptr(), N, H, W, c, hh, vv, qt, at_pre, len(pre), at_pre + len(pre), len(post),
+                        tables.data_ptr(), *tail))
+                    _, plain_med = events(plain)
+                    plain_total = int(info[0])
+                    _, opt_med = events(optimised)
+                    opt_total = int(info[0])
+                    assert plain_total <= cap and opt_total <= plain_total
+                    enc = {flag: wall(lambda: ops.jpeg_encode(stack, Q, ret_packed=True, sampling=(hh, vv), optimize=flag),
+                                      args.reps) for flag in (False, True)}
+                    name = "%s/%s" % ("noise" if noise else "smooth", layout)
+                    emit({"leg": "optimize/" + name, "frames": N, "h": H, "w": W, "quality": Q,
+                          "plain_ms_per_call_median": round(plain_med, 4), "optimized_ms_per_call_median": round(opt_med, 4),
+                          "of_the_plain_time": round(opt_med / plain_med, 3), "table_kernel_ms_median": round(table_med, 4),
+                          "plain_bytes_per_frame": plain_total // N, "optimized_bytes_per_frame": opt_total // N,
+                          "of_the_plain_bytes": round(opt_total / plain_total, 4),
+                          "pillow_frame0_plain_optimized_bytes": pillow[name],
+                          "pillow_of_the_plain_bytes": round(pillow[name][1] / pillow[name][0], 4),
+                          "jpeg_encode_with_downloads_ms_median": round(enc[False], 2),
+                          "jpeg_encode_optimized_with_downloads_ms_median": round(enc[True], 2),
+                          "note": "both calls by HIP events on resident frames in one run; the optimised call: zero, "
+                                  "histogram, tables, count, scan, write; the table kernel alone on 4 tables; jpeg_encode: "
+                                  "wall clock on a resident stack"})
+                stack.release()
+                del frames, out
     if "composer" in LEGS:
         rng = np.random.default_rng(41)
         for noise in (False, True):

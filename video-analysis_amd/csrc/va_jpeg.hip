@@ -20,7 +20,8 @@
 //       8 V pixel rows and a chunk 24 (4:2:2) or 16 (4:2:0) MCUs of 16 pixels' width; a wave loads 8 V rows of 64 / V
 //       pixels, 4 / V MCUs, at a time, box-averages Cb and Cr in the lane and, for 4:2:0, with the lane of the
 //       neighbouring row, and gathers the samples of every block of the MCU from the lanes that hold them
-//   B1  one lane per coefficient: the length of its bit string (va_jpeg::coefficient_bits), summed per block
+//   B1  one lane per coefficient: the length of its bit string (va_jpeg::coefficient_bits; with tables made on the
+//       device, whose codes have up to 16 bits, its two strings of up to 48 + 27 bits), summed per block
 //   --  a scan of the blocks' bit counts gives every block its bit position behind the chunk's carry
 //   B2  the same strings again, ORed into the chunk's bit buffer in LDS at block position + lane prefix
 //   E   the complete 32-bit words (all bytes, padded with 1-bits, in the last chunk) go out in tiles of 256 words:
@@ -28,6 +29,18 @@
 //       chunk's carry
 // The LDS atomics of B2 only OR disjoint bits into shared words: the result does not depend on their order, and
 // every byte written depends on its segment alone.
+//
+// va_jpeg_encode_optimized_u8 ("Optimised Huffman tables") writes the same stream with Huffman tables
+// made for the call, six steps on one stream with no host synchronisation between them:
+//   zero      the call's counts, int64 [class][dc | ac][256]
+//   histogram one workgroup per segment: phase A as above, then one lane per coefficient adds the symbols of its string
+//             (va_jpeg::coefficient_symbols) to a histogram in LDS, and the workgroup adds the non-zero entries to the
+//             call's counts.  Integer atomics only: the counts do not depend on the order
+//   tables    one workgroup, a wave per table: the code sizes (va_jpeg::huff_code_sizes over 64 lanes: two arg-min
+//             reductions and a parallel update per merge), BITS and HUFFVAL, the encoder's entries, and the header
+//             with its DHT segments and its length
+//   count, scan, write   as above, with the tables, the header and its length read from device memory.  The count
+//             adds the header's length to the length of a frame's first segment, so the scan is the plain one
 #include "va_common.h"
 #include "va_jpeg_math.h"
 
@@ -46,8 +59,11 @@ constexpr int mcu_blocks(int c, int hs, int vs) { return c == 1 ? 1 : hs * vs + 
 // a block has at most 22 + 63 * 26 bits: a DC string of 11 + 11, and an AC coefficient behind a run r adds at most
 // 11 (r / 16) + 26 bits over its r + 1 lanes
 constexpr int kMaxBlockBits = 22 + 63 * 26;
+// with tables made on the device a code has up to 16 bits: a DC string of 16 + 11, and an AC coefficient behind a run r
+// adds at most 16 (r / 16) + 26 bits over its r + 1 lanes, an EOB 16 on its one
+constexpr int kMaxBlockBitsDevice = 27 + 63 * 26;
 // words of a chunk's bit buffer: its blocks, the carry, the padding, and put_bits' reach
-constexpr int bit_words(int blocks) { return (blocks * kMaxBlockBits + 31 + 7) / 32 + 3; }
+constexpr int bit_words(int blocks, int block_bits = kMaxBlockBits) { return (blocks * block_bits + 31 + 7) / 32 + 3; }
 constexpr int kScanBlock = 256;
 constexpr int kScanPerThread = 4;
 
@@ -63,7 +79,14 @@ struct JpegArgs {
     const int64_t *totals;
     uint8_t *out;
     int64_t cap;
+    // the optimised call: the encoder's entries [4][256] (DC0, AC0, DC1, AC1), the header's length, the call's counts
+    const uint32_t *huff;
+    const int32_t *header_len;
+    unsigned long long *freq;
 };
+
+// how a segment kernel gets its Huffman tables, or that it counts symbols for them
+enum { kHuffAnnexK = 0, kHuffDevice = 1, kHuffCount = 2 };
 
 __device__ __forceinline__ int wave_sum(int v)
 {
@@ -128,14 +151,15 @@ __device__ __forceinline__ int16_t transform_block(int sample, const int (&t_row
 }
 
 // C components with luma sampling HS x VS: <1, 1, 1> monochrome, <3, 1, 1> 4:4:4, <3, 2, 1> 4:2:2, <3, 2, 2> 4:2:0
-template <int C, int HS, int VS, bool WRITE>
+template <int C, int HS, int VS, bool WRITE, int HUFF = kHuffAnnexK>
 __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
 {
+    static_assert(!(WRITE && HUFF == kHuffCount), "the histogram writes no stream");
     static_assert(C == 3 ? (HS == 1 || HS == 2) && (VS == 1 || VS == HS) : C == 1 && HS == 1 && VS == 1, "layout");
     constexpr int HV = HS * VS, BPM = mcu_blocks(C, HS, VS);         // luma blocks and all blocks of an MCU
     constexpr int kMcus = chunk_mcus(HS, VS), kBlocks = kMcus * BPM;
     static_assert(kBlocks <= 2 * kWave, "the block-position scan takes two entries a lane");
-    constexpr int kBitWords = bit_words(kBlocks);
+    constexpr int kBitWords = bit_words(kBlocks, HUFF == kHuffDevice ? kMaxBlockBitsDevice : kMaxBlockBits);
     constexpr int CG = 8 / VS;           // 8-pixel column groups a wave loads at once: lane = CG * row + group
     __shared__ int16_t coef[kBlocks][64];
     __shared__ uint32_t bitbuf[kBitWords];
@@ -145,6 +169,7 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
     __shared__ int32_t wave_total[kJpegWaves];
     __shared__ int32_t pred[3];
     __shared__ uint32_t chunk_end;
+    __shared__ uint32_t hist[HUFF == kHuffCount ? 4 * 256 : 1];
 
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const int64_t seg = blockIdx.x;
@@ -152,7 +177,16 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
     if (WRITE && a.totals[0] > a.cap)
         return;
 
-    {
+    if constexpr (HUFF == kHuffCount) {
+        for (int i = tid; i < 4 * 256; i += kJpegBlock)
+            hist[i] = 0;
+    } else if constexpr (HUFF == kHuffDevice) {
+        constexpr int kClasses = C == 1 ? 1 : 2;
+        for (int i = tid; i < 16 * kClasses; i += kJpegBlock)
+            huff_dc[i / 16][i % 16] = a.huff[(i / 16) * 512 + i % 16];
+        for (int i = tid; i < 256 * kClasses; i += kJpegBlock)
+            huff_ac[i / 256][i % 256] = a.huff[(i / 256) * 512 + 256 + i % 256];
+    } else {
         constexpr va_jpeg::HuffTables huff = va_jpeg::make_huff();
         for (int i = tid; i < 32; i += kJpegBlock)
             huff_dc[i / 16][i % 16] = huff.dc[i / 16][i % 16];
@@ -172,10 +206,11 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
         out_at = a.seg_start[seg];
         out_end = a.seg_start[seg + 1] - (j == a.nseg - 1 ? 2 : 0);
         if (j == 0) {
-            for (int i = tid; i < a.header_bytes; i += kJpegBlock)
+            const int header_bytes = HUFF == kHuffDevice ? a.header_len[0] : a.header_bytes;
+            for (int i = tid; i < header_bytes; i += kJpegBlock)
                 if (out_at + i < out_end)
                     a.out[out_at + i] = a.header[i];
-            out_at += a.header_bytes;
+            out_at += header_bytes;
         } else {
             if (tid < 2 && out_at + tid < out_end)
                 a.out[out_at + tid] = tid == 0 ? (uint8_t)0xFF : (uint8_t)(0xD0 + (j - 1) % 8);
@@ -298,6 +333,24 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
             }
         }
         __syncthreads();
+        if constexpr (HUFF == kHuffCount) {
+            // ------------------------------------------------------------ the symbols of every block, in place of B1 .. E
+            for (int q = wave; q < nblk; q += kJpegWaves) {
+                const int k = q % BPM, ch = va_jpeg::block_component(k, HV), tab = ch ? 1 : 0;
+                const int back = va_jpeg::predictor_back(k, HV, BPM);
+                const int v = coef[q][lane];
+                const int p = q >= back ? coef[q - back][0] : pred[ch];
+                const uint64_t nonzero = __ballot(v != 0);
+                va_jpeg::coefficient_symbols(lane, v, p, nonzero, [&](int ac, int symbol, int times) {
+                    atomicAdd(&hist[(2 * tab + ac) * 256 + symbol], (uint32_t)times);
+                });
+            }
+            __syncthreads();
+            if (tid < C)
+                pred[tid] = coef[(cm - 1) * BPM + HV - 1 + tid][0];
+            __syncthreads();
+            continue;
+        }
         // ---------------------------------------------------------------- B1: bits of every block
         for (int q = wave; q < nblk; q += kJpegWaves) {
             const int k = q % BPM, ch = va_jpeg::block_component(k, HV), tab = ch ? 1 : 0;
@@ -305,8 +358,14 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
             const int v = coef[q][lane];
             const int p = q >= back ? coef[q - back][0] : pred[ch];
             const uint64_t nonzero = __ballot(v != 0);
-            const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
-            const int total = wave_sum(b.len);
+            int len;
+            if constexpr (HUFF == kHuffDevice) {         // codes of up to 16 bits: two strings (coefficient_bits_wide)
+                const va_jpeg::WideBits b = va_jpeg::coefficient_bits_wide(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
+                len = b.zrl.len + b.rest.len;
+            } else {
+                len = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero).len;
+            }
+            const int total = wave_sum(len);
             if (lane == 0)
                 block_bits[q] = total;
         }
@@ -334,12 +393,21 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
             const int v = coef[q][lane];
             const int p = q >= back ? coef[q - back][0] : pred[ch];
             const uint64_t nonzero = __ballot(v != 0);
-            const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
-            const uint32_t pos = (uint32_t)(block_bits[q] + wave_inclusive(b.len, lane) - b.len);
-            va_jpeg::put_bits(pos, b, [&](uint32_t wi, uint32_t val) {
+            auto or_in = [&](uint32_t wi, uint32_t val) {
                 if (wi < (uint32_t)kBitWords)
                     atomicOr(&bitbuf[wi], val);
-            });
+            };
+            if constexpr (HUFF == kHuffDevice) {
+                const va_jpeg::WideBits b = va_jpeg::coefficient_bits_wide(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
+                const int len = b.zrl.len + b.rest.len;
+                const uint32_t pos = (uint32_t)(block_bits[q] + wave_inclusive(len, lane) - len);
+                va_jpeg::put_bits(pos, b.zrl, or_in);
+                va_jpeg::put_bits(pos + (uint32_t)b.zrl.len, b.rest, or_in);
+            } else {
+                const va_jpeg::Bits b = va_jpeg::coefficient_bits(huff_dc[tab], huff_ac[tab], lane, v, p, nonzero);
+                const uint32_t pos = (uint32_t)(block_bits[q] + wave_inclusive(b.len, lane) - b.len);
+                va_jpeg::put_bits(pos, b, or_in);
+            }
         }
         __syncthreads();
         if (tid < C)
@@ -392,9 +460,14 @@ __global__ void __launch_bounds__(kJpegBlock) jpeg_segment_kernel(JpegArgs a)
             carry_bits = end & 31u;
         }
     }
-    if (!WRITE) {
+    if constexpr (HUFF == kHuffCount) {
+        // (a segment has fewer than 2^32 symbols: at most 8192 MCUs of 6 blocks of 64 coefficients with 4 symbols)
+        for (int i = tid; i < 4 * 256; i += kJpegBlock)
+            if (hist[i])
+                atomicAdd(&a.freq[i], (unsigned long long)hist[i]);
+    } else if (!WRITE) {
         if (tid == 0)
-            a.seg_len[seg] = (int32_t)emitted;
+            a.seg_len[seg] = (int32_t)emitted + (HUFF == kHuffDevice && j == 0 ? a.header_len[0] : 0);
     } else if (j == a.nseg - 1 && tid < 2) {
         const int64_t at = out_at + emitted + tid;             // EOI
         if (at < a.seg_start[seg + 1])
@@ -462,33 +535,121 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
         sizes[f] = offsets[f + 1] - offsets[f];
 }
 
-template <bool WRITE>
+// ------------------------------------------------------------------------------------------------ optimised tables
+constexpr int kTableWaves = 4;                         // tables of a workgroup, a wave each
+constexpr int kTableBytes = 16 + 256;                  // BITS, HUFFVAL
+constexpr int kDhtMaxBytes[2] = {5 + 16 + 12, 5 + 16 + 162};     // a DHT segment of the encoder's DC and AC symbols
+
+struct TableArgs {
+    const int64_t *freq;             // [t][256]
+    int t;
+    uint8_t *bits_vals;              // [t][kTableBytes]
+    // the encoder's call (one workgroup, t = 2 or 4 in the order DC0, AC0, DC1, AC1), else NULL:
+    uint32_t *huff;                  // [t][256] length << 16 | code
+    const uint8_t *pre, *post;       // the header in front of and behind the DHT segments
+    int pre_bytes, post_bytes;
+    uint8_t *header;                 // [header_cap] pre | DHT * t | post
+    int header_cap;
+    int32_t *header_len;
+};
+
+__global__ void __launch_bounds__(kTableWaves * kWave) jpeg_tables_kernel(TableArgs a)
+{
+    __shared__ int codesize[kTableWaves][va_jpeg::kHuffSymbols];
+    __shared__ int work[kTableWaves][2][va_jpeg::kHuffSymbols];
+    __shared__ uint8_t bv[kTableWaves][kTableBytes];
+    __shared__ uint32_t codes[kTableWaves][256];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int t = blockIdx.x * kTableWaves + wave;
+    // (a wave without a table builds the last one again and stores nothing: the barriers stay uniform)
+    const int64_t *freq = a.freq + (int64_t)min(t, a.t - 1) * 256;
+    va_jpeg::huff_code_sizes<kWave>(lane, freq, [](va_jpeg::HuffPick p) {
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            va_jpeg::HuffPick o;
+            o.freq = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)p.freq, d, kWave) |
+                     (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(p.freq >> 32), d, kWave) << 32;
+            o.index = __shfl_xor(p.index, d, kWave);
+            p = va_jpeg::huff_better(p, o);
+        }
+        return p;
+    }, codesize[wave]);
+    __syncthreads();
+    if (lane == 0) {
+        va_jpeg::huff_bits_vals(codesize[wave], bv[wave], bv[wave] + 16, work[wave][0], work[wave][1]);
+        va_jpeg::huff_encoder_table(bv[wave], bv[wave] + 16, codes[wave]);
+    }
+    __syncthreads();
+    if (t < a.t) {
+        for (int i = lane; i < kTableBytes; i += kWave)
+            a.bits_vals[(int64_t)t * kTableBytes + i] = bv[wave][i];
+        if (a.huff)
+            for (int i = lane; i < 256; i += kWave)
+                a.huff[t * 256 + i] = codes[wave][i];
+    }
+    if (!a.header)
+        return;
+    auto put = [&](int at, uint8_t v) {
+        if (at < a.header_cap)
+            a.header[at] = v;
+    };
+    for (int i = tid; i < a.pre_bytes; i += kTableWaves * kWave)
+        put(i, a.pre[i]);
+    int at = a.pre_bytes;
+    for (int u = 0; u < a.t; u++) {
+        int nsym = 0;
+        for (int i = 0; i < 16; i++)
+            nsym += bv[u][i];
+        // FF C4, the length, Tc << 4 | Th, BITS, the HUFFVAL in use
+        for (int i = tid; i < 5 + 16 + nsym; i += kTableWaves * kWave)
+            put(at + i, i == 0 ? 0xFF : i == 1 ? 0xC4 : i == 2 ? (uint8_t)((19 + nsym) >> 8) : i == 3 ? (uint8_t)(19 + nsym)
+                        : i == 4 ? (uint8_t)((u & 1) << 4 | u >> 1) : bv[u][i - 5]);
+        at += 5 + 16 + nsym;
+    }
+    for (int i = tid; i < a.post_bytes; i += kTableWaves * kWave)
+        put(at + i, a.post[i]);
+    if (tid == 0)
+        a.header_len[0] = min(at + a.post_bytes, a.header_cap);
+}
+
+template <bool WRITE, int HUFF>
 void launch_segments(int c, int hs, int vs, int64_t nsegs, hipStream_t st, const JpegArgs &a)
 {
     const dim3 grid((unsigned)nsegs), block(kJpegBlock);
     if (c == 1)
-        hipLaunchKernelGGL((jpeg_segment_kernel<1, 1, 1, WRITE>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((jpeg_segment_kernel<1, 1, 1, WRITE, HUFF>), grid, block, 0, st, a);
     else if (hs == 1)
-        hipLaunchKernelGGL((jpeg_segment_kernel<3, 1, 1, WRITE>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 1, 1, WRITE, HUFF>), grid, block, 0, st, a);
     else if (vs == 1)
-        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 1, WRITE>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 1, WRITE, HUFF>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 2, WRITE>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((jpeg_segment_kernel<3, 2, 2, WRITE, HUFF>), grid, block, 0, st, a);
 }
 
-// both entry points; `sampled`: the luma sampling is an argument and checked
+// what the optimised call adds to the plain one's arguments
+struct OptimizedArgs {
+    const uint8_t *pre, *post;
+    int pre_bytes, post_bytes;
+    uint8_t *bits_vals_out;
+};
+
+// the three entry points; `sampled`: the luma sampling is an argument and checked; opt: the optimised call, whose header
+// is opt's two pieces (header: the first, header_bytes: the sum of their lengths)
 int jpeg_encode(const char *what, bool sampled, const uint8_t *frames, int n, int h, int w, int c, int hs, int vs,
                 const uint8_t *qtables, const uint8_t *header, int header_bytes, int64_t *sizes_out,
-                int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out, int64_t cap_bytes, void *stream)
+                int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out, int64_t cap_bytes, void *stream,
+                const OptimizedArgs *opt = nullptr)
 {
     VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0,
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && header_bytes > 0 && cap_bytes >= 0 &&
+                   (!opt || (opt->pre_bytes > 0 && opt->post_bytes > 0)),
                "%s: negative or zero size (n %d, h %d, w %d, header %d, cap %lld)", what, n, h, w, header_bytes,
                (long long)cap_bytes);
     VA_REQUIRE(c == 1 || c == 3, "%s: channels must be 1 or 3, got %d", what, c);
     if (n == 0)
         return VA_OK;
-    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0),
+    VA_REQUIRE(frames && qtables && header && sizes_out && offsets_out && totals && (bytes_out || cap_bytes == 0) &&
+                   (!opt || (opt->post && opt->bits_vals_out)),
                "%s: NULL argument", what);
     VA_REQUIRE(aligned(sizes_out, 8) && aligned(offsets_out, 8) && aligned(totals, 8),
                "%s: the int64 buffers must be 8-byte aligned", what);
@@ -506,20 +667,50 @@ int jpeg_encode(const char *what, bool sampled, const uint8_t *frames, int n, in
     Carve ws;                                        // [seg_len | seg_start]
     const size_t o_len = ws.take((size_t)nsegs * sizeof(int32_t));
     const size_t o_start = ws.take(((size_t)nsegs + 1) * sizeof(int64_t));
+    // the optimised call: [counts | encoder entries | header length | header]
+    const int tables = c == 1 ? 2 : 4;
+    const int header_cap = header_bytes + (tables / 2) * (kDhtMaxBytes[0] + kDhtMaxBytes[1]);
+    const size_t o_freq = opt ? ws.take(4 * 256 * sizeof(int64_t)) : 0;
+    const size_t o_huff = opt ? ws.take(4 * 256 * sizeof(uint32_t)) : 0;
+    const size_t o_hlen = opt ? ws.take(sizeof(int32_t)) : 0;
+    const size_t o_head = opt ? ws.take((size_t)header_cap) : 0;
     ScratchLease scratch;
     int rc = scratch.acquire(ws.total, st);
     if (rc)
         return rc;
     int32_t *seg_len = at<int32_t>(scratch.ptr, o_len);
     int64_t *seg_start = at<int64_t>(scratch.ptr, o_start);
+    if (opt) {
+        int64_t *freq = at<int64_t>(scratch.ptr, o_freq);
+        const JpegArgs a{frames, n, h, w, nseg, (w + 8 * hs - 1) / (8 * hs), qtables, at<uint8_t>(scratch.ptr, o_head), 0,
+                         seg_len, seg_start, totals, bytes_out, cap_bytes, at<uint32_t>(scratch.ptr, o_huff),
+                         at<int32_t>(scratch.ptr, o_hlen), reinterpret_cast<unsigned long long *>(freq)};
+        VA_HIP(hipMemsetAsync(freq, 0, 4 * 256 * sizeof(int64_t), st));
+        launch_segments<false, kHuffCount>(c, hs, vs, nsegs, st, a);
+        VA_LAUNCH_CHECK("jpeg_segment_kernel (histogram)");
+        const TableArgs ta{freq, tables, opt->bits_vals_out, at<uint32_t>(scratch.ptr, o_huff), opt->pre, opt->post,
+                           opt->pre_bytes, opt->post_bytes, at<uint8_t>(scratch.ptr, o_head), header_cap,
+                           at<int32_t>(scratch.ptr, o_hlen)};
+        hipLaunchKernelGGL(jpeg_tables_kernel, dim3(1), dim3(kTableWaves * kWave), 0, st, ta);
+        VA_LAUNCH_CHECK("jpeg_tables_kernel");
+        launch_segments<false, kHuffDevice>(c, hs, vs, nsegs, st, a);
+        VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
+        // (the count has added the header's length to every frame's first segment)
+        hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, 0, seg_start,
+                           offsets_out, sizes_out, totals);
+        VA_LAUNCH_CHECK("jpeg_scan_kernel");
+        launch_segments<true, kHuffDevice>(c, hs, vs, nsegs, st, a);
+        VA_LAUNCH_CHECK("jpeg_segment_kernel (write)");
+        return VA_OK;
+    }
     const JpegArgs a{frames, n, h, w, nseg, (w + 8 * hs - 1) / (8 * hs), qtables, header, header_bytes, seg_len,
-                     seg_start, totals, bytes_out, cap_bytes};
-    launch_segments<false>(c, hs, vs, nsegs, st, a);
+                     seg_start, totals, bytes_out, cap_bytes, nullptr, nullptr, nullptr};
+    launch_segments<false, kHuffAnnexK>(c, hs, vs, nsegs, st, a);
     VA_LAUNCH_CHECK("jpeg_segment_kernel (count)");
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, seg_len, nsegs, nseg, n, header_bytes,
                        seg_start, offsets_out, sizes_out, totals);
     VA_LAUNCH_CHECK("jpeg_scan_kernel");
-    launch_segments<true>(c, hs, vs, nsegs, st, a);
+    launch_segments<true, kHuffAnnexK>(c, hs, vs, nsegs, st, a);
     VA_LAUNCH_CHECK("jpeg_segment_kernel (write)");
     return VA_OK;
 }
@@ -547,6 +738,35 @@ int va_jpeg_encode_sampled_u8(const uint8_t *frames, int n, int h, int w, int c,
 {
     return jpeg_encode("va_jpeg_encode_sampled_u8", true, frames, n, h, w, c, luma_h, luma_v, qtables, header,
                        header_bytes, sizes_out, offsets_out, totals, bytes_out, cap_bytes, stream);
+}
+
+int va_jpeg_encode_optimized_u8(const uint8_t *frames, int n, int h, int w, int c, int luma_h, int luma_v,
+                                const uint8_t *qtables, const uint8_t *header_pre, int pre_bytes,
+                                const uint8_t *header_post, int post_bytes, uint8_t *bits_vals_out, int64_t *sizes_out,
+                                int64_t *offsets_out, int64_t *totals, uint8_t *bytes_out, int64_t cap_bytes,
+                                void *stream)
+{
+    const OptimizedArgs opt{header_pre, header_post, pre_bytes, post_bytes, bits_vals_out};
+    // (lengths of 2^30 and more are not a header's, and their sum stays an int)
+    const int sum = pre_bytes > 0 && post_bytes > 0 && pre_bytes < (1 << 30) && post_bytes < (1 << 30)
+                        ? pre_bytes + post_bytes : 0;
+    return jpeg_encode("va_jpeg_encode_optimized_u8", true, frames, n, h, w, c, luma_h, luma_v, qtables, header_pre, sum,
+                       sizes_out, offsets_out, totals, bytes_out, cap_bytes, stream, &opt);
+}
+
+int va_jpeg_optimal_tables(const int64_t *freq, int t, uint8_t *bits_vals_out, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(t >= 0, "va_jpeg_optimal_tables: a negative number of tables (%d)", t);
+    if (t == 0)
+        return VA_OK;
+    VA_REQUIRE(freq && bits_vals_out, "va_jpeg_optimal_tables: NULL argument");
+    VA_REQUIRE(aligned(freq, 8), "va_jpeg_optimal_tables: the counts must be 8-byte aligned");
+    const TableArgs ta{freq, t, bits_vals_out, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr};
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)((t + kTableWaves - 1) / kTableWaves)), dim3(kTableWaves * kWave),
+                       0, as_stream(stream), ta);
+    VA_LAUNCH_CHECK("jpeg_tables_kernel");
+    return VA_OK;
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // average, the edge rule and the maps from a block's place in its MCU to its component and DC predictor.  va_jpeg.hip
 // runs it with one lane per coefficient of a block; tests/jpeg_shim.cpp and tests/jpeg_sampled_shim.cpp compile it with
 // the host compiler (under sanitizers) into serial encoders whose bytes are the NumPy restatements'
-// (tests/jpeg_checks.py, tests/jpeg_subsampled_checks.py: encode_frame).
+// (tests/jpeg_checks.py, tests/jpeg_subsampled_checks.py: encode_frame).  The construction of optimised Huffman tables
+// from symbol counts is here too (tests/jpeg_optimize_shim.cpp, tests/jpeg_optimize_checks.py).
 //
 // Integers only.  A block is 64 samples minus 128; T[k][n] = rint(2^13 A[k][n]) with A the orthonormal 8-point
 // DCT-II matrix.  The row pass keeps (sum + 1024) >> 11, four times the row coefficient; the column pass's sum is the
@@ -121,6 +122,14 @@ VA_JPEG_FN constexpr void huff_fill(const uint8_t *bits, const uint8_t *vals, ui
     }
 }
 
+// the encoder's 256 entries of one table from run-time BITS and HUFFVAL
+VA_JPEG_FN void huff_encoder_table(const uint8_t *bits, const uint8_t *vals, uint32_t *out)
+{
+    for (int i = 0; i < 256; i++)
+        out[i] = 0;
+    huff_fill(bits, vals, out);
+}
+
 VA_JPEG_FN constexpr HuffTables make_huff()
 {
     constexpr uint8_t dc_bits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
@@ -155,8 +164,119 @@ VA_JPEG_FN constexpr HuffTables make_huff()
     return h;
 }
 
+// ------------------------------------------------------------------------------------------------ optimised tables
+// ("Optimised Huffman tables").  One table from its 256 counts as libjpeg's jpeg_gen_optimal_table
+// builds it (T.81 K.2 with symbol 256 reserved, so that no code is all 1-bits), without its limits on a count and on a
+// size before the lengths are limited to 16.  Two steps: the code sizes, spread over LANES lanes that each hold the
+// symbols lane, lane + LANES, ..; then, serially, BITS and HUFFVAL from the sizes.
+constexpr int kHuffSymbols = 257;       // 0 .. 255 and the reserved one
+
+struct HuffPick {                       // the smallest non-zero count and where it is; index -1: there is none
+    uint64_t freq;
+    int index;
+};
+
+// of two picks the one with the smaller count, of equal counts the one with the larger index
+VA_JPEG_FN HuffPick huff_better(HuffPick a, HuffPick b)
+{
+    if (a.index < 0)
+        return b;
+    if (b.index < 0)
+        return a;
+    return b.freq < a.freq || (b.freq == a.freq && b.index > a.index) ? b : a;
+}
+
+// the code size of every symbol before the limit: codesize[0 .. 256], which every lane fills for its own symbols.
+// freq: the 256 counts, not negative and with a sum below 2^63 (the merges add them in 64 bits); reduce(pick): huff_better over the picks of all lanes, the same answer in every lane.
+// libjpeg's `others` chain from a root lists the symbols of that root's tree, so a merge is: every symbol of either
+// tree gets one more bit, and both trees are c1's.
+template <int LANES, class Reduce>
+VA_JPEG_FN void huff_code_sizes(int lane, const int64_t *freq, Reduce reduce, int *codesize)
+{
+    constexpr int S = (kHuffSymbols + LANES - 1) / LANES;
+    uint64_t f[S];
+    int tree[S], size[S];
+    for (int k = 0; k < S; k++) {
+        const int i = lane + LANES * k;
+        f[k] = i < 256 ? (uint64_t)freq[i] : i == 256 ? 1u : 0u;
+        tree[k] = i;
+        size[k] = 0;
+    }
+    for (;;) {
+        HuffPick mine{0, -1};
+        for (int k = 0; k < S; k++)
+            if (f[k])
+                mine = huff_better(mine, HuffPick{f[k], lane + LANES * k});
+        const HuffPick c1 = reduce(mine);
+        mine = HuffPick{0, -1};
+        for (int k = 0; k < S; k++)
+            if (f[k] && lane + LANES * k != c1.index)
+                mine = huff_better(mine, HuffPick{f[k], lane + LANES * k});
+        const HuffPick c2 = reduce(mine);
+        if (c2.index < 0)
+            break;
+        for (int k = 0; k < S; k++) {
+            const int i = lane + LANES * k;
+            if (i == c1.index)
+                f[k] += c2.freq;
+            if (i == c2.index)
+                f[k] = 0;
+            if (tree[k] == c1.index || tree[k] == c2.index) {
+                size[k]++;
+                tree[k] = c1.index;
+            }
+        }
+    }
+    for (int k = 0; k < S; k++)
+        if (lane + LANES * k < kHuffSymbols)
+            codesize[lane + LANES * k] = size[k];
+}
+
+// BITS (16) and HUFFVAL (256, the unused ones 0) from codesize[0 .. 256]; count, start: kHuffSymbols ints of
+// workspace each.  Counts that are all 0 give an empty table.
+VA_JPEG_FN void huff_bits_vals(const int *codesize, uint8_t *bits, uint8_t *vals, int *count, int *start)
+{
+    int top = 0;
+    for (int s = 0; s < kHuffSymbols; s++)
+        count[s] = 0;
+    for (int i = 0; i < kHuffSymbols; i++)
+        if (codesize[i] > 0) {
+            count[codesize[i]]++;
+            top = codesize[i] > top ? codesize[i] : top;
+        }
+    // HUFFVAL: the symbols 0 .. 255 by size, then by value; the limit below moves the borders between the sizes only
+    int at = 0;
+    for (int s = 1; s <= top; s++) {
+        start[s] = at;
+        at += count[s];
+    }
+    for (int i = 0; i < 256; i++)
+        vals[i] = 0;
+    for (int i = 0; i < 256; i++)
+        if (codesize[i] > 0)             // (the reserved symbol, the last of its size, is not listed)
+            vals[start[codesize[i]]++ - (codesize[i] > codesize[256] ? 1 : 0)] = (uint8_t)i;
+    // T.81 K.2, figure K.3: no code longer than 16
+    for (int i = top; i > 16; i--)
+        while (count[i] > 0) {
+            int j = i - 2;
+            while (count[j] == 0)
+                j--;
+            count[i] -= 2;
+            count[i - 1]++;
+            count[j + 1] += 2;
+            count[j]--;
+        }
+    int last = top < 16 ? top : 16;
+    while (last > 0 && count[last] == 0)
+        last--;
+    if (last > 0)
+        count[last]--;                   // the reserved symbol leaves
+    for (int s = 1; s <= 16; s++)
+        bits[s - 1] = (uint8_t)(s <= last ? count[s] : 0);
+}
+
 // ------------------------------------------------------------------------------------------------ one coefficient
-// a bit string of at most 59 bits, the first bit of the stream in the highest of the `len` low bits
+// a bit string of at most 59 bits (the Annex K tables: 3 ZRLs of 11 bits, a code of 16, 10 magnitude bits), the first bit of the stream in the highest of the `len` low bits
 struct Bits {
     uint64_t code;
     int len;
@@ -213,6 +333,49 @@ VA_JPEG_FN Bits coefficient_bits(const uint32_t *dc, const uint32_t *ac, int k, 
         append(b, ac[0]);
     }
     return b;
+}
+
+// coefficient_bits for run-time tables ("Optimised Huffman tables"), whose codes have up to 16 bits: a
+// coefficient behind a run of 48 or more adds up to 3 * 16 + 16 + 10 = 74 bits, more than a Bits holds.  Two strings,
+// the ZRLs (at most 48 bits) and behind them the rest (at most 16 + 11 = 27 bits, the DC string)
+struct WideBits {
+    Bits zrl, rest;
+};
+
+VA_JPEG_FN WideBits coefficient_bits_wide(const uint32_t *dc, const uint32_t *ac, int k, int v, int pred, uint64_t nonzero)
+{
+    WideBits b{{0, 0}, {0, 0}};
+    if (k == 0) {
+        const int diff = v - pred, size = bit_size(diff);
+        append(b.rest, dc[size & 15]);
+        append_magnitude(b.rest, diff, size);
+    } else if (v != 0) {
+        const int run = run_before(nonzero, k), size = bit_size(v);
+        for (int z = run >> 4; z > 0; z--)
+            append(b.zrl, ac[0xF0]);
+        append(b.rest, ac[(((run & 15) << 4) | size) & 255]);
+        append_magnitude(b.rest, v, size);
+    } else if (k == 63) {
+        append(b.rest, ac[0]);
+    }
+    return b;
+}
+
+// the Huffman symbols coefficient k adds, wherever coefficient_bits looks up a code, through count(ac, symbol, times):
+// ac 0 for the DC table, 1 for the AC table of the block's class
+template <class Count>
+VA_JPEG_FN void coefficient_symbols(int k, int v, int pred, uint64_t nonzero, Count count)
+{
+    if (k == 0) {
+        count(0, bit_size(v - pred) & 15, 1);
+    } else if (v != 0) {
+        const int run = run_before(nonzero, k), size = bit_size(v);
+        if (run >> 4)
+            count(1, 0xF0, run >> 4);
+        count(1, (((run & 15) << 4) | size) & 255, 1);
+    } else if (k == 63) {
+        count(1, 0, 1);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ bit writer

@@ -151,6 +151,9 @@ SIGNATURES = {
     "va_draw_contours_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, C.c_uint32, _vp, _vp]),
     "va_jpeg_encode_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "va_jpeg_encode_sampled_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "va_jpeg_encode_optimized_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _vp]),
+    "va_jpeg_optimal_tables": (_i, [_vp, _i, _vp, _vp]),
     "va_jpeg_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "va_jpeg_decode_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "va_jpeg_decode_sampled_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),

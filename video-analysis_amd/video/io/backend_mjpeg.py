@@ -61,15 +61,18 @@ def _avi_header(size, fps, frames, movi_bytes, idx_bytes, largest):
 class VideoWriterMJPEG(object):
     """writes uint8 frames into a Motion-JPEG AVI file, `batch` frames per encoder call"""
 
-    def __init__(self, filename, size, fps, is_color=True, quality=90, batch=32, sampling=(1, 1), **kwargs):
+    def __init__(self, filename, size, fps, is_color=True, quality=90, batch=32, sampling=(1, 1),
+                 optimize=False, **kwargs):
         """`size` = (width, height); `quality` 1 .. 100 (the IJG scale); `sampling` of a colour video: (1, 1) /
-        "4:4:4", (2, 1) / "4:2:2" or (2, 2) / "4:2:0" ("Subsampled Motion-JPEG encoding"); further
-        keyword arguments -- the codec and bitrate of the reference's writers -- have no meaning here and are
-        refused"""
+        "4:4:4", (2, 1) / "4:2:2" or (2, 2) / "4:2:0" ("Subsampled Motion-JPEG encoding"); `optimize`:
+        every encoder call writes its `batch` frames with Huffman tables made for them ("Optimised
+        Huffman tables"), so the file's frames share their header in runs of `batch`; further keyword arguments --
+        the codec and bitrate of the reference's writers -- have no meaning here and are refused"""
         if kwargs:
-            raise TypeError("VideoWriterMJPEG: unknown arguments %s (the codec is MJPG; quality, batch and sampling "
-                            "are what can be set)" % ", ".join(sorted(kwargs)))
+            raise TypeError("VideoWriterMJPEG: unknown arguments %s (the codec is MJPG; quality, batch, sampling and "
+                            "optimize are what can be set)" % ", ".join(sorted(kwargs)))
         self.sampling = ops.jpeg_sampling(sampling, 3 if is_color else 1, "VideoWriterMJPEG")
+        self.optimize = ops.jpeg_optimize_flag(optimize, "VideoWriterMJPEG")
         if batch < 1:
             raise ValueError("batch must be positive")
         self.filename = os.fspath(filename)
@@ -136,6 +139,8 @@ class VideoWriterMJPEG(object):
 
     def _encode(self, stack):
         layout = {} if self.sampling == (1, 1) else {"sampling": self.sampling}        # (1, 1): the call as it was
+        if self.optimize:
+            layout["optimize"] = True
         blob, offsets = ops.jpeg_encode(stack, quality=self.quality, color=self.is_color, ret_packed=True,
                                         **layout)
         blob = np.asarray(blob, np.uint8)

@@ -2695,7 +2695,57 @@ def jpeg_header(h, w, c, quality, sampling=(1, 1)):
     return out
 
 
-def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, sampling=(1, 1)):
+def jpeg_optimize_flag(optimize, what="jpeg_optimize_flag"):
+    """`optimize` as a bool; a TypeError for anything but True and False (host only)"""
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise TypeError("%s: optimize is True or False, got %r" % (what, optimize))
+    return bool(optimize)
+
+
+def jpeg_header_pieces(head):
+    """(the bytes in front of the DHT segments, the bytes behind them) of a header that jpeg_header built (host only)"""
+    head = bytes(head)
+    at, first, last = 2, None, None
+    while at < len(head):
+        end = at + 2 + ((head[at + 2] << 8) | head[at + 3])
+        if head[at + 1] == 0xC4:
+            first, last = at if first is None else first, end
+        at = end
+    return head[:first], head[last:]
+
+
+JPEG_TABLE_BYTES = 16 + 256      # one Huffman table at the ABI: BITS, then HUFFVAL with the unused entries 0
+JPEG_COUNT_SUM_MAX = 2 ** 63 - 1 # of the 256 counts of one table
+
+
+def jpeg_optimal_tables(freq, stream=None):
+    """the optimised Huffman table of each row of symbol counts in one va_jpeg_optimal_tables call (DESIGN.md §9,
+    "Optimised Huffman tables"): libjpeg's jpeg_gen_optimal_table without its limits on a count and on a size before
+    the limit to 16 bits.  freq: non-negative integers (t, 256) or (256,), each row's sum at most JPEG_COUNT_SUM_MAX
+    (the merges add counts in 64 bits).  Returns uint8 (t, JPEG_TABLE_BYTES) or
+    (JPEG_TABLE_BYTES,): BITS (16), then HUFFVAL with the unused entries 0; a row of zeros gives an empty table."""
+    what = "jpeg_optimal_tables"
+    freq = np.asarray(freq)
+    if freq.dtype.kind not in "iu" or freq.ndim not in (1, 2) or freq.shape[-1] != 256:
+        raise ValueError("%s: the counts are integers (t, 256) or (256,), got %s %r" % (what, freq.dtype, freq.shape))
+    if freq.size and freq.min() < 0:
+        raise ValueError("%s: the counts are not negative" % what)
+    if freq.size and max(int(np.sum(row, dtype=object)) for row in freq.reshape(-1, 256)) > JPEG_COUNT_SUM_MAX:
+        raise ValueError("%s: the sum of a table's counts is at most 2^63 - 1 (the device adds them in 64 bits)" % what)
+    rows = np.ascontiguousarray(freq.reshape(-1, 256), np.int64)
+    t = len(rows)
+    if t == 0:
+        return np.zeros((0, JPEG_TABLE_BYTES), np.uint8)
+    with _Lease.on(stream) as d:
+        src = d.upload(rows)
+        out = d.take(t * JPEG_TABLE_BYTES)
+        check(_hip.lib().va_jpeg_optimal_tables(src.ptr, t, out.ptr, stream))
+        tables = out.download((t, JPEG_TABLE_BYTES), np.uint8, stream)
+    return tables[0] if freq.ndim == 1 else tables
+
+
+def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, sampling=(1, 1), optimize=False,
+                ret_tables=False):
     """one baseline JFIF file per frame of a stack in one va_jpeg_encode_u8 call ("Motion-JPEG"): 4:4:4
     or monochrome, the Annex K Huffman tables, one restart interval per MCU row; the bytes are pinned and equal the
     restatement's.  sampling: (2, 1) / "4:2:2" or (2, 2) / "4:2:0" write colour frames with box-averaged chroma in
@@ -2705,9 +2755,16 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, s
     One upload of the frames and one of [tables | header], one call, and the downloads of the sizes and of the used
     bytes.  The first launch has room for the headers and 1 / JPEG_ROOM_DIVISOR of the raw bytes; a batch that
     needs more runs exactly once more, with exact room.
+    optimize: the files are written with Huffman tables made for this call, one set shared by its frames, in one
+    va_jpeg_encode_optimized_u8 call ("Optimised Huffman tables"): counts, tables and header are made on
+    the device, and the same uploads, downloads and room apply (the plain header is never shorter than the optimised
+    one).  ret_tables (with optimize): the tables follow as uint8 (2 or 4, JPEG_TABLE_BYTES), DC0, AC0[, DC1, AC1].
     Returns the list of n `bytes`; ret_packed: (uint8 blob, int64 offsets of n + 1 entries), frame k being
     blob[offsets[k]:offsets[k + 1]]."""
     what = "jpeg_encode"
+    optimize = jpeg_optimize_flag(optimize, what)
+    if ret_tables and not optimize:
+        raise ValueError("%s: ret_tables needs optimize=True (the plain files hold the Annex K tables, JPEG_DHT)" % what)
     hh, vv = jpeg_sampling(sampling, what=what)
     if not isinstance(frames, DeviceFrames):
         frames = np.asarray(frames)                 # (_frames_in checks the dtype and the shape)
@@ -2720,11 +2777,19 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, s
     if n and not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
         raise ValueError("%s: sides are 1 .. %d, got %d x %d" % (what, JPEG_MAX_SIDE, w, h))
     tables = jpeg_tables(quality)
+    ntab = 2 if c == 1 else 4
     if n == 0:
-        return (np.zeros(0, np.uint8), np.zeros(1, np.int64)) if ret_packed else []
+        out = (np.zeros(0, np.uint8), np.zeros(1, np.int64)) if ret_packed else []
+        return (out, np.zeros((ntab, JPEG_TABLE_BYTES), np.uint8)) if ret_tables else out
     head = np.frombuffer(jpeg_header(h, w, c, quality, (hh, vv)), np.uint8)
-    consts = _Layout(luma=tables[0], chroma=tables[1], head=head)
-    sizes = _Layout(total=(1, np.int64), offsets=(n + 1, np.int64), sizes=(n, np.int64))
+    if optimize:
+        pre, post = (np.frombuffer(piece, np.uint8) for piece in jpeg_header_pieces(head.tobytes()))
+        consts = _Layout(luma=tables[0], chroma=tables[1], pre=pre, post=post)
+        sizes = _Layout(total=(1, np.int64), offsets=(n + 1, np.int64), sizes=(n, np.int64),
+                        tables=(ntab * JPEG_TABLE_BYTES, np.uint8))
+    else:
+        consts = _Layout(luma=tables[0], chroma=tables[1], head=head)
+        sizes = _Layout(total=(1, np.int64), offsets=(n + 1, np.int64), sizes=(n, np.int64))
     nseg = -(-h // (8 * vv))
     room = n * (len(head) + 2 * nseg) + (n * h * w * c) // JPEG_ROOM_DIVISOR
     L = _hip.lib()
@@ -2735,21 +2800,28 @@ def jpeg_encode(frames, quality=90, color=None, stream=None, ret_packed=False, s
 
         def run(cap):
             out = d.take(max(cap, 1))
-            outs = (consts.ptr(cb, "luma"), consts.ptr(cb, "head"), len(head), sizes.ptr(info, "sizes"),
-                    sizes.ptr(info, "offsets"), sizes.ptr(info, "total"), out.ptr, cap, stream)
-            if (hh, vv) == (1, 1):
-                check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, *outs))
+            tail = (sizes.ptr(info, "sizes"), sizes.ptr(info, "offsets"), sizes.ptr(info, "total"), out.ptr, cap, stream)
+            if optimize:
+                check(L.va_jpeg_encode_optimized_u8(src.ptr, n, h, w, c, hh, vv, consts.ptr(cb, "luma"),
+                                                    consts.ptr(cb, "pre"), len(pre), consts.ptr(cb, "post"), len(post),
+                                                    sizes.ptr(info, "tables"), *tail))
+            elif (hh, vv) == (1, 1):
+                check(L.va_jpeg_encode_u8(src.ptr, n, h, w, c, consts.ptr(cb, "luma"), consts.ptr(cb, "head"), len(head),
+                                          *tail))
             else:
-                check(L.va_jpeg_encode_sampled_u8(src.ptr, n, h, w, c, hh, vv, *outs))
+                check(L.va_jpeg_encode_sampled_u8(src.ptr, n, h, w, c, hh, vv, consts.ptr(cb, "luma"),
+                                                  consts.ptr(cb, "head"), len(head), *tail))
             meta = info.download((sizes.nbytes,), np.uint8, stream)
             return (out, meta), sizes.view(meta, "total")
         (out, meta), (total,) = _rerun(run, room)   # a total beyond the room: nothing was written
         blob = out.download((int(total),), np.uint8, stream)
     offsets = sizes.view(meta, "offsets").copy()
     if ret_packed:
-        return blob, offsets
-    raw = blob.tobytes()
-    return [raw[offsets[k]:offsets[k + 1]] for k in range(n)]
+        files = (blob, offsets)
+    else:
+        raw = blob.tobytes()
+        files = [raw[offsets[k]:offsets[k + 1]] for k in range(n)]
+    return (files, sizes.view(meta, "tables").reshape(ntab, JPEG_TABLE_BYTES).copy()) if ret_tables else files
 
 
 # ------------------------------------------------------------------------------------------------ Motion-JPEG decoding
