@@ -328,6 +328,38 @@ int va_find_contours(const uint8_t *mask_dev, int n, int h, int w, int32_t *ncon
                      int32_t *points_dev, int64_t cap_points, void *workspace_dev, size_t workspace_bytes,
                      void *stream);
 
+/* ------------------------------------------------------------------ A8b region links between consecutive frames
+ * replaces  no call of the reference.  It is what a tracker does first with the labels of
+ *           video/analysis/regions.py:159-174 on consecutive frames -- which region of frame t is which region of
+ *           frame t - 1 -- computed where the labels lie, so that no label plane crosses to the host.
+ * labels_dev: (n, h, w) int32; prev_dev: (h, w) int32 or NULL.  A value <= 0 is background, any value >= 1 a
+ * region label (the planes need not be a connected-component labelling).  Pair t = (E, L) with L = labels[t] and
+ * E = labels[t - 1], or prev for t = 0; without prev pair 0 has no links.  The links of pair t are all
+ * (a, b, count) with a >= 1, b >= 1 and count = #{pixels: E = a and L = b} > 0, ordered by the raster index of the
+ * first such pixel; the links of pair t follow those of pair t - 1.
+ *   nlinks_dev[n]         links of each pair, always the true numbers
+ *   totals_dev[2]         [0] links of the batch, always the true total; [1] `need`: a capacity that is sure to
+ *                         suffice
+ *   links_dev[cap_links]  the records, 16-byte aligned
+ * need is always computed, without the tables: the number of pixels with a key (a, b) whose left and upper
+ * neighbours carry another key or do not exist, so links <= need <= #{pixels with both labels >= 1}.
+ * need <= cap_links: every record is written.  Otherwise nothing is stored in links_dev, the counts and both totals
+ * still report, and one more call with cap_links = need succeeds.  Exceeding the capacity is no error.  Nothing is
+ * written beyond the capacity or outside the caller's buffers.  Slots come from counts and scans, never from the
+ * order of atomics: two calls write identical bytes.  The workspace (16-byte aligned) holds the per-pair hash
+ * tables: 32 bytes a link of capacity, and never less than 32 bytes a pixel of one frame.  Where the tables of all
+ * pairs fit it together -- always when need <= cap_links -- the pairs are counted side by side; below that the
+ * links are still counted exactly, a table at a time, which takes longer.  A workspace_bytes above what the size
+ * function asks for is used: 32 bytes more hold one more candidate side by side.  n == 0 writes two zero totals.
+ * Shape: any n >= 0 (pieces of 65535 pairs in a grid), h, w >= 1, frames below 2^29 pixels, batches below 2^37. */
+typedef struct va_region_link {
+    int32_t frame, a, b, count;
+} va_region_link;
+size_t va_region_links_workspace_bytes(int n, int h, int w, int64_t cap_links);
+int va_region_links(const int32_t *prev_dev, const int32_t *labels_dev, int n, int h, int w, int32_t *nlinks_dev,
+                    int64_t *totals_dev, va_region_link *links_dev, int64_t cap_links, void *workspace_dev,
+                    size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ A10 geodesic distance maps
  * 8-neighbour geodesics inside masks: straight steps cost 1, diagonal steps sqrt2 (a diagonal step may
  * pass between two wall pixels).  A distance d = a + b*sqrt2 is kept as the exact pair (a, b) and

@@ -110,6 +110,8 @@ SIGNATURES = {
     "va_largest_contour": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "va_find_contours_workspace_bytes": (_sz, [_i, _i, _i]),
     "va_find_contours": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "va_region_links_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
+    "va_region_links": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "va_normalize": (_i, [_vp, _i, _vp, _i, _sz, _d, _d, _d, _d, _vp]),
     "va_prepare_u8": (_i, [_vp, _vp] + [_i] * 10 + [_d, _d, _d, _d, _vp]),
     "va_gaussian_noise": (_i, [_vp, _i, _sz, _d, _d, C.c_uint64, C.c_uint64, _vp]),

@@ -64,6 +64,7 @@ class FrameEngine(object):
         check(self._lib.va_pipeline_create(C.byref(cfg), C.byref(self._handle)))
         self.bg_mode = cfg.bg_mode
         self._dev = {}      # name -> DeviceBuffer cache for run()
+        self._links_prev = False    # _dev["links_prev"] holds the last label plane of the previous links-run
         self.prepare = None
         if prepare is not None:
             if self.dtype != np.uint8:
@@ -135,10 +136,31 @@ class FrameEngine(object):
         if n > self.max_batch:
             raise ValueError("batch of %d exceeds max_batch=%d" % (n, self.max_batch))
         want = set(want)
-        unknown = want - {"filtered", "mask", "labels", "counts", "stats"}
+        unknown = want - {"filtered", "mask", "labels", "counts", "stats", "links"}
         if unknown:
             raise ValueError("unknown outputs %r" % sorted(unknown))
+        if "links" in want and not self.connectivity:
+            raise ValueError("'links' needs an engine that labels (connectivity 4 or 8)")
         return want
+
+    def reset_links(self):
+        """forget the last label plane of the previous links-run (a new video): the first frame of the next run
+        with 'links' in `want` has no links"""
+        self._links_prev = False
+
+    def _links(self, labels_ptr, n):
+        """the RegionLinks of the n label planes at labels_ptr, the first against the plane kept from the previous
+        links-run; keeps the last plane for the next one"""
+        from . import ops
+        plane = self.width * self.height * 4
+        prev = self._buf("links_prev", plane)
+        links = ops.region_links(ops.DeviceLabels(labels_ptr, n, self.height, self.width),
+                                 prev=prev.ptr if self._links_prev else None)
+        if n:
+            check(self._lib.va_memcpy_d2d(prev.ptr, labels_ptr + (n - 1) * plane, plane, None))
+            check(self._lib.va_stream_sync(None))
+            self._links_prev = True
+        return links
 
     def _run_resident(self, raw_ptr, n, want, keep=()):
         """the chain on `n` source frames at device address `raw_ptr` (raw frames where the engine has prepare
@@ -163,7 +185,7 @@ class FrameEngine(object):
             ptr["filtered"] = self._buf("filtered", n * frame_bytes)
         if "mask" in want:
             ptr["mask"] = self._buf("mask", n * px)
-        if "labels" in want:
+        if "labels" in want or "links" in want:       # (links: the engine labels into its own buffer)
             ptr["labels"] = self._buf("labels", n * px * 4)
         if "counts" in want or "stats" in want:
             ptr["counts"] = self._buf("counts", n * 4)
@@ -193,6 +215,8 @@ class FrameEngine(object):
             out["mask"] = ptr["mask"].download((n, self.height, self.width), np.uint8)
         if "labels" in want:
             out["labels"] = ptr["labels"].download((n, self.height, self.width), np.int32)
+        if "links" in want:
+            out["links"] = self._links(ptr["labels"].ptr, n)
         if "counts" in ptr:
             out["counts"] = ptr["counts"].download((n,), np.int32)
         if "stats" in want:
@@ -201,9 +225,11 @@ class FrameEngine(object):
 
     def run(self, frames, want=("mask", "labels", "counts"), keep=()):
         """frames: (n, H, W[, C]) array; returns a dict with the requested outputs among
-        'filtered', 'mask', 'labels', 'counts', 'stats'.  The outputs named in `keep` ('mask', and 'filtered' on a
-        uint8 engine) are not downloaded: they come back as ops.DeviceFrames that the caller owns and releases, and
-        that the engine's next run does not change.  Any other name in `keep` is a ValueError."""
+        'filtered', 'mask', 'labels', 'counts', 'stats', 'links'.  'links' is an ops.RegionLinks: the overlap
+        tables between consecutive label planes, computed on the device; frame 0 links to the last frame of the
+        previous run that wanted links (reset_links() starts a new video).  The outputs named in `keep` ('mask', and
+        'filtered' on a uint8 engine) are not downloaded: they come back as ops.DeviceFrames that the caller owns and
+        releases, and that the engine's next run does not change.  Any other name in `keep` is a ValueError."""
         arr = np.ascontiguousarray(frames, self.dtype)
         want = self._check_batch(arr.shape[1:], arr.shape[0], want)
         self._check_keep(keep)
@@ -269,6 +295,7 @@ class FrameEngine(object):
         for b in self._dev.values():
             b.free()
         self._dev = {}
+        self._links_prev = False
 
     def __del__(self):
         try:

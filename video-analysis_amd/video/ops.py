@@ -4,6 +4,7 @@ These are the per-call building blocks behind ``video.filters`` and ``video.anal
 batched, device-resident path is :class:`video.engine.FrameEngine`.  Everything here runs on
 the GPU through ``libvideoanalysis_hip.so`` -- nothing is computed with NumPy.
 """
+import collections
 import ctypes as C
 import math
 import threading
@@ -697,6 +698,70 @@ def find_contours(masks, ret_info=False, moments=False, stream=None, keep=False)
     if single:
         res = tuple(r[0] for r in res) if isinstance(res, tuple) else res[0]
     return res
+
+
+# ------------------------------------------------------------------------ region links between consecutive frames
+DEFAULT_LINK_CAPACITY = 1 << 16          # links of a region_links batch the first launch has room for
+LINK_WORKSPACE_ROOM = 256 << 20          # ... and the workspace it may get beyond what that capacity needs
+RegionLinks = collections.namedtuple("RegionLinks", "offsets a b count")
+
+
+class DeviceLabels(object):
+    """an int32 label stack (n, h, w) at the device address `ptr`, which stays its owner's (the engine's label
+    buffer, a torch tensor's data_ptr()): what region_links takes in place of an array, and does not upload"""
+
+    def __init__(self, ptr, n, h, w):
+        self.ptr, self.n, self.h, self.w = int(ptr), int(n), int(h), int(w)
+
+
+def region_links(labels, prev=None, stream=None, cap=None):
+    """the overlap tables between consecutive label planes ("Region links"; va_region_links): pair t is
+    (labels[t - 1], labels[t]), pair 0 is (prev, labels[0]) and has no links without prev.  A link is (a, b, count):
+    count > 0 pixels hold the label a >= 1 in the earlier plane and b >= 1 in the later one (values <= 0 are
+    background); the links of a pair come in the order of their first pixel.  Returns RegionLinks(offsets, a, b,
+    count): pair t owns offsets[t] : offsets[t + 1] (int64, n + 1 entries) of the int32 arrays a, b and count.
+    labels: an (n, h, w) array, or a DeviceLabels; prev: an (h, w) array, or the device address of such a plane.
+    The first launch has room for `cap` links (DEFAULT_LINK_CAPACITY); a batch that may hold more runs exactly once
+    more, with the room the first run asked for.  Only the tables cross to the host."""
+    L = _hip.lib()
+    if isinstance(labels, DeviceLabels):
+        arr, n, h, w = None, labels.n, labels.h, labels.w
+    else:
+        arr = np.ascontiguousarray(np.asarray(labels), np.int32)
+        if arr.ndim != 3:
+            raise ValueError("region_links: labels are an (n, h, w) stack, got shape %r" % (arr.shape,))
+        n, h, w = arr.shape
+    prev_arr = None
+    if prev is not None and not isinstance(prev, (int, np.integer)):
+        prev_arr = np.ascontiguousarray(np.asarray(prev), np.int32)
+        if prev_arr.shape != (h, w):
+            raise ValueError("region_links: prev of shape %r does not match frames of %r" % (prev_arr.shape, (h, w)))
+    if h <= 0 or w <= 0:
+        raise ValueError("region_links: frames of shape %r have no pixels" % ((h, w),))
+    cap = DEFAULT_LINK_CAPACITY if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("region_links: negative capacity %d" % cap)
+    if n == 0:
+        return RegionLinks(np.zeros(1, np.int64), *(np.zeros(0, np.int32) for _ in range(3)))
+    with _Lease.on(stream) as d:
+        src = labels.ptr if arr is None else d.upload(arr).ptr
+        first = _ptr(d.upload(prev_arr)) if prev_arr is not None else (int(prev or 0) or None)
+        nl, tot = d.take(n * 4), d.take(16)
+
+        def run(room):
+            # a launch whose capacity is short still counts the links; with room for the tables of a candidate every
+            # fourth pixel (up to LINK_WORKSPACE_ROOM) it counts all pairs side by side on all but the busiest stacks
+            ws_bytes = max(L.va_region_links_workspace_bytes(n, h, w, room),
+                           min(L.va_region_links_workspace_bytes(n, h, w, n * h * w // 4), LINK_WORKSPACE_ROOM))
+            ws, rec = d.take(ws_bytes), d.take(max(room, 1) * 16)
+            check(L.va_region_links(first, src, n, h, w, nl.ptr, tot.ptr, rec.ptr, room, ws.ptr, ws_bytes, stream))
+            total, need = tot.download((2,), np.int64, stream)
+            return (rec, int(total)), (need,)
+        (rec, total), _ = _rerun(run, cap)
+        counts = nl.download((n,), np.int32, stream)
+        table = rec.download((total, 4), np.int32, stream)
+    offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    return RegionLinks(offsets, *(np.ascontiguousarray(table[:, k]) for k in (1, 2, 3)))
 
 
 # ------------------------------------------------------------------------ geodesic distance maps
