@@ -764,6 +764,88 @@ def region_links(labels, prev=None, stream=None, cap=None):
     return RegionLinks(offsets, *(np.ascontiguousarray(table[:, k]) for k in (1, 2, 3)))
 
 
+# ------------------------------------------------------------------------ region intensity
+INTENSITY_STRIDE = 8                     # int64 per (frame, label, channel) of an intensity table
+INTENSITY_NAMES = ("sum", "sumsq", "sumx", "sumy", "min", "max", "count")        # its slots 0 .. 6; slot 7 is zero
+_SLOT = {name: k for k, name in enumerate(INTENSITY_NAMES)}
+
+
+class RegionIntensity(object):
+    """an intensity table as DESIGN.md §9, "Region intensity", pins it, and its float64 completion on the host (NumPy
+    on the small table; the device call that fills such a table is not part of the library yet, see there).
+    raw: (..., labels, c, 8) int64 -- sum v, sum v^2, sum v x, sum v y, min, max, pixels, 0 -- label l at [l - 1];
+    hist: (..., labels, c, 256) uint32 or None.  The leading axes are the call's (n,), or none for one frame
+    (frame(t)).  An empty region gives NaN, or -1 where the result is an integer."""
+
+    def __init__(self, raw, hist=None):
+        self.raw, self.hist = raw, hist
+
+    def frame(self, t, count=None):
+        """frame t of a stack alone, cut to its first `count` labels"""
+        cut = slice(None) if count is None else slice(0, max(int(count), 0))
+        return RegionIntensity(self.raw[t][cut], None if self.hist is None else self.hist[t][cut])
+
+    def _slot(self, k):
+        return self.raw[..., k].astype(np.float64)
+
+    @property
+    def count(self):
+        """(..., labels) int64: the pixels of each region"""
+        return self.raw[..., 0, _SLOT["count"]]
+
+    @property
+    def mean(self):
+        """(..., labels, c): S0 / N"""
+        n = self._slot(_SLOT["count"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, self._slot(_SLOT["sum"]) / n, np.nan)
+
+    @property
+    def var(self):
+        """(..., labels, c): the population variance S1 / N - mean^2, clipped at 0"""
+        n, mean = self._slot(_SLOT["count"]), self.mean
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, np.maximum(self._slot(_SLOT["sumsq"]) / n - mean * mean, 0.0), np.nan)
+
+    @property
+    def std(self):
+        return np.sqrt(self.var)
+
+    @property
+    def min(self):
+        """(..., labels, c) int64, -1 for an empty region"""
+        return np.where(self.raw[..., _SLOT["count"]] > 0, self.raw[..., _SLOT["min"]], -1)
+
+    @property
+    def max(self):
+        return np.where(self.raw[..., _SLOT["count"]] > 0, self.raw[..., _SLOT["max"]], -1)
+
+    @property
+    def weighted_centroid(self):
+        """(..., labels, c, 2): (S2 / S0, S3 / S0), the centroid (x, y) weighted by brightness; NaN where S0 = 0"""
+        s0 = self._slot(_SLOT["sum"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((s0 > 0)[..., None],
+                            np.stack([self._slot(_SLOT["sumx"]), self._slot(_SLOT["sumy"])], -1) / s0[..., None], np.nan)
+
+    def percentile(self, q):
+        """(..., labels, c) int64: the smallest v whose cumulative count is >= max(1, ceil(q / 100 N)) (nearest rank),
+        -1 for an empty region; needs the histograms"""
+        if self.hist is None:
+            raise ValueError("percentile needs the histograms (this table was made without them)")
+        q = float(q)
+        if not 0.0 <= q <= 100.0:
+            raise ValueError("percentile: q is 0 .. 100, got %r" % (q,))
+        n = self.raw[..., _SLOT["count"]]
+        rank = np.maximum(1, np.ceil(q / 100.0 * n.astype(np.float64))).astype(np.int64)
+        below = (np.cumsum(self.hist, axis=-1, dtype=np.int64) < rank[..., None]).sum(-1)
+        return np.where(n > 0, below, -1).astype(np.int64)
+
+    @property
+    def median(self):
+        return self.percentile(50)
+
+
 # ------------------------------------------------------------------------ geodesic distance maps
 _I32_MAX = 2 ** 31 - 1
 
