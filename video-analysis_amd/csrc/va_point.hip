@@ -112,7 +112,6 @@ struct RecipArgs {
     // (a non-dyadic quotient stays 2^-54 / d away from every rounding midpoint; tools/verify_small_div.c checks
     // all d <= 2^24 and random d up to 2^40 exhaustively over the 256 frame values)
     double lo[256];
-    __device__ double operator[](int f) const { return r[f]; }
 };
 __device__ __forceinline__ double clear_low9(double y)        // (uniform operand: scalar ALU)
 {
@@ -136,18 +135,60 @@ __device__ __forceinline__ unsigned pack_bytes(const int *d)   // the low bytes 
 
 constexpr int kAhead = 8;   // frames per prefetch group, see bg_mean_u8_fast_kernel
 
-template <int V> struct BgGroup {
+// the reciprocal table entry of frame f: the argument table always holds 256 entries (launch_bg fills the
+// ones past the batch), the table in memory holds n
+__device__ __forceinline__ int recip_slot(const RecipArgs &, int f, int) { return f; }
+__device__ __forceinline__ int recip_slot(const double *, int f, int n) { return min(f, n - 1); }
+// (the table in memory was written by an earlier launch and is constant for this one: read as constant memory
+// it stays on the scalar unit whatever the kernel has stored or waited for in between)
+__device__ __forceinline__ double recip_at(const RecipArgs &r, int slot) { return r.r[slot]; }
+__device__ __forceinline__ double recip_at(const double *r, int slot)
+{
+    return ((const __attribute__((address_space(4))) double *)r)[slot];
+}
+
+// One group of kAhead frames on its way to the registers: a thread's pixels of every frame and, wave-uniform in
+// scalar registers, the reciprocals of the frames' divisors.  Everything a group needs is asked for in load(),
+// one group of arithmetic before it is used.
+template <int V, typename RECIP, bool SPLIT> struct BgGroup {
     typedef unsigned int vec __attribute__((ext_vector_type(V / 4)));
     vec v[kAhead];
+    double y[kAhead], lo[kAhead];
     // frames and differences are one-touch streams: non-temporal loads/stores keep them out of L2.
     // CLAMP: the group may reach past the batch (its surplus slots re-read the last frame and are never used)
+    // The barrier keeps the loads together where they stand: left alone, the scheduler moves each down to the
+    // frame before its use, where a wait for it also waits for every older store (loads and stores complete in
+    // order on one counter).
     template <bool CLAMP>
-    __device__ __forceinline__ void load(const uint8_t *frames, size_t i0, size_t px, int f0, int n)
+    __device__ __forceinline__ void load(const uint8_t *frames, const RECIP &recip, size_t i0, size_t px, int f0,
+                                         int n)
+    {
+        // Scalar loads return in any order, so a wait for one of them is a wait for all.  The other group's
+        // reciprocals, asked for a group ago and used next, are waited for here and not at their first use,
+        // where the wait would take in the loads below.
+        __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0) alone
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            v[j] = __builtin_nontemporal_load(reinterpret_cast<const vec *>(
+                frames + (size_t)(CLAMP ? min(f0 + j, n - 1) : f0 + j) * px + i0));
+            __builtin_amdgcn_sched_barrier(0);      // (in this order too: the waits count the loads behind v[j])
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            const int slot = CLAMP ? recip_slot(recip, f0 + j, n) : f0 + j;
+            y[j] = recip_at(recip, slot);
+            if constexpr (SPLIT)
+                lo[j] = recip.lo[slot];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // the frames have arrived from here on (said where a loop is entered, so that no wait inside it is one for
+    // loads issued before it)
+    __device__ __forceinline__ void arrived()
     {
 #pragma unroll
         for (int j = 0; j < kAhead; j++)
-            v[j] = __builtin_nontemporal_load(reinterpret_cast<const vec *>(
-                frames + (size_t)(CLAMP ? min(f0 + j, n - 1) : f0 + j) * px + i0));
+            asm volatile("" : "+v"(v[j]));
     }
 };
 
@@ -155,22 +196,23 @@ template <int V> struct BgGroup {
 // the divisor n_seen + f as a double from frame to frame: + 1.0 is exact below 2^53 (launch_bg sees to that), and
 // a wave-uniform integer -> float64 conversion would run on the vector unit like everything else in float64.
 template <int V, typename RECIP, bool BOUNDED, bool SPLIT, bool DIFF, bool FULL>
-__device__ __forceinline__ void bg_mean_group(const BgGroup<V> &g, double (&m)[V], double &dn, const RECIP &recip,
-                                              int f0, int cnt, uint8_t *diff, size_t i0, size_t px)
+__device__ __forceinline__ void bg_mean_group(const BgGroup<V, RECIP, SPLIT> &g, double (&m)[V], double &dn, int f0,
+                                              int cnt, uint8_t *diff, size_t i0, size_t px)
 {
+    typedef typename BgGroup<V, RECIP, SPLIT>::vec vec;
 #pragma unroll
     for (int j = 0; j < kAhead; j++) {
         if (!FULL && j >= cnt)
             break;
         const int f = f0 + j;
         const double dn1 = dn + 1.0;
-        const double y = recip[f];
+        const double y = g.y[j];
         double yh = 0.0, yl = 0.0;
         if constexpr (SPLIT) {
             yh = clear_low9(y);
-            yl = recip.lo[f];
+            yl = g.lo[j];
         }
-        typename BgGroup<V>::vec out;
+        vec out;
 #pragma unroll
         for (int w = 0; w < V / 4; w++) {
             int d[4];
@@ -193,7 +235,7 @@ __device__ __forceinline__ void bg_mean_group(const BgGroup<V> &g, double (&m)[V
                 out[w] = pack_bytes(d);
         }
         if constexpr (DIFF)
-            __builtin_nontemporal_store(out, reinterpret_cast<typename BgGroup<V>::vec *>(diff + (size_t)f * px + i0));
+            __builtin_nontemporal_store(out, reinterpret_cast<vec *>(diff + (size_t)f * px + i0));
         dn = dn1;
     }
 }
@@ -223,26 +265,42 @@ bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__
     // Two register sets take turns (the first loop walks two groups per round), so nothing is
     // copied between them, and its rounds neither test the frame index nor clamp a load address;
     // what is left of the batch, fewer than three groups, goes through the second loop, which
-    // tests, clamps and copies.  So the first loop starts at batches of 24 frames: a shorter
-    // batch runs in the second loop alone.
+    // clamps and copies, and the last group, which tests.  So the first loop starts at batches
+    // of 24 frames: a shorter batch runs in the second loop and the last group alone.
+    // The first group of such a batch is worked off ahead of the first loop.  The memory counter then looks the
+    // same on entry as after a round (eight loads, then eight stores), so the waits inside a round are counted
+    // for the round itself: none of them asks for a store, and none is left over from the loads of the state,
+    // which that first group has consumed.
     double dn = dn0;
-    BgGroup<V> a, b;
-    a.template load<true>(frames, i0, px, 0, n);
+    BgGroup<V, RECIP, SPLIT> a, b;
     int f0 = 0;
-    for (; f0 + 3 * kAhead <= n; f0 += 2 * kAhead) {
-        b.template load<false>(frames, i0, px, f0 + kAhead, n);
-        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(a, m, dn, recip, f0, kAhead, diff, i0, px);
-        a.template load<false>(frames, i0, px, f0 + 2 * kAhead, n);
-        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(b, m, dn, recip, f0 + kAhead, kAhead, diff, i0, px);
+    if (n >= 3 * kAhead) {
+        a.template load<false>(frames, recip, i0, px, 0, n);
+        b.template load<false>(frames, recip, i0, px, kAhead, n);
+        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(a, m, dn, 0, kAhead, diff, i0, px);
+        for (f0 = kAhead; f0 + 3 * kAhead <= n; f0 += 2 * kAhead) {
+            a.template load<false>(frames, recip, i0, px, f0 + kAhead, n);
+            bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(b, m, dn, f0, kAhead, diff, i0, px);
+            b.template load<false>(frames, recip, i0, px, f0 + 2 * kAhead, n);
+            bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(a, m, dn, f0 + kAhead, kAhead, diff, i0, px);
+        }
+        b.arrived();                            // (with the stores of the last group still on their way)
+    } else {
+        b.template load<true>(frames, recip, i0, px, 0, n);
+#pragma unroll
+        for (int k = 0; k < V; k++)
+            asm volatile("" : "+v"(m[k]));      // the state, like the group, is there before the second loop
+        b.arrived();
     }
-    for (; f0 < n; f0 += kAhead) {
-        const bool more = f0 + kAhead < n;
-        if (more)
-            b.template load<true>(frames, i0, px, f0 + kAhead, n);
-        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, false>(a, m, dn, recip, f0, min(kAhead, n - f0), diff, i0, px);
-        if (more)
-            a = b;
+    // the second loop: full groups with another group behind them, which is there when its turn comes (the copy
+    // needs it); the last group of the batch, full or not, follows the loop
+    for (; f0 + kAhead < n; f0 += kAhead) {
+        a.template load<true>(frames, recip, i0, px, f0 + kAhead, n);
+        bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, true>(b, m, dn, f0, kAhead, diff, i0, px);
+        a.arrived();
+        b = a;
     }
+    bg_mean_group<V, RECIP, BOUNDED, SPLIT, DIFF, false>(b, m, dn, f0, n - f0, diff, i0, px);
 #pragma unroll
     for (int k = 0; k < V; k++)
         mean[i0 + k] = m[k];
