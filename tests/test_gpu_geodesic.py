@@ -1,5 +1,5 @@
 """GPU: geodesic distance maps, the shortest-path walk and the farthest-point iteration
-(va_geodesic.hip, va_ccl.hip) bit-exact against the restatements of tests/golden/make_golden_geodesic.py,
+(va_geodesic.hip, va_contours.hip) bit-exact against the restatements of tests/golden/make_golden_geodesic.py,
 the committed fixture, scipy's Dijkstra and the oracle's cv2.findContours restatement."""
 import ctypes as C
 import importlib.util

@@ -14,7 +14,7 @@ Groups A and B run twice: plainly, and in the test fill mode (tests/test_gpu_hos
 a write behind a tiny frame's buffer lands in a guarded tail instead of the slack of a size class.
 
 Which case guards which launch code:
-  the pieces of edge_labels_kernel (va_ccl.hip)        test_c_contours_of_more_than_65535_frames (va_find_contours) and
+  the pieces of edge_labels_kernel (va_contours.hip)   test_c_contours_of_more_than_65535_frames (va_find_contours) and
                                                        test_c_farthest_points_of_more_than_65535_frames
   the pieces of the float row pass                     test_c_gaussian[65537x4x8]: sigma 1 takes the fused kernels
   the periodic reflection of col_sym_f32_kernel        test_b_gaussian_f32_gates, heights 1, 2 and r - 1, hook 0

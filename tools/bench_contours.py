@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time of every outer contour of a frame stack on the GPU (va_find_contours, va_ccl.hip):
+"""Time of every outer contour of a frame stack on the GPU (va_find_contours, va_contours.hip):
   blobs     64 x 1080p masks of the cfg#3 kind (40 moving discs of radius 8 .. 60 a frame, as bench.py's
             synth_batch places them, already thresholded and closed: no salt), resident in HBM, HIP events around
             the call; va_largest_contour on the same stack for the ratio

@@ -1,10 +1,7 @@
-// va_api.hip -- the runtime plumbing of libvideoanalysis_hip.so and the entry points that sequence launchers of
-// more than one file (include/videoanalysis_hip.h)
+// va_api.hip -- the runtime plumbing of libvideoanalysis_hip.so and the fused pipeline (include/videoanalysis_hip.h)
 //
-// Host code only: the error message, the device and the entry prologue; memory, streams and events; the tap
-// tables; the entries of the Gaussian, background, pointwise, morphology, stencil and labelling launchers that
-// the pipeline shares; the contour and geodesic entries, whose workspaces hold labelling rows; the fused
-// pipeline; the lazy RCCL binding.  A stand-alone op's entry points are in the file of its kernels.  No exception
+// Host code only: the error message, the device and the entry prologue; memory, streams and events; the fused
+// pipeline; the lazy RCCL binding.  Every op's entry points are in the file of its kernels.  No exception
 // crosses the ABI; every failure sets the thread-local message returned by va_last_error().
 #include <dlfcn.h>
 #include <stdarg.h>
@@ -287,118 +284,6 @@ int va_event_elapsed_ms(void *start_event, void *stop_event, float *ms_out)
     return VA_OK;
 }
 
-// ------------------------------------------------------------------------------ Gaussian
-int va_gauss_taps_q8(double sigma, int *ksize_out, uint16_t *taps_out, int capacity)
-{
-    return va_gauss_taps_q8_rule(sigma, VA_TAPS_CV4, ksize_out, taps_out, capacity);
-}
-int va_gauss_taps_q8_rule(double sigma, int tap_rule, int *ksize_out, uint16_t *taps_out, int capacity)
-{
-    VA_REQUIRE(ksize_out && taps_out, "va_gauss_taps_q8: NULL argument");
-    TapsQ8 t;
-    int rc = gauss_taps_q8(sigma, &t.ksize, t.t, kMaxTaps, tap_rule);
-    if (rc)
-        return rc;
-    if (t.ksize > capacity) {
-        set_error("va_gauss_taps_q8: %d taps > capacity %d", t.ksize, capacity);
-        return VA_ERR_RANGE;
-    }
-    memcpy(taps_out, t.t, sizeof(uint16_t) * t.ksize);
-    *ksize_out = t.ksize;
-    return VA_OK;
-}
-int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacity)
-{
-    VA_REQUIRE(ksize_out && taps_out, "va_gauss_taps_f32: NULL argument");
-    TapsF32 t;
-    int rc = gauss_taps_f32(sigma, &t.ksize, t.t, kMaxTaps);
-    if (rc)
-        return rc;
-    if (t.ksize > capacity) {
-        set_error("va_gauss_taps_f32: %d taps > capacity %d", t.ksize, capacity);
-        return VA_ERR_RANGE;
-    }
-    memcpy(taps_out, t.t, sizeof(float) * t.ksize);
-    *ksize_out = t.ksize;
-    return VA_OK;
-}
-
-// The stand-alone Gaussian calls: argument checks, a plan, a scratch lease and a launch.  The test hooks
-// (force != None) keep their terse messages; the dot4/dot2 hook takes one channel only.
-static int gaussian_call(const char *who, int dtype, const void *src, void *dst, int n, int h, int w, int c,
-                         double sigma, int tap_rule, GaussFamily force, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "%s: frames above 2^29 pixels are not supported", who);
-    const bool hook = force != GaussFamily::None;
-    VA_REQUIRE(src && dst && src != dst, hook ? "%s: bad pointers" : "%s: src/dst must be distinct non-NULL", who);
-    VA_REQUIRE(!hook || (n >= 0 && h > 0 && w > 0 && c > 0 && (c == 1 || force != GaussFamily::U8Dot)),
-               "%s: bad shape", who);
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "%s: bad shape (%d,%d,%d,%d)", who, n, h, w, c);
-    const bool aligned = (uintptr_t)src % 16 == 0 && (dtype == VA_F32 || (uintptr_t)dst % 4 == 0);
-    GaussPlan g;
-    int rc = plan_gaussian(&g, dtype, h, w, c, sigma, tap_rule, aligned, false, force);
-    if (rc)
-        return rc;
-    ScratchLease scratch;
-    if (!g.single_pass() && (rc = scratch.acquire(gauss_scratch_bytes(g, n), as_stream(stream))))
-        return rc;
-    return launch_gaussian(g, src, dst, nullptr, -1, 0, scratch.ptr, n, as_stream(stream), nullptr);
-}
-
-int va_gaussian_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
-                   void *stream)
-{
-    return va_gaussian_u8_rule(src, dst, n, h, w, c, sigma, VA_TAPS_CV4, stream);
-}
-
-int va_gaussian_u8_rule(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
-                        int tap_rule, void *stream)
-{
-    return gaussian_call("va_gaussian_u8", VA_U8, src, dst, n, h, w, c, sigma, tap_rule, GaussFamily::None,
-                         stream);
-}
-
-// test hook: force the generic two-pass implementation
-int va_gaussian_u8_generic(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c,
-                           double sigma, void *stream)
-{
-    return gaussian_call("va_gaussian_u8_generic", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
-                         GaussFamily::U8Generic, stream);
-}
-
-// test hook: force the LDS/VALU (dot4/dot2) fused implementation
-int va_gaussian_u8_valu(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
-                        void *stream)
-{
-    return gaussian_call("va_gaussian_u8_valu", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
-                         GaussFamily::U8Dot, stream);
-}
-
-// test hook: pin the labelling code path of every later call in this process
-int va_test_hook_labelling(int path, int lds_runs)
-{
-    VA_REQUIRE(path >= 0 && path <= 5 && lds_runs >= 0, "va_test_hook_labelling: bad arguments");
-    ccl_test_hook(path, lds_runs);
-    return VA_OK;
-}
-
-// test / measurement hook: pipelines created while this is set run their 8-bit Gaussian on the VALU
-// (dot4/dot2 LDS kernel) instead of the matrix cores -- the north star's "no MFMA" form of the chain
-static int g_gauss_u8_valu = 0;
-int va_test_hook_gaussian_u8(int force_valu)
-{
-    g_gauss_u8_valu = force_valu != 0;
-    return VA_OK;
-}
-
-int va_test_hook_gaussian_f32(int generic_columns)
-{
-    gauss_f32_test_hook(generic_columns);
-    return VA_OK;
-}
-
 // test hook: -1 = off, 0..255 = every scratch lease and every plane of a pipeline created from now on starts
 // out filled with that byte (undefined memory that is not zero)
 int va_test_hook_fill(int byte)
@@ -406,560 +291,6 @@ int va_test_hook_fill(int byte)
     VA_REQUIRE(byte >= -1 && byte <= 255, "va_test_hook_fill: byte must be -1 (off) or 0..255");
     g_test_fill = byte;
     return VA_OK;
-}
-
-int va_gaussian_f32(const float *src, float *dst, int n, int h, int w, int c, double sigma,
-                    void *stream)
-{
-    return gaussian_call("va_gaussian_f32", VA_F32, src, dst, n, h, w, c, sigma, VA_TAPS_CV4, GaussFamily::None,
-                         stream);
-}
-
-// ------------------------------------------------------------------------------ background
-int va_bg_update(int mode, int dtype, const void *frames, void *diff_out, void *state,
-                 int64_t n_seen, double rate, int n, size_t px, void *stream)
-{
-    VA_ENTER();
-    double *recip = nullptr;
-    ScratchLease scratch;
-    if (mode == VA_BG_MEAN && dtype == VA_U8 && n > 0) {
-        int rc = scratch.acquire(bg_scratch_bytes(n), as_stream(stream));
-        if (rc)
-            return rc;
-        recip = (double *)scratch.ptr;
-    }
-    return launch_bg(mode, dtype, frames, diff_out, state, n_seen, rate, n, px, as_stream(stream),
-                     recip);
-}
-int va_welford_u8(const uint8_t *frames, double *mean, double *m2, int64_t n_seen, int n,
-                  size_t px, void *stream)
-{
-    VA_ENTER();
-    return launch_welford(frames, mean, m2, n_seen, n, px, as_stream(stream));
-}
-
-int va_mean_any(const void *frames, int dtype, double *mean, int64_t n_seen, int n, size_t px, void *stream)
-{
-    VA_ENTER();
-    return launch_temporal_stats(frames, dtype, mean, nullptr, n_seen, n, px, as_stream(stream));
-}
-int va_welford_any(const void *frames, int dtype, double *mean, double *m2, int64_t n_seen, int n, size_t px,
-                   void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(m2, "va_welford_any: NULL argument");
-    return launch_temporal_stats(frames, dtype, mean, m2, n_seen, n, px, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ pointwise
-int va_time_difference_u8(const uint8_t *a, const uint8_t *b, int16_t *out, size_t count,
-                          void *stream)
-{
-    VA_ENTER();
-    return launch_time_difference(a, b, out, count, as_stream(stream));
-}
-int va_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thresh, int maxval,
-                    void *stream)
-{
-    VA_ENTER();
-    return launch_threshold_u8(src, dst, count, thresh, maxval, as_stream(stream));
-}
-int va_mono_mean_u8(const uint8_t *src, uint8_t *dst, size_t pixels, void *stream)
-{
-    VA_ENTER();
-    return launch_mono_mean(src, dst, pixels, as_stream(stream));
-}
-int va_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double fmin, double fmax,
-                    double alpha, double tmin, void *stream)
-{
-    VA_ENTER();
-    return launch_normalize_u8(src, dst, count, fmin, fmax, alpha, tmin, as_stream(stream));
-}
-
-int va_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
-                 double fmax, double alpha, double tmin, void *stream)
-{
-    VA_ENTER();
-    return launch_normalize(src, src_dtype, dst, dst_dtype, count, fmin, fmax, alpha, tmin, as_stream(stream));
-}
-
-int va_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int src_c, int left, int top,
-                  int width, int height, int mono, int normalize, double fmin, double fmax, double alpha,
-                  double tmin, void *stream)
-{
-    VA_ENTER();
-    return launch_prepare_u8(src, dst, n, src_h, src_w, src_c, left, top, width, height, mono, normalize, fmin,
-                             fmax, alpha, tmin, as_stream(stream));
-}
-
-int va_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
-                      uint64_t first_index, void *stream)
-{
-    VA_ENTER();
-    return launch_gaussian_noise(dst, dtype, count, mean, stdev, seed, first_index, as_stream(stream));
-}
-
-int va_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes, int k, void *stream)
-{
-    VA_ENTER();
-    return launch_rot90(src, dst, n, h, w, elem_bytes, k, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ morphology
-int va_morph_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int op, int shape,
-                int ksize, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_morph_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_morph_u8: src/dst must be distinct non-NULL");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_morph_u8: bad shape (%d,%d,%d)", n, h, w);
-    VA_REQUIRE(op == VA_MORPH_ERODE || op == VA_MORPH_DILATE, "va_morph_u8: bad op %d", op);
-    RowSpans se;
-    int rc = make_row_spans(shape, ksize, &se);
-    if (rc)
-        return rc;
-    ScratchLease scratch;
-    if (shape == VA_SHAPE_RECT && ksize >= 3 && n > 0) {
-        rc = scratch.acquire((size_t)n * h * w, as_stream(stream));
-        if (rc)
-            return rc;
-    }
-    return launch_morph_u8(src, dst, n, h, w, op, se, as_stream(stream), (uint8_t *)scratch.ptr);
-}
-
-// test hook: morphology on the bit-packed representation used inside the pipeline
-// (mask: any non-zero byte is foreground; dst gets 0 / 255)
-int va_morph_bits_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int op, int shape,
-                     int ksize, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_morph_bits_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst, "va_morph_bits_u8: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_morph_bits_u8: bad shape");
-    RowSpans se;
-    int rc = make_row_spans(shape, ksize, &se);
-    if (rc)
-        return rc;
-    Carve c;                                 // [b0 | b1]
-    const size_t words = (size_t)n * h * words_per_row(w) * sizeof(uint32_t);
-    const size_t o0 = c.take(words), o1 = c.take(words);
-    hipStream_t st = as_stream(stream);
-    ScratchLease scratch;
-    rc = scratch.acquire(c.total, st);
-    if (rc)
-        return rc;
-    uint32_t *b0 = at<uint32_t>(scratch.ptr, o0), *b1 = at<uint32_t>(scratch.ptr, o1);
-    if ((rc = launch_pack_bits(src, b0, n, h, w, 0, st)))
-        return rc;
-    if ((rc = launch_morph_bits(b0, b1, n, h, w, op, se, st)))
-        return rc;
-    return launch_unpack_bits(b1, dst, n, h, w, 255, st);
-}
-
-// ------------------------------------------------------------------------------ labelling
-size_t va_label_workspace_bytes(int n, int h, int w)
-{
-    if (n <= 0 || h <= 0 || w <= 0)
-        return 256;
-    return ccl_layout(n, h, w).total;
-}
-
-int va_label_i32(const uint8_t *mask, int32_t *labels, int32_t *counts, int n, int h, int w,
-                 int connectivity, void *workspace, size_t workspace_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_label_i32: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(mask && labels && counts && workspace, "va_label_i32: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_label_i32: bad shape (%d,%d,%d)", n, h, w);
-    VA_REQUIRE(workspace_bytes >= va_label_workspace_bytes(n, h, w),
-               "va_label_i32: workspace of %zu bytes < required %zu", workspace_bytes,
-               va_label_workspace_bytes(n, h, w));
-    if (n == 0)
-        return VA_OK;
-    hipStream_t st = as_stream(stream);
-    const CclLayout L = ccl_layout(n, h, w);
-    uint32_t *bits = at<uint32_t>(workspace, L.bits);
-    int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
-    if (rc)
-        return rc;
-    return launch_ccl(bits, labels, counts, n, h, w, connectivity, at(workspace, L.rows), workspace_bytes - L.rows,
-                      nullptr, 0, st);
-}
-
-int va_moments_i64(const int32_t *labels, int n, int h, int w, int max_labels, int64_t *stats,
-                   void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_moments_i64: bad shape (%d,%d,%d)", n, h, w);
-    return launch_stats_from_labels(labels, n, h, w, max_labels, stats, as_stream(stream));
-}
-
-int va_largest_region(const int32_t *labels, const int32_t *counts, const int64_t *stats, int n,
-                      int h, int w, int max_labels, int32_t *largest, int64_t *largest_area,
-                      uint8_t *mask_out, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_largest_region: bad shape (%d,%d,%d)", n, h, w);
-    return launch_largest_region(labels, counts, stats, n, h, w, max_labels, largest, largest_area,
-                                 mask_out, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ stencils
-int va_detect_peaks_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
-                       void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_detect_peaks_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && src != dst, "va_detect_peaks_u8: bad pointers");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_detect_peaks_u8: bad shape");
-    return launch_detect_peaks(src, dst, n, h, w, include_plateaus, as_stream(stream));
-}
-
-int va_detect_peaks_f32(const float *src, uint8_t *dst, int n, int h, int w, int include_plateaus, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_detect_peaks_f32: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && dst && (const void *)src != (const void *)dst, "va_detect_peaks_f32: bad pointers");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_detect_peaks_f32: bad shape");
-    return launch_detect_peaks_f32(src, dst, n, h, w, include_plateaus, as_stream(stream));
-}
-
-int va_image_statistics_f32(const float *src, double *mean_out, double *var_out, int n, int h, int w, int kernel,
-                            int ksize, double prior, int exclude_center, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_image_statistics_f32: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && mean_out, "va_image_statistics_f32: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ksize >= 0, "va_image_statistics_f32: bad shape");
-    VA_REQUIRE(kernel == 0 || kernel == 1, "va_image_statistics_f32: kernel must be 0 (box) or 1 (ellipse)");
-    RowSpans se;
-    int rc = make_row_spans(kernel == 0 ? VA_SHAPE_RECT : VA_SHAPE_ELLIPSE, 2 * ksize + 1, &se);
-    if (rc)
-        return rc;
-    return launch_image_statistics_f32(src, mean_out, var_out, n, h, w, se, prior, exclude_center,
-                                       as_stream(stream));
-}
-
-int va_mask_thinning_u8(uint8_t *img, uint8_t *scratch, uint8_t *skel, int h, int w,
-                        int *iterations_out, void *stream)
-{
-    VA_REQUIRE(img && scratch && skel, "va_mask_thinning_u8: NULL argument");
-    VA_REQUIRE(h > 0 && w > 0, "va_mask_thinning_u8: bad shape");
-    VA_ENTER();
-    hipStream_t st = as_stream(stream);
-    // a 3x3-cross erosion empties any mask within min(h,w)/2 + 1 steps, except one that fills the
-    // frame (the border never wins): the reference would loop forever there, we stop
-    const int max_it = (h < w ? h : w) / 2 + 2;
-    // One flag per iteration (set when a pixel survived the erosion); the exit condition is read back once per
-    // kCheck iterations (steps enqueued past the emptying one see an empty image and change
-    // nothing: eroded = temp = 0, skeleton |= 0), so the host waits ceil(iterations / kCheck)
-    // times instead of once per step.
-    const int kCheck = 16;
-    const int total_it = max_it + 1;
-    ScratchLease cnt;
-    int rc = cnt.acquire(sizeof(unsigned long long) * (size_t)total_it, st);
-    if (rc)
-        return rc;
-    unsigned long long *cnt_dev = (unsigned long long *)cnt.ptr;
-    VA_HIP(hipMemsetAsync(cnt_dev, 0, sizeof(unsigned long long) * (size_t)total_it, st));
-    VA_HIP(hipMemsetAsync(skel, 0, (size_t)h * w, st));
-    uint8_t *cur = img, *nxt = scratch;
-    unsigned long long host_cnt[kCheck];
-    int done_it = -1;
-    for (int it0 = 0; it0 < total_it && done_it < 0; it0 += kCheck) {
-        const int k = (total_it - it0 < kCheck) ? total_it - it0 : kCheck;
-        for (int j = 0; j < k; j++) {
-            rc = launch_thinning_step(cur, nxt, skel, 1, h, w, cnt_dev + it0 + j, st);
-            if (rc)
-                return rc;
-            uint8_t *t = cur;
-            cur = nxt;
-            nxt = t;
-        }
-        VA_HIP(hipStreamSynchronize(st));
-        VA_HIP(hipMemcpy(host_cnt, cnt_dev + it0, sizeof(unsigned long long) * (size_t)k, hipMemcpyDeviceToHost));
-        for (int j = 0; j < k; j++)
-            if (host_cnt[j] == 0) {
-                done_it = it0 + j;
-                break;
-            }
-    }
-    if (done_it < 0)
-        done_it = max_it;
-    if (iterations_out)
-        *iterations_out = done_it + 1;
-    return VA_OK;
-}
-
-int va_image_statistics_u8(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
-                           int w, int kernel, int ksize, double prior, int exclude_center,
-                           void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_image_statistics_u8: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(src && mean_out, "va_image_statistics_u8: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ksize >= 0, "va_image_statistics_u8: bad shape");
-    VA_REQUIRE(kernel == 0 || kernel == 1, "va_image_statistics_u8: kernel must be 0 (box) or 1 (ellipse)");
-    RowSpans se;
-    int rc = make_row_spans(kernel == 0 ? VA_SHAPE_RECT : VA_SHAPE_ELLIPSE, 2 * ksize + 1, &se);
-    if (rc)
-        return rc;
-    ScratchLease scratch;
-    rc = scratch.acquire(image_statistics_scratch_bytes(n, h, w), as_stream(stream));
-    if (rc)
-        return rc;
-    return launch_image_statistics(src, mean_out, var_out, n, h, w, se, prior, exclude_center,
-                                   scratch.ptr, as_stream(stream));
-}
-
-// ------------------------------------------------------------------------------ contour
-// [bits | labelling rows | forest | keys]
-namespace {
-struct ContourLayout { size_t bits, rows, rows_bytes, forest, keys, total; };
-ContourLayout contour_layout(int n, int h, int w)
-{
-    Carve c;
-    const CclLayout ccl = ccl_layout(n, h, w);
-    const size_t label = c.take(ccl.total);
-    return {label + ccl.bits, label + ccl.rows, ccl.rows_bytes, c.take((size_t)n * h * w * sizeof(int32_t)),
-            c.take((size_t)n * sizeof(unsigned long long)), c.total};
-}
-}  // namespace
-
-size_t va_contour_workspace_bytes(int n, int h, int w)
-{
-    if (n <= 0 || h <= 0 || w <= 0)
-        return 256;
-    return contour_layout(n, h, w).total;
-}
-
-int va_largest_contour(const uint8_t *mask, int n, int h, int w, int32_t *points, int max_points,
-                       int32_t *npoints, double *area, int32_t *ncomponents, void *workspace,
-                       size_t workspace_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_largest_contour: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(mask && points && npoints && ncomponents && workspace, "va_largest_contour: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && max_points > 0, "va_largest_contour: bad shape");
-    VA_REQUIRE(workspace_bytes >= va_contour_workspace_bytes(n, h, w),
-               "va_largest_contour: workspace of %zu bytes < required %zu", workspace_bytes,
-               va_contour_workspace_bytes(n, h, w));
-    if (n == 0)
-        return VA_OK;
-    hipStream_t st = as_stream(stream);
-    const ContourLayout L = contour_layout(n, h, w);
-    uint32_t *bits = at<uint32_t>(workspace, L.bits);
-    int32_t *forest = at<int32_t>(workspace, L.forest);
-    unsigned long long *keys = at<unsigned long long>(workspace, L.keys);
-    int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
-    if (rc)
-        return rc;
-    rc = launch_ccl(bits, forest, ncomponents, n, h, w, 8, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st,
-                    nullptr, /*paint=*/false);
-    if (rc)
-        return rc;
-    return launch_largest_contour(bits, forest, n, h, w, keys, points, max_points, npoints, area, st);
-}
-
-// ------------------------------------------------------------------------------ all contours
-// [bits | labelling rows | forest | inverted bits | background labels | edge bits | counts | cells | frame_first |
-//  frame_pts | pt_first | starts | npts]
-namespace {
-struct FindContoursLayout {
-    size_t bits, rows, rows_bytes, forest, inv, bgl, edge, counts, cells, frame_first, frame_pts, pt_first, starts,
-        npts, total;
-};
-FindContoursLayout find_contours_layout(int n, int h, int w)
-{
-    FindContoursLayout g;
-    Carve c;
-    const CclLayout ccl = ccl_layout(n, h, w);
-    const size_t label = c.take(ccl.total), px = (size_t)n * h * w, slots = (size_t)n * max_contours_per_frame(h, w);
-    g.bits = label + ccl.bits;
-    g.rows = label + ccl.rows;
-    g.rows_bytes = ccl.rows_bytes;
-    g.forest = c.take(px * sizeof(int32_t));
-    g.inv = c.take((size_t)n * h * words_per_row(w) * sizeof(uint32_t));
-    g.bgl = c.take(px * sizeof(int32_t));
-    g.edge = c.take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
-    g.counts = c.take((size_t)2 * n * sizeof(int32_t));
-    g.cells = c.take((size_t)n * h * 8 * sizeof(int32_t));
-    g.frame_first = c.take(((size_t)n + 1) * sizeof(int64_t));
-    g.frame_pts = c.take((size_t)n * sizeof(int64_t));
-    g.pt_first = c.take(((size_t)n + 1) * sizeof(int64_t));
-    g.starts = c.take(slots * 8);
-    g.npts = c.take(slots * sizeof(int32_t));
-    g.total = c.total;
-    return g;
-}
-}  // namespace
-
-size_t va_find_contours_workspace_bytes(int n, int h, int w)
-{
-    if (n <= 0 || h <= 0 || w <= 0)
-        return 256;
-    return find_contours_layout(n, h, w).total;
-}
-
-int va_find_contours(const uint8_t *mask, int n, int h, int w, int32_t *ncontours, int64_t *totals,
-                     va_contour_info *info, int64_t *point_off, int64_t cap_contours, int32_t *points,
-                     int64_t cap_points, void *workspace, size_t workspace_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
-               "va_find_contours: frames above 2^29 pixels are not supported");
-    VA_REQUIRE(mask && ncontours && totals && info && point_off && points && workspace,
-               "va_find_contours: NULL argument");
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_find_contours: bad shape");
-    VA_REQUIRE(cap_contours >= 0 && cap_points >= 0, "va_find_contours: negative capacity (%lld contours, %lld points)",
-               (long long)cap_contours, (long long)cap_points);
-    VA_REQUIRE(aligned(points, 8) && aligned(info, 8) && aligned(point_off, 8) && aligned(totals, 8),
-               "va_find_contours: points, records, offsets and totals must be 8-byte aligned");
-    VA_REQUIRE(workspace_bytes >= va_find_contours_workspace_bytes(n, h, w),
-               "va_find_contours: workspace of %zu bytes < required %zu", workspace_bytes,
-               va_find_contours_workspace_bytes(n, h, w));
-    if (n == 0)
-        return VA_OK;
-    hipStream_t st = as_stream(stream);
-    const FindContoursLayout L = find_contours_layout(n, h, w);
-    uint32_t *bits = at<uint32_t>(workspace, L.bits), *inv = at<uint32_t>(workspace, L.inv);
-    int32_t *forest = at<int32_t>(workspace, L.forest), *bgl = at<int32_t>(workspace, L.bgl);
-    int32_t *counts = at<int32_t>(workspace, L.counts);
-    int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
-    if (!rc)
-        rc = launch_ccl(bits, forest, counts, n, h, w, 8, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st, nullptr,
-                        /*paint=*/false);
-    if (!rc)
-        rc = launch_invert_bits(bits, inv, n, h, w, st);
-    if (!rc)
-        rc = launch_ccl(inv, bgl, counts + n, n, h, w, 4, at(workspace, L.rows), L.rows_bytes, nullptr, 0, st, nullptr,
-                        /*paint=*/true);
-    if (rc)
-        return rc;
-    const FindContoursScratch s = {at<uint32_t>(workspace, L.edge),       at<int32_t>(workspace, L.cells),
-                                   at<int64_t>(workspace, L.frame_first), at<int64_t>(workspace, L.frame_pts),
-                                   at<int64_t>(workspace, L.pt_first),    at(workspace, L.starts),
-                                   at<int32_t>(workspace, L.npts)};
-    return launch_find_contours(bits, forest, bgl, s, n, h, w, ncontours, totals, info, point_off, cap_contours, points,
-                                cap_points, st);
-}
-
-// ------------------------------------------------------------------------------ geodesic
-// [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the default
-// start is chosen the pairs hold the 8-connected forest and the background labels, the visited
-// bitmap the bit mask (the distance maps come after, in stream order)
-namespace {
-struct GeoLayout {
-    size_t pairs, visited, inv, rows, edge, keys, counts, p1, total;
-};
-GeoLayout geo_layout(int n, int h, int w)
-{
-    GeoLayout g;
-    Carve c;
-    g.pairs = c.take(geodesic_pairs_bytes(n, h, w));
-    g.visited = c.take(geodesic_visited_bytes(n, h, w));
-    g.inv = c.take(geodesic_visited_bytes(n, h, w));
-    g.rows = c.take(ccl_rows_workspace_bytes(n, h));
-    g.edge = c.take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
-    g.keys = c.take((size_t)2 * n * sizeof(unsigned long long));
-    g.counts = c.take((size_t)2 * n * sizeof(int32_t));
-    g.p1 = c.take((size_t)2 * n * sizeof(int32_t));
-    g.total = c.total;
-    return g;
-}
-}  // namespace
-
-size_t va_geodesic_workspace_bytes(int n, int h, int w)
-{
-    if (n <= 0 || h <= 0 || w <= 0)
-        return 256;
-    return geo_layout(n, h, w).total;
-}
-
-#define VA_GEO_REQUIRE_SHAPE(name)                                                                        \
-    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,                               \
-               name ": frames above 2^29 pixels are not supported");                                     \
-    VA_REQUIRE(n >= 0 && h > 0 && w > 0, name ": bad shape");                                             \
-    VA_REQUIRE(geodesic_width_ok(w), name ": frames wider than 8192 columns are not supported");          \
-    VA_REQUIRE(ws && ws_bytes >= va_geodesic_workspace_bytes(n, h, w),                                    \
-               name ": workspace of %zu bytes < required %zu", ws_bytes, va_geodesic_workspace_bytes(n, h, w))
-
-int va_distance_map_i32(const uint8_t *fillable, int n, int h, int w, const int32_t *starts, const int32_t *nstarts,
-                        int max_starts, const int32_t *ends, const int32_t *nends, int max_ends, int32_t *map_out,
-                        void *ws, size_t ws_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_GEO_REQUIRE_SHAPE("va_distance_map_i32");
-    VA_REQUIRE(fillable && map_out && starts && nstarts && max_starts > 0, "va_distance_map_i32: NULL argument");
-    VA_REQUIRE(!ends || (nends && max_ends > 0), "va_distance_map_i32: end points without counts");
-    if (n == 0)
-        return VA_OK;
-    const GeoLayout g = geo_layout(n, h, w);
-    char *base = (char *)ws;
-    return launch_distance_map(fillable, n, h, w, starts, nstarts, max_starts, ends, nends, ends ? max_ends : 0,
-                               map_out, (unsigned long long *)(base + g.pairs), nullptr, as_stream(stream));
-}
-
-int va_distance_map_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path_out,
-                         int max_points, int32_t *npath_out, void *ws, size_t ws_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_GEO_REQUIRE_SHAPE("va_distance_map_path");
-    VA_REQUIRE(map && end_points && path_out && npath_out && max_points > 0, "va_distance_map_path: NULL argument");
-    if (n == 0)
-        return VA_OK;
-    const GeoLayout g = geo_layout(n, h, w);
-    return launch_distance_path(map, n, h, w, end_points, path_out, max_points, npath_out,
-                                (uint32_t *)((char *)ws + g.visited), as_stream(stream));
-}
-
-int va_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1, int32_t *p1_out, int32_t *p2_out,
-                       int32_t *dist_out, int32_t *rounds_out, int32_t *path_out, int max_points, int32_t *npath_out,
-                       void *ws, size_t ws_bytes, void *stream)
-{
-    VA_ENTER();
-    VA_GEO_REQUIRE_SHAPE("va_farthest_points");
-    VA_REQUIRE(mask && p1_out && p2_out && dist_out && rounds_out, "va_farthest_points: NULL argument");
-    VA_REQUIRE(!path_out || (npath_out && max_points > 0), "va_farthest_points: path without npath / max_points");
-    if (n == 0)
-        return VA_OK;
-    hipStream_t st = as_stream(stream);
-    const GeoLayout g = geo_layout(n, h, w);
-    char *base = (char *)ws;
-    unsigned long long *pairs = (unsigned long long *)(base + g.pairs);
-    uint32_t *visited = (uint32_t *)(base + g.visited);
-    const bool default_start = p1 == nullptr;
-    if (default_start) {
-        uint32_t *bits = visited, *inv = (uint32_t *)(base + g.inv);
-        int32_t *forest = (int32_t *)pairs, *bg_labels = forest + (size_t)n * h * w;
-        int32_t *counts = (int32_t *)(base + g.counts);
-        int32_t *start = (int32_t *)(base + g.p1);
-        int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
-        if (!rc)
-            rc = launch_ccl(bits, forest, counts, n, h, w, 8, base + g.rows, ccl_rows_workspace_bytes(n, h), nullptr,
-                            0, st, nullptr, /*paint=*/false);
-        if (!rc)
-            rc = launch_invert_bits(bits, inv, n, h, w, st);
-        if (!rc)
-            rc = launch_ccl(inv, bg_labels, counts + n, n, h, w, 4, base + g.rows, ccl_rows_workspace_bytes(n, h),
-                            nullptr, 0, st, nullptr, /*paint=*/true);
-        if (!rc)
-            rc = launch_longest_external_start(bits, forest, bg_labels, (uint32_t *)(base + g.edge), n, h, w,
-                                               (unsigned long long *)(base + g.keys), start, st);
-        if (rc)
-            return rc;
-        p1 = start;
-    }
-    return launch_farthest_points(mask, n, h, w, p1, p1_out, p2_out, dist_out, rounds_out, path_out, max_points,
-                                  npath_out, pairs, visited, default_start, st);
 }
 
 // ------------------------------------------------------------------------------ pipeline

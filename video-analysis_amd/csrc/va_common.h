@@ -55,6 +55,11 @@ constexpr int kWave = 64;  // CDNA wavefront width
 // largest frame the kernels take: per-frame byte offsets (4-byte labels) travel in the 32-bit
 // fields of raw buffer descriptors / uint32 arithmetic, so h*w*4 must stay below 2^31
 constexpr size_t kMaxFramePixels = (size_t)1 << 29;
+// the frame-shape guard of an entry that takes (n, h, w) frames and has nothing to check between the two
+#define VA_REQUIRE_FRAME_SHAPE(entry)                                                       \
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < va::kMaxFramePixels,             \
+               "%s: frames above 2^29 pixels are not supported", entry);                    \
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: bad shape (%d,%d,%d)", entry, n, h, w)
 // largest gridDim.y / gridDim.z the library launches: a batch or a frame that would need more goes out in pieces,
 // takes a kernel with a one-dimensional grid, or is refused before anything is enqueued
 constexpr int kMaxGridYZ = 65535;
@@ -145,9 +150,9 @@ int gauss_taps_f32(double sigma, int *ksize, float *taps, int cap);
 void gauss_taps_f64(double sigma, int n, double *out);
 
 // ---- launchers (each enqueues on `stream`, returns VA_OK or an error) -------------------
-// Only what has callers in more than one file is declared here: the launchers the pipeline and the entries of
-// va_api.hip sequence, and what one op's file borrows from another's.  The launchers, workspace layouts and limits
-// of a stand-alone op are private to the file of its kernels, which also holds its extern "C" entry points.
+// Only what has callers in more than one file is declared here: the launchers the pipeline sequences, and what
+// one op's file borrows from another's.  The launchers, workspace layouts and limits of an op are private to the
+// file of its kernels, which also holds its extern "C" entry points.
 constexpr int kMaxTaps = 255;  // by-value tap tables in the kernel arguments
 struct TapsQ8 {
     int ksize;
@@ -213,6 +218,7 @@ struct GaussPlan {
 // that family (the stand-alone test hooks; the launcher checks the shape).
 int plan_gaussian(GaussPlan *g, int dtype, int h, int w, int c, double sigma, int tap_rule, bool aligned,
                   bool valu_hook = false, GaussFamily force = GaussFamily::None);
+extern int g_gauss_u8_valu;    // what va_test_hook_gaussian_u8 set: the valu_hook of pipelines created from now on
 size_t gauss_scratch_bytes(const GaussPlan &g, size_t n);    // device scratch of n frames (0: none)
 const char *gauss_plan_name(const GaussPlan &g);             // the pipeline description's name of the family
 // Enqueues the planned kernels and marks their stage on prof (F32Fused marks its row and column passes itself).
@@ -229,28 +235,12 @@ size_t bg_scratch_bytes(int n);
 int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, int64_t n_seen,
               double rate, int n, size_t px, hipStream_t st, double *recip_scratch = nullptr,
               bool mean_in_u8_range = false);
-int launch_welford(const uint8_t *frames, double *mean, double *m2, int64_t n_seen, int n,
-                   size_t px, hipStream_t st);
-
-// running mean (m2 == nullptr) or Welford mean + M2 over frames of dtype VA_U8 / VA_I16 / VA_F32
-int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m2, int64_t n_seen, int n,
-                          size_t px, hipStream_t st);
-int launch_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thresh, int maxval,
-                        hipStream_t st);
-int launch_time_difference(const uint8_t *a, const uint8_t *b, int16_t *out, size_t count,
-                           hipStream_t st);
-int launch_mono_mean(const uint8_t *src, uint8_t *dst, size_t pixels, hipStream_t st);
 // (va_synth.hip) four samples per thread, table-driven normalisation; false: shape not supported, nothing launched
 bool launch_pointwise_u8_x4(const uint8_t *src, uint8_t *dst, size_t out_samples, int src_c, int mono, int normalize,
                             double fmin, double fmax, double alpha, double tmin, hipStream_t st);
 // (n, h, w, c) interleaved u8 <-> (n, c, h, wp) planes padded to wp columns by reflection
 int launch_channel_planes(const uint8_t *src, uint8_t *dst, int n, int h, int w, int wp, int c,
                           bool split, hipStream_t st);
-// np.rot90(frame, k) on (N,H,W) frames of opaque elem_bytes-byte pixels
-int launch_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes, int k,
-                 hipStream_t st);
-int launch_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double fmin, double fmax,
-                        double alpha, double tmin, hipStream_t st);
 
 // u8 (src > thresh) or (src != 0 when thresh < 0 ... see .hip) -> bit mask, and back
 int launch_pack_bits(const uint8_t *src, uint32_t *bits, int n, int h, int w, int thresh,
@@ -271,21 +261,6 @@ int launch_morph_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int o
                     const RowSpans &se, hipStream_t st, uint8_t *scratch = nullptr);
 int launch_morph_bits(const uint32_t *src, uint32_t *dst, int n, int h, int w, int op,
                       const RowSpans &se, hipStream_t st);
-
-// small stencils (va_stencil.hip)
-int launch_detect_peaks(const uint8_t *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
-                        hipStream_t st);
-int launch_detect_peaks_f32(const float *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
-                            hipStream_t st);
-int launch_image_statistics_f32(const float *src, double *mean_out, double *var_out, int n, int h, int w,
-                                const RowSpans &se, double prior, int exclude_center, hipStream_t st);
-int launch_thinning_step(const uint8_t *img, uint8_t *eroded, uint8_t *skel, int n, int h, int w,
-                         unsigned long long *nonzero, hipStream_t st);
-size_t image_statistics_scratch_bytes(int n, int h, int w);
-int launch_image_statistics(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
-                            int w, const RowSpans &se, double prior, int exclude_center,
-                            void *scratch, hipStream_t st);
-
 // the whole op sequence in one kernel (register-streaming for one or two small rectangles,
 // LDS-resident otherwise)
 bool morph_fused_supported(int w, const RowSpans *se, int count);
@@ -296,7 +271,6 @@ int launch_morph_fused(const uint32_t *src, uint32_t *dst, int n, int h,
 // workspace of the entry points that label a u8 mask: its packed bits, then launch_ccl's workspace
 struct CclLayout { size_t bits, rows, rows_bytes, total; };
 CclLayout ccl_layout(int n, int h, int w);
-void ccl_test_hook(int path, int lds_runs);   // see va_test_hook_labelling
 size_t ccl_rows_workspace_bytes(int n, int h);   // launch_ccl's workspace (the caller owns the bit mask)
 int launch_ccl(const uint32_t *bits, int32_t *labels, int32_t *counts, int n, int h, int w,
                int connectivity, void *workspace, size_t ws_bytes, int64_t *stats, int max_labels,
@@ -319,57 +293,13 @@ int launch_ccl_front(const uint32_t *bits, int32_t *labels, int32_t *counts, int
                      int connectivity, void *workspace, size_t ws_bytes, int64_t *stats, int max_labels,
                      hipStream_t st, StageProfiler *prof, CclPaintPlan *plan);
 int launch_ccl_paint(const CclPaintPlan &plan, hipStream_t st, StageProfiler *prof = nullptr);
-// outer contour of the component with the largest contour area (8-connectivity), on a forest
-// prepared by launch_ccl(..., paint = false): roots hold -(label) at their first pixel
-int launch_largest_contour(const uint32_t *bits, const int32_t *forest, int n, int h, int w,
-                           unsigned long long *best_keys, int32_t *points, int max_points,
-                           int32_t *npoints, double *area, hipStream_t st);
-// get_farthest_points' default start: the first point of the longest (cv2.arcLength) RETR_EXTERNAL
-// contour, per frame, (-1, -1) without one.  forest as for launch_largest_contour; bg_labels: the
-// painted 4-connected labels of the inverted mask (launch_invert_bits); edge_bits: edge_label_words
-// words per frame; keys: 2 n
+// what the geodesic default start borrows from va_contours.hip (which states the arguments)
+int launch_outline_labels(const uint32_t *bits, uint32_t *inv, int32_t *forest, int32_t *bg_labels, int32_t *counts,
+                          void *rows_ws, size_t rows_bytes, int n, int h, int w, hipStream_t st);
 int edge_label_words(int h, int w);
-int launch_invert_bits(const uint32_t *bits, uint32_t *inv, int n, int h, int w, hipStream_t st);
 int launch_longest_external_start(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
                                   uint32_t *edge_bits, int n, int h, int w, unsigned long long *keys,
                                   int32_t *p1, hipStream_t st);
-// every RETR_EXTERNAL contour of every frame as one ragged list (va_find_contours states the outputs); forest and
-// bg_labels as for launch_longest_external_start.  Scratch: edge_bits edge_label_words words per frame; cells 8
-// int32 per row; frame_first, pt_first n + 1 and frame_pts n int64; starts (8 bytes) and npts (int32) one per
-// possible contour, n * max_contours_per_frame of them
-struct FindContoursScratch {
-    uint32_t *edge_bits;
-    int32_t *cells;
-    int64_t *frame_first, *frame_pts, *pt_first;
-    void *starts;
-    int32_t *npts;
-};
-size_t max_contours_per_frame(int h, int w);   // 8-connected components of a frame: every other row and column
-int launch_find_contours(const uint32_t *bits, const int32_t *forest, const int32_t *bg_labels,
-                         const FindContoursScratch &s, int n, int h, int w, int32_t *ncontours, int64_t *totals,
-                         va_contour_info *info, int64_t *point_off, int64_t cap_contours, int32_t *points,
-                         int64_t cap_points, hipStream_t st);
-// geodesic distance maps (va_geodesic.hip): pairs = geodesic_pairs_bytes, visited = geodesic_visited_bytes
-size_t geodesic_pairs_bytes(int n, int h, int w);
-size_t geodesic_visited_bytes(int n, int h, int w);
-bool geodesic_width_ok(int w);
-int launch_distance_map(const uint8_t *fillable, int n, int h, int w, const int32_t *starts,
-                        const int32_t *nstarts, int max_starts, const int32_t *ends, const int32_t *nends,
-                        int max_ends, int32_t *out, unsigned long long *pairs, int32_t *sweeps, hipStream_t st);
-int launch_distance_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path,
-                         int max_points, int32_t *npath, uint32_t *visited, hipStream_t st);
-int launch_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1_in, int32_t *p1_out,
-                           int32_t *p2_out, int32_t *dist_out, int32_t *rounds_out, int32_t *path, int max_points,
-                           int32_t *npath, unsigned long long *pairs, uint32_t *visited, bool default_start,
-                           hipStream_t st);
-// FilterNormalize for uint8 / float32 frames, any of the three target dtypes; seeded noise frames
-int launch_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
-                     double fmax, double alpha, double tmin, hipStream_t st);
-int launch_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int src_c, int left, int top,
-                      int width, int height, int mono, int normalize, double fmin, double fmax, double alpha,
-                      double tmin, hipStream_t st);
-int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
-                          uint64_t first_index, hipStream_t st);
 // cv2.resize for float32 frames (va_resize.hip), as the optical flow's pyramid calls it; mode 0 nearest, 1 linear,
 // 2 cubic, 3 area, 4 lanczos4; scratch: resize_scratch_bytes
 size_t resize_scratch_bytes(int sh, int sw, int dh, int dw);
@@ -381,10 +311,5 @@ int launch_resize_f32(const float *src, float *dst, int n, int sh, int sw, int c
                       void *scratch, hipStream_t st, ResizeStage stage = ResizeStage::Both);
 // the largest coordinate the rasterisers of va_polygon.hip and va_compose.hip take
 constexpr int64_t kPolyMaxCoord = VA_FILL_MAX_COORD;
-int launch_stats_from_labels(const int32_t *labels, int n, int h, int w, int max_labels,
-                             int64_t *stats, hipStream_t st);
-int launch_largest_region(const int32_t *labels, const int32_t *counts, const int64_t *stats,
-                          int n, int h, int w, int max_labels, int32_t *largest,
-                          int64_t *largest_area, uint8_t *mask_out, hipStream_t st);
 
 }  // namespace va

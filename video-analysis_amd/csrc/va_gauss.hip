@@ -354,4 +354,121 @@ int launch_gaussian(const GaussPlan &g, const void *src, void *dst, uint32_t *bi
     }
 }
 
+// The stand-alone Gaussian calls: argument checks, a plan, a scratch lease and a launch.  The test hooks
+// (force != None) keep their terse messages; the dot4/dot2 hook takes one channel only.
+static int gaussian_call(const char *who, int dtype, const void *src, void *dst, int n, int h, int w, int c,
+                         double sigma, int tap_rule, GaussFamily force, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "%s: frames above 2^29 pixels are not supported", who);
+    const bool hook = force != GaussFamily::None;
+    VA_REQUIRE(src && dst && src != dst, hook ? "%s: bad pointers" : "%s: src/dst must be distinct non-NULL", who);
+    VA_REQUIRE(!hook || (n >= 0 && h > 0 && w > 0 && c > 0 && (c == 1 || force != GaussFamily::U8Dot)),
+               "%s: bad shape", who);
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "%s: bad shape (%d,%d,%d,%d)", who, n, h, w, c);
+    const bool aligned = (uintptr_t)src % 16 == 0 && (dtype == VA_F32 || (uintptr_t)dst % 4 == 0);
+    GaussPlan g;
+    int rc = plan_gaussian(&g, dtype, h, w, c, sigma, tap_rule, aligned, false, force);
+    if (rc)
+        return rc;
+    ScratchLease scratch;
+    if (!g.single_pass() && (rc = scratch.acquire(gauss_scratch_bytes(g, n), as_stream(stream))))
+        return rc;
+    return launch_gaussian(g, src, dst, nullptr, -1, 0, scratch.ptr, n, as_stream(stream), nullptr);
+}
+
+int g_gauss_u8_valu = 0;
+
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_gauss_taps_q8(double sigma, int *ksize_out, uint16_t *taps_out, int capacity)
+{
+    return va_gauss_taps_q8_rule(sigma, VA_TAPS_CV4, ksize_out, taps_out, capacity);
+}
+int va_gauss_taps_q8_rule(double sigma, int tap_rule, int *ksize_out, uint16_t *taps_out, int capacity)
+{
+    VA_REQUIRE(ksize_out && taps_out, "va_gauss_taps_q8: NULL argument");
+    TapsQ8 t;
+    int rc = gauss_taps_q8(sigma, &t.ksize, t.t, kMaxTaps, tap_rule);
+    if (rc)
+        return rc;
+    if (t.ksize > capacity) {
+        set_error("va_gauss_taps_q8: %d taps > capacity %d", t.ksize, capacity);
+        return VA_ERR_RANGE;
+    }
+    memcpy(taps_out, t.t, sizeof(uint16_t) * t.ksize);
+    *ksize_out = t.ksize;
+    return VA_OK;
+}
+int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacity)
+{
+    VA_REQUIRE(ksize_out && taps_out, "va_gauss_taps_f32: NULL argument");
+    TapsF32 t;
+    int rc = gauss_taps_f32(sigma, &t.ksize, t.t, kMaxTaps);
+    if (rc)
+        return rc;
+    if (t.ksize > capacity) {
+        set_error("va_gauss_taps_f32: %d taps > capacity %d", t.ksize, capacity);
+        return VA_ERR_RANGE;
+    }
+    memcpy(taps_out, t.t, sizeof(float) * t.ksize);
+    *ksize_out = t.ksize;
+    return VA_OK;
+}
+
+int va_gaussian_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
+                   void *stream)
+{
+    return va_gaussian_u8_rule(src, dst, n, h, w, c, sigma, VA_TAPS_CV4, stream);
+}
+
+int va_gaussian_u8_rule(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
+                        int tap_rule, void *stream)
+{
+    return gaussian_call("va_gaussian_u8", VA_U8, src, dst, n, h, w, c, sigma, tap_rule, GaussFamily::None,
+                         stream);
+}
+
+// test hook: force the generic two-pass implementation
+int va_gaussian_u8_generic(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c,
+                           double sigma, void *stream)
+{
+    return gaussian_call("va_gaussian_u8_generic", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
+                         GaussFamily::U8Generic, stream);
+}
+
+// test hook: force the LDS/VALU (dot4/dot2) fused implementation
+int va_gaussian_u8_valu(const uint8_t *src, uint8_t *dst, int n, int h, int w, int c, double sigma,
+                        void *stream)
+{
+    return gaussian_call("va_gaussian_u8_valu", VA_U8, src, dst, n, h, w, c, sigma, VA_TAPS_CV4,
+                         GaussFamily::U8Dot, stream);
+}
+
+int va_gaussian_f32(const float *src, float *dst, int n, int h, int w, int c, double sigma,
+                    void *stream)
+{
+    return gaussian_call("va_gaussian_f32", VA_F32, src, dst, n, h, w, c, sigma, VA_TAPS_CV4, GaussFamily::None,
+                         stream);
+}
+
+// test / measurement hook: pipelines created while this is set run their 8-bit Gaussian on the VALU
+// (dot4/dot2 LDS kernel) instead of the matrix cores -- the north star's "no MFMA" form of the chain
+int va_test_hook_gaussian_u8(int force_valu)
+{
+    g_gauss_u8_valu = force_valu != 0;
+    return VA_OK;
+}
+
+int va_test_hook_gaussian_f32(int generic_columns)
+{
+    gauss_f32_test_hook(generic_columns);
+    return VA_OK;
+}
+
+}  // extern "C"

@@ -594,10 +594,29 @@ int cols_per_thread(int w)
 
 }  // namespace
 
-size_t geodesic_pairs_bytes(int n, int h, int w) { return (size_t)n * h * w * sizeof(unsigned long long); }
-size_t geodesic_visited_bytes(int n, int h, int w) { return (size_t)n * h * row_words(w) * sizeof(uint32_t); }
-
-bool geodesic_width_ok(int w) { return cols_per_thread(w) <= kMaxK; }
+// The workspace: [pairs | visited | inverted bits | labelling rows | edge bits | keys | counts | p1]; while the
+// default start is chosen the pairs hold the 8-connected forest and the background labels, the visited
+// bitmap the bit mask (the distance maps come after, in stream order)
+struct GeoLayout {
+    size_t pairs, visited, inv, rows, rows_bytes, edge, keys, counts, p1, total;
+};
+static GeoLayout geo_layout(int n, int h, int w)
+{
+    GeoLayout g;
+    Carve c;
+    const size_t visited_bytes = (size_t)n * h * row_words(w) * sizeof(uint32_t);
+    g.pairs = c.take((size_t)n * h * w * sizeof(unsigned long long));
+    g.visited = c.take(visited_bytes);
+    g.inv = c.take(visited_bytes);
+    g.rows_bytes = ccl_rows_workspace_bytes(n, h);
+    g.rows = c.take(g.rows_bytes);
+    g.edge = c.take((size_t)n * edge_label_words(h, w) * sizeof(uint32_t));
+    g.keys = c.take((size_t)2 * n * sizeof(unsigned long long));
+    g.counts = c.take((size_t)2 * n * sizeof(int32_t));
+    g.p1 = c.take((size_t)2 * n * sizeof(int32_t));
+    g.total = c.total;
+    return g;
+}
 
 #define VA_GEO_DISPATCH(KERNEL, ...)                                                  \
     switch (cols_per_thread(w)) {                                                     \
@@ -611,38 +630,91 @@ bool geodesic_width_ok(int w) { return cols_per_thread(w) <= kMaxK; }
         return VA_ERR_INVALID;                                                        \
     }
 
-int launch_distance_map(const uint8_t *fillable, int n, int h, int w, const int32_t *starts,
-                        const int32_t *nstarts, int max_starts, const int32_t *ends, const int32_t *nends,
-                        int max_ends, int32_t *out, unsigned long long *pairs, int32_t *sweeps, hipStream_t st)
+#define VA_GEO_REQUIRE_SHAPE(name)                                                                        \
+    VA_REQUIRE_FRAME_SHAPE(name);                                                                         \
+    VA_REQUIRE(cols_per_thread(w) <= kMaxK, name ": frames wider than 8192 columns are not supported");   \
+    VA_REQUIRE(ws && ws_bytes >= va_geodesic_workspace_bytes(n, h, w),                                    \
+               name ": workspace of %zu bytes < required %zu", ws_bytes, va_geodesic_workspace_bytes(n, h, w))
+
+}  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+size_t va_geodesic_workspace_bytes(int n, int h, int w)
 {
+    if (n <= 0 || h <= 0 || w <= 0)
+        return 256;
+    return geo_layout(n, h, w).total;
+}
+
+int va_distance_map_i32(const uint8_t *fillable, int n, int h, int w, const int32_t *starts, const int32_t *nstarts,
+                        int max_starts, const int32_t *ends, const int32_t *nends, int max_ends, int32_t *map_out,
+                        void *ws, size_t ws_bytes, void *stream)
+{
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_distance_map_i32");
+    VA_REQUIRE(fillable && map_out && starts && nstarts && max_starts > 0, "va_distance_map_i32: NULL argument");
+    VA_REQUIRE(!ends || (nends && max_ends > 0), "va_distance_map_i32: end points without counts");
     if (n == 0)
         return VA_OK;
-    VA_GEO_DISPATCH(distance_map_kernel, fillable, h, w, starts, nstarts, max_starts, ends, nends, max_ends, out,
-                    pairs, sweeps);
+    hipStream_t st = as_stream(stream);
+    VA_GEO_DISPATCH(distance_map_kernel, fillable, h, w, starts, nstarts, max_starts, ends, nends, ends ? max_ends : 0,
+                    map_out, at<unsigned long long>(ws, geo_layout(n, h, w).pairs), nullptr);
     VA_LAUNCH_CHECK("distance_map_kernel");
     return VA_OK;
 }
 
-int launch_distance_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path,
-                         int max_points, int32_t *npath, uint32_t *visited, hipStream_t st)
+int va_distance_map_path(const int32_t *map, int n, int h, int w, const int32_t *end_points, int32_t *path_out,
+                         int max_points, int32_t *npath_out, void *ws, size_t ws_bytes, void *stream)
 {
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_distance_map_path");
+    VA_REQUIRE(map && end_points && path_out && npath_out && max_points > 0, "va_distance_map_path: NULL argument");
     if (n == 0)
         return VA_OK;
-    distance_path_kernel<<<n, kGeoThreads, 0, st>>>(map, h, w, end_points, path, max_points, npath, visited);
+    distance_path_kernel<<<n, kGeoThreads, 0, as_stream(stream)>>>(map, h, w, end_points, path_out, max_points,
+                                                                  npath_out,
+                                                                  at<uint32_t>(ws, geo_layout(n, h, w).visited));
     VA_LAUNCH_CHECK("distance_path_kernel");
     return VA_OK;
 }
 
-int launch_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1_in, int32_t *p1_out,
-                           int32_t *p2_out, int32_t *dist_out, int32_t *rounds_out, int32_t *path, int max_points, int32_t *npath,
-                           unsigned long long *pairs, uint32_t *visited, bool default_start, hipStream_t st)
+int va_farthest_points(const uint8_t *mask, int n, int h, int w, const int32_t *p1, int32_t *p1_out, int32_t *p2_out,
+                       int32_t *dist_out, int32_t *rounds_out, int32_t *path_out, int max_points, int32_t *npath_out,
+                       void *ws, size_t ws_bytes, void *stream)
 {
+    VA_ENTER();
+    VA_GEO_REQUIRE_SHAPE("va_farthest_points");
+    VA_REQUIRE(mask && p1_out && p2_out && dist_out && rounds_out, "va_farthest_points: NULL argument");
+    VA_REQUIRE(!path_out || (npath_out && max_points > 0), "va_farthest_points: path without npath / max_points");
     if (n == 0)
         return VA_OK;
-    VA_GEO_DISPATCH(farthest_points_kernel, mask, h, w, p1_in, p1_out, p2_out, dist_out, rounds_out, path, max_points, npath,
-                    pairs, visited, default_start ? 1 : 0);
+    hipStream_t st = as_stream(stream);
+    const GeoLayout g = geo_layout(n, h, w);
+    unsigned long long *pairs = at<unsigned long long>(ws, g.pairs);
+    uint32_t *visited = at<uint32_t>(ws, g.visited);
+    const bool default_start = p1 == nullptr;
+    if (default_start) {
+        uint32_t *bits = visited;
+        int32_t *forest = (int32_t *)pairs, *bg_labels = forest + (size_t)n * h * w;
+        int32_t *start = at<int32_t>(ws, g.p1);
+        int rc = launch_pack_bits(mask, bits, n, h, w, 0, st);
+        if (!rc)
+            rc = launch_outline_labels(bits, at<uint32_t>(ws, g.inv), forest, bg_labels, at<int32_t>(ws, g.counts),
+                                       at(ws, g.rows), g.rows_bytes, n, h, w, st);
+        if (!rc)
+            rc = launch_longest_external_start(bits, forest, bg_labels, at<uint32_t>(ws, g.edge), n, h, w,
+                                               at<unsigned long long>(ws, g.keys), start, st);
+        if (rc)
+            return rc;
+        p1 = start;
+    }
+    VA_GEO_DISPATCH(farthest_points_kernel, mask, h, w, p1, p1_out, p2_out, dist_out, rounds_out, path_out, max_points,
+                    npath_out, pairs, visited, default_start ? 1 : 0);
     VA_LAUNCH_CHECK("farthest_points_kernel");
     return VA_OK;
 }
 
-}  // namespace va
+}  // extern "C"

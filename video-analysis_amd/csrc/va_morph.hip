@@ -826,3 +826,61 @@ int launch_morph_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int o
 }
 
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_morph_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int op, int shape,
+                int ksize, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_morph_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && dst && src != dst, "va_morph_u8: src/dst must be distinct non-NULL");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_morph_u8: bad shape (%d,%d,%d)", n, h, w);
+    VA_REQUIRE(op == VA_MORPH_ERODE || op == VA_MORPH_DILATE, "va_morph_u8: bad op %d", op);
+    RowSpans se;
+    int rc = make_row_spans(shape, ksize, &se);
+    if (rc)
+        return rc;
+    ScratchLease scratch;
+    if (shape == VA_SHAPE_RECT && ksize >= 3 && n > 0) {
+        rc = scratch.acquire((size_t)n * h * w, as_stream(stream));
+        if (rc)
+            return rc;
+    }
+    return launch_morph_u8(src, dst, n, h, w, op, se, as_stream(stream), (uint8_t *)scratch.ptr);
+}
+
+// test hook: morphology on the bit-packed representation used inside the pipeline
+// (mask: any non-zero byte is foreground; dst gets 0 / 255)
+int va_morph_bits_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int op, int shape,
+                     int ksize, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_morph_bits_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && dst, "va_morph_bits_u8: NULL argument");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_morph_bits_u8: bad shape");
+    RowSpans se;
+    int rc = make_row_spans(shape, ksize, &se);
+    if (rc)
+        return rc;
+    Carve c;                                 // [b0 | b1]
+    const size_t words = (size_t)n * h * words_per_row(w) * sizeof(uint32_t);
+    const size_t o0 = c.take(words), o1 = c.take(words);
+    hipStream_t st = as_stream(stream);
+    ScratchLease scratch;
+    rc = scratch.acquire(c.total, st);
+    if (rc)
+        return rc;
+    uint32_t *b0 = at<uint32_t>(scratch.ptr, o0), *b1 = at<uint32_t>(scratch.ptr, o1);
+    if ((rc = launch_pack_bits(src, b0, n, h, w, 0, st)))
+        return rc;
+    if ((rc = launch_morph_bits(b0, b1, n, h, w, op, se, st)))
+        return rc;
+    return launch_unpack_bits(b1, dst, n, h, w, 255, st);
+}
+
+}  // extern "C"

@@ -706,8 +706,8 @@ int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, 
     return VA_OK;
 }
 
-int launch_welford(const uint8_t *frames, double *mean, double *m2, int64_t n_seen, int n,
-                   size_t px, hipStream_t st)
+static int launch_welford(const uint8_t *frames, double *mean, double *m2, int64_t n_seen, int n,
+                          size_t px, hipStream_t st)
 {
     VA_REQUIRE(frames && mean && m2, "va_welford_u8: NULL argument");
     if (n <= 0)
@@ -722,8 +722,8 @@ int launch_welford(const uint8_t *frames, double *mean, double *m2, int64_t n_se
     return VA_OK;
 }
 
-int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m2, int64_t n_seen, int n,
-                          size_t px, hipStream_t st)
+static int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m2, int64_t n_seen, int n,
+                                 size_t px, hipStream_t st)
 {
     VA_REQUIRE(frames && mean, "temporal statistics: NULL argument");
     VA_REQUIRE(dtype == VA_U8 || dtype == VA_I16 || dtype == VA_F32 || dtype == VA_F64,
@@ -751,8 +751,8 @@ int launch_temporal_stats(const void *frames, int dtype, double *mean, double *m
     return VA_OK;
 }
 
-int launch_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thresh, int maxval,
-                        hipStream_t st)
+static int launch_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thresh, int maxval,
+                               hipStream_t st)
 {
     VA_REQUIRE(src && dst, "va_threshold_u8: NULL argument");
     if (count == 0)
@@ -764,8 +764,8 @@ int launch_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thre
     return VA_OK;
 }
 
-int launch_time_difference(const uint8_t *a, const uint8_t *b, int16_t *out, size_t count,
-                           hipStream_t st)
+static int launch_time_difference(const uint8_t *a, const uint8_t *b, int16_t *out, size_t count,
+                                  hipStream_t st)
 {
     VA_REQUIRE(a && b && out, "va_time_difference_u8: NULL argument");
     if (count == 0)
@@ -777,7 +777,7 @@ int launch_time_difference(const uint8_t *a, const uint8_t *b, int16_t *out, siz
     return VA_OK;
 }
 
-int launch_mono_mean(const uint8_t *src, uint8_t *dst, size_t pixels, hipStream_t st)
+static int launch_mono_mean(const uint8_t *src, uint8_t *dst, size_t pixels, hipStream_t st)
 {
     VA_REQUIRE(src && dst, "va_mono_mean_u8: NULL argument");
     if (pixels == 0)
@@ -967,8 +967,8 @@ struct Elem3 { uint8_t b[3]; };
 struct Elem6 { uint16_t b[3]; };
 struct Elem12 { uint32_t b[3]; };
 
-int launch_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes, int k,
-                 hipStream_t st)
+static int launch_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes, int k,
+                        hipStream_t st)
 {
     VA_REQUIRE(src && dst && src != dst, "va_rot90: src/dst must be distinct non-NULL");
     VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_rot90: bad shape (%d,%d,%d)", n, h, w);
@@ -995,8 +995,8 @@ int launch_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes
     return VA_OK;
 }
 
-int launch_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double fmin, double fmax,
-                        double alpha, double tmin, hipStream_t st)
+static int launch_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double fmin, double fmax,
+                               double alpha, double tmin, hipStream_t st)
 {
     VA_REQUIRE(src && dst, "va_normalize_u8: NULL argument");
     if (count == 0)
@@ -1013,3 +1013,74 @@ int launch_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double f
 }
 
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_bg_update(int mode, int dtype, const void *frames, void *diff_out, void *state,
+                 int64_t n_seen, double rate, int n, size_t px, void *stream)
+{
+    VA_ENTER();
+    double *recip = nullptr;
+    ScratchLease scratch;
+    if (mode == VA_BG_MEAN && dtype == VA_U8 && n > 0) {
+        int rc = scratch.acquire(bg_scratch_bytes(n), as_stream(stream));
+        if (rc)
+            return rc;
+        recip = (double *)scratch.ptr;
+    }
+    return launch_bg(mode, dtype, frames, diff_out, state, n_seen, rate, n, px, as_stream(stream),
+                     recip);
+}
+int va_welford_u8(const uint8_t *frames, double *mean, double *m2, int64_t n_seen, int n,
+                  size_t px, void *stream)
+{
+    VA_ENTER();
+    return launch_welford(frames, mean, m2, n_seen, n, px, as_stream(stream));
+}
+
+int va_mean_any(const void *frames, int dtype, double *mean, int64_t n_seen, int n, size_t px, void *stream)
+{
+    VA_ENTER();
+    return launch_temporal_stats(frames, dtype, mean, nullptr, n_seen, n, px, as_stream(stream));
+}
+int va_welford_any(const void *frames, int dtype, double *mean, double *m2, int64_t n_seen, int n, size_t px,
+                   void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(m2, "va_welford_any: NULL argument");
+    return launch_temporal_stats(frames, dtype, mean, m2, n_seen, n, px, as_stream(stream));
+}
+
+int va_time_difference_u8(const uint8_t *a, const uint8_t *b, int16_t *out, size_t count,
+                          void *stream)
+{
+    VA_ENTER();
+    return launch_time_difference(a, b, out, count, as_stream(stream));
+}
+int va_threshold_u8(const uint8_t *src, uint8_t *dst, size_t count, int thresh, int maxval,
+                    void *stream)
+{
+    VA_ENTER();
+    return launch_threshold_u8(src, dst, count, thresh, maxval, as_stream(stream));
+}
+int va_mono_mean_u8(const uint8_t *src, uint8_t *dst, size_t pixels, void *stream)
+{
+    VA_ENTER();
+    return launch_mono_mean(src, dst, pixels, as_stream(stream));
+}
+int va_normalize_u8(const uint8_t *src, uint8_t *dst, size_t count, double fmin, double fmax,
+                    double alpha, double tmin, void *stream)
+{
+    VA_ENTER();
+    return launch_normalize_u8(src, dst, count, fmin, fmax, alpha, tmin, as_stream(stream));
+}
+
+int va_rot90(const void *src, void *dst, int n, int h, int w, int elem_bytes, int k, void *stream)
+{
+    VA_ENTER();
+    return launch_rot90(src, dst, n, h, w, elem_bytes, k, as_stream(stream));
+}
+
+}  // extern "C"

@@ -407,8 +407,8 @@ image_statistics_box_kernel(const uint8_t *__restrict__ src, double *__restrict_
 
 }  // namespace
 
-int launch_detect_peaks(const uint8_t *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
-                        hipStream_t st)
+static int launch_detect_peaks(const uint8_t *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
+                               hipStream_t st)
 {
     size_t total = (size_t)n * h * w;
     if (total == 0)
@@ -425,8 +425,8 @@ int launch_detect_peaks(const uint8_t *src, uint8_t *dst, int n, int h, int w, i
     return VA_OK;
 }
 
-int launch_detect_peaks_f32(const float *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
-                            hipStream_t st)
+static int launch_detect_peaks_f32(const float *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
+                                   hipStream_t st)
 {
     size_t total = (size_t)n * h * w;
     if (total == 0)
@@ -446,8 +446,8 @@ static double element_count(const RowSpans &se, int exclude_center)
 }
 
 // float32 images: truncated to integers like the reference, then direct window sums in float64
-int launch_image_statistics_f32(const float *src, double *mean_out, double *var_out, int n, int h, int w,
-                                const RowSpans &se, double prior, int exclude_center, hipStream_t st)
+static int launch_image_statistics_f32(const float *src, double *mean_out, double *var_out, int n, int h, int w,
+                                       const RowSpans &se, double prior, int exclude_center, hipStream_t st)
 {
     size_t total = (size_t)n * h * w;
     if (total == 0)
@@ -458,13 +458,12 @@ int launch_image_statistics_f32(const float *src, double *mean_out, double *var_
     return VA_OK;
 }
 
-int launch_thinning_step(const uint8_t *img, uint8_t *eroded, uint8_t *skel, int n, int h, int w,
-                         unsigned long long *nonzero, hipStream_t st)
+static int launch_thinning_step(const uint8_t *img, uint8_t *eroded, uint8_t *skel, int n, int h, int w,
+                                unsigned long long *nonzero, hipStream_t st)
 {
     size_t total = (size_t)n * h * w;
     if (total == 0)
         return VA_OK;
-    // `nonzero` is this iteration's own counter; the caller zeroes the counter array once
     // `nonzero` is this iteration's own counter; the caller zeroes the counter array once
     if (w % 4 == 0 && h <= 65535 && n <= 65535 && reinterpret_cast<uintptr_t>(img) % 4 == 0 &&
         reinterpret_cast<uintptr_t>(eroded) % 4 == 0 && reinterpret_cast<uintptr_t>(skel) % 4 == 0) {
@@ -487,16 +486,16 @@ int launch_thinning_step(const uint8_t *img, uint8_t *eroded, uint8_t *skel, int
     return VA_OK;
 }
 
-size_t image_statistics_scratch_bytes(int n, int h, int w)
+static size_t image_statistics_scratch_bytes(int n, int h, int w)
 {
     if (w > 65536)
         return 256;                                     // (generic kernel: no scratch)
     return 2 * (size_t)n * h * ((size_t)w + 1) * sizeof(uint32_t) + 256;
 }
 
-int launch_image_statistics(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
-                            int w, const RowSpans &se, double prior, int exclude_center,
-                            void *scratch, hipStream_t st)
+static int launch_image_statistics(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
+                                   int w, const RowSpans &se, double prior, int exclude_center,
+                                   void *scratch, hipStream_t st)
 {
     size_t total = (size_t)n * h * w;
     if (total == 0)
@@ -534,3 +533,120 @@ int launch_image_statistics(const uint8_t *src, double *mean_out, double *var_ou
 }
 
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_detect_peaks_u8(const uint8_t *src, uint8_t *dst, int n, int h, int w, int include_plateaus,
+                       void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_detect_peaks_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && dst && src != dst, "va_detect_peaks_u8: bad pointers");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_detect_peaks_u8: bad shape");
+    return launch_detect_peaks(src, dst, n, h, w, include_plateaus, as_stream(stream));
+}
+
+int va_detect_peaks_f32(const float *src, uint8_t *dst, int n, int h, int w, int include_plateaus, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_detect_peaks_f32: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && dst && (const void *)src != (const void *)dst, "va_detect_peaks_f32: bad pointers");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0, "va_detect_peaks_f32: bad shape");
+    return launch_detect_peaks_f32(src, dst, n, h, w, include_plateaus, as_stream(stream));
+}
+
+int va_image_statistics_f32(const float *src, double *mean_out, double *var_out, int n, int h, int w, int kernel,
+                            int ksize, double prior, int exclude_center, void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_image_statistics_f32: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && mean_out, "va_image_statistics_f32: NULL argument");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ksize >= 0, "va_image_statistics_f32: bad shape");
+    VA_REQUIRE(kernel == 0 || kernel == 1, "va_image_statistics_f32: kernel must be 0 (box) or 1 (ellipse)");
+    RowSpans se;
+    int rc = make_row_spans(kernel == 0 ? VA_SHAPE_RECT : VA_SHAPE_ELLIPSE, 2 * ksize + 1, &se);
+    if (rc)
+        return rc;
+    return launch_image_statistics_f32(src, mean_out, var_out, n, h, w, se, prior, exclude_center,
+                                       as_stream(stream));
+}
+
+int va_image_statistics_u8(const uint8_t *src, double *mean_out, double *var_out, int n, int h,
+                           int w, int kernel, int ksize, double prior, int exclude_center,
+                           void *stream)
+{
+    VA_ENTER();
+    VA_REQUIRE(h <= 0 || w <= 0 || (size_t)h * (size_t)w < kMaxFramePixels,
+               "va_image_statistics_u8: frames above 2^29 pixels are not supported");
+    VA_REQUIRE(src && mean_out, "va_image_statistics_u8: NULL argument");
+    VA_REQUIRE(n >= 0 && h > 0 && w > 0 && ksize >= 0, "va_image_statistics_u8: bad shape");
+    VA_REQUIRE(kernel == 0 || kernel == 1, "va_image_statistics_u8: kernel must be 0 (box) or 1 (ellipse)");
+    RowSpans se;
+    int rc = make_row_spans(kernel == 0 ? VA_SHAPE_RECT : VA_SHAPE_ELLIPSE, 2 * ksize + 1, &se);
+    if (rc)
+        return rc;
+    ScratchLease scratch;
+    rc = scratch.acquire(image_statistics_scratch_bytes(n, h, w), as_stream(stream));
+    if (rc)
+        return rc;
+    return launch_image_statistics(src, mean_out, var_out, n, h, w, se, prior, exclude_center,
+                                   scratch.ptr, as_stream(stream));
+}
+
+int va_mask_thinning_u8(uint8_t *img, uint8_t *scratch, uint8_t *skel, int h, int w,
+                        int *iterations_out, void *stream)
+{
+    VA_REQUIRE(img && scratch && skel, "va_mask_thinning_u8: NULL argument");
+    VA_REQUIRE(h > 0 && w > 0, "va_mask_thinning_u8: bad shape");
+    VA_ENTER();
+    hipStream_t st = as_stream(stream);
+    // a 3x3-cross erosion empties any mask within min(h,w)/2 + 1 steps, except one that fills the
+    // frame (the border never wins): the reference would loop forever there, we stop
+    const int max_it = (h < w ? h : w) / 2 + 2;
+    // One flag per iteration (set when a pixel survived the erosion); the exit condition is read back once per
+    // kCheck iterations (steps enqueued past the emptying one see an empty image and change
+    // nothing: eroded = temp = 0, skeleton |= 0), so the host waits ceil(iterations / kCheck)
+    // times instead of once per step.
+    const int kCheck = 16;
+    const int total_it = max_it + 1;
+    ScratchLease cnt;
+    int rc = cnt.acquire(sizeof(unsigned long long) * (size_t)total_it, st);
+    if (rc)
+        return rc;
+    unsigned long long *cnt_dev = (unsigned long long *)cnt.ptr;
+    VA_HIP(hipMemsetAsync(cnt_dev, 0, sizeof(unsigned long long) * (size_t)total_it, st));
+    VA_HIP(hipMemsetAsync(skel, 0, (size_t)h * w, st));
+    uint8_t *cur = img, *nxt = scratch;
+    unsigned long long host_cnt[kCheck];
+    int done_it = -1;
+    for (int it0 = 0; it0 < total_it && done_it < 0; it0 += kCheck) {
+        const int k = (total_it - it0 < kCheck) ? total_it - it0 : kCheck;
+        for (int j = 0; j < k; j++) {
+            rc = launch_thinning_step(cur, nxt, skel, 1, h, w, cnt_dev + it0 + j, st);
+            if (rc)
+                return rc;
+            uint8_t *t = cur;
+            cur = nxt;
+            nxt = t;
+        }
+        VA_HIP(hipStreamSynchronize(st));
+        VA_HIP(hipMemcpy(host_cnt, cnt_dev + it0, sizeof(unsigned long long) * (size_t)k, hipMemcpyDeviceToHost));
+        for (int j = 0; j < k; j++)
+            if (host_cnt[j] == 0) {
+                done_it = it0 + j;
+                break;
+            }
+    }
+    if (done_it < 0)
+        done_it = max_it;
+    if (iterations_out)
+        *iterations_out = done_it + 1;
+    return VA_OK;
+}
+
+}  // extern "C"

@@ -208,8 +208,8 @@ gaussian_noise_kernel(DST *__restrict__ dst, size_t count, double mean, double s
 
 }  // namespace
 
-int launch_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
-                     double fmax, double alpha, double tmin, hipStream_t st)
+static int launch_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
+                            double fmax, double alpha, double tmin, hipStream_t st)
 {
     VA_REQUIRE(src && dst, "va_normalize: NULL argument");
     VA_REQUIRE(src_dtype == VA_U8 || src_dtype == VA_F32, "va_normalize: source dtype must be VA_U8 or VA_F32");
@@ -233,9 +233,9 @@ int launch_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, s
     return VA_OK;
 }
 
-int launch_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int src_c, int left, int top,
-                      int width, int height, int mono, int normalize, double fmin, double fmax, double alpha,
-                      double tmin, hipStream_t st)
+static int launch_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int src_c, int left, int top,
+                             int width, int height, int mono, int normalize, double fmin, double fmax, double alpha,
+                             double tmin, hipStream_t st)
 {
     VA_REQUIRE(src && dst && src != dst, "va_prepare_u8: src/dst must be distinct non-NULL");
     VA_REQUIRE(n >= 0 && src_h > 0 && src_w > 0 && src_c >= 1 && src_c <= 4, "va_prepare_u8: bad source shape");
@@ -277,8 +277,8 @@ bool launch_pointwise_u8_x4(const uint8_t *src, uint8_t *dst, size_t out_samples
     return true;
 }
 
-int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
-                          uint64_t first_index, hipStream_t st)
+static int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
+                                 uint64_t first_index, hipStream_t st)
 {
     VA_REQUIRE(dst, "va_gaussian_noise: NULL argument");
     VA_REQUIRE(dtype == VA_U8 || dtype == VA_F32 || dtype == VA_F64, "va_gaussian_noise: bad dtype %d", dtype);
@@ -297,3 +297,32 @@ int launch_gaussian_noise(void *dst, int dtype, size_t count, double mean, doubl
 }
 
 }  // namespace va
+
+using namespace va;
+
+extern "C" {
+
+int va_normalize(const void *src, int src_dtype, void *dst, int dst_dtype, size_t count, double fmin,
+                 double fmax, double alpha, double tmin, void *stream)
+{
+    VA_ENTER();
+    return launch_normalize(src, src_dtype, dst, dst_dtype, count, fmin, fmax, alpha, tmin, as_stream(stream));
+}
+
+int va_prepare_u8(const uint8_t *src, uint8_t *dst, int n, int src_h, int src_w, int src_c, int left, int top,
+                  int width, int height, int mono, int normalize, double fmin, double fmax, double alpha,
+                  double tmin, void *stream)
+{
+    VA_ENTER();
+    return launch_prepare_u8(src, dst, n, src_h, src_w, src_c, left, top, width, height, mono, normalize, fmin,
+                             fmax, alpha, tmin, as_stream(stream));
+}
+
+int va_gaussian_noise(void *dst, int dtype, size_t count, double mean, double stdev, uint64_t seed,
+                      uint64_t first_index, void *stream)
+{
+    VA_ENTER();
+    return launch_gaussian_noise(dst, dtype, count, mean, stdev, seed, first_index, as_stream(stream));
+}
+
+}  // extern "C"
