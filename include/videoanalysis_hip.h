@@ -164,6 +164,20 @@ int va_welford_any(const void *frames_dev, int dtype, double *mean_dev, double *
 int va_welford_u8(const uint8_t *frames_dev, double *mean_dev, double *m2_dev, int64_t n_seen,
                   int n, size_t px, void *stream);
 
+/* ------------------------------------------------------------------ A2b temporal median and rank planes
+ * replaces  np.median(stack, axis=0) / np.percentile(stack, q, axis=0) on a downloaded uint8 stack; the reference
+ *           has no counterpart (its only static background image is measure_mean, video/analysis/video.py:26-35).
+ * frames_dev: t planes of px bytes, plane i at frames_dev + i * frame_stride (1 <= t <= 255, px >= 1,
+ * frame_stride >= px: a stride of several frames samples a longer stack without a gather).  ranks_host: nranks
+ * integers in HOST memory, 1 <= nranks <= 8, each 0 .. t - 1, in any order, repeats allowed.
+ *   out_dev[j * px + p] = sort(frames[:, p])[ranks_host[j]]        (nranks, px) uint8, exact
+ * Exactly nranks * px bytes are written, every one of them; nothing beyond byte px - 1 of a plane is read; two calls
+ * write identical bytes.  t <= 64: the stack is read once, whatever nranks.  t >= 65: eight passes over it.  Dword
+ * loads and stores where frames_dev, out_dev, frame_stride and px are all multiples of 4, byte accesses otherwise.
+ * Anything outside the ranges above is VA_ERR_INVALID, and nothing is written. */
+int va_temporal_ranks_u8(const uint8_t *frames_dev, int t, size_t px, size_t frame_stride,
+                         const int32_t *ranks_host, int nranks, uint8_t *out_dev, void *stream);
+
 /* ------------------------------------------------------------------ A3 / A4 / A5 pointwise
  * Shape: the calls that take `count` or `pixels` see one flat array of any length >= 0; va_prepare_u8,
  * va_rot90: any n >= 0 and frames of any h, w >= 1 (a crop must lie inside its source frame).

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import ops
 from .analysis.regions import rect_to_slices
+from .analysis.video import measure_median
 from .engine import FrameEngine
 from .io.base import VideoBase, VideoFilterBase
 
@@ -807,6 +808,17 @@ class FilterBackground(_GpuStage, _SequentialStateFilter):
             self._reset_state()
             self._state_pos = 0
         return self._model.state
+
+
+class FilterMedianBackground(FilterBackground):
+    """FilterBackground(source, mode='static') against the temporal median of `source`: at construction up to `frames`
+    (<= 255) frames spread evenly over the video are read and their per-pixel median taken on the GPU
+    (analysis.video.measure_median).  From then on it is the static stage: the same contraction into one engine, the
+    same `background` property (the float64 median plane)."""
+
+    def __init__(self, source, frames=101):
+        super(FilterMedianBackground, self).__init__(source, mode="static",
+                                                     background=measure_median(source, max_frames=frames))
 
 
 class FilterAnalysisChain(_SequentialStateFilter):

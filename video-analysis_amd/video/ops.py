@@ -387,6 +387,110 @@ def running_mean(frames, mean=None, n_seen=0):
         return dm.download(fshape, np.float64)
 
 
+# ------------------------------------------------------------------------ temporal median and rank planes
+TEMPORAL_MAX_PLANES = 255        # kMaxPlanes and kMaxRanks of va_median_math.h: the planes and ranks of one call
+TEMPORAL_MAX_RANKS = 8
+PERCENTILE_METHODS = ("lower", "higher", "nearest")
+
+
+def _temporal_planes(frames, step, what):
+    """(DeviceFrames or contiguous uint8 array, planes in use, frame shape) of a stack read every `step` frames;
+    every check of the stack is here, and none of them needs a device"""
+    src, n, h, w, c, _ = _frames_in(frames, what)
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 1:
+        raise ValueError("%s: step is an integer >= 1, got %r" % (what, step))
+    t = (n + int(step) - 1) // int(step)
+    if t < 1 or h * w * c == 0:
+        raise ValueError("%s: the stack %r holds no pixels" % (what, (n, h, w, c)))
+    if t > TEMPORAL_MAX_PLANES:
+        raise ValueError("%s: at most %d planes a call, got %d (every %d of %d frames)"
+                         % (what, TEMPORAL_MAX_PLANES, t, step, n))
+    return src, t, (h, w) + ((3,) if c == 3 else ())
+
+
+def _check_ranks(ranks, t, what):
+    ranks = [ranks] if isinstance(ranks, (int, np.integer)) else list(ranks)
+    if not 1 <= len(ranks) <= TEMPORAL_MAX_RANKS:
+        raise ValueError("%s: 1 .. %d ranks a call, got %d" % (what, TEMPORAL_MAX_RANKS, len(ranks)))
+    for r in ranks:
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < t:
+            raise ValueError("%s: ranks of %d planes are integers 0 .. %d, got %r" % (what, t, t - 1, r))
+    return np.array(ranks, np.int32)
+
+
+def temporal_ranks(frames, ranks, step=1, stream=None):
+    """out[j] = np.sort(frames[::step], axis=0)[ranks[j]]: the rank planes of a uint8 stack over time (DESIGN.md §9,
+    "Temporal median"; va_temporal_ranks_u8), exact.  frames: a uint8 array (t, h, w) or (t, h, w, 3), or a
+    DeviceFrames, which is not changed; step > 1 reads the planes 0, step, 2 step, ... where they lie (a frame stride,
+    no gather).  At most 255 planes in use and 8 ranks, each 0 .. planes - 1, in any order, repeats allowed.
+    Returns (len(ranks), h, w[, 3]) uint8."""
+    src, t, fshape = _temporal_planes(frames, step, "temporal_ranks")
+    rk = _check_ranks(ranks, t, "temporal_ranks")
+    px = math.prod(fshape)
+    L = _hip.lib()
+    with _Lease.on(stream) as d:
+        ptr = src.buf.ptr if isinstance(src, DeviceFrames) else d.upload(src).ptr
+        out = d.take(len(rk) * px)
+        check(L.va_temporal_ranks_u8(ptr, t, px, int(step) * px, rk.ctypes.data, len(rk), out.ptr, stream))
+        return out.download((len(rk),) + fshape, np.uint8, stream)
+
+
+def median_ranks(t):
+    """the two ranks whose mean is the median of t values (equal for odd t)"""
+    return (t - 1) // 2, t // 2
+
+
+def median_of_ranks(lower, upper):
+    """np.median from the planes of median_ranks: float64, bit for bit"""
+    return (lower.astype(np.float64) + upper) / 2
+
+
+def temporal_median(frames, step=1):
+    """np.median(frames[::step], axis=0) of a uint8 stack (or DeviceFrames), float64, bit for bit"""
+    src, t, _ = _temporal_planes(frames, step, "temporal_median")
+    lo, hi = median_ranks(t)
+    planes = temporal_ranks(src, [lo] if lo == hi else [lo, hi], step)
+    return median_of_ranks(planes[0], planes[-1])
+
+
+def percentile_rank(t, q, method="lower"):
+    """the index into t sorted values that np.percentile(..., q, method=method) takes, for the methods that take one
+    value.  The ends are integers.  In between NumPy computes (t - 1) * (q / 100) in float64 and rounds that; the
+    exact quotient (t - 1) * q // 100 differs from it for some (t, q) -- t = 26, q = 28, 'higher' gives 8, not 7 --
+    so NumPy's own expression is used."""
+    if method not in PERCENTILE_METHODS:
+        raise ValueError("percentile method is one of %r (the interpolating ones are not built), got %r"
+                         % (PERCENTILE_METHODS, method))
+    if not 0 <= q <= 100:                                   # (a NaN fails this too)
+        raise ValueError("percentiles lie in 0 .. 100, got %r" % (q,))
+    if q == 0 or q == 100:
+        return 0 if q == 0 else t - 1
+    virtual = (t - 1) * np.true_divide(q, 100)
+    return int({"lower": np.floor, "higher": np.ceil, "nearest": np.around}[method](virtual))
+
+
+def temporal_percentiles(frames, q, method="lower", step=1):
+    """np.percentile(frames[::step], q, axis=0, method=method) of a uint8 stack (or DeviceFrames) for method 'lower',
+    'higher' or 'nearest': one uint8 plane for a scalar q, a stack of one plane per entry for a sequence.  The
+    distinct ranks go to the device eight a call."""
+    src, t, fshape = _temporal_planes(frames, step, "temporal_percentiles")
+    scalar = np.ndim(q) == 0
+    want = [percentile_rank(t, float(v), method) for v in np.atleast_1d(np.asarray(q, np.float64)).ravel()]
+    distinct = sorted(set(want))
+    planes, uploaded = {}, None
+    if len(distinct) > TEMPORAL_MAX_RANKS and not isinstance(src, DeviceFrames):
+        src = uploaded = DeviceFrames.upload(src)           # several calls: one upload
+    try:
+        for a in range(0, len(distinct), TEMPORAL_MAX_RANKS):
+            part = distinct[a:a + TEMPORAL_MAX_RANKS]
+            planes.update(zip(part, temporal_ranks(src, part, step)))
+    finally:
+        if uploaded is not None:
+            uploaded.release()
+    out = np.stack([planes[r] for r in want]) if want else np.zeros((0,) + fshape, np.uint8)
+    return out[0] if scalar else out
+
+
 def time_difference(this_frame, prev_frame):
     """this.astype(int16) - prev  (FilterTimeDifference, video/filters.py:564-568)"""
     a = np.ascontiguousarray(this_frame, np.uint8)
