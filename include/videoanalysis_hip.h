@@ -149,6 +149,10 @@ int va_gauss_taps_f32(double sigma, int *ksize_out, float *taps_out, int capacit
  * mode VA_BG_EMA   : state = float32[px], rate; the very first frame initialises bg = frame
  * mode VA_BG_STATIC: state = float64[px], read only
  * dtype VA_U8 (all modes) or VA_F32 (EMA only).  diff_out may be NULL (state update only).
+ * Values: the state is the caller's and may hold anything -- NaN, infinities, subnormals, 1e308: the new state is the
+ * IEEE result of the expressions above, operation by operation (a NaN it generates may differ in sign and payload
+ * from another machine's).  The uint8 difference of a pixel whose state is NaN is unspecified (C leaves the
+ * conversion undefined); the state update of that pixel is not.
  * Shape (this call and the three below): any n >= 0, px >= 1 (px = h*w*c: the frame's shape does not matter). */
 int va_bg_update(int mode, int dtype, const void *frames_dev, void *diff_out_dev,
                  void *state_dev, int64_t n_seen, double rate, int n, size_t px, void *stream);
@@ -197,7 +201,10 @@ int va_mono_mean_u8(const uint8_t *src_dev, uint8_t *dst_dev, size_t pixels, voi
 int va_normalize_u8(const uint8_t *src_dev, uint8_t *dst_dev, size_t count, double fmin,
                     double fmax, double alpha, double tmin, void *stream);
 /* the same for float32 or uint8 frames and uint8 / float32 / float64 targets (the reference takes
- * any dtype, video/filters.py:101-135): clip, affine map in float64, C cast to the target */
+ * any dtype, video/filters.py:101-135): clip, affine map, C cast to the target, with NumPy's types: uint8 frames are
+ * mapped in float64; float32 frames stay float32 throughout (fmin, fmax, alpha and tmin are rounded to float32 first),
+ * whatever the target.  A NaN pixel stays NaN in a float target; in a uint8 target, NaN and values beyond int32 are
+ * unspecified (C leaves the conversion undefined). */
 int va_normalize(const void *src_dev, int src_dtype, void *dst_dev, int dst_dtype, size_t count,
                  double fmin, double fmax, double alpha, double tmin, void *stream);
 /* FilterCrop -> FilterMonochrome -> FilterNormalize in ONE pass over the source frames, on the device

@@ -79,12 +79,19 @@ bg_mean_u8_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__ diff
 // are computed as  q0 = RN(x*y);  r = fma(-q0,d,x) (exact);  q = RN(q0 + r*y)  with y = RN(1/d)
 // divided once per frame.  This is the final step of Markstein's division algorithm (IBM
 // RS/6000, Itanium): with a correctly rounded reciprocal the result is the correctly rounded
-// quotient, i.e. bit-identical to IEEE division (the exceptional divisors have an all-ones
-// significand, impossible for an integer n+1 < 2^53).  Checked on the CPU exhaustively for
+// quotient (the exceptional divisors have an all-ones significand, impossible for an integer
+// n+1 < 2^53) -- PROVIDED that nothing overflows and that r is exact, which needs q to be a normal
+// number with room below it.  So it is bit-identical to IEEE division for x = 0 and for finite x with
+// 2^-960 <= |x| <= 2^1020, and NOT outside: an infinite x, or a product mean*n that overflowed, gives
+// fma(-Inf, d, Inf) = NaN where the division gives Inf, and a subnormal x loses the half-way cases
+// (x = 9 * 2^-1074, d = 6: the division gives 8 * 2^-1074, the three lines 7 * 2^-1074, because
+// RN(1/6) < 1/6 pulls the exact tie 7.5 below the midpoint).  bg_mean_u8_fast_kernel keeps its
+// pixels inside that domain (kFastMeanMin, kFastMeanMax below).  Checked on the CPU exhaustively for
 // frame/(n+1) (all 256 values x every n+1 <= 2^24, plus random n+1 < 2^45) and on 1.6e9 random
 // (mean*n, n+1) pairs, and on the GPU against the oracle's plain divisions
-// (tests/test_gpu_parity.py).  It replaces two ~30-instruction float64 division sequences per
-// pixel by six FMA-class operations.
+// (tests/test_gpu_parity.py, tests/test_gpu_special_values.py; the two failures above:
+// tests/test_special_values_host.py).  It replaces two ~30-instruction float64 division sequences
+// per pixel by six FMA-class operations.
 __device__ __forceinline__ double div_by_uniform(double x, double d, double y)
 {
     const double q = x * y;
@@ -240,12 +247,45 @@ __device__ __forceinline__ void bg_mean_group(const BgGroup<V, RECIP, SPLIT> &g,
     }
 }
 
+// The state values a thread may take through the division-free arithmetic: zero, and kFastMeanMin <= |mean| <=
+// kFastMeanMax.  A thread that loads anything else -- NaN, an infinity, a subnormal, 1e308 -- folds its pixels with
+// plain divisions (bg_mean_plain, the arithmetic of bg_mean_u8_kernel).  The test at load covers the whole launch,
+// because from frame to frame a state inside these bounds stays inside div_by_uniform's domain (0 <= n_seen and
+// n_seen + n <= 2^53: launch_bg sends nothing else here):
+//   * downwards: after a non-zero pixel the new state a + frame/(n+1) is zero or at least 2^-107 in size (frame/(n+1)
+//     >= 2^-53, and a sum of two doubles is a multiple of the smaller operand's last place); a zero pixel shrinks
+//     the state by n/(n+1), over a launch by n_seen/(n_seen + n) >= 2^-31 in all (n is an int), or to zero at
+//     n_seen = 0.  So |mean| >= 2^-900 * 2^-31 and |mean*n| >= 2^-931 throughout, above the 2^-960 it needs;
+//   * upwards: the state grows by at most 255 a frame, to less than 2^960 + 2^39 < 2^961, and n < 2^53, so
+//     |mean*n| < 2^1014: no overflow, and below the 2^1020.
+constexpr double kFastMeanMin = 0x1p-900, kFastMeanMax = 0x1p960;
+
+// one pixel after the other, state and bytes straight from memory: the rare path takes no register from the common one
+template <int V, bool DIFF>
+__device__ __forceinline__ void bg_mean_plain(const uint8_t *frames, uint8_t *diff, double *mean, double dn0, int n,
+                                              size_t i0, size_t px)
+{
+#pragma unroll 1
+    for (int k = 0; k < V; k++) {
+        double m = mean[i0 + k], dn = dn0;
+#pragma unroll 1
+        for (int f = 0; f < n; f++) {
+            const double fr = (double)frames[(size_t)f * px + i0 + k], dn1 = dn + 1.0;
+            if constexpr (DIFF)
+                diff[(size_t)f * px + i0 + k] = sat_u8_trunc(fabs(fr - m));
+            m = m * dn / dn1 + fr / dn1;
+            dn = dn1;
+        }
+        mean[i0 + k] = m;
+    }
+}
+
 // BOUNDED: the caller vouches that every mean lies in [0, 255] (true for a state that started at zero or
 // inside that range: a mean of uint8 values stays there up to rounding), so |frame - mean| < 256 and the
 // saturation of the difference -- one of the 14 operations per pixel -- can go
 // SPLIT (RECIP = RecipArgs only): the second quotient in two operations, see RecipArgs::lo
 // DIFF: the difference images are written (false: the state-only update, diff is not touched)
-// dn0 = (double)n_seen: launch_bg sends only |n_seen|, |n_seen + n| <= 2^53 here
+// dn0 = (double)n_seen: launch_bg sends only 0 <= n_seen, n_seen + n <= 2^53 here
 template <int V, typename RECIP, bool BOUNDED, bool SPLIT, bool DIFF>
 __global__ void __launch_bounds__(kBlock)
 bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__ diff,
@@ -258,6 +298,17 @@ bg_mean_u8_fast_kernel(const uint8_t *__restrict__ frames, uint8_t *__restrict__
 #pragma unroll
     for (int k = 0; k < V; k++)
         m[k] = mean[i0 + k];
+    // once per thread and launch: a state value outside the division-free domain (see kFastMeanMin; false for NaN)
+    bool fast = true;
+#pragma unroll
+    for (int k = 0; k < V; k++) {
+        const double a = fabs(m[k]);
+        fast &= a == 0.0 || (a >= kFastMeanMin && a <= kFastMeanMax);
+    }
+    if (!fast) {
+        bg_mean_plain<V, DIFF>(frames, diff, mean, dn0, n, i0, px);
+        return;
+    }
     // Frames are walked in groups of kAhead: the next group's loads are issued before this
     // group's arithmetic (only 2 waves per SIMD exist at 16 px per thread), so a load has kAhead
     // frame steps to arrive and a CU keeps 8 waves x 8 KB in flight (measured per 256 x 1080p:
@@ -627,8 +678,10 @@ int launch_bg(int mode, int dtype, const void *frames, void *diff, void *state, 
             // (8 px per thread, i.e. twice the waves with 8-byte accesses: 0.271-0.276 against 0.259-0.265 ms)
             const bool wide = px % 16 == 0 && aligned(fr, 16) && (!df || aligned(df, 16));
             // the fast kernels count the divisor up in float64, which is exact up to 2^53; beyond that the
-            // plain-division kernel converts every n_seen + f (no performance case)
-            const bool countable = n_seen >= -(1ll << 53) && n_seen <= (1ll << 53) - n;
+            // plain-division kernel converts every n_seen + f (no performance case).  So it does for a negative
+            // n_seen, which no caller has a use for: the divisor would pass through 0 and n/(n+1) exceed 1, and the
+            // fast kernels' domain argument (kFastMeanMin) stands on 0 <= n_seen
+            const bool countable = n_seen >= 0 && n_seen <= (1ll << 53) - n;
             // the saturation concerns the difference alone: a state-only update needs no vouching
             const bool bounded = mean_in_u8_range && df;
             const double dn0 = (double)n_seen;

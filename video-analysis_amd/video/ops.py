@@ -560,7 +560,8 @@ def resize(frames, size, interpolation="linear", color=False):
 
 def normalize_any(frames, fmin, fmax, alpha, tmin, dtype):
     """FilterNormalize for uint8 / float32 frames and uint8 / float32 / float64 targets
-    (video/filters.py:126-132): clip, (f - fmin)*alpha + tmin in float64, astype(dtype)"""
+    (video/filters.py:126-132): clip, (f - fmin)*alpha + tmin, astype(dtype), with NumPy's types: in float64 for uint8
+    frames, in float32 throughout for float32 frames"""
     a = np.ascontiguousarray(frames)
     dtype = np.dtype(dtype)
     if a.dtype not in (np.uint8, np.float32) or dtype not in _TARGET_DTYPES:
