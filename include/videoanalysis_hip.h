@@ -1130,7 +1130,12 @@ typedef struct va_pipeline va_pipeline_t;
 int va_pipeline_create(const va_config *cfg, va_pipeline_t **out);
 int va_pipeline_destroy(va_pipeline_t *p);
 /* frames_dev: (n,H,W[,C]) of cfg.dtype (float32 pipelines: 16-byte aligned, as is filtered_out_dev;
- * VA_ERR_INVALID otherwise).  Any output may be NULL:
+ * VA_ERR_INVALID otherwise).  8-bit pipelines whose Gaussian is a single-launch kernel (va_pipeline_describe:
+ * "mfma-i8" or "fused-lds") need frames_dev 16-byte aligned when there is no background model (with one, the
+ * Gaussian reads the pipeline's own difference image and frames_dev may start anywhere), and "mfma-i8" needs
+ * filtered_out_dev 4-byte aligned; VA_ERR_INVALID otherwise, checked before anything is enqueued: a rejected
+ * run leaves the background model and n_seen as they were.  mask_out_dev may start at any byte, labels_out_dev
+ * at any int32.  Any output may be NULL:
  *   filtered_out_dev : (n,H,W[,C]) cfg.dtype, the blurred background-subtracted frames
  *   mask_out_dev     : (n,H,W) u8 0/maxval after threshold + morphology
  *   labels_out_dev   : (n,H,W) int32

@@ -1,7 +1,10 @@
 """Host: the argument guards of the entry points that sit beside their kernels (labelling, contours, geodesic maps,
 Gaussian, pointwise, morphology, stencils).  Every call here is refused with VA_ERR_INVALID before anything touches a
 device or a pointer, so no GPU is needed: the pointers are made-up addresses.  Where an entry has several guards the
-cases are in the order the entry checks them, and each case trips exactly one more than the one before."""
+cases are in the order the entry checks them, and each case trips exactly one more than the one before.  The
+misaligned pointers the header promises VA_ERR_INVALID for come from the table of tests/pointer_offset_cases.py, one
+pointer at a time (tests/test_gpu_pointer_offsets.py repeats them on real buffers and checks that nothing was
+written)."""
 import pytest
 
 INVALID = -22
@@ -97,6 +100,40 @@ CASES += [
 def lib():
     from video import _hip
     return _hip.load_library()
+
+
+def _misaligned():
+    """every pointer that include/videoanalysis_hip.h promises VA_ERR_INVALID for when it is misaligned, one at a time
+    (the table of tests/pointer_offset_cases.py; on the GPU the same calls run on sentinel-filled buffers)"""
+    import pointer_offset_cases as T
+    return [(entry, name, by) for entry in sorted(T.REJECTIONS) for name, by in T.rejection_calls(entry)]
+
+
+@pytest.mark.parametrize("entry,name,by", _misaligned(), ids=["%s-%s" % c[:2] for c in _misaligned()])
+def test_misaligned_pointer_is_refused_and_named(lib, entry, name, by):
+    import pointer_offset_cases as T
+    names = [a.name for a in T.REJECTIONS[entry] if isinstance(a, T.ptr)]
+    args = T.rejection_args(entry, lambda n: P * (1 + names.index(n)), name, by)
+    rc = getattr(lib, entry)(*args)
+    said = lib.va_last_error().decode()
+    assert rc == INVALID and entry in said and "aligned" in said, (entry, name, by, rc, said)
+
+
+def test_every_promised_alignment_is_in_the_table():
+    """the calls whose header text names an alignment or a misaligned pointer"""
+    import pointer_offset_cases as T
+    assert set(T.REJECTIONS) == {
+        "va_find_contours", "va_skeleton_graph", "va_region_links", "va_simplify_rdp", "va_simplify_visvalingam",
+        "va_curves_equidistant", "va_compose_layers_u8", "va_draw_u8", "va_draw_contours_u8", "va_jpeg_encode_u8",
+        "va_jpeg_encode_sampled_u8", "va_jpeg_encode_optimized_u8", "va_jpeg_optimal_tables", "va_jpeg_decode_u8",
+        "va_jpeg_decode_sampled_u8", "va_jpeg_decode_split_u8"}
+    for entry, args in T.REJECTIONS.items():
+        assert len(args) == len(_signature(entry)), entry
+
+
+def _signature(entry):
+    from video import _hip
+    return _hip.SIGNATURES[entry][1]
 
 
 @pytest.mark.parametrize("entry,args,message", CASES, ids=["%s-%d" % (c[0], i) for i, c in enumerate(CASES)])

@@ -594,6 +594,17 @@ int va_pipeline_run(va_pipeline_t *p, const void *frames, int n, void *filtered_
     VA_REQUIRE(c.connectivity || !(labels_out || counts_out || stats_out),
                "va_pipeline_run: label outputs requested but connectivity == 0");
     VA_REQUIRE(!stats_out || c.max_labels > 0, "va_pipeline_run: stats_out needs max_labels > 0");
+    // 8-bit frames, single-pass Gaussian planned (with aligned = true, at creation): what its launcher will ask
+    // of the caller's pointers is asked here, before the background model is updated or anything is counted.
+    // With a background model the Gaussian reads the pipeline's own difference buffer, not frames_dev.
+    if (p->gauss.single_pass()) {
+        VA_REQUIRE(c.bg_mode != VA_BG_NONE || reinterpret_cast<uintptr_t>(frames) % 16 == 0,
+                   "va_pipeline_run: frames_dev must be 16-byte aligned for the %s Gaussian of a pipeline "
+                   "without a background model", gauss_plan_name(p->gauss));
+        VA_REQUIRE(!p->gauss.byte_mask() || !filtered_out || reinterpret_cast<uintptr_t>(filtered_out) % 4 == 0,
+                   "va_pipeline_run: filtered_out_dev must be 4-byte aligned for the %s Gaussian",
+                   gauss_plan_name(p->gauss));
+    }
     const size_t esz = c.dtype == VA_U8 ? 1 : 4;
     int rc;
     const void *cur = frames;

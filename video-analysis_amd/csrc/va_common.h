@@ -213,7 +213,7 @@ struct GaussPlan {
     bool folds_ema() const { return family == GaussFamily::F32Fused; }   // the f32 EMA update in the row pass
 };
 // aligned: the pointers suit the single-pass kernels (u8: src % 16, dst % 4; f32: src % 16); pipelines pass
-// true, their launchers check every run.  valu_hook (va_test_hook_gaussian_u8): the dot4/dot2 single pass in
+// true and va_pipeline_run checks the caller's pointers at its top, every run (the launchers check again).  valu_hook (va_test_hook_gaussian_u8): the dot4/dot2 single pass in
 // place of the matrix-core one (what it cannot take still goes to the planes).  force: U8Dot / U8Generic pin
 // that family (the stand-alone test hooks; the launcher checks the shape).
 int plan_gaussian(GaussPlan *g, int dtype, int h, int w, int c, double sigma, int tap_rule, bool aligned,
