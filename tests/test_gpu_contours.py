@@ -284,6 +284,32 @@ def test_blob_masks(ops, fx, oracle):
     assert longest > 1500      # walks of a few thousand steps
 
 
+# ------------------------------------------------------------------- scans over more than a wave
+def test_scans_with_several_cells_contours_and_frames_a_thread(ops, oracle):
+    """The scans are one workgroup of 256 threads each.  Two frames of 40 x 72 (320 cells, 3 mask words a row) with
+    one-pixel blobs in row 0, row 39 and every third row between: two cells a thread in the cell scan, contours in
+    three waves.  300 frames of 3 x 5 with 0, 1 or 2 contours: two frames a thread in the scans over the frames."""
+    tall = np.zeros((2, 40, 72), np.uint8)
+    for f in range(2):
+        for y in sorted(set(range(0, 40, 3)) | {39}):
+            tall[f, y, (y + 7 * f) % 5::5] = 1
+    tall[1, 39] = 0
+    tall[1, 39, 71] = 1
+    many = np.zeros((300, 3, 5), np.uint8)
+    many[::2, 0, 0] = 1
+    many[::3, 2, 4] = 1
+    for stack in (tall, many):
+        ref = [oracle.find_contours_external_simple(m) for m in stack]
+        assert len({len(r) for r in ref}) >= 2
+        total, npts = sum(len(r) for r in ref), sum(len(c) for r in ref for c in r)
+        rc, out = raw(stack, total, npts)
+        assert rc == 0 and out["totals"][:2].tolist() == [total, npts]
+        assert out["ncontours"][:len(stack)].tolist() == [len(r) for r in ref]
+        assert np.array_equal(out["point_off"][:total + 1], np.arange(total + 1))       # every contour is one point
+        assert all(same_lists(g, r) for g, r in zip(lists_of(out, len(stack)), ref))
+    assert len(oracle.find_contours_external_simple(tall[0])) > 128
+
+
 # -------------------------------------------------------------------------------- determinism
 def test_two_runs_give_identical_bytes(batch):
     stack, ref = batch

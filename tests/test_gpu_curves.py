@@ -125,7 +125,7 @@ def test_counts(gpu):
     _check(cs, spacing=[2.5, None, 0.7, None, 20, None, 5, None, 1.0], count=[None, 4, 9, None, 1, 3, 2, 2, 6])
 
 
-@pytest.mark.parametrize("m", (1, 63, 64, 65, 257))
+@pytest.mark.parametrize("m", (1, 63, 64, 65, 257, 513))    # the offsets' scan takes 256 curves a round: 2 and 3 rounds
 def test_batch_sizes(gpu, m):
     cs = K.mixed_curves(100 + m, m, 2, 300)
     rng = np.random.default_rng(m)

@@ -117,6 +117,19 @@ def test_frame_stack_serpentine_and_nested_rings():
     _same(got[1], want, "rings")
 
 
+def test_more_scan_workgroups_than_one_round_takes():
+    """the scan of the workgroups' sums takes 1024 of them (2^20 pixels) a round: an empty item puts the rings into
+    the second round, behind the node, edge and point counts that the serpentine left in the carry"""
+    from video import ops
+    imgs = [G.serpentine(64, 64), np.zeros((1023, 1024), np.uint8), G.nested_rings(8)]
+    assert imgs[0].size + imgs[1].size > 1 << 20
+    got = ops.skeleton_graphs(imgs)
+    for k, (g, m) in enumerate(zip(got, imgs)):
+        _same(g, _restate(m), k)
+        assert np.all(g.nodes["item"] == k) and np.all(g.edges["item"] == k), k
+    assert len(got[0].edges) == 1 and len(got[2].nodes) == 8
+
+
 # ---------------------------------------------------------------------------- 3, 4: the C ABI's own rules
 def _abi_run(imgs, capn, cape, capp, fill=0xA5):
     """one va_skeleton_graph call into fresh buffers filled with `fill`: (counts, totals, and the raw bytes of the

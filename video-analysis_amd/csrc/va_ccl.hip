@@ -647,6 +647,7 @@ __device__ __forceinline__ int count_starts(const uint32_t (&m)[NCH][kChunk + 2]
 __device__ __forceinline__ uint32_t upto(int b) { return (2u << b) - 1u; }
 
 // exclusive scan of one value per thread over the workgroup; *total (LDS) receives the sum
+// (not va_scan.h's block_exclusive, nor wave_inclusive in the paint: ccl_frame_kernel then takes 1-2 VGPRs more)
 __device__ __forceinline__ int block_exclusive_scan(int v, int *s_part, int *total)
 {
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;

@@ -139,6 +139,22 @@ __device__ __forceinline__ int reflect101(int p, int len)
         p = p < 0 ? -p : 2 * (len - 1) - p;
     return p;
 }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// the points of curve k of a packed buffer: false when its offsets are not in order inside 0 .. npoints
+__device__ __forceinline__ bool curve_range(const int64_t *__restrict__ point_off, int64_t k, int64_t npoints,
+                                            int64_t &start, int64_t &n)
+{
+    const int64_t s = point_off[k], e = point_off[k + 1];
+    if (!(s >= 0 && s <= e && e <= npoints))
+        return false;
+    start = s;
+    n = e - s;
+    return true;
+}
+// packed fp32: both halves of a register pair are independent values (v_pk_fma_f32)
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 #endif
 
 // ---- host-side kernels shared between translation units --------------------------------

@@ -8,6 +8,7 @@
 // The tracers start from the labelling forest of va_ccl.hip: launch_ccl(..., paint = false) leaves -(label) at
 // the first raster pixel of every component, which is where OpenCV's border following starts too.
 #include "va_ccl_device.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -384,36 +385,18 @@ contour_cell_count_kernel(const uint32_t *__restrict__ bits, const int32_t *__re
         cell_cnt[c.row * kCellsPerRow + (c.lane >> 3)] = cnt;
 }
 
-// exclusive prefix of one value per thread over a kBlock workgroup (Hillis-Steele in LDS); *sum: the total
-__device__ __forceinline__ long long block_prefix(long long v, long long *part, long long *sum)
-{
-    const int t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const long long x = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    const long long r = part[t] - v;
-    *sum = part[kBlock - 1];
-    __syncthreads();
-    return r;
-}
-
 // in place, one workgroup per frame: cell counts -> exclusive prefix within the frame (ascending raster order)
 __global__ void __launch_bounds__(kBlock)
 contour_cell_scan_kernel(int32_t *__restrict__ cells, int32_t *__restrict__ ncontours, long long cells_per_frame)
 {
-    __shared__ long long part[kBlock];
+    __shared__ long long part[kBlock / kWave];
     int32_t *c = cells + (size_t)blockIdx.x * cells_per_frame;
     const long long per = (cells_per_frame + kBlock - 1) / kBlock;
     const long long i0 = min(cells_per_frame, threadIdx.x * per), i1 = min(cells_per_frame, i0 + per);
     long long s = 0, sum;
     for (long long i = i0; i < i1; i++)
         s += c[i];
-    int run = (int)block_prefix(s, part, &sum);
+    int run = (int)block_exclusive<kBlock / kWave>(s, part, sum);
     for (long long i = i0; i < i1; i++) {
         const int v = c[i];
         c[i] = run;
@@ -429,13 +412,13 @@ __global__ void __launch_bounds__(kBlock)
 contour_frame_scan_kernel(const T *__restrict__ in, int n, long long *__restrict__ first,
                           long long *__restrict__ total)
 {
-    __shared__ long long part[kBlock];
+    __shared__ long long part[kBlock / kWave];
     const int per = (n + kBlock - 1) / kBlock;
     const int i0 = min(n, (int)threadIdx.x * per), i1 = min(n, i0 + per);
     long long s = 0, sum;
     for (int i = i0; i < i1; i++)
         s += in[i];
-    long long run = block_prefix(s, part, &sum);
+    long long run = block_exclusive<kBlock / kWave>(s, part, sum);
     for (int i = i0; i < i1; i++) {
         first[i] = run;
         run += in[i];
@@ -512,12 +495,12 @@ __global__ void __launch_bounds__(kBlock)
 contour_frame_points_kernel(const int32_t *__restrict__ npts, const long long *__restrict__ frame_first,
                             long long *__restrict__ frame_pts)
 {
-    __shared__ long long part[kBlock];
+    __shared__ long long part[kBlock / kWave];
     const long long a = frame_first[blockIdx.x], b = frame_first[blockIdx.x + 1];
     long long s = 0, sum;
     for (long long i = a + threadIdx.x; i < b; i += kBlock)
         s += npts[i];
-    block_prefix(s, part, &sum);
+    block_exclusive<kBlock / kWave>(s, part, sum);
     if (threadIdx.x == 0)
         frame_pts[blockIdx.x] = sum;
 }
@@ -528,14 +511,14 @@ contour_offsets_kernel(const int32_t *__restrict__ npts, const long long *__rest
                        const long long *__restrict__ pt_first, const long long *__restrict__ totals,
                        long long *__restrict__ point_off, long long cap_contours)
 {
-    __shared__ long long part[kBlock];
+    __shared__ long long part[kBlock / kWave];
     const long long a = frame_first[blockIdx.x], b = frame_first[blockIdx.x + 1], total = totals[0];
     const long long per = (b - a + kBlock - 1) / kBlock;
     const long long i0 = min(b, a + threadIdx.x * per), i1 = min(b, i0 + per);
     long long s = 0, sum;
     for (long long i = i0; i < i1; i++)
         s += npts[i];
-    long long run = pt_first[blockIdx.x] + block_prefix(s, part, &sum);
+    long long run = pt_first[blockIdx.x] + block_exclusive<kBlock / kWave>(s, part, sum);
     for (long long i = i0; i < i1; i++) {
         if (i <= cap_contours)
             point_off[i] = run;

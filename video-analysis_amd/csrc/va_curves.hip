@@ -19,6 +19,7 @@
 // points plus its own, is refused instead of being run to an end that a lane may never reach.
 #include "va_common.h"
 #include "va_curves_math.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -26,18 +27,6 @@ namespace {
 
 constexpr int kCurvesBlock = 64;     // one wave: m serial curves spread over as many CUs as there are waves
 constexpr int kScanBlock = 256;
-
-// the points of curve k: false when its offsets are not in order inside 0 .. npoints
-__device__ __forceinline__ bool curve_range(const int64_t *__restrict__ point_off, int64_t k, int64_t npoints,
-                                            int64_t &start, int64_t &n)
-{
-    const int64_t s = point_off[k], e = point_off[k + 1];
-    if (!(s >= 0 && s <= e && e <= npoints))
-        return false;
-    start = s;
-    n = e - s;
-    return true;
-}
 
 // the walk's step and the most points its result may have: false for a curve the walk is not run on
 __device__ __forceinline__ bool walk_plan(double L, double spacing, int64_t n, double &dx, int64_t &limit)
@@ -93,29 +82,16 @@ __global__ void __launch_bounds__(kScanBlock)
 curves_scan_kernel(const int32_t *__restrict__ out_count, int m, int64_t *__restrict__ out_off,
                    int64_t *__restrict__ totals)
 {
-    __shared__ int64_t part[kScanBlock];
-    __shared__ int64_t carry;
+    __shared__ int64_t part[kScanBlock / kWave];
     const int t = (int)threadIdx.x;
-    if (t == 0)
-        carry = 0;
-    __syncthreads();
+    int64_t carry = 0;
     for (int64_t base = 0; base < m; base += kScanBlock) {
         const int64_t k = base + t;
-        const int64_t v = k < m ? (int64_t)out_count[k] : 0;
-        part[t] = v;
-        __syncthreads();
-        for (int d = 1; d < kScanBlock; d <<= 1) {
-            const int64_t add = t >= d ? part[t - d] : 0;
-            __syncthreads();
-            part[t] += add;
-            __syncthreads();
-        }
+        int64_t sum;
+        const int64_t excl = block_exclusive<kScanBlock / kWave>(k < m ? (int64_t)out_count[k] : 0, part, sum);
         if (k < m)
-            out_off[k] = carry + part[t] - v;
-        __syncthreads();
-        if (t == kScanBlock - 1)
-            carry += part[t];
-        __syncthreads();
+            out_off[k] = carry + excl;
+        carry += sum;
     }
     if (t == 0) {
         out_off[m] = carry;

@@ -195,11 +195,6 @@ gauss_col_f32_kernel(const float *__restrict__ tmp, float *__restrict__ dst, int
 //   col pass : a workgroup stages a (32 + 2r)-row x 128-sample tile in LDS once (3.25 loads per
 //              output instead of 9.25 through L2); a thread owns TWO adjacent sample columns
 //              (float2) for 8 rows, with the same two 8-row rings as above fed from LDS.
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
 constexpr int kRowThreads = 384;
 
 template <int C, int P>

@@ -36,12 +36,8 @@ namespace va {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 constexpr int kT = 256;        // threads per workgroup (4 waves, one per SIMD; 4 workgroups per CU)
 constexpr int kP = 15;         // outputs per thread and half (multiple of the channel count)

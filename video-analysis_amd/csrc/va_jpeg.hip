@@ -43,6 +43,7 @@
 //             adds the header's length to the length of a frame's first segment, so the scan is the plain one
 #include "va_common.h"
 #include "va_jpeg_math.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -87,25 +88,6 @@ struct JpegArgs {
 
 // how a segment kernel gets its Huffman tables, or that it counts symbols for them
 enum { kHuffAnnexK = 0, kHuffDevice = 1, kHuffCount = 2 };
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1)
-        v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
-__device__ __forceinline__ int wave_inclusive(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int u = __shfl_up(v, d, kWave);
-        if (lane >= d)
-            v += u;
-    }
-    return v;
-}
 
 // the 8 pixels x0 .. x0 + 7 of row y as bytes; columns beyond the frame repeat the last one
 template <int C>
@@ -482,12 +464,9 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
                  int64_t *__restrict__ seg_start, int64_t *offsets, int64_t *__restrict__ sizes,
                  int64_t *__restrict__ totals)
 {
-    __shared__ int64_t part[kScanBlock];
-    __shared__ int64_t carry;
+    __shared__ int64_t part[kScanBlock / kWave];
     const int t = (int)threadIdx.x;
-    if (t == 0)
-        carry = 0;
-    __syncthreads();
+    int64_t carry = 0;
     for (int64_t base = 0; base < nsegs; base += kScanBlock * kScanPerThread) {
         int64_t v[kScanPerThread], mine = 0;
 #pragma unroll
@@ -500,15 +479,8 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
             }
             mine += v[i];
         }
-        part[t] = mine;
-        __syncthreads();
-        for (int d = 1; d < kScanBlock; d <<= 1) {
-            const int64_t add = t >= d ? part[t - d] : 0;
-            __syncthreads();
-            part[t] += add;
-            __syncthreads();
-        }
-        int64_t at = carry + part[t] - mine;
+        int64_t sum;
+        int64_t at = carry + block_exclusive<kScanBlock / kWave>(mine, part, sum);
 #pragma unroll
         for (int i = 0; i < kScanPerThread; i++) {
             const int64_t s = base + (int64_t)t * kScanPerThread + i;
@@ -519,10 +491,7 @@ jpeg_scan_kernel(const int32_t *__restrict__ seg_len, int64_t nsegs, int nseg, i
             }
             at += v[i];
         }
-        __syncthreads();
-        if (t == kScanBlock - 1)
-            carry += part[t];
-        __syncthreads();
+        carry += sum;
     }
     if (t == 0) {
         seg_start[nsegs] = carry;

@@ -38,6 +38,7 @@
 
 #include "va_common.h"
 #include "va_jpeg_decode_math.h"
+#include "va_scan.h"
 
 static_assert(sizeof(va_jpeg::HuffDecode) == VA_JPEG_HUFF_DECODE_BYTES, "the table size is part of the ABI");
 
@@ -51,17 +52,6 @@ constexpr int kLocPer = 8;                               // bytes a lane looks a
 constexpr int kLocTile = kLocBlock * kLocPer;
 constexpr int kEntBlock = kWave;
 constexpr int kRecBlock = 256;
-
-__device__ __forceinline__ int wave_inclusive_i(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int u = __shfl_up(v, d, kWave);
-        if (lane >= d)
-            v += u;
-    }
-    return v;
-}
 
 __device__ __forceinline__ long long wave_min_ll(long long v)
 {
@@ -113,7 +103,7 @@ jpeg_locate_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict_
             if (b[i] == 0xFFu && b[i + 1] != 0u && b[i + 1] != 0xFFu)
                 mask |= 1u << i;
         const int mine = __popc(mask);
-        const int incl = wave_inclusive_i(mine, lane);
+        const int incl = wave_inclusive(mine, lane);
         if (lane == kWave - 1)
             wave_count[par][wave] = incl;
         __syncthreads();
@@ -636,42 +626,11 @@ __global__ void __launch_bounds__(kEntBlock) jpeg_split_scan_kernel(SplitArgs a)
         a.dc[3 * g + ch] = r.dc[ch];
 }
 
-template <class T>
-__device__ __forceinline__ T wave_inclusive(T v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const T u = __shfl_up(v, d, kWave);
-        if (lane >= d)
-            v += u;
-    }
-    return v;
-}
-
-// the exclusive scan of v over the workgroup's kRecBlock lanes; total: the sum.  `part` holds a value per wave.
-template <class T>
-__device__ __forceinline__ T block_exclusive(T v, T *part, T &total)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const T incl = wave_inclusive(v, lane);
-    __syncthreads();                                     // the last use of `part`
-    if (lane == kWave - 1)
-        part[wave] = incl;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kRecBlock / kWave; k++) {
-        before += k < wave ? part[k] : (T)0;
-        total += part[k];
-    }
-    return before + incl - v;
-}
-
 __global__ void __launch_bounds__(kRecBlock) jpeg_split_check_kernel(SplitArgs a)
 {
-    __shared__ long long part64[kRecBlock / kWave];
-    __shared__ uint32_t part32[kRecBlock / kWave];
+    constexpr int kRecWaves = kRecBlock / kWave;
+    __shared__ long long part64[kRecWaves];
+    __shared__ uint32_t part32[kRecWaves];
     __shared__ int32_t rounds;
     const int64_t f = blockIdx.x;
     int64_t b, e;
@@ -692,14 +651,14 @@ __global__ void __launch_bounds__(kRecBlock) jpeg_split_check_kernel(SplitArgs a
             mine = a.last[g] > mine ? a.last[g] : mine;
         }
         long long total = 0;
-        const long long at = block_exclusive<long long>(in ? a.begun[g] : 0, part64, total);
+        const long long at = block_exclusive<kRecWaves>(in ? (long long)a.begun[g] : 0, part64, total);
         if (in)
             a.start[g] = carry + at;
         carry += total;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             uint32_t sum = 0;
-            const uint32_t front = block_exclusive<uint32_t>(in ? a.dc[3 * g + ch] : 0u, part32, sum);
+            const uint32_t front = block_exclusive<kRecWaves>(in ? (uint32_t)a.dc[3 * g + ch] : 0u, part32, sum);
             if (in)
                 a.pred[3 * g + ch] = carry_dc[ch] + front;
             carry_dc[ch] += sum;

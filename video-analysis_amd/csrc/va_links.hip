@@ -25,6 +25,7 @@
 // slot and counter is written before it is read.  Nothing is written beyond cap_links records.
 #include "va_common.h"
 #include "va_links_math.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -81,30 +82,6 @@ __device__ __forceinline__ bool pair_planes(const LinksArgs &a, int t, const int
     return E != nullptr;
 }
 
-// exclusive scan of v over the workgroup (blockDim.x a multiple of 64, at most 1024); total: the sum, in every lane
-__device__ __forceinline__ int64_t block_scan(int64_t v, int64_t *wave_sums, int64_t &total)
-{
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
-    int64_t incl = v;
-    for (int off = 1; off < kWave; off <<= 1) {
-        const int64_t up = __shfl_up(incl, off, kWave);
-        if (lane >= off)
-            incl += up;
-    }
-    __syncthreads();                            // the sums of an earlier scan have been read
-    if (lane == kWave - 1)
-        wave_sums[wave] = incl;
-    __syncthreads();
-    int64_t before = 0, all = 0;
-    for (int k = 0; k < nwaves; k++) {
-        const int64_t s = wave_sums[k];
-        before += k < wave ? s : 0;
-        all += s;
-    }
-    total = all;
-    return before + incl - v;
-}
-
 __global__ void __launch_bounds__(kLinkBlock)
 links_count_kernel(LinksArgs a, int32_t *__restrict__ ncand)
 {
@@ -136,9 +113,9 @@ links_scan_pairs_kernel(const int32_t *__restrict__ in, int n, int64_t cap, int6
         const int t = base + threadIdx.x;
         const int64_t c = t < n ? in[t] : 0;
         int64_t sum, csum = 0;
-        const int64_t excl = block_scan(kNeed ? va_links::table_slots(c) : c, wave_sums, sum);
+        const int64_t excl = block_exclusive<0>(kNeed ? va_links::table_slots(c) : c, wave_sums, sum);
         if (kNeed)
-            block_scan(c, wave_sums, csum);
+            block_exclusive<0>(c, wave_sums, csum);
         if (t < n)
             out[t] = carry + excl;
         carry += sum;
@@ -199,9 +176,7 @@ links_accumulate_kernel(LinksArgs a, const int32_t *__restrict__ ncand, const in
     for (int round = 0; round < kMergedKeys && todo; round++) {
         const int leader = __ffsll((long long)todo) - 1;
         const bool mine = head && key == __shfl(key, leader, kWave);
-        int sum = mine ? len : 0;
-        for (int off = kWave / 2; off > 0; off >>= 1)
-            sum += __shfl_xor(sum, off, kWave);
+        const int sum = wave_sum(mine ? len : 0);
         if (lane == leader)
             va_links::insert(tab, slots, key, sum, p);
         todo &= ~__ballot(mine);
@@ -290,7 +265,7 @@ links_scan_blocks_kernel(int32_t *__restrict__ block_cnt, int blocks, int first_
     for (int base = 0; base < blocks; base += kLinkBlock) {
         const int k = base + threadIdx.x;
         int64_t sum;
-        const int64_t excl = block_scan(k < blocks ? cnt[k] : 0, wave_sums, sum);
+        const int64_t excl = block_exclusive<0>(k < blocks ? (int64_t)cnt[k] : 0, wave_sums, sum);
         if (k < blocks)
             cnt[k] = (int32_t)(carry + excl);
         carry += sum;

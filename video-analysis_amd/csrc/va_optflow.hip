@@ -31,8 +31,6 @@ struct PolyConsts {
     double ig11, ig03, ig33, ig55;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // GaussianBlur row pass (SymmRowSmallFilter for ksize <= 5, RowFilter above), converting to float on the fly
 template <class T>
 __global__ void __launch_bounds__(kBlock)

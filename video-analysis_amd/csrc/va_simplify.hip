@@ -28,18 +28,6 @@ constexpr int kRdpStagePoints = 2048;        // 32 KiB of LDS a workgroup: five 
 constexpr int kRdpMaxGrid = 65535;           // curves of one launch; a larger batch runs in pieces
 static_assert((1 << (va_simplify::kSpanStack / 2)) >= VA_SIMPLIFY_MAX_POINTS, "the span stack holds 2 log2(n) spans");
 
-// the points of curve k: false when its offsets are not in order inside 0 .. npoints
-__device__ __forceinline__ bool curve_range(const int64_t *__restrict__ point_off, int64_t k, int64_t npoints,
-                                            int64_t &start, int64_t &n)
-{
-    const int64_t s = point_off[k], e = point_off[k + 1];
-    if (!(s >= 0 && s <= e && e <= npoints))
-        return false;
-    start = s;
-    n = e - s;
-    return true;
-}
-
 // the spans of one curve of n >= 3 points, by the whole wave; returns the number of points kept (the same in every
 // lane).  Every lane holds the same span and stack pointer and stores the same stack entry, so each reads back what
 // it wrote itself and no barrier is needed.

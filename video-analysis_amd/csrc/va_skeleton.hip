@@ -21,6 +21,7 @@
 // Every slot comes from these counts and scans; the atomics are integer min / max / add, whose results do not
 // depend on their order, so two calls write identical bytes.
 #include "va_common.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -28,6 +29,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanBlock = 1024;
+constexpr int kScanWaves = kScanBlock / kWave;
 constexpr uint32_t kBg = 0xFFFFFFFEu;      // forest word of a background pixel
 constexpr uint32_t kChain = 0xFFFFFFFFu;   // forest word of a chain pixel (pass 2)
 constexpr uint32_t kRingBit = 0x80000000u;
@@ -313,30 +315,6 @@ __device__ __forceinline__ void pixel_counts(const uint32_t *P, const uint8_t *o
     }
 }
 
-// exclusive scan of one value per thread over a workgroup of kScanBlock threads; returns the workgroup's sum
-__device__ long long block_scan(long long v, long long *excl, long long *lds)
-{
-    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    long long inc = v;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const long long o = __shfl_up(inc, d, kWave);
-        if (lane >= d)
-            inc += o;
-    }
-    if (lane == kWave - 1)
-        lds[wave] = inc;
-    __syncthreads();
-    long long base = 0, sum = 0;
-    for (int k = 0; k < kScanBlock / kWave; ++k) {
-        if (k < wave)
-            base += lds[k];
-        sum += lds[k];
-    }
-    __syncthreads();
-    *excl = base + inc - v;
-    return sum;
-}
-
 // what each workgroup of the scan adds to (nodes, edges, points), and the items' (nodes, edges).  A workgroup whose
 // first and last pixel lie in one item -- every one in a frame stack -- adds its sums to that item's counters once;
 // elsewhere each node pixel and owner adds its own.  Integer adds: the counters do not depend on their order
@@ -345,8 +323,8 @@ __global__ void __launch_bounds__(kScanBlock) skel_block_sums(const uint32_t *P,
                                                               int32_t *counts)
 {
     __shared__ int one_item;
-    __shared__ int wave_ne[kScanBlock / kWave];            // nodes | edges << 16 (at most 1024 and 4096 a workgroup)
-    __shared__ long long wave_pt[kScanBlock / kWave];
+    __shared__ int wave_ne[kScanWaves];                    // nodes | edges << 16 (at most 1024 and 4096 a workgroup)
+    __shared__ long long wave_pt[kScanWaves];
     const int64_t first = (int64_t)blockIdx.x * kScanBlock, g = first + threadIdx.x;
     if (threadIdx.x == 0) {
         const int64_t last = (first + kScanBlock < it.total ? first + kScanBlock : it.total) - 1;
@@ -355,12 +333,8 @@ __global__ void __launch_bounds__(kScanBlock) skel_block_sums(const uint32_t *P,
     }
     int nodes, edges, points;
     pixel_counts(P, owned, npts, g, it.total, &nodes, &edges, &points);
-    int ne = nodes | (edges << 16);
-    long long pt = points;
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        ne += __shfl_xor(ne, d, kWave);
-        pt += __shfl_xor(pt, d, kWave);
-    }
+    const int ne = wave_sum(nodes | (edges << 16));
+    const long long pt = wave_sum((long long)points);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         wave_ne[threadIdx.x / kWave] = ne;
         wave_pt[threadIdx.x / kWave] = pt;
@@ -377,7 +351,7 @@ __global__ void __launch_bounds__(kScanBlock) skel_block_sums(const uint32_t *P,
     if (threadIdx.x == 0) {
         int sne = 0;
         long long sp = 0;
-        for (int k = 0; k < kScanBlock / kWave; ++k) {
+        for (int k = 0; k < kScanWaves; ++k) {
             sne += wave_ne[k];
             sp += wave_pt[k];
         }
@@ -397,14 +371,14 @@ __global__ void __launch_bounds__(kScanBlock) skel_scan_sums(long long *sums, in
                                                              int m, long long *first_node, int64_t *totals,
                                                              int64_t *point_off)
 {
-    __shared__ long long lds[kScanBlock / kWave];
+    __shared__ long long lds[kScanWaves];
     for (int c = 0; c < 3; ++c) {
         long long carry = 0;
         for (int64_t at = 0; at < nblocks; at += kScanBlock) {
             const int64_t i = at + threadIdx.x;
             const long long v = i < nblocks ? sums[3 * i + c] : 0;
-            long long e;
-            const long long s = block_scan(v, &e, lds);
+            long long s;
+            const long long e = block_exclusive<kScanWaves>(v, lds, s);
             if (i < nblocks)
                 sums[3 * i + c] = carry + e;
             carry += s;
@@ -416,8 +390,8 @@ __global__ void __launch_bounds__(kScanBlock) skel_scan_sums(long long *sums, in
     for (int at = 0; at < m; at += kScanBlock) {
         const int i = at + threadIdx.x;
         const long long v = i < m ? counts[2 * i] : 0;
-        long long e;
-        const long long s = block_scan(v, &e, lds);
+        long long s;
+        const long long e = block_exclusive<kScanWaves>(v, lds, s);
         if (i < m)
             first_node[i] = carry + e;
         carry += s;
@@ -432,17 +406,15 @@ __global__ void __launch_bounds__(kScanBlock) skel_apply(const uint32_t *P, cons
                                                          unsigned long long *tally, long long *point_base,
                                                          va_skeleton_node *nodes_out, int64_t cap_nodes)
 {
-    __shared__ long long lds[kScanBlock / kWave];
+    __shared__ long long lds[kScanWaves];
     const int64_t g = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
     int nodes, edges, points;
     pixel_counts(P, owned, npts, g, it.total, &nodes, &edges, &points);
-    long long en, ee, ep;
-    block_scan(nodes, &en, lds);
-    block_scan(edges, &ee, lds);
-    block_scan(points, &ep, lds);
-    en += sums[3 * (int64_t)blockIdx.x];
-    ee += sums[3 * (int64_t)blockIdx.x + 1];
-    ep += sums[3 * (int64_t)blockIdx.x + 2];
+    const long long *before = sums + 3 * (int64_t)blockIdx.x;          // what the workgroups in front add up to
+    long long all;                                                      // (this workgroup's own sums: not needed here)
+    const long long en = before[0] + block_exclusive<kScanWaves>((long long)nodes, lds, all);
+    const long long ee = before[1] + block_exclusive<kScanWaves>((long long)edges, lds, all);
+    const long long ep = before[2] + block_exclusive<kScanWaves>((long long)points, lds, all);
     Where p;
     if (nodes && locate(it, g, &p)) {
         const unsigned long long t = tally[g];

@@ -5,6 +5,7 @@
 // One thread per pixel; the 3x3 / 5-point neighbourhoods are served by L1 (each byte is re-read
 // by its 8 neighbours within the same wave or the next row's wave).
 #include "va_common.h"
+#include "va_scan.h"
 
 namespace va {
 
@@ -12,8 +13,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
-// scipy.ndimage 'reflect' border (d c b a | a b c d | d c b a) for a 3x3 window == clamping
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// scipy.ndimage 'reflect' border (d c b a | a b c d | d c b a) for a 3x3 window == clamping: clampi
 
 // detect_peaks: include_plateaus -> (img == max over the 3x3 window) XOR (whole 3x3 window is
 // background, pixels outside the frame counting as background); else img > max over the 8
@@ -266,16 +266,8 @@ row_prefix_kernel(const uint8_t *__restrict__ src, uint32_t *__restrict__ p1, ui
         a1 += v;
         a2 += v * v;
     }
-    uint32_t e1 = a1, e2 = a2;                          // inclusive scan over the lanes' totals
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t t1 = __shfl_up(e1, d, kWave), t2 = __shfl_up(e2, d, kWave);
-        if (lane >= d) {
-            e1 += t1;
-            e2 += t2;
-        }
-    }
-    uint32_t r1 = e1 - a1, r2 = e2 - a2;                // exclusive: sum of everything left of xa
+    // exclusive over the lanes' totals: sum of everything left of xa
+    uint32_t r1 = wave_inclusive(a1, lane) - a1, r2 = wave_inclusive(a2, lane) - a2;
     for (int x = xa; x < xb; x++) {
         o1[x] = r1;
         o2[x] = r2;
