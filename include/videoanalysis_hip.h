@@ -182,6 +182,35 @@ int va_welford_u8(const uint8_t *frames_dev, double *mean_dev, double *m2_dev, i
 int va_temporal_ranks_u8(const uint8_t *frames_dev, int t, size_t px, size_t frame_stride,
                          const int32_t *ranks_host, int nranks, uint8_t *out_dev, void *stream);
 
+/* ------------------------------------------------------------------ A2c sliding-window median
+ * replaces  one va_temporal_ranks_u8 call per emitted frame on the window of the `window` frames before it
+ *           (np.median over a sliding_window_view of a downloaded stack); the reference has no counterpart.
+ * For every pixel and absolute frame index k = n_seen + j, j = 0 .. n - 1, with cnt = min(k, window):
+ *   lower[j] = sort(frames[max(0, k - window) .. k - 1])[(cnt - 1) / 2],  upper[j] = the same at rank cnt / 2
+ *   (both 0 at k = 0, the empty window);  diff[j] = min(255, |2 frame[k] - lower[j] - upper[j]| >> 1),
+ *   which is sat_u8(trunc(|frame - median|)) for the float median (lower + upper) / 2.  All integer, all exact.
+ * After its outputs are taken, frame k enters the window and frame k - window leaves it.
+ * frames_dev: n planes of px bytes, plane j at frames_dev + j * frame_stride.  1 <= window <= 65535, px >= 1, n >= 0
+ * (n = 0 writes nothing), frame_stride >= px, n_seen >= 0: the frames folded into the state so far, which the caller
+ * counts (as for va_bg_update).  state_dev: va_sliding_median_state_bytes(px, window) bytes of the caller's device
+ * memory on a 16-byte boundary, opaque between calls; all zeros (va_memset) is the empty state of n_seen = 0.  Per
+ * tile of 128 pixels it holds a bin-major histogram [256][128] (uint8 counters for window <= 255, uint16 above),
+ * the tracker planes lower, upper (u8) and below (u16), and behind the tiles a ring of the last `window` frames,
+ * frame k in slot k % window: 260 + window bytes a pixel (516 + window above 255), in whole tiles.  A state belongs
+ * to one (px, window); state_bytes is 0 for arguments outside the ranges above.
+ * Each of lower / upper / diff_out_dev is (n, px) uint8 or NULL: exactly n * px bytes are written per non-NULL output,
+ * nothing beyond byte px - 1 of a plane is read, and two identical call sequences from a zero state leave identical
+ * outputs and identical state bytes, however the frames are split into calls.  Dword accesses where frames_dev,
+ * frame_stride, px and the outputs are all multiples of 4, byte accesses otherwise.  One launch a call.
+ * va_sliding_median_current writes the planes of the window as it stands (what the next frame would get as lower /
+ * upper), (px) uint8 each or NULL.  Anything outside the ranges above is VA_ERR_INVALID, and nothing is written. */
+size_t va_sliding_median_state_bytes(size_t px, int window);
+int va_sliding_median_u8(const uint8_t *frames_dev, int n, size_t px, size_t frame_stride, int window,
+                         int64_t n_seen, void *state_dev, uint8_t *lower_out_dev, uint8_t *upper_out_dev,
+                         uint8_t *diff_out_dev, void *stream);
+int va_sliding_median_current(const void *state_dev, size_t px, int window, int64_t n_seen,
+                              uint8_t *lower_out_dev, uint8_t *upper_out_dev, void *stream);
+
 /* ------------------------------------------------------------------ A3 / A4 / A5 pointwise
  * Shape: the calls that take `count` or `pixels` see one flat array of any length >= 0; va_prepare_u8,
  * va_rot90: any n >= 0 and frames of any h, w >= 1 (a crop must lie inside its source frame).

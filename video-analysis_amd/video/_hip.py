@@ -92,6 +92,9 @@ SIGNATURES = {
     "va_mean_any": (_i, [_vp, _i, _vp, _i64, _i, _sz, _vp]),
     "va_welford_any": (_i, [_vp, _i, _vp, _vp, _i64, _i, _sz, _vp]),
     "va_temporal_ranks_u8": (_i, [_vp, _i, _sz, _sz, _vp, _i, _vp, _vp]),
+    "va_sliding_median_state_bytes": (_sz, [_sz, _i]),
+    "va_sliding_median_u8": (_i, [_vp, _i, _sz, _sz, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "va_sliding_median_current": (_i, [_vp, _sz, _i, _i64, _vp, _vp, _vp]),
     "va_time_difference_u8": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "va_threshold_u8": (_i, [_vp, _vp, _sz, _i, _i, _vp]),
     "va_mono_mean_u8": (_i, [_vp, _vp, _sz, _vp]),

@@ -821,6 +821,123 @@ class FilterMedianBackground(FilterBackground):
                                                      background=measure_median(source, max_frames=frames))
 
 
+class FilterSlidingMedianBackground(_SequentialStateFilter):
+    """BUILD-DEFINED background subtraction against the exact median of the `window` frames before each frame
+    (ops.SlidingMedian; DESIGN.md §9, "Sliding median"): frame k -> sat_u8(trunc(|frame_k - median(frames
+    max(0, k - window) .. k - 1)|)), FilterBackground's rule, with the median of the empty window 0 as mode 'mean'
+    has bg_{-1} = 0.  Lighting drift is followed; an object that rests for less than half the window is not absorbed.
+
+    On a seekable source, reads compute `batch` frames in one launch and serve the following frames from it; other
+    sources go frame by frame.  A seek replays only the `window` frames before its target, not the history from
+    frame 0.  uint8 frames; 1 <= window <= 65535.  The filter is no stage of a contracted chain."""
+
+    batch = 32          # frames per GPU call (seekable sources)
+
+    def __init__(self, source, window=101):
+        self.window = ops._check_window(window, "FilterSlidingMedianBackground")
+        self._model = None
+        self._cache, self._cache_start = None, 0
+        self._reader_pos = 0
+        super(FilterSlidingMedianBackground, self).__init__(source)
+
+    def _frames(self, start, stop):
+        frames = np.stack([np.asarray(self._source.get_frame(k)) for k in range(start, stop)])
+        if frames.dtype != np.uint8:
+            raise TypeError("FilterSlidingMedianBackground expects uint8 frames, got %s" % frames.dtype)
+        return frames
+
+    def _reset_state(self):
+        if self._model is None:
+            self._model = ops.SlidingMedian(self.shape[1:], self.window)
+        else:
+            self._model.reset()
+
+    def _advance_state(self, frames):
+        self._model.process(frames, want=())
+
+    def _emit(self, frame):
+        if frame.dtype != np.uint8:
+            raise TypeError("FilterSlidingMedianBackground expects uint8 frames, got %s" % frame.dtype)
+        return self._model.process(frame[None])["diff"][0]
+
+    def _seek_state(self, index):
+        """the window of frame `index` from the empty state: its frames alone, in calls of `batch` (an empty window
+        and the `window` frames before `index` leave the same histogram and tracker as the whole history does)"""
+        self._reset_state()
+        first = max(0, index - self.window)
+        for a in range(first, index, max(1, int(self.batch))):
+            self._advance_state(self._frames(a, min(index, a + max(1, int(self.batch)))))
+        self._state_pos = index
+
+    def _batched(self, index):
+        """frame `index` of the filter from the current batch, computing the batch that starts there if needed"""
+        if self._cache is None or not 0 <= index - self._cache_start < len(self._cache["diff"]):
+            if self._model is None or index != getattr(self, "_state_pos", None):
+                self._seek_state(index)
+            stop = min(self.frame_count, index + max(1, int(self.batch)))
+            self._cache = None
+            self._cache = self._model.process(self._frames(index, stop), want=("diff", "lower", "upper"))
+            self._cache_start, self._state_pos = index, stop
+        return self._cache["diff"][index - self._cache_start]
+
+    def set_frame_pos(self, index):
+        if not self._source.seekable:
+            super(FilterSlidingMedianBackground, self).set_frame_pos(index)
+        else:
+            if index < 0:
+                index += self.frame_count
+            if not 0 <= index < self.frame_count:
+                raise IndexError("Seeking to frame %d was not possible." % index)
+            self._frame_pos = index
+        self._reader_pos = self._frame_pos
+
+    def get_frame(self, index):
+        if not self._source.seekable:
+            out = super(FilterSlidingMedianBackground, self).get_frame(index)
+            self._reader_pos = self._frame_pos + 1
+            return out
+        if index < 0:
+            index += self.frame_count
+        if not 0 <= index < self.frame_count:
+            raise IndexError("frame %d is out of range" % index)
+        out = self._batched(index)
+        self._frame_pos, self._reader_pos = index, index + 1
+        return self._process_frame(out)
+
+    def get_next_frame(self):
+        if not self._source.seekable:
+            out = super(FilterSlidingMedianBackground, self).get_next_frame()
+            self._reader_pos = self._frame_pos
+            return out
+        if self._frame_pos >= self.frame_count:
+            raise StopIteration
+        out = self._batched(self._frame_pos)
+        self._frame_pos += 1
+        self._reader_pos = self._frame_pos
+        return self._process_frame(out)
+
+    @property
+    def background(self):
+        """the float64 median at the reader's position p -- behind the last frame read, or where a seek went: that of
+        the frames max(0, p - window) .. p - 1 (zeros at p = 0).  The model works a batch ahead of the reader; the
+        planes of a position inside the batch come from the batch."""
+        pos = self._reader_pos
+        if self._cache is not None and 0 <= pos - self._cache_start < len(self._cache["diff"]):
+            at = pos - self._cache_start
+            return ops.median_of_ranks(self._cache["lower"][at], self._cache["upper"][at])
+        if self._model is None or pos != getattr(self, "_state_pos", None):
+            if not self._source.seekable and self._model is not None:
+                raise ValueError("FilterSlidingMedianBackground: a forward-only source cannot be replayed")
+            self._seek_state(pos)
+        return self._model.median
+
+    def close(self, propagate=True):
+        model, self._model, self._cache = self._model, None, None
+        if model is not None:
+            model.close()
+        super(FilterSlidingMedianBackground, self).close(propagate)
+
+
 class FilterAnalysisChain(_SequentialStateFilter):
     """BUILD-DEFINED: the whole chain, fused and batched on the GPU.
 

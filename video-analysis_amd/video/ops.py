@@ -491,6 +491,149 @@ def temporal_percentiles(frames, q, method="lower", step=1):
     return out[0] if scalar else out
 
 
+# ------------------------------------------------------------------------ sliding-window median
+SLIDING_MAX_WINDOW = 65535       # kMaxWindow of va_sliding_median_math.h: a uint16 counter holds the whole window
+SLIDING_WANTS = ("diff", "lower", "upper", "median")
+
+
+def _check_window(window, what):
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= SLIDING_MAX_WINDOW:
+        raise ValueError("%s: window is an integer 1 .. %d, got %r" % (what, SLIDING_MAX_WINDOW, window))
+    return int(window)
+
+
+class SlidingMedian(object):
+    """the exact median of the `window` frames before each frame of a uint8 stream, streaming ("Sliding
+    median"; va_sliding_median_u8).  The object holds the device state -- per-pixel histograms, the rank tracker and a
+    ring of the last `window` frames, allocated once -- and n_seen, the frames folded in so far.
+
+    For frame k: lower[k] / upper[k] are the sorted window max(0, k - window) .. k - 1 at ranks (cnt - 1) // 2 and
+    cnt // 2 (cnt = min(k, window); both 0 for the empty window), median = (lower + upper) / 2 in float64 = np.median
+    of the window, diff = sat_u8(trunc(|frame - median|)), FilterBackground's rule.  Then frame k enters the window.
+    frame_shape: (h, w) or (h, w, 3); 1 <= window <= 65535."""
+
+    def __init__(self, frame_shape, window, stream=None):
+        shape = tuple(int(v) for v in frame_shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3) or min(shape) < 1:
+            raise ValueError("SlidingMedian: frames are (h, w) or (h, w, 3) with at least one pixel, got %r"
+                             % (frame_shape,))
+        self.window = _check_window(window, "SlidingMedian")
+        self.frame_shape, self.px, self.stream = shape, math.prod(shape), stream
+        self.n_seen = 0
+        L = _hip.lib()
+        self.state_bytes = int(L.va_sliding_median_state_bytes(self.px, self.window))
+        if self.state_bytes < 1:
+            raise ValueError("SlidingMedian: no state for %d pixels and a window of %d" % (self.px, self.window))
+        self._state = _take(self.state_bytes)
+        self.reset()
+
+    def reset(self):
+        """back to the empty window"""
+        check(_hip.lib().va_memset(self._state.ptr, 0, self.state_bytes, self.stream))
+        self.n_seen = 0
+
+    def close(self):
+        """hands the state back to the pool (after a synchronisation: a launch may still use it)"""
+        state, self._state = getattr(self, "_state", None), None
+        if state is not None:
+            check(_hip.lib().va_stream_sync(self.stream))
+            _give(state)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, frames, want=("diff",), keep=False):
+        """folds `frames` -- a uint8 array (n, *frame_shape) or a DeviceFrames of that shape, which is not changed --
+        into the window and returns {name: planes} for the names in `want`, any of 'diff', 'lower', 'upper' (uint8,
+        (n, *frame_shape)) and 'median' (float64); want=() updates the state only.  keep=True returns the uint8 planes
+        as DeviceFrames, the caller's to release ('median' is computed on the host and cannot be kept)."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for name in want:
+            if name not in SLIDING_WANTS:
+                raise ValueError("SlidingMedian.process: want holds any of %r, got %r" % (SLIDING_WANTS, name))
+        if keep and "median" in want:
+            raise ValueError("SlidingMedian.process: 'median' is float64 from the host and cannot be kept")
+        src, n, h, w, c, _ = _frames_in(frames, "SlidingMedian.process")
+        if (h, w) + ((3,) if c == 3 else ()) != self.frame_shape:
+            raise ValueError("SlidingMedian.process: frames of shape %r do not match %r"
+                             % ((h, w) + ((3,) if c == 3 else ()), self.frame_shape))
+        if self._state is None:
+            raise ValueError("SlidingMedian.process: the model is closed")
+        planes = [name for name in ("lower", "upper", "diff")
+                  if name in want or (name != "diff" and "median" in want)]
+        if n == 0:                                           # nothing enters the window
+            if keep:
+                return {name: DeviceFrames(_take(1), 0, h, w, c) for name in want}
+            return {name: np.zeros((0,) + self.frame_shape, np.float64 if name == "median" else np.uint8)
+                    for name in want}
+        L, nbytes = _hip.lib(), n * self.px
+        with _Lease.on(self.stream) as d:
+            ptr = src.buf.ptr if isinstance(src, DeviceFrames) else d.upload(src).ptr
+            bufs = {name: (d.result(nbytes) if keep else d.take(nbytes)) for name in planes}
+            check(L.va_sliding_median_u8(ptr, n, self.px, self.px, self.window, self.n_seen, self._state.ptr,
+                                         _ptr(bufs.get("lower")), _ptr(bufs.get("upper")), _ptr(bufs.get("diff")),
+                                         self.stream))
+            self.n_seen += n
+            if keep:
+                check(L.va_stream_sync(self.stream))        # the uploaded frames go back to the pool with the lease
+                return {name: DeviceFrames(bufs[name], n, h, w, c) for name in want}
+            host = {name: buf.download((n,) + self.frame_shape, np.uint8, self.stream) for name, buf in bufs.items()}
+            if not host:
+                check(L.va_stream_sync(self.stream))
+        out = {name: host[name] for name in want if name != "median"}
+        if "median" in want:
+            out["median"] = median_of_ranks(host["lower"], host["upper"])
+        return out
+
+    def _current(self):
+        L = _hip.lib()
+        with _Lease.on(self.stream) as d:
+            lo, up = d.take(self.px), d.take(self.px)
+            check(L.va_sliding_median_current(self._state.ptr, self.px, self.window, self.n_seen, lo.ptr, up.ptr,
+                                              self.stream))
+            return (lo.download(self.frame_shape, np.uint8, self.stream),
+                    up.download(self.frame_shape, np.uint8, self.stream))
+
+    @property
+    def lower(self):
+        """the window as it stands at rank (cnt - 1) // 2: what the next frame would get as `lower`"""
+        return self._current()[0]
+
+    @property
+    def upper(self):
+        return self._current()[1]
+
+    @property
+    def median(self):
+        """np.median of the frames in the window now, float64 (zeros for the empty window)"""
+        return median_of_ranks(*self._current())
+
+
+def sliding_median(frames, window, stream=None):
+    """out[k] = np.median(frames[max(0, k - window + 1):k + 1], axis=0): the trailing medians of a uint8 stack (or a
+    DeviceFrames), frame k included, float64 (n, h, w[, 3]), bit for bit.  One SlidingMedian pass: the planes before
+    frame k + 1 are those of the window that ends with frame k, and the last ones are the state's current planes."""
+    src, n, h, w, c, _ = _frames_in(frames, "sliding_median")
+    window = _check_window(window, "sliding_median")
+    fshape = (h, w) + ((3,) if c == 3 else ())
+    if h * w == 0:
+        raise ValueError("sliding_median: the stack %r holds no pixels" % ((n, h, w, c),))
+    if n == 0:
+        return np.zeros((0,) + fshape, np.float64)
+    model = SlidingMedian(fshape, window, stream)
+    try:
+        before = model.process(src, want=("lower", "upper"))
+        now = model._current()
+        lower = np.concatenate([before["lower"][1:], now[0][None]])
+        upper = np.concatenate([before["upper"][1:], now[1][None]])
+    finally:
+        model.close()
+    return median_of_ranks(lower, upper)
+
+
 def time_difference(this_frame, prev_frame):
     """this.astype(int16) - prev  (FilterTimeDifference, video/filters.py:564-568)"""
     a = np.ascontiguousarray(this_frame, np.uint8)
