@@ -102,17 +102,22 @@ int va_host_free(void *host_ptr);
 /* Host <-> device copies.  Pinned host memory (va_host_alloc, or registered by the caller): asynchronous on `stream`.
  * Pageable host memory (a NumPy array): the call waits for the stream's earlier work and returns when the copy is
  * complete -- large asynchronous copies to pageable memory were seen to leave part of the destination unwritten
- * after the stream had been synchronised. */
+ * after the stream had been synchronised.  So with pageable memory each of the two synchronises
+ * `stream`, in front of the copy; the copy sees, or delivers, what the stream's earlier work has written. */
 int va_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, void *stream);
 int va_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, void *stream);
+/* device to device, and a byte fill: enqueued on `stream`, never waited for */
 int va_memcpy_d2d(void *dst_dev, const void *src_dev, size_t bytes, void *stream);
 int va_memset(void *dst_dev, int value, size_t bytes, void *stream);
+/* synchronises `stream`: returns when everything enqueued on it so far is complete */
 int va_stream_sync(void *stream);
 
 /* streams and events, for hosts that overlap uploads, the chain and downloads (the role of the
  * reference's reader process / VideoPreprocessor threads, video/io/parallel.py:345-488) */
 int va_stream_create(void **stream_out);
-int va_stream_destroy(void *stream);   /* waits for the stream, frees the scratch cached for it */
+/* synchronises `stream`, then frees the scratch cached for it and the stream */
+int va_stream_destroy(void *stream);
+/* events: recording and waiting are enqueued, only va_event_sync blocks the host */
 int va_event_create(void **event_out);
 int va_event_destroy(void *event);
 int va_event_record(void *event, void *stream);
@@ -272,7 +277,11 @@ int va_rot90(const void *src_dev, void *dst_dev, int n, int h, int w, int elem_b
  * same algorithms -- float coefficients, products summed from the first tap to the last, no rounding.
  * Shape: any n >= 0 (more than 65535 frames go out in pieces); source frames of any src_h, src_w >= 1; targets of
  * dst_w >= 1 and 1 <= dst_h <= 65535 (the kernels count target rows in gridDim.y): a taller target is refused
- * with VA_ERR_INVALID before the tables are uploaded. */
+ * with VA_ERR_INVALID before the tables are uploaded.
+ * Each call synchronises `stream` once, before it uploads its coefficient tables: the upload is a blocking copy from
+ * the host into leased scratch, which the stream's earlier kernels may still read.  The kernels are then enqueued
+ * on `stream` and the call returns without waiting for them.  (An area shrink by integer factors, which the exact
+ * 2 x 2 linear shrink is too, has no tables and waits for nothing.) */
 #define VA_INTER_NEAREST 0
 #define VA_INTER_LINEAR 1
 #define VA_INTER_CUBIC 2
@@ -474,8 +483,9 @@ size_t va_farneback_workspace_bytes(int n, int h, int w, double pyr_scale, int l
  * poly_n 5 or 7, flags 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not supported), else
  * VA_ERR_INVALID; a workspace smaller than va_farneback_workspace_bytes is VA_ERR_RANGE.  Shape: 2 <= n, at most
  * 65535 frames and at most 65535 rows in one call (both count in gridDim.y / gridDim.z of the pyramid kernels, and
- * a pair needs both of its frames in one call), any w >= 1; beyond: VA_ERR_INVALID, nothing enqueued.  The call drains
- * `stream` before it uploads its resize tables, then enqueues its kernels on it. */
+ * a pair needs both of its frames in one call), any w >= 1; beyond: VA_ERR_INVALID, nothing enqueued.  The call
+ * synchronises `stream` before it uploads its resize tables (a blocking copy from the host into leased scratch that
+ * the stream's earlier kernels may still read), then enqueues its kernels on it. */
 int va_optical_flow_farneback(const void *frames_dev, int dtype, int n, int h, int w, double pyr_scale,
                               int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                               float *flow_out_dev, float *mag_out_dev, void *workspace_dev,
@@ -1111,7 +1121,7 @@ int va_detect_peaks_f32(const float *src_dev, uint8_t *dst_dev, int n, int h, in
  *           eroded = cv2.erode(img); temp = cv2.dilate(eroded); cv2.subtract(img, temp, temp);
  *           cv2.bitwise_or(skel, temp, skel); img = eroded   ... until img is empty.
  * img_dev is consumed (used as ping-pong scratch with scratch_dev); skel_dev receives the
- * skeleton.  Synchronises the stream once per 16 iterations (the loop's exit test reads one
+ * skeleton.  Synchronises `stream` once per 16 iterations (the loop's exit test reads one
  * survivor counter per iteration; steps past the emptying one change nothing). */
 int va_mask_thinning_u8(uint8_t *img_dev, uint8_t *scratch_dev, uint8_t *skel_dev, int h, int w,
                         int *iterations_out, void *stream);

@@ -12,6 +12,9 @@ product (tests/test_gpu_pointer_offsets.py).
 Each case carries, in `gate`, the file and condition of the pointer gate it crosses (or "none": a control case for an
 entry point that has no gate today).  Shapes are the smallest at which aligned pointers take the vector kernel, so
 that the offset alone changes the path, plus one that takes the byte kernel anyway.
+
+The stream-order suite (tests/stream_order_cases.py; DESIGN.md, "Stream order") runs the same table on a created
+stream: every call passes `ON.stream`, which is None here, and every data plane has a decoy (`Arg.decoy`).
 """
 import ctypes as C
 import importlib.util
@@ -31,6 +34,15 @@ U8_LATE, F32_LATE = (0, 1), (0, 4)      # the offsets of a control case: an entr
 VA_ERR_INVALID = -22
 VA_U8, VA_F32, VA_F64, VA_I16 = 0, 1, 2, 3
 BG_MEAN, BG_EMA, BG_STATIC = 1, 2, 3
+
+
+class _On(object):
+    """the stream every case's call is enqueued on: None (the null stream) unless a runner sets another for the time
+    of its run (tests/stream_order_cases.py)"""
+    stream = None
+
+
+ON = _On()
 
 
 def generator(name):
@@ -124,10 +136,16 @@ class Arg(object):
     reference), "inout" (uploaded and compared), "work" (entered late and guarded, contents unspecified afterwards:
     consumed inputs and caller scratch), "scratch" (never late: int64 tables and workspaces, whose alignment the
     header asks for).  array: the payload ("in", "inout", optionally "work"), or a function of the oracle that makes
-    it on first use (then nbytes and itemsize are given); nbytes may be a function of the library (workspace sizes)."""
+    it on first use (then nbytes and itemsize are given); nbytes may be a function of the library (workspace sizes).
+    decoy: a second valid payload of the same shape and dtype for the stream-order runner: None = the payload in
+    reverse element order for the data planes ("in", "inout", "work" with a payload; reversal keeps the value domain),
+    False = none, or an array.  Tables ("scratch") never have one: a kernel that ran ahead of its inputs must find
+    nothing it could use as an address or a trip count but what the case itself passes."""
 
-    def __init__(self, name, role, array=None, nbytes=None, itemsize=None, offsets=None):
+    def __init__(self, name, role, array=None, nbytes=None, itemsize=None, offsets=None, decoy=None):
         self.name, self.role = name, role
+        assert decoy is None or decoy is False or role != "scratch", name
+        self._decoy = decoy
         self.array = array if array is None or callable(array) else np.ascontiguousarray(array)
         self._nbytes = self.array.nbytes if nbytes is None else nbytes
         itemsize = itemsize or (self.array.itemsize if isinstance(self.array, np.ndarray) else 1)
@@ -141,6 +159,16 @@ class Arg(object):
             self.array = np.ascontiguousarray(self.array(oracle))
             self.array.setflags(write=False)
 
+    def decoy(self):
+        """the decoy payload (after resolve()), or None"""
+        if self._decoy is False or self.role in ("out", "scratch") or not isinstance(self.array, np.ndarray):
+            return None
+        if self._decoy is None:
+            return np.ascontiguousarray(self.array.reshape(-1)[::-1]).reshape(self.array.shape)
+        decoy = np.ascontiguousarray(self._decoy)
+        assert decoy.shape == self.array.shape and decoy.dtype == self.array.dtype, self.name
+        return decoy
+
 
 def out(name, shape, dtype, offsets=None):
     return Arg(name, "out", nbytes=int(np.prod(shape)) * np.dtype(dtype).itemsize, itemsize=np.dtype(dtype).itemsize,
@@ -153,12 +181,16 @@ class Case(object):
     array} for every "out" / "inout" buffer; setup(lib) -> ctx and teardown(lib, ctx): hooks and handles around the
     offsets of the case; rejects(late) -> True: the call must return VA_ERR_INVALID, name the alignment and leave
     every buffer as it was; False (the default): it must succeed; None: either, never a wrong result; project: {name:
-    function(array, refs)} applied to both sides before they are compared (the defined part of an output)."""
+    function(array, refs)} applied to both sides before they are compared (the defined part of an output);
+    prepare(lib, ctx): host-side state put back before every call, outside the call itself (it may synchronise);
+    rejoin(lib, ctx, stream): makes `stream` wait for whatever the call enqueued elsewhere (a pipeline's side stream)."""
 
-    def __init__(self, name, entries, gate, args, call, ref, setup=None, teardown=None, rejects=None, project=None):
+    def __init__(self, name, entries, gate, args, call, ref, setup=None, teardown=None, rejects=None, project=None,
+                 prepare=None, rejoin=None):
         self.name, self.gate, self.args, self.call, self.ref = name, gate, list(args), call, ref
         self.entries = (entries,) if isinstance(entries, str) else tuple(entries)
         self.setup, self.teardown, self.rejects, self.project = setup, teardown, rejects, project or {}
+        self.prepare, self.rejoin = prepare, rejoin
 
     def runs_on(self, lib):
         return all(hasattr(lib, e) for e in self.entries)
@@ -223,6 +255,8 @@ def run_case(be, case, oracle, sentinels=SENTINELS):
                 ptr = {a.name: bufs[a.name].arm(late[a.name], sentinel,
                                                 a.array if a.role != "out" else None)
                        for a in case.args}
+                if case.prepare:
+                    case.prepare(L, ctx)
                 rc = case.call(L, ptr, ctx)
                 calls += 1
                 message = L.va_last_error().decode("utf-8", "replace") if rc else ""
@@ -307,27 +341,27 @@ for _count in (4096, 4096 + 16 + 3):
         _add("threshold_u8[%d]" % count, "va_threshold_u8",
              "va_point.hip launch_threshold_u8: aligned(src, 16) && aligned(dst, 16)",
              [Arg("src", "in", a), out("dst", a.shape, np.uint8)],
-             lambda L, p, _: L.va_threshold_u8(p["src"], p["dst"], count, 100, 255, None),
+             lambda L, p, _: L.va_threshold_u8(p["src"], p["dst"], count, 100, 255, ON.stream),
              lambda O: {"dst": O.threshold_u8(a, 100)})
         # gate: va_point.hip launch_time_difference, `aligned(a, 8) && aligned(b, 8) && aligned(out, 16)`
         _add("time_difference_u8[%d]" % count, "va_time_difference_u8",
              "va_point.hip launch_time_difference: aligned(a, 8) && aligned(b, 8) && aligned(out, 16)",
              [Arg("a", "in", a), Arg("b", "in", b), out("out", a.shape, np.int16)],
-             lambda L, p, _: L.va_time_difference_u8(p["a"], p["b"], p["out"], count, None),
+             lambda L, p, _: L.va_time_difference_u8(p["a"], p["b"], p["out"], count, ON.stream),
              lambda O: {"out": O.time_difference_u8(a, b)})
         # gate: va_synth.hip:271 launch_pointwise_u8_x4 (dst % 4), and :107, the kernel's per-row `row_aligned` test of src;
         # slow side: normalize_u8_kernel, one byte per thread
         _add("normalize_u8[%d]" % count, "va_normalize_u8",
              "va_synth.hip:271 launch_pointwise_u8_x4: dst % 4; :107 row_aligned(src) in prepare_u8_x4_kernel",
              [Arg("src", "in", a), out("dst", a.shape, np.uint8)],
-             lambda L, p, _: L.va_normalize_u8(p["src"], p["dst"], count, 30.0, 200.0, alpha, 0.0, None),
+             lambda L, p, _: L.va_normalize_u8(p["src"], p["dst"], count, 30.0, 200.0, alpha, 0.0, ON.stream),
              lambda O: {"dst": ((np.clip(a.astype(np.float64), 30, 200) - 30) * alpha + 0).astype(np.int64)
                         .astype(np.uint8)})
         # gate: the same launcher with three channels; slow side: mono_mean_kernel
         _add("mono_mean_u8[%d]" % count, "va_mono_mean_u8",
              "va_synth.hip:271 launch_pointwise_u8_x4 (3 channels): dst % 4; :107 row_aligned(src)",
              [Arg("src", "in", col), out("dst", (count,), np.uint8)],
-             lambda L, p, _: L.va_mono_mean_u8(p["src"], p["dst"], count, None),
+             lambda L, p, _: L.va_mono_mean_u8(p["src"], p["dst"], count, ON.stream),
              lambda O: {"dst": O.mono_mean_u8(col)})
     _pointwise()
 
@@ -353,7 +387,7 @@ def _prepare_cases():
                          [Arg("src", "in", src), out("dst", shape, np.uint8)],
                          lambda L, p, _, sw=sw, left=left, mono=mono, norm=norm: L.va_prepare_u8(
                              p["src"], p["dst"], 2, 12, sw, 3, left, 1, 60, 10, mono, norm, 30.0, 200.0, alpha, 0.0,
-                             None),
+                             ON.stream),
                          ref)
 
 
@@ -386,37 +420,37 @@ def _temporal_cases():
              "va_point.hip launch_bg (EMA u8): px % 16 == 0 && aligned(fr, 16) && aligned(df, 16)",
              [Arg("frames", "in", fr8), out("diff", fr8.shape, np.uint8), Arg("state", "inout", np.zeros(shape, np.float32))],
              two_calls(lambda L, p, f, d, seen, n, px=px: L.va_bg_update(BG_EMA, VA_U8, f, d, p["state"], seen, 0.05, n,
-                                                                         px, None), 1),
+                                                                         px, ON.stream), 1),
              lambda O, fr8=fr8: dict(zip(("diff", "state"), O.bg_ema_u8(fr8, rate=0.05))))
         _add("bg_update[ema,f32,%s]" % tag, "va_bg_update",
              "va_point.hip:747 launch_bg (EMA f32): px % 4 == 0 && aligned(fr, 16) && aligned(df, 16)",
              [Arg("frames", "in", fr32), out("diff", fr32.shape, np.float32),
               Arg("state", "inout", np.zeros(shape, np.float32))],
              two_calls(lambda L, p, f, d, seen, n, px=px: L.va_bg_update(BG_EMA, VA_F32, f, d, p["state"], seen, 0.05, n,
-                                                                         px, None), 4),
+                                                                         px, ON.stream), 4),
              lambda O, fr32=fr32: dict(zip(("diff", "state"), O.bg_ema_f32(fr32, rate=0.05))))
         _add("bg_update[static,%s]" % tag, "va_bg_update",
              "va_point.hip launch_bg (static): px % 8 == 0 && aligned(fr, 8) && aligned(df, 8)",
              [Arg("frames", "in", fr8), out("diff", fr8.shape, np.uint8), Arg("state", "in", static)],
              two_calls(lambda L, p, f, d, seen, n, px=px: L.va_bg_update(BG_STATIC, VA_U8, f, d, p["state"], seen, 0.0,
-                                                                         n, px, None), 1),
+                                                                         n, px, ON.stream), 1),
              lambda O, fr8=fr8, static=static: {"diff": O.bg_static_u8(fr8, static)})
         # gate: va_point.hip:768 launch_welford, `px % 8 == 0 && aligned(frames, 8)`
         _add("welford_u8[%s]" % tag, "va_welford_u8", "va_point.hip:768 launch_welford: px % 8 == 0 && aligned(frames, 8)",
              [Arg("frames", "in", fr8), Arg("mean", "inout", np.zeros(shape)), Arg("m2", "inout", np.zeros(shape))],
-             two_calls(lambda L, p, f, d, seen, n, px=px: L.va_welford_u8(f, p["mean"], p["m2"], seen, n, px, None), 1),
+             two_calls(lambda L, p, f, d, seen, n, px=px: L.va_welford_u8(f, p["mean"], p["m2"], seen, n, px, ON.stream), 1),
              lambda O, fr8=fr8: dict(zip(("mean", "m2"), O.welford_u8(fr8))))
         for code, fr, name in ((VA_U8, fr8, "u8"), (VA_I16, fr16, "i16"), (VA_F32, fr32, "f32")):
             # no gate: one element per thread (control)
             _add("mean_any[%s,%s]" % (name, tag), "va_mean_any", "none (va_point.hip temporal_stats_kernel: control)",
                  [Arg("frames", "in", fr), Arg("mean", "inout", np.zeros(shape))],
                  two_calls(lambda L, p, f, d, seen, n, px=px, code=code: L.va_mean_any(f, code, p["mean"], seen, n, px,
-                                                                                       None), fr.itemsize),
+                                                                                       ON.stream), fr.itemsize),
                  lambda O, fr=fr: {"mean": O.mean_any(fr)})
             _add("welford_any[%s,%s]" % (name, tag), "va_welford_any", "none (va_point.hip temporal_stats_kernel: control)",
                  [Arg("frames", "in", fr), Arg("mean", "inout", np.zeros(shape)), Arg("m2", "inout", np.zeros(shape))],
                  two_calls(lambda L, p, f, d, seen, n, px=px, code=code: L.va_welford_any(f, code, p["mean"], p["m2"],
-                                                                                          seen, n, px, None), fr.itemsize),
+                                                                                          seen, n, px, ON.stream), fr.itemsize),
                  lambda O, fr=fr: dict(zip(("mean", "m2"), O.welford_any(fr))))
 
 
@@ -434,7 +468,7 @@ def _rank_cases():
                  "va_median.hip:100: aligned(frames, 4) && aligned(out, 4) && frame_stride % 4 == 0 && px % 4 == 0",
                  [Arg("frames", "in", fr), out("out", (3, px), np.uint8)],
                  lambda L, p, _, t=t, px=px, ranks=ranks: L.va_temporal_ranks_u8(p["frames"], t, px, px, ranks.ctypes.data,
-                                                                                 3, p["out"], None),
+                                                                                 3, p["out"], ON.stream),
                  lambda O, fr=fr, ranks=ranks: {"out": np.sort(fr, axis=0)[ranks]})
 
 
@@ -448,7 +482,7 @@ def _gaussian_cases():
         n, h, w = shape[:3]
         c = shape[3] if len(shape) == 4 else 1
         _add(name, entry, gate, [Arg("src", "in", im), out("dst", shape, np.uint8, dst_offsets)],
-             lambda L, p, _: getattr(L, entry)(p["src"], p["dst"], n, h, w, c, sigma, None),
+             lambda L, p, _: getattr(L, entry)(p["src"], p["dst"], n, h, w, c, sigma, ON.stream),
              lambda O: {"dst": O.gaussian_u8(im, sigma)}, rejects=rejects)
 
     plan = "va_gauss.hip:370 gaussian_call: src % 16 == 0 && dst % 4 == 0 picks the single-pass families"
@@ -485,7 +519,7 @@ def _gaussian_cases():
                                                                                         if hook else ()),
                  "va_gauss.hip:370 gaussian_call (f32): src % 16; va_gauss_f32.hip:466 vec4, :471 vec4s, :479 vec4c (dst % 8)",
                  [Arg("src", "in", f), out("dst", f.shape, np.float32)],
-                 lambda L, p, _, w=w: L.va_gaussian_f32(p["src"], p["dst"], 2, 40, w, 1, 2.0, None),
+                 lambda L, p, _, w=w: L.va_gaussian_f32(p["src"], p["dst"], 2, 40, w, 1, 2.0, ON.stream),
                  lambda O, f=f: {"dst": O.gaussian_f32(f, 2.0)},
                  setup=setup if hook else None,
                  teardown=(lambda L, _: L.va_test_hook_gaussian_f32(0)) if hook else None)
@@ -505,16 +539,16 @@ def _morph_cases():
                      "va_morph.hip:770 grey morphology: w % 4 == 0 && src % 4 == 0 && dst % 4 == 0",
                      [Arg("src", "in", g), out("dst", g.shape, np.uint8)],
                      lambda L, p, _, w=w, op=op, shape=shape, k=k: L.va_morph_u8(p["src"], p["dst"], 2, 24, w, op, shape,
-                                                                                k, None),
+                                                                                k, ON.stream),
                      lambda O, g=g, op=op, shape=shape, k=k: {"dst": O.morph_u8(g, op, shape, k)})
     for w in (64, 70):
-        b = ((np.random.default_rng(w).random((2, 24, w)) < 0.45) * 255).astype(np.uint8)
+        b = blob_masks(2, 24, w, seed=w) * np.uint8(255)         # (blobs: neither op gives one value everywhere)
         for op, oname in ((0, "erode"), (1, "dilate")):
             # gates: va_morph.hip:531 (pack) `w % 32 == 0 && aligned(src, 16)`, :545 (unpack) `aligned(dst, 16)`
             _add("morph_bits_u8[%s,w%d]" % (oname, w), "va_morph_bits_u8",
                  "va_morph.hip:531 pack: w % 32 == 0 && aligned(src, 16); :545 unpack: w % 32 == 0 && aligned(dst, 16)",
                  [Arg("src", "in", b), out("dst", b.shape, np.uint8)],
-                 lambda L, p, _, w=w, op=op: L.va_morph_bits_u8(p["src"], p["dst"], 2, 24, w, op, 0, 5, None),
+                 lambda L, p, _, w=w, op=op: L.va_morph_bits_u8(p["src"], p["dst"], 2, 24, w, op, 0, 5, ON.stream),
                  lambda O, b=b, op=op: {"dst": O.morph_u8(b, op, 0, 5)})
 
 
@@ -568,8 +602,8 @@ def _label_cases():
                 def call(L, p, _, shape=shape, conn=conn):
                     n, h, w = shape
                     return _first(L.va_label_i32(p["mask"], p["labels"], p["counts"], n, h, w, conn, p["ws"],
-                                                 L.va_label_workspace_bytes(n, h, w), None),
-                                  L.va_moments_i64(p["labels"], n, h, w, MAX_LABELS, p["stats"], None))
+                                                 L.va_label_workspace_bytes(n, h, w), ON.stream),
+                                  L.va_moments_i64(p["labels"], n, h, w, MAX_LABELS, p["stats"], ON.stream))
                 hooked = path != "default"
                 # gates: the paint, va_ccl.hip:1804 `w % 4 == 0 && aligned(pl.labels, 16)` (16-byte stores), and the
                 # statistics of va_moments_i64 on the late label planes, va_ccl.hip:1534 `x1 - x0 == 32 && (w & 3) == 0
@@ -578,7 +612,8 @@ def _label_cases():
                 _add("label_i32+moments_i64[%s,conn%d,%s]" % (tag, conn, path),
                      ("va_label_i32", "va_moments_i64") + (("va_test_hook_labelling",) if hooked else ()),
                      "va_ccl.hip:1804 paint: w % 4 == 0 && aligned(pl.labels, 16); va_ccl.hip:1534 statistics: (labels & 15) == 0",
-                     [Arg("mask", "in", masks), out("labels", shape, np.int32), out("counts", (n,), np.int32),
+                     [Arg("mask", "in", masks, decoy=blob_masks(n, h, w, seed=w + 1)),     # (other masks: other counts)
+                      out("labels", shape, np.int32), out("counts", (n,), np.int32),
                       Arg("ws", "scratch", nbytes=lambda L, shape=shape: L.va_label_workspace_bytes(*shape)),
                       out("stats", (n, MAX_LABELS, 16), np.int64)],
                      call, lambda O, masks=masks, conn=conn: _label_reference(O, masks, conn),
@@ -597,7 +632,7 @@ def _label_cases():
                   out("largest", (n,), np.int32), out("area", (n,), np.int64), out("sel", shape, np.uint8)],
                  lambda L, p, _, shape=shape: L.va_largest_region(p["labels"], p["counts"], p["stats"], shape[0],
                                                                   shape[1], shape[2], MAX_LABELS, p["largest"],
-                                                                  p["area"], p["sel"], None),
+                                                                  p["area"], p["sel"], ON.stream),
                  lambda O, masks=masks, conn=conn: _largest_reference(O, masks, conn))
 
 
@@ -614,7 +649,7 @@ def _resize_rot_cases():
                  "va_resize.hip:438: c == 1 && dw % 4 == 0 && dst % 4 == 0",
                  [Arg("src", "in", a), out("dst", (2, dh, dw), np.uint8)],
                  lambda L, p, _, dh=dh, dw=dw, mode=mode: L.va_resize_u8(p["src"], p["dst"], 2, 24, 40, 1, dh, dw, mode,
-                                                                         None),
+                                                                         ON.stream),
                  lambda O, dh=dh, dw=dw, name=name: {"dst": O.resize_u8(a, (dw, dh), name)})
     for eb in (1, 3):
         r = _u8(90 + eb, 2, 9, 14, eb)
@@ -622,7 +657,7 @@ def _resize_rot_cases():
             # no gate: elements are moved one by one (control); elem_bytes 3 is the odd-sized struct
             _add("rot90[elem%d,k%d]" % (eb, k), "va_rot90", "none (va_point.hip rot90_kernel: control)",
                  [Arg("src", "in", r), out("dst", np.rot90(r, k, axes=(1, 2)).shape, np.uint8)],
-                 lambda L, p, _, eb=eb, k=k: L.va_rot90(p["src"], p["dst"], 2, 9, 14, eb, k, None),
+                 lambda L, p, _, eb=eb, k=k: L.va_rot90(p["src"], p["dst"], 2, 9, 14, eb, k, ON.stream),
                  lambda O, r=r, k=k: {"dst": np.rot90(r, k, axes=(1, 2))})
 
 
@@ -639,7 +674,7 @@ def _stencil_cases():
             _add("detect_peaks_u8[w%d,plateaus%d]" % (w, plateaus), "va_detect_peaks_u8",
                  "va_stencil.hip:416: w % 4 == 0 && src % 4 == 0 && dst % 4 == 0",
                  [Arg("src", "in", img), out("dst", img.shape, np.uint8)],
-                 lambda L, p, _, w=w, plateaus=plateaus: L.va_detect_peaks_u8(p["src"], p["dst"], 2, 12, w, plateaus, None),
+                 lambda L, p, _, w=w, plateaus=plateaus: L.va_detect_peaks_u8(p["src"], p["dst"], 2, 12, w, plateaus, ON.stream),
                  lambda O, img=img, plateaus=plateaus: {"dst": np.stack([O.detect_peaks(f, bool(plateaus)) for f in img])
                                                         .astype(np.uint8)})
         yy, xx = np.mgrid[:20, :w]
@@ -650,7 +685,7 @@ def _stencil_cases():
         _add("mask_thinning_u8[w%d]" % w, "va_mask_thinning_u8",
              "va_stencil.hip:468: w % 4 == 0 && img % 4 == 0 && eroded % 4 == 0 && skel % 4 == 0",
              [Arg("img", "work", m), Arg("tmp", "work", nbytes=m.size), out("skel", m.shape, np.uint8)],
-             lambda L, p, _, w=w: L.va_mask_thinning_u8(p["img"], p["tmp"], p["skel"], 20, w, C.byref(C.c_int()), None),
+             lambda L, p, _, w=w: L.va_mask_thinning_u8(p["img"], p["tmp"], p["skel"], 20, w, C.byref(C.c_int()), ON.stream),
              lambda O, m=m: {"skel": O.mask_thinning(m)[0]})
 
 
@@ -668,7 +703,7 @@ def _sobel_cases():
             _add("sobel5_f64[w%d,%s]" % (w, np.dtype(dt).name), "va_sobel5_f64",
                  "va_gradients.hip:213: fx_out % 16 == 0 && fy_out % 16 == 0",
                  [Arg("src", "in", x), out("fx", x.shape, np.float64), out("fy", x.shape, np.float64)],
-                 lambda L, p, _, w=w, code=code: L.va_sobel5_f64(p["src"], code, p["fx"], p["fy"], 2, 9, w, None),
+                 lambda L, p, _, w=w, code=code: L.va_sobel5_f64(p["src"], code, p["fx"], p["fy"], 2, 9, w, ON.stream),
                  lambda O, x=x: dict(zip(("fx", "fy"), AG.sobel5(x))))
 
 
@@ -698,7 +733,7 @@ def _ragged_gradient_cases():
               out("fx", (total,), np.float64), out("fy", (total,), np.float64), out("status", (3,), np.int32)],
              lambda L, p, _, sigma=sigma: L.va_potential_gradients_ragged(p["src"], VA_F32, p["shapes"], p["offsets"], total,
                                                                           3, int(sizes.max()), sigma, p["fx"], p["fy"],
-                                                                          p["status"], None),
+                                                                          p["status"], ON.stream),
              ref)
 
 
@@ -715,11 +750,12 @@ def _guo_hall_cases():
         # the unpack)
         _add("guo_hall_thinning_u8[w%d]" % w, ("va_guo_hall_thinning_u8", "va_guo_hall_thinning_scratch_bytes"),
              "va_thinning.hip:354: (w & 3) == 0 && ((src | dst) & 3) == 0",
-             [Arg("src", "in", stack), out("dst", stack.shape, np.uint8),
+             [Arg("src", "in", stack, decoy=stack[:, :, ::-1]),     # (mirrored: reversed, this stack is itself)
+              out("dst", stack.shape, np.uint8),
               Arg("scratch", "scratch", nbytes=lambda L, w=w: L.va_guo_hall_thinning_scratch_bytes(2, 20, w))],
              lambda L, p, _, w=w: L.va_guo_hall_thinning_u8(p["src"], p["scratch"],
                                                             L.va_guo_hall_thinning_scratch_bytes(2, 20, w), p["dst"], 2, 20,
-                                                            w, 0, 0, None, None, None),
+                                                            w, 0, 0, None, None, ON.stream),
              lambda O, stack=stack: {"dst": np.stack([TG.guo_hall(f)[0] for f in stack])})
 
 
@@ -760,7 +796,7 @@ def _region_links_cases():
           out("links", (n * cap, 4), np.int32, offsets=(0,)),
           Arg("ws", "scratch", nbytes=lambda L: L.va_region_links_workspace_bytes(n, h, w, n * cap))],
          lambda L, p, _: L.va_region_links(p["prev"], p["labels"], n, h, w, p["nlinks"], p["totals"], p["links"], n * cap,
-                                           p["ws"], L.va_region_links_workspace_bytes(n, h, w, n * cap), None),
+                                           p["ws"], L.va_region_links_workspace_bytes(n, h, w, n * cap), ON.stream),
          ref, project={"links": _links_rows})
 
 
@@ -784,7 +820,7 @@ def _compose_cases():
                   Arg("layers", "scratch", table.view(np.uint8)), Arg("off", "scratch", off)],
                  lambda L, p, _, w=w, c=c, nb=len(packed): L.va_compose_layers_u8(p["src"], c, p["dst"], 2, 8, w, c,
                                                                                   p["layers"], p["off"], 2, None, 0,
-                                                                                  p["masks"], nb, None),
+                                                                                  p["masks"], nb, ON.stream),
                  lambda O, frames=frames, layers=layers: {"dst": K.compose_layers(frames, layers)})
 
 
@@ -806,7 +842,7 @@ def _draw_control_cases():
               Arg("off", "scratch", off), Arg("points", "scratch", np.ascontiguousarray(pts, np.int32)),
               out("status", (2,), np.int32, (0,))],
              lambda L, p, _, c=c, nc=len(recs), npts=len(pts): L.va_draw_u8(p["frames"], 2, 8, 61, c, p["cmds"], p["off"], nc,
-                                                                            p["points"], npts, p["status"], None),
+                                                                            p["points"], npts, p["status"], ON.stream),
              lambda O, frames=frames, commands=commands: {"frames": K.draw(frames, commands),
                                                          "status": np.zeros(2, np.int32)})
 
@@ -835,7 +871,7 @@ def _jpeg_cases():
               out("bytes", (len(blob),), np.uint8)],
              lambda L, p, _, c=c, nh=len(head), cap=len(blob): L.va_jpeg_encode_u8(
                  p["frames"], 2, 16, 24, c, p["qtables"], p["header"], nh, p["sizes"], p["offsets"], p["totals"],
-                 p["bytes"], cap, None),
+                 p["bytes"], cap, ON.stream),
              lambda O, blob=blob, file_off=file_off: {"sizes": np.diff(file_off), "offsets": file_off,
                                                       "totals": file_off[-1:], "bytes": blob})
         # the decoder's pixel stores: 8 bytes at once where `(p & 7) == 0`; the output frames late by 1 and 4
@@ -845,13 +881,13 @@ def _jpeg_cases():
         scan_begin = np.full(2, hd["scan_begin"], np.int64)
         _add("jpeg_decode_u8[2x16x24,c%d]" % c, ("va_jpeg_decode_u8", "va_jpeg_decode_workspace_bytes"),
              "va_jpeg_decode.hip:321 pixel stores: x0 + 8 <= w && (dst & 7) == 0",
-             [Arg("bytes", "in", blob), Arg("offsets", "scratch", file_off), Arg("scan_begin", "scratch", scan_begin),
+             [Arg("bytes", "in", blob, decoy=False), Arg("offsets", "scratch", file_off), Arg("scan_begin", "scratch", scan_begin),
               Arg("qtables", "in", np.ascontiguousarray(hd["qtables"])), Arg("huff", "scratch", tables),
               out("frames", frames.shape, np.uint8, offsets=(0, 1, 4)), out("status", (2,), np.int32, offsets=(0,)),
               Arg("ws", "scratch", nbytes=lambda L, c=c, ri=hd["ri"]: L.va_jpeg_decode_workspace_bytes(2, 16, 24, c, ri))],
              lambda L, p, _, c=c, ri=hd["ri"], nt=len(tables): L.va_jpeg_decode_u8(
                  p["bytes"], p["offsets"], p["scan_begin"], 2, 16, 24, c, ri, p["qtables"], p["huff"], nt, p["frames"],
-                 p["status"], p["ws"], L.va_jpeg_decode_workspace_bytes(2, 16, 24, c, ri), None),
+                 p["status"], p["ws"], L.va_jpeg_decode_workspace_bytes(2, 16, 24, c, ri), ON.stream),
              lambda O, files=files: {"frames": np.stack([D.decode(f)[0] for f in files]), "status": np.zeros(2, np.int32)})
 
 
@@ -876,7 +912,7 @@ def _jpeg_sampled_cases():
           out("sizes", (2,), np.int64), out("offsets", (3,), np.int64), out("totals", (1,), np.int64),
           out("bytes", (len(blob),), np.uint8)],
          lambda L, p, _: L.va_jpeg_encode_sampled_u8(p["frames"], 2, 16, 24, 3, 2, 2, p["qtables"], p["header"], len(head),
-                                                     p["sizes"], p["offsets"], p["totals"], p["bytes"], len(blob), None),
+                                                     p["sizes"], p["offsets"], p["totals"], p["bytes"], len(blob), ON.stream),
          lambda O: {"sizes": np.diff(file_off), "offsets": file_off, "totals": file_off[-1:], "bytes": blob})
     hd = ops.jpeg_parse_header(files[0], sampling="any")
     assert tuple(hd["sampling"]) == (2, 2)
@@ -885,14 +921,14 @@ def _jpeg_sampled_cases():
     ri = hd["ri"]
     _add("jpeg_decode_sampled_u8[2x16x24,4:2:0]", ("va_jpeg_decode_sampled_u8", "va_jpeg_decode_sampled_workspace_bytes"),
          "none (va_jpeg_decode.hip subsampled reconstruction: control)",
-         [Arg("bytes", "in", blob), Arg("offsets", "scratch", file_off),
+         [Arg("bytes", "in", blob, decoy=False), Arg("offsets", "scratch", file_off),
           Arg("scan_begin", "scratch", np.full(2, hd["scan_begin"], np.int64)),
           Arg("qtables", "in", np.ascontiguousarray(hd["qtables"])), Arg("huff", "scratch", tables),
           out("frames", frames.shape, np.uint8, offsets=(0, 1, 4)), out("status", (2,), np.int32, offsets=(0,)),
           Arg("ws", "scratch", nbytes=lambda L: L.va_jpeg_decode_sampled_workspace_bytes(2, 16, 24, 3, ri, 2, 2))],
          lambda L, p, _: L.va_jpeg_decode_sampled_u8(
              p["bytes"], p["offsets"], p["scan_begin"], 2, 16, 24, 3, ri, 2, 2, p["qtables"], p["huff"], len(tables),
-             p["frames"], p["status"], p["ws"], L.va_jpeg_decode_sampled_workspace_bytes(2, 16, 24, 3, ri, 2, 2), None),
+             p["frames"], p["status"], p["ws"], L.va_jpeg_decode_sampled_workspace_bytes(2, 16, 24, 3, ri, 2, 2), ON.stream),
          lambda O: {"frames": np.stack([SS.decode(f)[0] for f in files]), "status": np.zeros(2, np.int32)})
 
 
@@ -910,11 +946,11 @@ def _control_cases():
     f = (np.random.default_rng(3371).random((2, 33, 70)) * 200 - 50).astype(np.float32)
     _add("gaussian_u8_rule[2x33x70,cv3]", "va_gaussian_u8_rule", "va_gauss.hip:370 gaussian_call (the cv3 tap set)",
          [Arg("src", "in", im, offsets=U8_LATE), out("dst", im.shape, np.uint8, U8_LATE)],
-         lambda L, p, _: L.va_gaussian_u8_rule(p["src"], p["dst"], 2, 33, 70, 1, 2.0, 1, None),
+         lambda L, p, _: L.va_gaussian_u8_rule(p["src"], p["dst"], 2, 33, 70, 1, 2.0, 1, ON.stream),
          lambda O: {"dst": O.gaussian_u8(im, 2.0, tap_rule="cv3")})
     _add("gaussian_u8_generic[2x33x70]", "va_gaussian_u8_generic", none % "va_gauss.hip generic two-pass kernels",
          [Arg("src", "in", im, offsets=U8_LATE), out("dst", im.shape, np.uint8, U8_LATE)],
-         lambda L, p, _: L.va_gaussian_u8_generic(p["src"], p["dst"], 2, 33, 70, 1, 2.0, None),
+         lambda L, p, _: L.va_gaussian_u8_generic(p["src"], p["dst"], 2, 33, 70, 1, 2.0, ON.stream),
          lambda O: {"dst": O.gaussian_u8(im, 2.0)})
     peaks = np.random.default_rng(3372).normal(0, 1, (2, 12, 30)).astype(np.float32)
     peaks[1, 4:7, 10:16] = 2.5
@@ -922,7 +958,7 @@ def _control_cases():
     for plateaus in (1, 0):
         _add("detect_peaks_f32[plateaus%d]" % plateaus, "va_detect_peaks_f32", none % "va_stencil.hip float peaks",
              [Arg("src", "in", peaks, offsets=F32_LATE), out("dst", peaks.shape, np.uint8, U8_LATE)],
-             lambda L, p, _, plateaus=plateaus: L.va_detect_peaks_f32(p["src"], p["dst"], 2, 12, 30, plateaus, None),
+             lambda L, p, _, plateaus=plateaus: L.va_detect_peaks_f32(p["src"], p["dst"], 2, 12, 30, plateaus, ON.stream),
              lambda O, plateaus=plateaus: {"dst": np.stack([O.detect_peaks(x, bool(plateaus)) for x in peaks])
                                            .astype(np.uint8)})
     for name, src, late in (("u8", im, U8_LATE), ("f32", f, F32_LATE)):
@@ -935,7 +971,7 @@ def _control_cases():
                  [Arg("src", "in", src, offsets=late), out("mean", src.shape, np.float64), out("var", src.shape, np.float64)],
                  lambda L, p, _, name=name, kernel=kernel, ksize=ksize, prior=prior, excl=excl: getattr(
                      L, "va_image_statistics_" + name)(p["src"], p["mean"], p["var"], 2, 33, 70, kernel, ksize, float(prior),
-                                                       excl, None),
+                                                       excl, ON.stream),
                  ref)
     # va_normalize: uint8 -> float32 and float32 -> uint8 (NumPy's types: float64 arithmetic on uint8 frames, float32 on
     # float32 frames)
@@ -943,16 +979,16 @@ def _control_cases():
     unit = (f / 200).astype(np.float32)
     _add("normalize[u8->f32]", "va_normalize", none % "va_synth.hip normalize, one element per thread",
          [Arg("src", "in", im, offsets=U8_LATE), out("dst", im.shape, np.float32, F32_LATE)],
-         lambda L, p, _: L.va_normalize(p["src"], VA_U8, p["dst"], VA_F32, im.size, 30.0, 200.0, 1.0 / 170.0, 0.0, None),
+         lambda L, p, _: L.va_normalize(p["src"], VA_U8, p["dst"], VA_F32, im.size, 30.0, 200.0, 1.0 / 170.0, 0.0, ON.stream),
          lambda O: {"dst": ((np.clip(im.astype(np.float64), 30, 200) - 30) * (1.0 / 170.0) + 0).astype(np.float32)})
     _add("normalize[f32->u8]", "va_normalize", none % "va_synth.hip normalize, one element per thread",
          [Arg("src", "in", unit, offsets=F32_LATE), out("dst", im.shape, np.uint8, U8_LATE)],
-         lambda L, p, _: L.va_normalize(p["src"], VA_F32, p["dst"], VA_U8, unit.size, 0.25, 0.75, 510.0, 0.0, None),
+         lambda L, p, _: L.va_normalize(p["src"], VA_F32, p["dst"], VA_U8, unit.size, 0.25, 0.75, 510.0, 0.0, ON.stream),
          lambda O: {"dst": S.normalize_numpy(unit, 0.25, 0.75, 510.0, 0.0, np.uint8)})
     rf = np.random.default_rng(3373).random((2, 24, 40), dtype=np.float32)
     _add("resize_f32[24x40->13x21,linear]", "va_resize_f32", none % "va_resize.hip float32 frames",
          [Arg("src", "in", rf, offsets=F32_LATE), out("dst", (2, 13, 21), np.float32, F32_LATE)],
-         lambda L, p, _: L.va_resize_f32(p["src"], p["dst"], 2, 24, 40, 1, 13, 21, 1, None),
+         lambda L, p, _: L.va_resize_f32(p["src"], p["dst"], 2, 24, 40, 1, 13, 21, 1, ON.stream),
          lambda O: {"dst": O.resize_f32(rf, (21, 13), "linear")})
 
     # contours of blob masks: the mask plane late; the int32 / int64 tables stay aligned (REJECTIONS)
@@ -971,12 +1007,13 @@ def _control_cases():
                 "points": points}
     _add("find_contours[2x17x70]", ("va_find_contours", "va_find_contours_workspace_bytes"),
          none % "va_contours.hip border following",
-         [Arg("mask", "in", masks, offsets=U8_LATE), out("ncontours", (2,), np.int32, (0,)),
+         [Arg("mask", "in", masks, offsets=U8_LATE, decoy=blob_masks(2, 17, 70, seed=72)),      # (a turn keeps the totals)
+          out("ncontours", (2,), np.int32, (0,)),
           out("totals", (2,), np.int64, (0,)), Arg("info", "scratch", nbytes=64 * 48),
           out("point_off", (65,), np.int64, (0,)), out("points", (1024, 2), np.int32, (0,)),
           Arg("ws", "scratch", nbytes=lambda L: L.va_find_contours_workspace_bytes(2, 17, 70))],
          lambda L, p, _: L.va_find_contours(p["mask"], 2, 17, 70, p["ncontours"], p["totals"], p["info"], p["point_off"], 64,
-                                            p["points"], 1024, p["ws"], L.va_find_contours_workspace_bytes(2, 17, 70), None),
+                                            p["points"], 1024, p["ws"], L.va_find_contours_workspace_bytes(2, 17, 70), ON.stream),
          contours_ref,
          project={"point_off": lambda a, r: a[:int(r["totals"][0]) + 1], "points": lambda a, r: a[:int(r["totals"][1])]})
 
@@ -995,7 +1032,7 @@ def _control_cases():
           out("npoints", (2,), np.int32, (0,)), out("area", (2,), np.float64, (0,)), out("ncomp", (2,), np.int32, (0,)),
           Arg("ws", "scratch", nbytes=lambda L: L.va_contour_workspace_bytes(2, 17, 70))],
          lambda L, p, _: L.va_largest_contour(p["mask"], 2, 17, 70, p["points"], 256, p["npoints"], p["area"], p["ncomp"],
-                                              p["ws"], L.va_contour_workspace_bytes(2, 17, 70), None),
+                                              p["ws"], L.va_contour_workspace_bytes(2, 17, 70), ON.stream),
          largest_ref,
          project={"points": lambda a, r: np.concatenate([a[k, :int(r["npoints"][k])].ravel() for k in range(2)])})
 
@@ -1014,7 +1051,7 @@ def _control_cases():
               Arg("ws", "scratch", nbytes=lambda L, args=args: L.va_farneback_workspace_bytes(2, 9, 11, *args))],
              lambda L, p, _, code=code, args=args: L.va_optical_flow_farneback(
                  p["frames"], code, 2, 9, 11, *args, float(params["poly_sigma"]), 0, p["flow"], p["mag"], p["ws"],
-                 L.va_farneback_workspace_bytes(2, 9, 11, *args), None),
+                 L.va_farneback_workspace_bytes(2, 9, 11, *args), ON.stream),
              lambda O, fr=fr: dict(zip(("flow", "mag"), OG.optical_flow(fr, **params))))
 
 
@@ -1046,7 +1083,7 @@ def _ragged_control_cases():
          [Arg("masks", "in", flat, offsets=U8_LATE)] + tables
          + [out("out", (total,), np.float32, F32_LATE), out("status", (3,), np.int32, (0,))],
          lambda L, p, _: L.va_distance_transform_l2_5(p["masks"], p["shapes"], p["offsets"], total, 3,
-                                                      int(shapes[:, 1].max()), p["out"], p["status"], None),
+                                                      int(shapes[:, 1].max()), p["out"], p["status"], ON.stream),
          lambda O: {"out": packed([PG.distance_transform(m) for m in items], np.float32), "status": np.zeros(3, np.int32)})
     _add("guo_hall_thinning_batch[3 items]", "va_guo_hall_thinning_batch", none % "va_thinning.hip resident kernel",
          [Arg("masks", "in", flat, offsets=U8_LATE)] + tables
@@ -1054,7 +1091,7 @@ def _ragged_control_cases():
             out("status", (3,), np.int32, (0,))],
          lambda L, p, _: L.va_guo_hall_thinning_batch(p["masks"], p["shapes"], p["offsets"], total, 3,
                                                       max(h * ((w + 31) // 32) for h, w in shapes.tolist()), p["out"],
-                                                      p["iterations"], p["status"], None),
+                                                      p["iterations"], p["status"], ON.stream),
          lambda O: {"out": packed([TG.guo_hall(m)[0] for m in items], np.uint8),
                     "iterations": np.array([TG.guo_hall(m)[1] for m in items], np.int32), "status": np.zeros(3, np.int32)})
     # va_fill_poly writes the ragged masks: uint8 planes late by 1, int32 planes by 4
@@ -1068,10 +1105,11 @@ def _ragged_control_cases():
     ftotal = int(fsizes.sum())
     for dt, late in ((np.uint8, U8_LATE), (np.int32, F32_LATE)):
         _add("fill_poly[%s]" % np.dtype(dt).name, "va_fill_poly", none % "va_polygon.hip scanline fill",
-             [Arg("verts", "scratch", verts), Arg("vert_off", "scratch", vert_off), Arg("boxes", "scratch", boxes.astype(np.int32)),
+             [Arg("verts", "in", verts, offsets=(0,)), Arg("vert_off", "scratch", vert_off),      # (coordinates: a decoy)
+              Arg("boxes", "scratch", boxes.astype(np.int32)),
               Arg("out_off", "scratch", out_off), out("out", (ftotal,), dt, late), out("status", (3,), np.int32, (0,))],
              lambda L, p, _, dt=dt: L.va_fill_poly(p["verts"], p["vert_off"], len(verts), p["boxes"], p["out_off"], ftotal, 3,
-                                                   np.dtype(dt).itemsize, p["out"], p["status"], None),
+                                                   np.dtype(dt).itemsize, p["out"], p["status"], ON.stream),
              lambda O, dt=dt: {"out": packed([PG.fill_poly(c, b) for c, b in zip(contours, boxes)], dt),
                                "status": np.zeros(3, np.int32)})
 
@@ -1098,7 +1136,7 @@ def _warp_and_geodesic_control_cases():
           Arg("out_off", "scratch", out_off), Arg("prefix", "scratch", prefix), out("out", (total,), np.uint8, U8_LATE),
           out("status", (2,), np.int32, (0,))],
          lambda L, p, _: L.va_warp_affine_u8(p["frames"], 2, 20, 30, 2, p["fidx"], p["mats"], p["shapes"], p["flags"],
-                                             p["out_off"], p["prefix"], ntiles, total, p["out"], p["status"], None),
+                                             p["out_off"], p["prefix"], ntiles, total, p["out"], p["status"], ON.stream),
          lambda O: {"out": np.concatenate([LG.warp_affine(frames[f], M, (int(s[1]), int(s[0]))).ravel()
                                            for f, M, s in zip(fidx, mats, sizes)]), "status": np.zeros(2, np.int32)})
     p1, p2, hw = np.array([(3.0, 4.0), (25.0, 2.0)]), np.array([(26.0, 15.0), (6.0, 17.0)]), np.array([2.5, 3.0])
@@ -1111,7 +1149,7 @@ def _warp_and_geodesic_control_cases():
           Arg("shapes", "scratch", np.stack([rows, cols], 1).astype(np.int32)), Arg("out_off", "scratch", s_off),
           Arg("prefix", "scratch", sprefix), out("sums", (stotal,), np.int32, (0,)), out("status", (2,), np.int32, (0,))],
          lambda L, p, _: L.va_line_scan_u8(p["frames"], 2, 20, 30, 2, p["fidx"], p["mats"], p["shapes"], p["out_off"],
-                                           p["prefix"], chunks, stotal, p["sums"], p["status"], None),
+                                           p["prefix"], chunks, stotal, p["sums"], p["status"], ON.stream),
          lambda O: {"sums": np.concatenate([LG.line_scan_strip(frames[f], a, b, w)[1].sum(axis=0, dtype=np.int64)
                                             for f, a, b, w in zip(fidx, p1, p2, hw)]).astype(np.int32),
                     "status": np.zeros(2, np.int32)})
@@ -1131,18 +1169,18 @@ def _warp_and_geodesic_control_cases():
         tables += [Arg("ends", "scratch", ends), Arg("nends", "scratch", np.array([ends.shape[1]], np.int32))]
     ws = Arg("ws", "scratch", nbytes=lambda L: L.va_geodesic_workspace_bytes(1, h, w))
     _add("distance_map_i32[%s]" % name, ("va_distance_map_i32", "va_geodesic_workspace_bytes"), none % "va_geodesic.hip",
-         [Arg("fillable", "in", fillable, offsets=U8_LATE)] + tables + [out("map", (h, w), np.int32, F32_LATE), ws],
+         [Arg("fillable", "in", fillable, offsets=U8_LATE, decoy=np.ones_like(fillable))] + tables + [out("map", (h, w), np.int32, F32_LATE), ws],
          lambda L, p, _: L.va_distance_map_i32(p["fillable"], 1, h, w, p["starts"], p["nstarts"], starts.shape[1],
                                                p.get("ends"), p.get("nends"), ends.shape[1], p["map"], p["ws"],
-                                               L.va_geodesic_workspace_bytes(1, h, w), None),
+                                               L.va_geodesic_workspace_bytes(1, h, w), ON.stream),
          lambda O: {"map": np.where(fillable != 0, geo[name + "/map"], 0).astype(np.int32)})
-    fg = (mask != 0).astype(np.uint8)
+    fg = (mask != 0).astype(np.uint8)            # (the decoys: no walls.  This corridor is its own mirror image)
     _add("farthest_points[%s]" % name, ("va_farthest_points", "va_geodesic_workspace_bytes"), none % "va_geodesic.hip",
-         [Arg("mask", "in", fg, offsets=U8_LATE), Arg("p1", "scratch", np.asarray(geo[name + "/fp_p1_in"], np.int32)),
+         [Arg("mask", "in", fg, offsets=U8_LATE, decoy=np.ones_like(fg)), Arg("p1", "scratch", np.asarray(geo[name + "/fp_p1_in"], np.int32)),
           out("p1_out", (1, 2), np.int32, (0,)), out("p2_out", (1, 2), np.int32, (0,)), Arg("dist", "scratch", nbytes=4),
           Arg("rounds", "scratch", nbytes=8), ws],
          lambda L, p, _: L.va_farthest_points(p["mask"], 1, h, w, p["p1"], p["p1_out"], p["p2_out"], p["dist"], p["rounds"],
-                                              None, 0, None, p["ws"], L.va_geodesic_workspace_bytes(1, h, w), None),
+                                              None, 0, None, p["ws"], L.va_geodesic_workspace_bytes(1, h, w), ON.stream),
          lambda O: {"p1_out": np.asarray(geo[name + "/fp"][0], np.int32).reshape(1, 2),
                     "p2_out": np.asarray(geo[name + "/fp"][1], np.int32).reshape(1, 2)})
 
@@ -1182,14 +1220,15 @@ def _skeleton_control_case():
                 "point_off": np.concatenate([[0], np.cumsum([len(c) for c in curves])]).astype(np.int64)}
     _add("skeleton_graph[3 items]", ("va_skeleton_graph", "va_skeleton_graph_workspace_bytes"),
          "none (va_skeleton.hip: control)",
-         [Arg("masks", "in", np.concatenate([a.ravel() for a in items]), offsets=U8_LATE), Arg("shapes", "scratch", shapes),
+         [Arg("masks", "in", np.concatenate([a.ravel() for a in items]), offsets=U8_LATE, decoy=np.zeros(total, np.uint8)),
+          Arg("shapes", "scratch", shapes),     # (the decoy: empty items.  Reversed, these items are themselves)
           Arg("offsets", "scratch", offsets), out("counts", (3, 2), np.int32, (0,)), out("totals", (3,), np.int64, (0,)),
           out("nodes", (nn * 20,), np.uint8, (0,)), out("edges", (ne * 24,), np.uint8, (0,)),
           out("point_off", (ne + 1,), np.int64, (0,)), out("points", (npts, 2), np.int32, (0,)),
           Arg("ws", "scratch", nbytes=lambda L: L.va_skeleton_graph_workspace_bytes(total, 3))],
          lambda L, p, _: L.va_skeleton_graph(p["masks"], p["shapes"], p["offsets"], total, 3, p["counts"], p["totals"],
                                              p["nodes"], nn, p["edges"], p["point_off"], ne, p["points"], npts, p["ws"],
-                                             L.va_skeleton_graph_workspace_bytes(total, 3), None),
+                                             L.va_skeleton_graph_workspace_bytes(total, 3), ON.stream),
          ref)
 
 
@@ -1265,19 +1304,23 @@ def _pipeline_cases():
             assert ("gauss=%s(" % family).encode() in L.va_pipeline_describe(p), L.va_pipeline_describe(p)
             return p
 
-        def call(L, ptr, p):
+        def prepare(L, p):
             if background:
                 assert L.va_bg_set_state(p, None, 0, 0) == 0              # every run starts a fresh model
+
+        def call(L, ptr, p):
             return L.va_pipeline_run(p, ptr["frames"], n, ptr.get("filtered"), ptr.get("mask"), ptr.get("labels"),
-                                     ptr.get("counts"), None, None)
+                                     ptr.get("counts"), None, ON.stream)
 
         def ref(O):
             r = chain_reference(O, clip, background, 1.0, thresh, close, conn)
             return {k: r[k] for k in outputs}
         _add(name, ("va_pipeline_create", "va_pipeline_run", "va_pipeline_describe", "va_bg_set_state"), gate,
-             [Arg("frames", "in", clip, offsets=frame_offsets)]
+             # (the decoy under a model: the first frame twice, so the second frame's difference image is empty)
+             [Arg("frames", "in", clip, offsets=frame_offsets, decoy=np.repeat(clip[:1], n, 0) if background else None)]
              + [out(k, shapes[k][0], shapes[k][1], offsets.get(k)) for k in outputs],
-             call, ref, setup=setup, teardown=lambda L, p: p is not None and L.va_pipeline_destroy(p), rejects=rejects)
+             call, ref, setup=setup, teardown=lambda L, p: p is not None and L.va_pipeline_destroy(p), rejects=rejects,
+             prepare=prepare, rejoin=lambda L, p, stream: L.va_pipeline_fence(p, stream))
 
     for background in (True, False):
         bg = "mean" if background else "none"
