@@ -419,6 +419,89 @@ int va_region_links(const int32_t *prev_dev, const int32_t *labels_dev, int n, i
                     int64_t *totals_dev, va_region_link *links_dev, int64_t cap_links, void *workspace_dev,
                     size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ A8c template matching
+ * replaces  cv2.matchTemplate(frame, template, method) and cv2.minMaxLoc on its result, for a batch of (frame,
+ *           template, search window) queries, and the slicing that regions.get_overlapping_slices
+ *           (video/analysis/regions.py) does for a caller that compares a template with part of a frame.
+ * Frames are (n, h, w) uint8, frame f at frames_dev + f * frame_stride (frame_stride >= h * w bytes).  Templates are
+ * a ragged batch: template t is template_shapes_dev[2 t] rows x template_shapes_dev[2 t + 1] columns of uint8,
+ * row-major at templates_dev + template_offsets_dev[t]; the m + 1 offsets are in order.  1 <= th, tw and
+ * th * tw <= 65536, so that every sum below fits 32 unsigned bits (255 * 255 * 65536 < 2^32).
+ * Query k = (frame, templ, x0, y0, nx, ny) asks for the template's top-left corner at (x0 + i, y0 + j), 0 <= i < nx,
+ * 0 <= j < ny; every position must hold the whole template inside the frame.  With the exact integers S_it = sum I T,
+ * S_i = sum I, S_ii = sum I I over the window, S_t = sum T, S_tt = sum T T and N = th * tw, the float64 score is
+ *   VA_MATCH_SQDIFF         (double)(S_ii - 2 S_it + S_tt)
+ *   VA_MATCH_SQDIFF_NORMED  that / sqrt((double)S_ii * (double)S_tt)            (1.0 where the denominator is 0.0)
+ *   VA_MATCH_CCORR          (double)S_it
+ *   VA_MATCH_CCORR_NORMED   (double)S_it / sqrt((double)S_ii * (double)S_tt)    (0.0 where the denominator is 0.0)
+ *   VA_MATCH_CCOEFF         (double)(N S_it - S_i S_t) / (double)N
+ *   VA_MATCH_CCOEFF_NORMED  (double)(N S_it - S_i S_t) / sqrt((double)(N S_ii - S_i S_i) * (double)(N S_tt - S_t S_t))
+ *                           (0.0 where the denominator is 0.0)
+ * with int64 numerators and each multiply, sqrt and divide rounded once.  The codes are cv2.TM_*'s.  cv2 itself returns
+ * float32 from a DFT and thresholds small denominators; agreement is expected up to that rounding only.
+ *   best_out_dev[k]   (NULL: not wanted) the minimum (SQDIFF methods) or maximum score of query k and its frame
+ *                     position (x, y); at equal scores the first position in raster order (j, then i)
+ *   maps_out_dev      (NULL: not wanted) the scores of query k, (ny, nx) float64 row-major, at
+ *                     maps_out_dev + map_offsets_dev[k] (k + 1 offsets in elements; the caller lays them out)
+ * status of a query: 0, or VA_MATCH_STATUS_* bits.  A flagged query writes its status into best_out_dev[k].status and
+ * nothing else, neither the rest of its record nor its map, and the entry point still returns 0.
+ * total_positions: the sum of nx * ny over the valid queries, as the caller computed it; it sizes the workspace.  A
+ * call whose queries need more than it allows flags every query with VA_MATCH_STATUS_WORKSPACE and writes no score.
+ * Envelope: n_queries >= 0 (0 enqueues nothing); n_queries, n_templates and the tile bound of total_positions below
+ * 2^31; frames below 2^29 pixels; queries and tiles are counted in gridDim.x, never in gridDim.y or z.
+ * Alignment: every typed pointer may start at any multiple of its element size (queries and shapes 4, offsets, bests,
+ * maps and the workspace 8), frames and templates at any byte; a misaligned pointer is VA_ERR_INVALID.
+ * Refused with VA_ERR_INVALID and a message that names the limit, before anything is enqueued: a struct_size that is
+ * not sizeof(va_match_args), an unknown method, counts outside the envelope, a workspace below
+ * va_template_match_workspace_bytes (0 for counts outside the envelope), a misaligned pointer.  Template shapes live
+ * on the device: one beyond 65536 pixels is the status bit VA_MATCH_STATUS_TEMPLATE_SHAPE of the queries that name it.
+ * Asynchronous on args->stream; leases nothing: the workspace is the caller's.  Slots come from a scan and the bests
+ * from a rule that is a total order, never from the order of atomics: two calls write identical bytes. */
+#define VA_MATCH_SQDIFF 0
+#define VA_MATCH_SQDIFF_NORMED 1
+#define VA_MATCH_CCORR 2
+#define VA_MATCH_CCORR_NORMED 3
+#define VA_MATCH_CCOEFF 4
+#define VA_MATCH_CCOEFF_NORMED 5
+#define VA_MATCH_MAX_TEMPLATE_PIXELS 65536
+#define VA_MATCH_STATUS_FRAME 1           /* frame index outside 0 .. n - 1 */
+#define VA_MATCH_STATUS_TEMPLATE 2        /* template index outside 0 .. n_templates - 1 */
+#define VA_MATCH_STATUS_EMPTY 4           /* nx < 1 or ny < 1 */
+#define VA_MATCH_STATUS_OUTSIDE 8         /* a position puts the template outside the frame */
+#define VA_MATCH_STATUS_TEMPLATE_SHAPE 16 /* th or tw < 1, th * tw > 65536, or offsets that do not hold the template */
+#define VA_MATCH_STATUS_WORKSPACE 32      /* total_positions was below what the queries need */
+#define VA_MATCH_TILE 32                  /* positions of a tile, each way */
+#define VA_MATCH_CHUNK_ROWS 16            /* template rows and columns in LDS at a time */
+#define VA_MATCH_CHUNK_COLS 64
+typedef struct va_match_query {
+    int32_t frame, templ, x0, y0, nx, ny;
+} va_match_query; /* 24 bytes */
+typedef struct va_match_best {
+    double score;
+    int32_t x, y, status, reserved;
+} va_match_best; /* 24 bytes */
+typedef struct va_match_args {
+    int32_t struct_size; /* = sizeof(va_match_args), as va_config */
+    int32_t method;      /* VA_MATCH_SQDIFF ... VA_MATCH_CCOEFF_NORMED */
+    const uint8_t *frames_dev;
+    int32_t n, h, w, reserved;
+    int64_t frame_stride;
+    const uint8_t *templates_dev;
+    const int32_t *template_shapes_dev;  /* (n_templates, 2): rows, columns */
+    const int64_t *template_offsets_dev; /* n_templates + 1 */
+    int64_t n_templates;
+    const va_match_query *queries_dev;
+    int64_t n_queries, total_positions;
+    va_match_best *best_out_dev;
+    double *maps_out_dev;
+    const int64_t *map_offsets_dev; /* n_queries + 1 */
+    void *workspace_dev;
+    size_t workspace_bytes;
+    void *stream;
+} va_match_args; /* 144 bytes */
+size_t va_template_match_workspace_bytes(int64_t n_queries, int64_t total_positions, int64_t n_templates);
+int va_template_match_u8(const va_match_args *args);
+
 /* ------------------------------------------------------------------ A10 geodesic distance maps
  * 8-neighbour geodesics inside masks: straight steps cost 1, diagonal steps sqrt2 (a diagonal step may
  * pass between two wall pixels).  A distance d = a + b*sqrt2 is kept as the exact pair (a, b) and

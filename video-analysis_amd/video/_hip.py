@@ -55,6 +55,31 @@ class va_config(C.Structure):
                 ("connectivity", C.c_int32), ("max_labels", C.c_int32), ("tap_rule", C.c_int32)]
 
 
+class va_match_query(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("frame", "templ", "x0", "y0", "nx", "ny")]
+
+
+class va_match_best(C.Structure):
+    _fields_ = [("score", C.c_double), ("x", C.c_int32), ("y", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class va_match_args(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("method", C.c_int32), ("frames_dev", C.c_void_p),
+                ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("reserved", C.c_int32),
+                ("frame_stride", C.c_int64), ("templates_dev", C.c_void_p), ("template_shapes_dev", C.c_void_p),
+                ("template_offsets_dev", C.c_void_p), ("n_templates", C.c_int64), ("queries_dev", C.c_void_p),
+                ("n_queries", C.c_int64), ("total_positions", C.c_int64), ("best_out_dev", C.c_void_p),
+                ("maps_out_dev", C.c_void_p), ("map_offsets_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+MATCH_METHODS = {"sqdiff": 0, "sqdiff_normed": 1, "ccorr": 2, "ccorr_normed": 3, "ccoeff": 4, "ccoeff_normed": 5}
+MATCH_QUERY_DTYPE = np.dtype([(name, np.int32) for name in ("frame", "templ", "x0", "y0", "nx", "ny")])
+MATCH_BEST_DTYPE = np.dtype([("score", np.float64), ("x", np.int32), ("y", np.int32), ("status", np.int32),
+                             ("reserved", np.int32)])
+MATCH_MAX_TEMPLATE_PIXELS = 65536
+
 _vp, _i, _sz, _d, _i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_int64
 
 # name -> (restype, argtypes); mirrors include/videoanalysis_hip.h one to one
@@ -116,6 +141,8 @@ SIGNATURES = {
     "va_find_contours": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
     "va_region_links_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
     "va_region_links": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "va_template_match_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "va_template_match_u8": (_i, [C.POINTER(va_match_args)]),
     "va_normalize": (_i, [_vp, _i, _vp, _i, _sz, _d, _d, _d, _d, _vp]),
     "va_prepare_u8": (_i, [_vp, _vp] + [_i] * 10 + [_d, _d, _d, _d, _vp]),
     "va_gaussian_noise": (_i, [_vp, _i, _sz, _d, _d, C.c_uint64, C.c_uint64, _vp]),

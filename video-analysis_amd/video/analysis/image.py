@@ -296,3 +296,61 @@ def get_image_statistics(img, kernel="box", ksize=5, ret_var=True, prior=None,
     if kernel not in ("box", "ellipse", "circle"):
         raise ValueError("Unknown filter kernel `%s`" % kernel)
     return ops.image_statistics(img, kernel, int(ksize), prior, exclude_center, ret_var)
+
+
+def template_search_window(search_rect, t_shape, i_shape):
+    """(x0, y0, nx, ny): the positions of a template's top-left corner that keep the template inside the part of
+    `search_rect` = (left, top, width, height) that lies in an image of `i_shape` = (height, width); None is the whole
+    image.  The rectangle is clipped with the arithmetic of regions.get_overlapping_slices (RuntimeError where it
+    misses the image); ValueError where what is left does not hold the template of `t_shape` = (height, width)."""
+    from .regions import get_overlapping_slices
+    th, tw = int(t_shape[0]), int(t_shape[1])
+    if search_rect is None:
+        search_rect = (0, 0, i_shape[1], i_shape[0])
+    left, top, width, height = (int(v) for v in search_rect)
+    if width < 1 or height < 1:
+        raise ValueError("the search rectangle %r is empty" % (tuple(search_rect),))
+    _, (x0, y0, w, h) = get_overlapping_slices((left, top), (height, width), i_shape, anchor="upper left",
+                                               ret_rect=True)
+    if w < tw or h < th:
+        raise ValueError("the search rectangle %r leaves %d x %d pixels of the image, the template has %d x %d"
+                         % (tuple(search_rect), w, h, tw, th))
+    return x0, y0, w - tw + 1, h - th + 1
+
+
+def match_template(img, template, method="ccoeff_normed"):
+    """cv2.matchTemplate(img, template, cv2.TM_*) for a monochrome uint8 image: the (h - th + 1, w - tw + 1) float64
+    map of scores (ops.match_templates; DESIGN.md §9, "Template matching", pins the arithmetic, which is exact up to
+    the final float64 operations where cv2 returns float32 from a DFT).  method: 'sqdiff', 'sqdiff_normed', 'ccorr',
+    'ccorr_normed', 'ccoeff' or 'ccoeff_normed'."""
+    from .. import ops
+    img = _uint8_image(img, "match_template")
+    template = _uint8_image(template, "match_template")
+    window = template_search_window(None, template.shape, img.shape)
+    _, maps = ops.match_templates(img[None], [template], [(0, 0) + window], method=method, maps=True)
+    return maps[0]
+
+
+def find_template(img_or_stack, template, search_rect=None, method="ccoeff_normed"):
+    """the best match of `template` in an image: cv2.minMaxLoc of cv2.matchTemplate, restricted to the part of the
+    image inside search_rect = (left, top, width, height) (None: the whole image; template_search_window clips it).
+    Returns ((x, y), score), the top-left corner of the best position -- the minimum for the sqdiff methods, the
+    maximum otherwise, the first in raster order among equals -- and its score.  For a stack (n, h, w), or an
+    ops.DeviceFrames, every frame is searched in the same rectangle by one call, and the result is ((n, 2) int32
+    positions, (n,) float64 scores).  Only the best records cross to the host."""
+    from .. import ops
+    template = _uint8_image(template, "find_template")
+    if isinstance(img_or_stack, ops.DeviceFrames):
+        frames, single = img_or_stack, False
+        n, shape = frames.n, (frames.h, frames.w)
+    else:
+        frames = _uint8_image(img_or_stack, "find_template", ndims=(2, 3))
+        single = frames.ndim == 2
+        frames = frames[None] if single else frames
+        n, shape = len(frames), frames.shape[1:]
+    window = template_search_window(search_rect, template.shape, shape)
+    best = ops.match_templates(frames, [template], [(f, 0) + window for f in range(n)], method=method)
+    positions = np.stack([best["x"], best["y"]], axis=1)
+    if single:
+        return (int(positions[0, 0]), int(positions[0, 1])), float(best["score"][0])
+    return positions, best["score"].copy()

@@ -3,6 +3,9 @@
 The reference has no tracker of regions; this is the consumer of `FrameEngine.run(..., want=(..., "links"))` and of
 `ops.region_links` ("Region links"): host arithmetic with NumPy on the small link tables.  The label
 planes themselves never leave the device.
+
+`TemplateTracker` is the second way to follow objects, for where blobs touch, rest or the camera moves: template
+matching in a window around each object's last position (`ops.match_templates`; DESIGN.md §9, "Template matching").
 """
 import collections
 
@@ -115,3 +118,57 @@ def track_regions(engine, frames, batch=None):
             stats.extend(out["stats"][t, :min(int(k), engine.max_labels)] for t, k in enumerate(out["counts"]))
     return Tracks(ids, np.concatenate(counts) if counts else np.zeros(0, np.int32), stats if "stats" in want else None,
                   lin, lout)
+
+
+class TemplateTracker(object):
+    """follows k templates through batches of frames by template matching (ops.match_templates; DESIGN.md §9,
+    "Template matching").
+
+    templates: 2-d uint8 arrays; positions: (k, 2) integer (x, y) of their top-left corners in the frame before the
+    first batch; radius: how far, in pixels along each axis, a template is looked for around its position.
+    update(frames) asks one query per frame of the batch and template: the positions within `radius` of the template's
+    position at the start of the batch, clipped to the frame (image.template_search_window).  So `radius` must cover
+    the motion of a whole batch, not of one frame: choose the batch and the radius together.  The positions found in
+    the last frame of a batch centre the next one.  A batch is one launch chain, and only the best records cross to
+    the host.  The templates stay what they were given as: refreshing them from the frames is not built."""
+
+    def __init__(self, templates, positions, radius, method="ccoeff_normed"):
+        from .. import ops
+        self.templates = ops._match_templates_in(list(templates), "TemplateTracker")
+        self.positions = np.array(positions, np.int64).reshape(-1, 2)
+        if len(self.positions) != len(self.templates) or not self.templates:
+            raise ValueError("TemplateTracker: %d templates and %d positions" % (len(self.templates), len(self.positions)))
+        if not (isinstance(radius, (int, np.integer)) and not isinstance(radius, bool) and radius >= 0):
+            raise ValueError("TemplateTracker: the radius is an integer >= 0, got %r" % (radius,))
+        if method not in ops.MATCH_METHODS:
+            raise ValueError("TemplateTracker: method %r is not one of %s" % (method, sorted(ops.MATCH_METHODS)))
+        self.radius, self.method = int(radius), method
+
+    def queries(self, n, frame_shape):
+        """the (n * k, 6) query table of a batch of n frames of `frame_shape` = (h, w), frame-major"""
+        from .image import template_search_window
+        r = self.radius
+        windows = [template_search_window((x - r, y - r, 2 * r + t.shape[1], 2 * r + t.shape[0]), t.shape, frame_shape)
+                   for t, (x, y) in zip(self.templates, self.positions.tolist())]
+        return np.array([(f, k) + window for f in range(n) for k, window in enumerate(windows)],
+                        np.int32).reshape(-1, 6)
+
+    def update(self, frames):
+        """frames: a monochrome uint8 stack (n, h, w) or an ops.DeviceFrames.  Returns (positions (n, k, 2) int32,
+        scores (n, k) float64) and moves the tracker to the positions of the last frame."""
+        from .. import ops
+        k = len(self.templates)
+        if isinstance(frames, ops.DeviceFrames):
+            n, shape = frames.n, (frames.h, frames.w)
+        else:
+            frames = np.asarray(frames)
+            if frames.dtype != np.uint8 or frames.ndim != 3:
+                raise TypeError("TemplateTracker.update: frames are a monochrome uint8 stack (n, h, w), got %s of shape "
+                                "%r" % (frames.dtype, frames.shape))
+            n, shape = len(frames), frames.shape[1:]
+        if n == 0:
+            return np.zeros((0, k, 2), np.int32), np.zeros((0, k))
+        best = ops.match_templates(frames, self.templates, self.queries(n, shape), method=self.method)
+        positions = np.stack([best["x"], best["y"]], axis=1).reshape(n, k, 2)
+        self.positions = positions[-1].astype(np.int64)
+        return positions, best["score"].reshape(n, k).copy()

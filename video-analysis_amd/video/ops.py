@@ -3525,3 +3525,126 @@ def jpeg_decode(streams, color=None, stream=None, keep=False, ret_status=False, 
             (n, h, w) + ((3,) if c == 3 else ()), np.uint8, stream)
     extra = ((status,) if ret_status else ()) + ((rounds,) if ret_rounds else ())
     return (frames,) + extra if extra else frames
+
+
+# ------------------------------------------------------------------------ template matching
+MATCH_METHODS = _hip.MATCH_METHODS
+MATCH_MAX_TEMPLATE_PIXELS = _hip.MATCH_MAX_TEMPLATE_PIXELS
+MATCH_RESULT_DTYPE = np.dtype([("score", np.float64), ("x", np.int32), ("y", np.int32), ("status", np.int32)])
+MATCH_STATUS_FRAME, MATCH_STATUS_TEMPLATE, MATCH_STATUS_EMPTY, MATCH_STATUS_OUTSIDE = 1, 2, 4, 8      # VA_MATCH_STATUS_*
+
+
+def match_query_table(queries, what="match_templates"):
+    """the (q, 6) int32 table (frame, templ, x0, y0, nx, ny) of queries given as such rows or as MATCH_QUERY_DTYPE
+    records"""
+    arr = np.asarray(queries)
+    if arr.dtype == _hip.MATCH_QUERY_DTYPE:
+        arr = arr.view(np.int32).reshape(-1, 6)
+    if arr.size == 0:
+        return np.zeros((0, 6), np.int32)
+    if not np.issubdtype(arr.dtype, np.integer) or arr.ndim != 2 or arr.shape[1] != 6:
+        raise ValueError("%s: queries are integer rows (frame, templ, x0, y0, nx, ny), got %s of shape %r"
+                         % (what, arr.dtype, arr.shape))
+    if np.any(np.abs(arr.astype(np.int64)) >= 2 ** 31):
+        raise ValueError("%s: a query field does not fit int32" % what)
+    return np.ascontiguousarray(arr, np.int32)
+
+
+def match_query_status(table, n, h, w, shapes):
+    """the status bits the device gives each query of `table` (match_query_table) on n frames (h, w) and templates of
+    `shapes` (m, 2): host arithmetic, which sizes the buffers of match_templates"""
+    q = table.astype(np.int64)
+    shapes = np.asarray(shapes, np.int64).reshape(-1, 2)
+    frame, templ, x0, y0, nx, ny = q.T
+    status = np.zeros(len(q), np.int32)
+    status[(frame < 0) | (frame >= n)] |= MATCH_STATUS_FRAME
+    empty = (nx < 1) | (ny < 1)
+    status[empty] |= MATCH_STATUS_EMPTY
+    known = (templ >= 0) & (templ < len(shapes))
+    status[~known] |= MATCH_STATUS_TEMPLATE
+    th, tw = (shapes[np.where(known, templ, 0), k] if len(shapes) else np.zeros(len(q), np.int64) for k in (0, 1))
+    outside = known & ~empty & ((x0 < 0) | (y0 < 0) | (x0 + nx - 1 + tw > w) | (y0 + ny - 1 + th > h))
+    status[outside] |= MATCH_STATUS_OUTSIDE
+    return status
+
+
+def _match_templates_in(templates, what):
+    arrs = []
+    for k, t in enumerate(templates):
+        t = np.asarray(t)
+        if t.dtype != np.uint8:
+            raise TypeError("%s: template %d must be uint8, got %s" % (what, k, t.dtype))
+        if t.ndim != 2 or t.size < 1 or t.size > MATCH_MAX_TEMPLATE_PIXELS:
+            raise ValueError("%s: template %d of shape %r: templates are 2-d with 1 .. %d pixels"
+                             % (what, k, t.shape, MATCH_MAX_TEMPLATE_PIXELS))
+        arrs.append(np.ascontiguousarray(t))
+    return arrs
+
+
+def match_templates(frames, templates, queries, method="ccoeff_normed", maps=False, keep=False, stream=None):
+    """cv2.matchTemplate + cv2.minMaxLoc for a batch of queries in one launch chain (DESIGN.md §9, "Template matching";
+    va_template_match_u8).  frames: a monochrome uint8 stack (n, h, w), or a DeviceFrames, which is not uploaded and
+    stays the caller's.  templates: a list of 2-d uint8 arrays of 1 .. 65536 pixels each.  queries: rows (frame,
+    templ, x0, y0, nx, ny): the template's top-left corner at (x0 + i, y0 + j) for 0 <= i < nx, 0 <= j < ny, all of
+    which must hold the template inside the frame.  method: one of MATCH_METHODS (cv2.TM_* in lower case).
+    Returns `best`, a MATCH_RESULT_DTYPE array: the minimum (sqdiff methods) or maximum score of each query and its
+    position, the first in raster order among equals; a query with status != 0 (MATCH_STATUS_*) has score nan and
+    position (-1, -1).  maps=True appends the list of (ny, nx) float64 score maps, (0, 0) for a flagged query.
+    keep=True appends the DeviceFrames the call ran on (the caller's own, or the upload of a host stack, which is
+    then the caller's to release).  TypeError / ValueError for arguments of the wrong type or shape, before a device
+    is touched."""
+    what = "match_templates"
+    if method not in MATCH_METHODS:
+        raise ValueError("%s: method %r is not one of %s" % (what, method, sorted(MATCH_METHODS)))
+    src, n, h, w, c, owned = _frames_in(frames, what)
+    if c != 1:
+        raise ValueError("%s: frames are a monochrome stack (n, h, w); convert colour frames first" % what)
+    if n and (h < 1 or w < 1):
+        raise ValueError("%s: frames of shape %r have no pixels" % (what, (h, w)))
+    arrs = _match_templates_in(templates, what)
+    table = match_query_table(queries, what)
+    nq, m = len(table), len(arrs)
+    shapes = np.array([t.shape for t in arrs], np.int32).reshape(m, 2)
+    status = match_query_status(table, n, h, w, shapes)
+    sizes = np.where(status == 0, table[:, 4].astype(np.int64) * table[:, 5], 0)
+    map_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    total = int(map_off[-1])
+    best = np.zeros(nq, MATCH_RESULT_DTYPE)
+    if nq == 0 or n == 0 or m == 0:
+        best["score"], best["x"], best["y"], best["status"] = np.nan, -1, -1, status
+        out = (best,) + (([np.zeros((0, 0))] * nq,) if maps else ())
+        if keep:
+            out += (DeviceFrames.upload(src, stream) if owned else src,)
+        return out if len(out) > 1 else best
+    L = _hip.lib()
+    flat, _, toff, tsizes, _ = _pack_ragged(arrs)
+    toff = np.concatenate([toff, [int(tsizes.sum())]]).astype(np.int64)
+    with _Lease.on(stream) as d:
+        dev = _frames_on_device(d, src, owned)
+        ws_bytes = L.va_template_match_workspace_bytes(nq, total, m)
+        if ws_bytes == 0:
+            raise ValueError("%s: %d queries of %d positions are beyond what one call takes" % (what, nq, total))
+        tb, sb, ob, qb = d.upload(flat), d.upload(shapes), d.upload(toff), d.upload(table)
+        bb, ws = d.take(nq * 24), d.take(ws_bytes)
+        mb, mo = (d.take(max(total, 1) * 8), d.upload(map_off)) if maps else (None, None)
+        args = _hip.va_match_args(C.sizeof(_hip.va_match_args), MATCH_METHODS[method], dev.buf.ptr, n, h, w, 0, h * w,
+                                  tb.ptr, sb.ptr, ob.ptr, m, qb.ptr, nq, total, bb.ptr, _ptr(mb), _ptr(mo), ws.ptr,
+                                  ws_bytes, stream)
+        check(L.va_template_match_u8(C.byref(args)))
+        raw = bb.download((nq,), _hip.MATCH_BEST_DTYPE, stream)
+        scores = mb.download((total,), np.float64, stream) if maps else None
+        if not keep and owned:
+            dev.release(into=d)
+    good = raw["status"] == 0
+    if not np.array_equal(good, status == 0):
+        raise _hip.HipError(-5, "%s: the device and the host disagree on the status of the queries" % what)
+    best["status"] = raw["status"]
+    best["score"] = np.where(good, raw["score"], np.nan)
+    best["x"], best["y"] = np.where(good, raw["x"], -1), np.where(good, raw["y"], -1)
+    out = (best,)
+    if maps:
+        out += ([scores[map_off[k]:map_off[k + 1]].reshape((table[k, 5], table[k, 4]) if good[k] else (0, 0))
+                 for k in range(nq)],)
+    if keep:
+        out += (dev,)
+    return out if len(out) > 1 else best
